@@ -1,14 +1,24 @@
 #!/usr/bin/env python3
 """Headline benchmark of the ResUNet hot path (BASELINE.json: 128^3 x 4ch volumes/sec fwd+bwd at 1/2/4/8 MI355X).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...;
      started bare with --gpus N > 1 the script launches exactly that command itself, as fresh child processes, before any GPU call)
 
 A "step" is one data-parallel training step on synthetic 128^3 4-modality crops, per-GPU batch 4 (BASELINE
 configs[2]/[3]; weak scaling): UNet forward + Dice/BCE criterion + backward + RCCL all-reduce of the criterion
 sums and of the flat gradient buffer + Adam(amsgrad) -- every kernel hand-written HIP behind the C-ABI.  Inputs
-are resident in HBM before the timed region.  Rank 0 prints ONE JSON line; at N=1 it also carries
+are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times
+the K steps and prints the headline (`value`, `ms_per_step`, the whole-step roofline fractions priced from the
+layer table); every further measurement runs only with --full.
+
+--dump-outputs DIR writes what the last timed step computed on rank 0 as DIR/<name>.npy (about 47 MB at the
+default size): loss / dice / bce (float64), the updated flat parameter buffer `params` and the all-reduced
+flat gradient `grads` (float32), and `probs_sample`, the probabilities at 2^20 fixed positions (seed 0, sorted)
+of the flattened [batch, 3, D, H, W] output (float32; all of it when smaller).  Inputs and weights are seeded:
+the same arguments give the same inputs in every run.
+
+With --full the line also carries, at N=1,
   roofline     : the dominant kernel (the 16->16 3x3x3 forward conv at 4 x 128^3: conv3_mx_kernel -- fp16 + MX-fp8 products -- on voxel-major tensors in the default
                  split-bf16 mode, conv3_f32_kernel with --precision f32) timed live with HIP events on the launch stream -- in place, around
                  its launches inside further steps of the timed workload (ru_unet_probe; `hot_loop_ms` = the same kernel in a loop of 20):
@@ -38,8 +48,8 @@ are resident in HBM before the timed region.  Rank 0 prints ONE JSON line; at N=
                  products, forward convolutions 2.07 / 1.41 and the 16-channel data gradients 2.07 under the MX-fp8 schemes; `_three_products`: the yardstick of rounds 1-5;
                  `_achievable` / `whole_step_achievable`: plus the bytes no fusion removes for fp32 tensors -- achievable_bounds),
 and at N > 1
-  allreduce_ms : the two collectives of a step timed in place (HIP event pairs on the kernels' stream, max over ranks), `step_ms_per_rank`,
-                 `rccl_ranks`, `dist_backend`, `transport`; `fwd` and `fwd_batch` are N independent replicas.
+  allreduce_ms : the two collectives of a step timed in place (HIP event pairs on the kernels' stream, max over ranks); `fwd` and `fwd_batch`
+                 are N independent replicas.  `step_ms_per_rank`, `rccl_ranks`, `dist_backend` and `transport` are in every line at N > 1.
 """
 import argparse
 import json
@@ -732,6 +742,25 @@ def cpu_baseline(size, threads=0):
             "fwd_only_value": round(1.0 / dtf, 4), "step_s": [round(v, 3) for v in dts]}
 
 
+DUMP_SAMPLE = 1 << 20      # probabilities kept by --dump-outputs: the whole output at 4 x 3 x 128^3 is 100 MB
+
+
+def dump_outputs(out_dir, last, stepper):
+    """--dump-outputs: the results of the last timed step (module docstring), before anything else runs on the buffers."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: last[k].detach().cpu().numpy().astype(np.float64) for k in ("loss", "dice", "bce")}
+    arrays["params"] = stepper.flat.detach().cpu().numpy()
+    arrays["grads"] = stepper.grads.detach().cpu().numpy()
+    probs = stepper.last_probs.detach().reshape(-1)
+    if probs.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(probs.numel(), DUMP_SAMPLE, replace=False))
+        probs = probs[torch.from_numpy(idx).to(probs.device)]
+    arrays["probs_sample"] = probs.cpu().numpy()
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def _first_error_line(text):
     """the line of a failed launch's stderr that names the failure: the first one that mentions RCCL / NCCL / an error, else the last one"""
     lines = [ln.strip() for ln in text.splitlines() if ln.strip()]
@@ -824,13 +853,21 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-power", action="store_true", help="skip the rocm-smi power sampling leg")
     ap.add_argument("--cpu-threads", type=int, default=0, help="torch threads for the cpu_baseline leg (0 = min(cores, %d))" % CPU_BASELINE_THREADS)
-    ap.add_argument("--no-extras", action="store_true", help="skip fwd-only / roofline / cpu legs")
-    ap.add_argument("--probe-steps", type=int, default=5, help="steps after the timed region in which the dominant kernel is timed in place (0 = off)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip fwd-only / roofline / cpu legs")
+    ap.add_argument("--probe-steps", type=int, default=5, help="with --full: steps after the timed region in which the dominant kernel is timed in place (0 = off)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend (nccl == RCCL; gloo only for plumbing tests)")
     ap.add_argument("--transport", default="torch", choices=["torch", "rccl"],
                     help="collectives of the step: torch.distributed (nccl == RCCL; default) or the library's own ru_allreduce on the kernels' stream")
     ap.add_argument("--shared-gpu", action="store_true", help="plumbing test: let every rank use cuda:0 (RCCL refuses two ranks on one device: gloo, asked for or fallen back to)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline: in-place kernel / family rooflines, collectives, forward-only, f32, bf16-gradient, "
+                         "trainer, sliding-window, CPU-baseline and power legs (the --no-* options and --probe-steps select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (see the module docstring)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    extras = args.full and not args.no_extras
+    probe_steps = args.probe_steps if args.full else 0
 
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) <= 1:
         raise SystemExit(self_launch(args.gpus))     # started bare: become the launcher (no GPU call has happened in this process)
@@ -863,12 +900,14 @@ def main():
     last = {}
 
     def one_step():
-        last["loss"] = stepper.step(x, g)[0]
+        last["loss"], last["dice"], last["bce"] = stepper.step(x, g)
 
     for _ in range(args.warmup):
         one_step()
     per_rank_s = []
     dt = time_region(one_step, args.steps, distributed, per_rank_s)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, stepper)
     vols = args.batch * world * args.steps
     value = vols / dt
     loss = float(last["loss"])
@@ -932,6 +971,7 @@ def main():
         out["dist_backend"] = dist.get_backend(DATA_GROUP)
         out["step_ms_per_rank"] = {"min": round(1e3 * min(per_rank_s) / args.steps, 3), "max": round(1e3 * max(per_rank_s) / args.steps, 3),
                                    "all": [round(1e3 * v / args.steps, 3) for v in per_rank_s]}
+    if distributed and args.full:
         # the two collectives of a step, timed in place with event pairs on the kernels' stream over further steps (every rank runs them)
         stepper.comm_probe = []
         nprobe = max(3, min(5, args.steps))
@@ -952,13 +992,13 @@ def main():
                                            "contains the wait for the slowest rank to arrive" % nprobe}
     # dominant kernel, timed inside the step (every rank runs the extra steps: they contain the collectives)
     insitu = None
-    if args.precision == "bf16x3" and args.probe_steps > 0:
+    if args.precision == "bf16x3" and probe_steps > 0:
         if rank == 0:
-            insitu = roofline_insitu(backend, one_step, args.probe_steps)
+            insitu = roofline_insitu(backend, one_step, probe_steps)
         else:
-            for _ in range(args.probe_steps):
+            for _ in range(probe_steps):
                 one_step()
-    if not args.no_extras:
+    if extras:
         # forward-only, batch 1, in the precision of the run -- at every N (BASELINE metric: forward volumes/s at 1/2/4/8 GPUs): inference
         # does not shard a volume, so the ranks are independent replicas; `value` = N volumes per max-over-ranks time
         x1 = x[:1].contiguous()
@@ -974,7 +1014,7 @@ def main():
                       "roofline_frac": round(step_roofline_ms(1, args.size, args.precision, forward_only=True, pricing="three") / (1e3 * dtf / it), 4),
                       "roofline_frac_executed": round(step_roofline_ms(1, args.size, args.precision, forward_only=True) / (1e3 * dtf / it), 4),
                       "roofline_frac_algorithmic": round(step_roofline_ms(1, args.size, args.precision, forward_only=True, pricing="algorithmic") / (1e3 * dtf / it), 4)}
-    if not args.no_extras:
+    if extras:
         backend.engine.freeze_params(True)
         # forward throughput at the batch of the training configuration (BASELINE configs[2]: batch 4): the same kernels with the deep
         # levels filled; `fwd` above is the batch-1 latency figure of configs[1].  At every N (replicas, like `fwd`).
@@ -988,7 +1028,7 @@ def main():
                       "roofline_frac_executed": round(step_roofline_ms(args.batch, args.size, args.precision, forward_only=True) / (1e3 * dtb / it), 4),
                       "roofline_frac_algorithmic": round(step_roofline_ms(args.batch, args.size, args.precision, forward_only=True, pricing="algorithmic") / (1e3 * dtb / it), 4)}
         backend.engine.freeze_params(False)
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and extras:
         backend.engine.freeze_params(True)
         if args.precision != "f32":
             # BASELINE configs[1]: fp32 forward, batch 1 -- exact-f32 MFMA arithmetic, its own engine and workspace
@@ -1029,9 +1069,9 @@ def main():
             out["predict_case"] = predict_case_probe(backend, flat, args.precision)
         if not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.size, args.cpu_threads)
-    if not args.no_extras and args.probe_steps > 0:    # every rank runs the probe steps (they contain the collectives); rank 0 reports
+    if extras and probe_steps > 0:                     # every rank runs the probe steps (they contain the collectives); rank 0 reports
         backend.engine.freeze_params(False)
-        rf = roofline_families(backend, one_step, args.batch, args.size, args.precision, 1e3 * dt / args.steps, steps=min(3, args.probe_steps))
+        rf = roofline_families(backend, one_step, args.batch, args.size, args.precision, 1e3 * dt / args.steps, steps=min(3, probe_steps))
         if rank == 0:
             out["roofline_top"] = rf.pop("top")       # the three largest kernel families of the step, each against its own roofline, then the three largest single instantiations
             out["roofline_instances"] = rf.pop("instances")    # every tagged instantiation
@@ -1039,13 +1079,13 @@ def main():
             if ft is not None:
                 out["pmc_families"] = ft
             out["roofline_families"] = rf
-    if rank == 0 and not args.no_extras:               # at every N: the dominant kernel as timed inside rank 0's steps
+    if rank == 0 and extras:                           # at every N: the dominant kernel as timed inside rank 0's steps
         out["roofline"] = roofline_probe(args.batch, args.size, args.precision, insitu=insitu,
                                          power_index=smi_index(local) if (world == 1 and not args.no_power) else None)
         out["roofline"]["whole_step_frac"] = out["whole_step_frac"]
         out["roofline"]["whole_step_frac_executed"] = out["whole_step_frac_executed"]
         out["roofline"]["whole_step_frac_achievable"] = out["whole_step_frac_achievable"]
-    if rank == 0 and world == 1 and not args.no_extras and not args.no_power:
+    if rank == 0 and world == 1 and extras and not args.no_power:
         # socket power under the workload (rocm-smi): the 3x3x3 kernels run at the package limit, which is what bounds them
         backend.engine.freeze_params(False)
         pw = power_probe(one_step, seconds=3.0, device_index=smi_index(local))

@@ -453,6 +453,19 @@ def gen_checkpoint():
     print("wrote ckpt/tiny/tinybest_model.pth %.1f KB" % (os.path.getsize(src) / 1024))
 
 
+# ------------------------------------------------------------------ (8b) state_dict layout the reference's Trainer._load loads into
+def gen_state_layout():
+    """Names (in order) and shapes of the state_dict of the reference's model.UNet at the tiny checkpoint configuration, plain and wrapped in
+    nn.DataParallel as main.py:61 builds it: what `model.load_state_dict(s['model'].state_dict())` (train.py:333) checks strictly."""
+    cfg = dict(depth=2, encoder_layers=[1, 1], decoder_layers=[1, 1], number_of_channels=[8, 16], number_of_outputs=3)
+    out = {}
+    for tag, net in (("plain", quiet_unet(**cfg)), ("wrapped", torch.nn.DataParallel(module=quiet_unet(**cfg)))):
+        sd = net.state_dict()
+        out[tag + "_names"] = np.asarray(list(sd.keys()))
+        out[tag + "_shapes"] = np.asarray([list(v.shape) + [-1] * (5 - v.dim()) for v in sd.values()], dtype=np.int64)
+    save("state_layout.npz", **out)
+
+
 # ------------------------------------------------------------------ (9) training input pipeline (dataloader.py)
 def gen_dataloader():
     """Runs the reference's SimpleReader.__getitem__ / FullReader.__getitem__ on a synthetic in-memory case (its NIfTI reader is
@@ -540,6 +553,8 @@ if __name__ == "__main__":
         gen_tiling()
     if want("ckpt"):
         gen_checkpoint()
+    if want("state_layout"):
+        gen_state_layout()
     if want("inference"):
         gen_inference()
     if want("dataloader"):

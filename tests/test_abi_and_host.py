@@ -125,7 +125,7 @@ def test_reference_checkpoint_unpickles_into_host_mirror(golden, tmp_path):
         torch.save({"state": tr.state, "model": plain}, tmp_path / "many" / "manylast_model.pth")
         trw = TR.Trainer(name="many", models_root=str(tmp_path), model=torch.nn.DataParallel(module=M.UNet(**cfg)), rewrite=False, connect_tb=False)
         trw.load_latest()
-        assert all(np.array_equal(trw.model.module.state_dict()[k].numpy(), v) for k, v in params.items())
+        assert all(np.array_equal(trw.model.module.state_dict()[k].cpu().numpy(), v) for k, v in params.items())   # (a GPU-visible wrapper moves its module to cuda:0)
         # state-dict route into a freshly constructed mirror, incl. the DataParallel `module.` prefix
         net = M.UNet(**cfg)
         tr2 = TR.Trainer(name="tiny", models_root=str(tmp_path), model=net, rewrite=False, connect_tb=False)
@@ -241,23 +241,33 @@ def test_inference_workspace_recycles_block_temporaries():
     assert ws(1, 36, 0) == 0                      # extents must be divisible by 8 (three stride-2 levels): size query says 0
 
 
-@pytest.mark.skipif(not os.path.isfile("/root/reference/model.py"), reason="needs the reference sources (build container only; the GPU box has none)")
-def test_checkpoint_written_here_loads_into_the_reference_unet(tmp_path):
+def _module_with_state_layout(names, shapes):
+    """An nn.Module whose state_dict has exactly these names (in order) and shapes: the stand-in for the reference model whose layout
+    tests/golden/state_layout.npz records (module tree from the dotted names, one Parameter per leaf)."""
+    root = torch.nn.Module()
+    for name, shape in zip(names, shapes):
+        *path, leaf = str(name).split(".")
+        m = root
+        for p in path:
+            if not hasattr(m, p):
+                m.add_module(p, torch.nn.Module())
+            m = getattr(m, p)
+        m.register_parameter(leaf, torch.nn.Parameter(torch.zeros([int(s) for s in shape if s >= 0])))
+    return root
+
+
+def test_checkpoint_written_here_loads_into_the_reference_unet(tmp_path, golden):
     """The reverse direction of test_reference_checkpoint_unpickles_into_host_mirror: `<name>best_model.pth` written by THIS Trainer._save,
     read the way the reference's Trainer._load reads it (train.py:326-333: torch.load, then `model.load_state_dict(s['model'].state_dict())`)
-    into the reference's own model.UNet -- un-wrapped and, as main.py:61 builds it, wrapped in nn.DataParallel."""
-    import contextlib
-    import importlib.util
-    import io
+    into the reference's model.UNet -- un-wrapped and, as main.py:61 builds it, wrapped in nn.DataParallel.  The reference model is stood in
+    for by a module with its state_dict layout (names in order, shapes), recorded from it in tests/golden/state_layout.npz."""
     from brats2019_amd import train as TR, model as M
     cfg = dict(depth=2, encoder_layers=[1, 1], decoder_layers=[1, 1], number_of_channels=[8, 16], number_of_outputs=3)
     params = O.make_params(29, **cfg)
-    spec = importlib.util.spec_from_file_location("_reference_model_py", "/root/reference/model.py")
-    ref = importlib.util.module_from_spec(spec)
-    with contextlib.redirect_stdout(io.StringIO()):
-        spec.loader.exec_module(ref)
-        mk_ref = lambda: ref.UNet(cfg["depth"], cfg["encoder_layers"], cfg["decoder_layers"], cfg["number_of_channels"], cfg["number_of_outputs"])
-        ref_plain, ref_wrapped = mk_ref(), torch.nn.DataParallel(module=mk_ref())
+    lay = golden("state_layout")
+    ref_plain = _module_with_state_layout(lay["plain_names"], lay["plain_shapes"])
+    ref_wrapped = _module_with_state_layout(lay["wrapped_names"], lay["wrapped_shapes"])
+    assert list(ref_wrapped.state_dict()) == ["module." + k for k in ref_plain.state_dict()]
     for tag, wrap in (("plain", False), ("wrapped", True)):
         net = M.UNet(**cfg)
         net.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()})

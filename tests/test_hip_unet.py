@@ -5,6 +5,7 @@ Bars (BASELINE.json north_star): probabilities within 1e-3 of the CPU path (we h
 masks (> 0.5) bit-exact, allowing only voxels whose reference probability lies within 1e-5 of the threshold
 (SURVEY section 7 'Bit-exact masks': the CPU path's own thread-order noise is 2-3e-7)."""
 import hashlib
+import os
 
 import numpy as np
 import pytest
@@ -775,6 +776,37 @@ def test_bf16_gradient_precision_training_trajectory():
     print("bf16 vs three-product gradients after 6 steps: losses %s / %s; weights differ by %.2e relative L2, the update itself is %.2e" %
           (["%.6f" % v for v in la], ["%.6f" % v for v in lb], rel, upd))
     assert 0 < rel < 5e-5 and rel < 0.2 * upd
+
+
+def test_plain_bench_run_dumps_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` without --full: the line carries the headline and none of the --full legs, and DIR holds the last timed
+    step's loss terms, parameters, gradients and probabilities in float32 / float64.  Two runs with the same arguments agree."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--size", "32", "--batch", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0 and abs(out["value"] - 1e3 / out["ms_per_step"]) < 1e-2 * out["value"]
+        assert not {"fwd", "fwd_batch", "roofline", "roofline_families", "cpu_baseline", "power", "trainer_step"} & set(out)
+        got = {p.stem: np.load(p) for p in d.glob("*.npy")}
+        assert set(got) == {"loss", "dice", "bce", "params", "grads", "probs_sample"}
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        assert abs(float(got["loss"]) - out["final_loss"]) < 1e-5
+        assert got["params"].shape == got["grads"].shape and got["probs_sample"].size == 3 * 32 ** 3
+        assert np.isfinite(got["grads"]).all() and 0 <= got["probs_sample"].min() and got["probs_sample"].max() <= 1
+        dumps.append(got)
+    a, b = dumps
+    assert abs(float(a["loss"]) - float(b["loss"])) < 1e-6
+    np.testing.assert_allclose(a["params"], b["params"], rtol=0, atol=1e-6)
+    np.testing.assert_allclose(a["probs_sample"], b["probs_sample"], rtol=0, atol=1e-5)
 
 
 def test_forward_criterion_backward_capture_into_a_hip_graph():

@@ -129,7 +129,7 @@ def test_bare_bench_launches_its_own_ranks(tmp_path):
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--shared-gpu", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1",
-                        "--size", "64", "--batch", "1", "--no-cpu-baseline", "--no-power", "--probe-steps", "0"], env=env, capture_output=True, text=True, timeout=1500)
+                        "--size", "64", "--batch", "1", "--full", "--no-cpu-baseline", "--no-power", "--probe-steps", "0"], env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -159,7 +159,7 @@ def test_bench_prints_a_flagged_gloo_line_when_rccl_does_not_come_up(mode):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["RU_BENCH_INJECT_RCCL_FAIL"] = {"health-check-injected": "1", "health-check-real": "", "ranks-die": "2"}[mode]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--shared-gpu", "--steps", "2", "--warmup", "1", "--size", "32", "--batch", "1",
-                        "--no-extras", "--probe-steps", "0"], env=env, capture_output=True, text=True, timeout=2000)
+                        "--full", "--no-extras", "--probe-steps", "0"], env=env, capture_output=True, text=True, timeout=2000)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
