@@ -82,6 +82,9 @@ SIGNATURES = {
     "ru_compose_labels": (_i, [_vp, _vp, C.c_ulonglong, _vp, _sz, _vp]),
     "ru_dice_counts": (_i, [_vp, _vp, _vp, _i, _i, _sz, _vp]),
     "ru_dice_accumulate": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "ru_hausdorff_workspace_bytes": (_sz, [_i] * 6),
+    "ru_hausdorff_sq": (_i, [_vp, _vp] + [_i] * 6 + [_vp, _vp, _sz, _vp]),
+    "ru_hausdorff_accumulate": (_i, [_vp, _vp] + [_i] * 4 + [_vp]),
     "ru_tile_gather": (_i, [_vp, _vp] + [_i] * 6 + [C.POINTER(_i), _i, _i, _i, _vp]),
     "ru_tile_scatter": (_i, [_vp, _vp] + [_i] * 6 + [C.POINTER(_i), _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
     "ru_case_bbox": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),

@@ -350,6 +350,36 @@ def dice_accumulate(counts, acc, nacc):
     return acc
 
 
+HAUSDORFF_MAX_EXTENT = 512
+
+
+def hausdorff_sq(pred, target, mode=0):
+    """Hausdorff_ITK / Hausdorff_ITKWT.update measuring step (metrics.py:198-263) on the device: int64 device tensor [N,K,4] =
+    (max over P of d^2 to G, max over G of d^2 to P, #P, #G) with exact integer squared distances between voxel centres.
+    mode 0: K = C masks `x > 0.5`; mode 1: K = 1 mask `argmax over dim 1 > 0`.  Every extent must be <= 512 (else RuntimeError)."""
+    if mode not in (0, 1):
+        raise ValueError("hausdorff_sq: mode is 0 (per channel > 0.5) or 1 (argmax > 0)")
+    pred, target = _prep(pred), _prep(target)
+    if tuple(pred.shape) != tuple(target.shape):
+        raise ValueError("hausdorff_sq: shapes differ: %s vs %s" % (tuple(pred.shape), tuple(target.shape)))
+    n, c, d, h, w = _dims5(pred)
+    lib = L.load()
+    out = torch.empty((n, c if mode == 0 else 1, 4), dtype=torch.int64, device=pred.device)
+    ws = L.workspace(lib.ru_hausdorff_workspace_bytes(n, c, d, h, w, mode), pred.device)
+    L.check(lib.ru_hausdorff_sq(L.f32(pred), L.f32(target), n, c, d, h, w, mode, L.ptr(out), L.ptr(ws), ws.numel(), L.stream()),
+            "ru_hausdorff_sq")
+    return out
+
+
+def hausdorff_accumulate(sq, acc, nacc, mode=0):
+    """metrics.py:208-230 / 248-265 on the device: acc[i] += batch mean of the reference's result[n, i] (i < nacc) from hausdorff_sq's
+    output -- sqrt in float64, 1e6 for an empty mask, the reference's i-1 index slip for a channel empty on both sides (mode 0)."""
+    n, k = int(sq.shape[0]), int(sq.shape[1])
+    assert sq.dtype == torch.int64 and sq.is_contiguous() and acc.dtype == torch.float64 and acc.numel() >= nacc
+    L.check(L.load().ru_hausdorff_accumulate(L.ptr(sq), L.ptr(acc), n, k, int(nacc), int(mode), L.stream()), "ru_hausdorff_accumulate")
+    return acc
+
+
 # ---------------------------------------------------------------------- engine-internal voxel-major layout (tests / probes)
 def to_c16(x):
     """NCDHW [N,C,D,H,W] -> C16 storage [N,C/16,D,H,W,16] (device kernel ru_layout_convert)."""

@@ -350,6 +350,21 @@ int ru_dice_counts(const float* p, const float* g, unsigned long long* counts, i
  * in float32 like the reference's numpy line (0/0 -> NaN -> 1), the mean and the accumulator in float64; c < nacc (= classes - 1 <= C). */
 int ru_dice_accumulate(const unsigned long long* counts, double* acc, int N, int C, int nacc, ru_stream_t stream);
 
+/* ---------------------------------------------------------------- evaluation metric (metrics.py:188-271, `Hausdorff_ITK` / `Hausdorff_ITKWT`)
+ * Exact squared Euclidean distances between voxel centres (unit spacing on D, H, W), every extent in [1, 512] (larger: RU_EINVAL).
+ * p, g: [N][C][D][H][W] float32.  mode 0: K = C masks per sample, x > 0.5 per channel; mode 1: K = 1 mask, argmax over C > 0 (the
+ * first of equal maxima wins, so: max(x[1:]) > x[0]).
+ * out[(n*K + k)*4 + {0,1,2,3}] = { max over P of d^2 to G, max over G of d^2 to P, #P, #G } as exact integers (a directed maximum is
+ * meaningless when either count is 0).  ws: ru_hausdorff_workspace_bytes(N, C, D, H, W, mode) bytes (8 per voxel and mask). */
+size_t ru_hausdorff_workspace_bytes(int N, int C, int D, int H, int W, int mode);
+int ru_hausdorff_sq(const float* p, const float* g, int N, int C, int D, int H, int W, int mode, unsigned long long* out,
+                    void* ws, size_t ws_bytes, ru_stream_t stream);
+/* The rest of the metric's `update` on the device: result[n, i] for i < nacc (<= K) as the reference's loop fills it -- HD = sqrt of the
+ * larger squared maximum in float64, 1e6 when one mask is empty (ITK raises, the reference stores 1e+6); mode 0 only: both masks of
+ * channel i empty writes 0 to column i-1 (the reference's index slip, kept) and leaves column i at 0; mode 1: both empty -> 1e6 -- then
+ * acc[i] += mean over the N samples (float64). */
+int ru_hausdorff_accumulate(const unsigned long long* sq, double* acc, int N, int K, int nacc, int mode, ru_stream_t stream);
+
 /* ---------------------------------------------------------------- training input pipeline (dataloader.py:100-216, SimpleReader)
  * ru_zscore_stats: per channel stats[c] = { #(x > 0), sum x, sum x^2 } over all V voxels in float64 -- the three numbers the
  *   reference's normalisation is made of (dataloader.py:124-130: the count is over positive voxels, the sums over all).
