@@ -45,6 +45,11 @@ SIGNATURES = {
     "ru_criterion_grad": (_i, [_vp, _vp, _vp, _d, _f, _f, _f, _f, _vp, _i, _i, _sz, _vp]),
     "ru_criterion_value": (_i, [C.POINTER(_d), _i, _d, _d, C.POINTER(_d), C.POINTER(_d)]),
     "ru_criterion_value_device": (_i, [_vp, _i, _d, _d, _d, _d, _vp, _vp]),
+    "ru_crit_moments_workspace_bytes": (_sz, [_i, _i, _sz]),
+    "ru_crit_moments": (_i, [_vp, _vp, _i, _i, _sz, C.c_uint, _vp, _vp, _sz, _vp]),
+    "ru_crit_reduce": (_i, [_vp, _i, _i, _vp, _vp]),
+    "ru_crit_eval": (_i, [_vp, _vp, _i, _i, _d, _d, _vp, _i, _vp, _vp, _vp]),
+    "ru_crit_grad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _sz, _i, _vp, _vp]),
     "ru_adam_amsgrad_step": (_i, [_vp] * 5 + [_sz] + [_f] * 5 + [_i, _vp]),
     "ru_adam_step": (_i, [_vp] * 5 + [_sz] + [_f] * 5 + [_i, _vp]),
     "ru_unet_create": (_vp, [_i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i]),
@@ -104,6 +109,17 @@ SIGNATURES = {
     "ru_conv3d_fwd_l": (_i, [_vp, _vp, _vp, _vp] + [_i] * 7 + [_vp, _sz, _vp]),
     "ru_conv3d_bwd_weight_l": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_vp, _sz, _vp]),
 }
+
+
+# ru_crit_* (include/resunet_hip.h): term kinds, moment indices, the term struct
+CRIT_KINDS = {"Dice_loss_joint": 0, "BCE_Loss": 1, "MSE_Loss": 2, "CE_Loss": 3, "Dice1D": 4, "GDL_joint": 5, "sens_loss_joint": 6,
+              "Dice_loss_separate": 7}
+CRIT_MOMENTS, CRIT_MAX_TERMS = 7, 8
+CRIT_MASK_LOGS, CRIT_MASK_ALL = (1 << 4) | (1 << 5), 0x7F
+
+
+class CritTerm(C.Structure):
+    _fields_ = [("kind", _i), ("weight", _d), ("priority", _d), ("bg_weight", _d)]
 
 
 def load():

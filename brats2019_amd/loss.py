@@ -9,13 +9,17 @@
 `FusedCriterion` is the training criterion of main.py:126-128 -- (Dice + BCE(bg 1e-2)) / 2 -- in one pass of
 each phase; the separate modules stay available so `criterion=[Dice_loss_joint(), BCE_Loss()]` lists keep working
 (train.py:203-205).
+
+The reference's other criteria on the same output -- MSE_Loss, CE_Loss, Dice1D, GDL_joint, sens_loss_joint, Dice_loss_separate
+(loss.py:15-195) -- and lists of any of them go through the criterion-list kernels (csrc/criteria.hip): one moments pass, one
+all-reduce of [7C+1] float64 totals, one evaluate launch, one gradient pass.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import _lib, ops
 
 
 def _all_reduce_sums(sums, group):
@@ -131,12 +135,14 @@ class _PairFn(torch.autograd.Function):
 def fuse_criterion_list(criterion):
     """`criterion=[Dice_loss_joint(index, priority), BCE_Loss(index, bg_weight)]` (main.py:126-128, either order, same index) ->
     a callable `(x_list, y_list) -> (loss, [value per list entry])` with loss == sum(values) / 2 exactly as train.py:203-205 forms it,
-    computed by one pass of each criterion phase instead of two.  Anything else -> None (the caller evaluates the list as written)."""
+    computed by one pass of each criterion phase instead of two.  Any other list of the device criteria below on one tensor index, with
+    one `data_parallel` -> the same contract through the criterion-list kernels (`_fuse_terms`).  Anything else -> None (the caller
+    evaluates the list as written)."""
     if not isinstance(criterion, (tuple, list)) or len(criterion) != 2:
-        return None
+        return _fuse_terms(criterion)
     kinds = [type(c) for c in criterion]
     if sorted(k.__name__ for k in kinds) != ["BCE_Loss", "Dice_loss_joint"] or not all(k in (Dice_loss_joint, BCE_Loss) for k in kinds):
-        return None
+        return _fuse_terms(criterion)
     dice = criterion[0] if kinds[0] is Dice_loss_joint else criterion[1]
     bce = criterion[0] if kinds[0] is BCE_Loss else criterion[1]
     if dice.index != bce.label_index or dice.data_parallel != bce.data_parallel:
@@ -196,3 +202,133 @@ class FusedCriterion(_LossBase):
 
     def forward(self, x, y):
         return self._run(x, y, self.index, 0.5, 0.5, float(self.bg_weight), float(self.priority))
+
+
+# ------------------------------------------------------------------ criterion lists (loss.py:15-195; csrc/criteria.hip)
+_LOG_KINDS = ("BCE_Loss", "CE_Loss")
+
+
+def _index_of(c):
+    return c.label_index if isinstance(c, (BCE_Loss, Dice1D)) else c.index
+
+
+def _term(c, weight):
+    """(kind, weight in the total, priority, bg_weight) of ru_crit_eval for a criterion module"""
+    return (type(c).__name__, weight, float(getattr(c, "priority", 1)), float(getattr(c, "bg_weight", 1)))
+
+
+class _TermsFn(torch.autograd.Function):
+    """A list of criterion terms on one (pred, gt) pair: one moments pass, one all-reduce of the [7C+1] totals, one evaluate launch
+    (values and the per-row gradient coefficients), and in backward one gradient pass that writes d(loss)/d(pred).  Returns
+    (sum_t weight_t * value_t, value per term); only the first is differentiable."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, terms, group):
+        logs = any(t[0] in _LOG_KINDS for t in terms)
+        moments = ops.crit_moments(pred, gt, _lib.CRIT_MASK_ALL if logs else _lib.CRIT_MASK_ALL & ~_lib.CRIT_MASK_LOGS)
+        totals = ops.crit_reduce(moments)
+        world = _all_reduce_sums(totals, group)
+        values, coef = ops.crit_eval(totals, moments, terms, float(pred.numel()) * world, int(pred.shape[0]) * world)
+        ctx.save_for_backward(pred, gt, coef)
+        ctx.logs = logs
+        out = values.to(torch.float32)
+        rest = tuple(out[1:])
+        ctx.mark_non_differentiable(*rest)
+        return (out[0],) + rest
+
+    @staticmethod
+    def backward(ctx, gout, *_):
+        pred, gt, coef = ctx.saved_tensors
+        dp = ops.crit_grad(pred, gt, coef, gout, ctx.logs)
+        return dp.to(pred.dtype), None, None, None
+
+
+def _fuse_terms(criterion):
+    """fuse_criterion_list for any list of 1..8 device criteria on the same tensor index with the same `data_parallel`:
+    (loss, [value per entry]) with loss = sum(values) / len(list) (train.py:203-205).  A lone Dice_loss_joint or BCE_Loss is left as
+    written: on its own it hands its gradient over to the network's backward, which this path does not."""
+    if not isinstance(criterion, (tuple, list)) or not 1 <= len(criterion) <= _lib.CRIT_MAX_TERMS:
+        return None
+    if not all(type(c) in _TERM_CLASSES for c in criterion):
+        return None
+    if len(criterion) == 1 and type(criterion[0]) in (Dice_loss_joint, BCE_Loss):
+        return None
+    index, group = _index_of(criterion[0]), criterion[0].data_parallel
+    if any(_index_of(c) != index or c.data_parallel != group for c in criterion):
+        return None
+
+    def run(x, y):
+        assert x[index].shape == y[index].shape
+        w = 1.0 / len(criterion)
+        out = _TermsFn.apply(x[index], y[index], tuple(_term(c, w) for c in criterion), group)
+        return out[0], list(out[1:])
+    return run
+
+
+class _TermLoss(_LossBase):
+    """One of the reference's criteria as a one-term list.  Its backward writes d(loss)/d(pred) -- one more ~100 MB pass at
+    4 x 3 x 128^3 -- and is not handed over to the network's backward (hand_over_to_network applies to Dice_loss_joint / BCE_Loss only);
+    a list that mixes them gets the right gradient either way (model.py's "somebody else also used the probabilities" branch)."""
+
+    def forward(self, x, y):
+        index = _index_of(self)
+        assert x[index].shape == y[index].shape
+        return _TermsFn.apply(x[index], y[index], (_term(self, 1.0),), self.data_parallel)[0]
+
+
+class MSE_Loss(_TermLoss):
+    """loss.py:15-29: priority * mean((p - g)^2).  See _TermLoss for the cost of its backward."""
+
+    def __init__(self, index=0, priority=1):
+        super().__init__()
+        self.index = index
+        self.priority = priority
+
+
+class CE_Loss(_TermLoss):
+    """loss.py:52-61: -mean(g log(p + 1e-6)).  See _TermLoss for the cost of its backward."""
+
+    def __init__(self, index=0):
+        super().__init__()
+        self.index = index
+
+
+class Dice1D(_TermLoss):
+    """loss.py:81-96: 1 - 2 mean_c (sum_{n,v} pg + 1) / (sum_{n,v} (p + g) + 2).  See _TermLoss for the cost of its backward."""
+
+    def __init__(self, label_index=0):
+        super().__init__()
+        self.label_index = label_index
+
+
+class GDL_joint(_TermLoss):
+    """loss.py:125-150: generalised Dice over channels 1.., w_c = 1 / sum_{n,v} g; priority * (1 - 2 sum w_c (I_c + 1) / sum w_c (U_c + 1)).
+    A class absent from the (global) batch makes w_c infinite and the value and gradient NaN, as in the reference.  See _TermLoss for
+    the cost of its backward."""
+
+    def __init__(self, index=0, priority=1):
+        super().__init__()
+        self.index = index
+        self.priority = priority
+
+
+class sens_loss_joint(_TermLoss):
+    """loss.py:153-174: priority * (1 - mean_c (sum pg + 1) / (sum g + 1)), all channels.  See _TermLoss for the cost of its backward."""
+
+    def __init__(self, index=0, priority=1):
+        super().__init__()
+        self.index = index
+        self.priority = priority
+
+
+class Dice_loss_separate(_TermLoss):
+    """loss.py:176-195: 1 - mean over samples and channels 1.. of (2 sum pg + 1) / (sum (p^2 + g) + 1).  `priority` is stored and, as in
+    the reference, not used.  Under data parallelism the mean runs over the global batch.  See _TermLoss for the cost of its backward."""
+
+    def __init__(self, index=0, priority=1):
+        super().__init__()
+        self.index = index
+        self.priority = priority
+
+
+_TERM_CLASSES = (Dice_loss_joint, BCE_Loss, MSE_Loss, CE_Loss, Dice1D, GDL_joint, sens_loss_joint, Dice_loss_separate)

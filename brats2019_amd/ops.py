@@ -183,6 +183,59 @@ def criterion_value(sums, count, priority=1.0):
     return out[1], out[2]                                                            # loss.py:114-122, loss.py:79
 
 
+def _rows(p):
+    n, c = int(p.shape[0]), int(p.shape[1])
+    return n, c, p.numel() // max(n * c, 1)
+
+
+def crit_moments(p, g, mask=L.CRIT_MASK_ALL):
+    """Criterion lists, pass 1 (loss.py:15-195): float64 device tensor [N, C, 7] of per-row moments over THIS shard --
+    sum pg, sum p^2, sum p, sum g, sum g log(p+1e-6), sum (1-g) log((1+1e-6)-p), sum (p-g)^2.  Without a bit of
+    `CRIT_MASK_LOGS` in `mask` the two log moments are skipped (written as 0)."""
+    p, g = _prep(p), _prep(g)
+    if p.shape != g.shape:
+        raise AssertionError("prediction/target shape mismatch")
+    lib = L.load()
+    n, c, v = _rows(p)
+    m = torch.empty((n, c, L.CRIT_MOMENTS), dtype=torch.float64, device=p.device)
+    ws = L.workspace(lib.ru_crit_moments_workspace_bytes(n, c, v), p.device)
+    L.check(lib.ru_crit_moments(L.f32(p), L.f32(g), n, c, v, int(mask), L.ptr(m), L.ptr(ws), ws.numel(), L.stream()), "ru_crit_moments")
+    return m
+
+
+def crit_reduce(moments):
+    """[C*7 + 1] float64: per-channel totals over the shard's samples, then the sum of Dice_loss_separate's per-sample terms -- the
+    buffer that is all-reduced across data-parallel ranks."""
+    n, c = int(moments.shape[0]), int(moments.shape[1])
+    out = torch.empty(c * L.CRIT_MOMENTS + 1, dtype=torch.float64, device=moments.device)
+    L.check(L.load().ru_crit_reduce(L.ptr(moments), n, c, L.ptr(out), L.stream()), "ru_crit_reduce")
+    return out
+
+
+def crit_eval(totals, moments, terms, count, n_global):
+    """terms: list of (kind name, weight, priority, bg_weight).  -> (values float64 [1 + len(terms)] = (weighted total, value per term),
+    coef float32 [N, C, 5] = the per-row coefficients of d(total)/dp), from the (all-reduced) totals and this shard's moments."""
+    n, c = int(moments.shape[0]), int(moments.shape[1])
+    arr = (L.CritTerm * max(len(terms), 1))(*[L.CritTerm(L.CRIT_KINDS[k], float(w), float(pr), float(bg)) for k, w, pr, bg in terms])
+    values = torch.empty(1 + len(terms), dtype=torch.float64, device=moments.device)
+    coef = torch.empty((n, c, 5), dtype=torch.float32, device=moments.device)
+    L.check(L.load().ru_crit_eval(L.ptr(totals), L.ptr(moments), n, c, float(count), float(n_global), C.cast(arr, C.c_void_p), len(terms),
+                                  L.ptr(values), L.ptr(coef), L.stream()), "ru_crit_eval")
+    return values, coef
+
+
+def crit_grad(p, g, coef, scale=None, with_logs=True):
+    """Criterion lists, pass 2: dp = a g + b p + c + d g/(p+1e-6) + e (1-g)/((1+1e-6)-p) with a..e = coef[n, c], times `scale`
+    (a float32 device scalar, autograd's incoming gradient) when given.  with_logs=False skips d and e (no CE / BCE term)."""
+    p, g = _prep(p), _prep(g)
+    n, c, v = _rows(p)
+    dp = torch.empty_like(p)
+    sc = None if scale is None else scale.detach().to(torch.float32).contiguous()
+    L.check(L.load().ru_crit_grad(L.f32(p), L.f32(g), L.ptr(coef), L.ptr(sc, True), n, c, v, int(bool(with_logs)), L.f32(dp), L.stream()),
+            "ru_crit_grad")
+    return dp
+
+
 def adam_amsgrad_step(w, g, m, v, vmax, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
     """torch.optim.Adam(amsgrad=True) update on flat float32 buffers (main.py:133-137)."""
     L.check(L.load().ru_adam_amsgrad_step(L.f32(w), L.f32(g), L.f32(m), L.f32(v), L.f32(vmax), w.numel(), lr, betas[0], betas[1],

@@ -125,6 +125,57 @@ int ru_criterion_value(const double* sums_host, int C, double count, double prio
 int ru_criterion_value_device(const double* sums, int C, double count, double priority, double w_dice, double w_bce,
                               double* out3, ru_stream_t stream);
 
+/* ---------------------------------------------------------------- criterion lists (loss.py:15-195; train.py:203-205)
+ * Every criterion of the reference's loss.py that applies to the [N, C, D, H, W] probabilities is a closed form in per-row moments
+ * (row = one (n, c), V voxels), and its gradient is dL/dp = a*g + b*p + c + d*g/(p+1e-6) + e*(1-g)/((1+1e-6)-p), a..e per row.
+ *   ru_crit_moments : moments[(n*C + c)*RU_CRIT_MOMENTS + m], float64, one streaming pass (float per 8192-voxel chunk, double across).
+ *                     `mask` (bits 1 << RU_CRIT_M_*): the two log moments are computed only when one of their bits is set, else 0;
+ *                     the other moments are always written.  ws: ru_crit_moments_workspace_bytes(N, C, V) bytes.  Any V.
+ *   ru_crit_reduce  : out[c*RU_CRIT_MOMENTS + m] = sum over the N samples of moments[n, c, m]; out[C*RU_CRIT_MOMENTS] = sum over n and
+ *                     c >= 1 of Dice_loss_separate's (2 sum pg + 1) / (sum (p^2 + g) + 1).  C*RU_CRIT_MOMENTS + 1 doubles: the
+ *                     buffer to all-reduce (SUM) across data-parallel ranks, and nothing else crosses ranks.
+ *   ru_crit_eval    : one launch, no host sync.  terms: HOST array of `nterms` (1..RU_CRIT_MAX_TERMS), copied into the kernel argument.
+ *                     From the all-reduced `totals` and this shard's `moments` [N, C, M]: values[0] = sum_t weight_t * L_t, values[1+t] =
+ *                     L_t (float64); coef[(n*C + c)*5 + {a,b,c,d,e}] (float32) = sum_t weight_t * (coefficients of dL_t/dp).  count =
+ *                     N_global*C*V, n_global = the global batch.  Reference quirks kept: GDL_joint and Dice_loss_separate skip channel 0,
+ *                     sens_loss_joint does not; Dice_loss_separate ignores its priority; a class absent from the global batch gives
+ *                     GDL_joint w_c = inf, so its value and gradient are NaN, as in torch.
+ *   ru_crit_grad    : dp = f(p, g, coef[row]) * (*scale when scale != NULL; a float32 DEVICE scalar).  with_logs = 0 skips the d and e
+ *                     terms (pass 1 whenever a CE or BCE term is in the list).  */
+#define RU_CRIT_DICE_JOINT 0      /* Dice_loss_joint(index, priority)     loss.py:98-122 */
+#define RU_CRIT_BCE 1             /* BCE_Loss(index, bg_weight)           loss.py:64-79 */
+#define RU_CRIT_MSE 2             /* MSE_Loss(index, priority)            loss.py:15-29 */
+#define RU_CRIT_CE 3              /* CE_Loss(index)                       loss.py:52-61 */
+#define RU_CRIT_DICE1D 4          /* Dice1D(label_index)                  loss.py:81-96 */
+#define RU_CRIT_GDL_JOINT 5       /* GDL_joint(index, priority)           loss.py:125-150 */
+#define RU_CRIT_SENS_JOINT 6      /* sens_loss_joint(index, priority)     loss.py:153-174 */
+#define RU_CRIT_DICE_SEPARATE 7   /* Dice_loss_separate(index, priority)  loss.py:176-195 */
+#define RU_CRIT_NUM_KINDS 8
+#define RU_CRIT_MAX_TERMS 8
+#define RU_CRIT_M_PG 0            /* sum p*g */
+#define RU_CRIT_M_PP 1            /* sum p*p */
+#define RU_CRIT_M_P 2             /* sum p */
+#define RU_CRIT_M_G 3             /* sum g */
+#define RU_CRIT_M_GLOGP 4         /* sum g*log(p + 1e-6) */
+#define RU_CRIT_M_QLOGQ 5         /* sum (1-g)*log((1+1e-6) - p) */
+#define RU_CRIT_M_D2 6            /* sum (p-g)^2 */
+#define RU_CRIT_MOMENTS 7
+#define RU_CRIT_MASK_ALL 0x7fu
+typedef struct {
+    int kind;                     /* RU_CRIT_* */
+    double weight;                /* weight in the total (train.py:203-205: 1 / len(list)) */
+    double priority;              /* the module's priority (1 where it has none) */
+    double bg_weight;             /* BCE_Loss only */
+} ru_crit_term_t;
+size_t ru_crit_moments_workspace_bytes(int N, int C, size_t V);
+int ru_crit_moments(const float* p, const float* g, int N, int C, size_t V, unsigned mask, double* moments,
+                    void* ws, size_t ws_bytes, ru_stream_t stream);
+int ru_crit_reduce(const double* moments, int N, int C, double* out, ru_stream_t stream);
+int ru_crit_eval(const double* totals, const double* moments, int N, int C, double count, double n_global,
+                 const ru_crit_term_t* terms, int nterms, double* values, float* coef, ru_stream_t stream);
+int ru_crit_grad(const float* p, const float* g, const float* coef, const float* scale, int N, int C, size_t V, int with_logs,
+                 float* dp, ru_stream_t stream);
+
 /* ---------------------------------------------------------------- optimizer (main.py:133-142)
  * torch.optim.Adam(amsgrad=True) with L2 weight decay added to the gradient; `step` is 1-based.  */
 int ru_adam_amsgrad_step(float* w, const float* g, float* m, float* v, float* vmax, size_t n,
