@@ -90,6 +90,10 @@ SIGNATURES = {
     "ru_hausdorff_workspace_bytes": (_sz, [_i] * 6),
     "ru_hausdorff_sq": (_i, [_vp, _vp] + [_i] * 6 + [_vp, _vp, _sz, _vp]),
     "ru_hausdorff_accumulate": (_i, [_vp, _vp] + [_i] * 4 + [_vp]),
+    "ru_label_confusion": (_i, [_vp, _vp, _i, _i, _i, _sz, _vp, _vp, _vp]),
+    "ru_overlap_accumulate": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "ru_dice1d_accumulate": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "ru_rmse_accumulate": (_i, [_vp, _vp, _vp]),
     "ru_tile_gather": (_i, [_vp, _vp] + [_i] * 6 + [C.POINTER(_i), _i, _i, _i, _vp]),
     "ru_tile_scatter": (_i, [_vp, _vp] + [_i] * 6 + [C.POINTER(_i), _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
     "ru_case_bbox": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
@@ -116,6 +120,11 @@ CRIT_KINDS = {"Dice_loss_joint": 0, "BCE_Loss": 1, "MSE_Loss": 2, "CE_Loss": 3, 
               "Dice_loss_separate": 7}
 CRIT_MOMENTS, CRIT_MAX_TERMS = 7, 8
 CRIT_MASK_LOGS, CRIT_MASK_ALL = (1 << 4) | (1 << 5), 0x7F
+CRIT_M_D2 = 6
+
+# ru_label_confusion / ru_overlap_accumulate (include/resunet_hip.h)
+CONF_PROB, CONF_LABEL, OVERLAP_MAX_LABELS = 0, 1, 8
+OVERLAP_MODES = {"itk": 0, "wt": 1, "validate": 2}
 
 
 class CritTerm(C.Structure):

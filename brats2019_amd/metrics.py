@@ -5,13 +5,18 @@ channel 2*sum(p*g)/sum(p+g) (NaN -> 1), mean over the batch, accumulated over up
 spacing, voxel centres) without SimpleITK: an exact squared distance transform on the device (ru_hausdorff_sq), then the
 reference's bookkeeping -- 1e6 for an empty mask, its i-1 index slip, the float64 batch mean -- in one more launch.  The counting runs on
 the device (ru_dice_counts, ru_hausdorff_sq) and the running sums stay there: `update` never synchronises, `get()` copies a few numbers
-to the host.  `update(ground, predict)` keeps the reference's argument order (train.py:304)."""
+to the host.  `update(ground, predict)` keeps the reference's argument order (train.py:304).
+
+The rest of the reference's metrics.py: `Dice1D`, `RMSE`, `RMSE_masked`, `DiceWT`, `Dice_ITK` (metrics.py:22-185) and `print_metrics`
+(metrics.py:273-280).  DiceWT and Dice_ITK read one per-sample label confusion matrix (ru_label_confusion), Dice1D the Dice counts,
+RMSE the squared-difference moment; a small launch turns each into the batch mean on the device (ru_overlap_accumulate,
+ru_dice1d_accumulate, ru_rmse_accumulate)."""
 from __future__ import annotations
 
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 
 
 class Metrics(object):
@@ -121,3 +126,173 @@ class Hausdorff_ITKWT(Metrics):
         if isinstance(acc, np.ndarray):
             acc = acc.reshape(-1)[0]                                            # a scalar, like the reference's result.mean()
         return acc / self.samples
+
+
+def _acc(m, n, device):
+    if not isinstance(m.accumulator, torch.Tensor):
+        m.accumulator = torch.full((n,), float(m.accumulator), dtype=torch.float64, device=device)
+    return m.accumulator
+
+
+def _get_array(m):
+    acc = m.accumulator
+    if isinstance(acc, torch.Tensor):
+        acc = acc.cpu().numpy()                                                 # the one device -> host copy
+    return acc / m.samples
+
+
+def _get_scalar(m):
+    acc = _get_array(m)
+    return acc.reshape(-1)[0] if isinstance(acc, np.ndarray) else acc       # a scalar, like the reference's
+
+
+def confusion_torch(pred, gr):
+    """label_confusion's kind-0 counts with torch ops on the device (argmax, bincount): the path for more channels than the kernel counts."""
+    n, c = int(pred.shape[0]), int(pred.shape[1])
+    a = torch.argmax(pred.reshape(n, c, -1), dim=1)
+    b = torch.argmax(gr.reshape(n, c, -1), dim=1)
+    idx = (torch.arange(n, device=pred.device).view(n, 1) * c + a) * c + b
+    return torch.bincount(idx.reshape(-1), minlength=n * c * c).view(n, c, c)
+
+
+def _confusion(pred, gr):
+    if int(pred.shape[1]) > _lib.OVERLAP_MAX_LABELS:
+        return confusion_torch(pred.float(), gr.float())
+    return ops.label_confusion(pred, gr)[0]
+
+
+class Dice1D(Metrics):
+    """metrics.py:22-52: per sample and channel c < classes, r = 2*sum(p*g) / (sum(p+g) + 1e-6) on the `> 0.5` masks in float32; the batch
+    mean and the accumulator in float64.  classes > C raises IndexError (the reference's pred[:, i] does; the default classes=4 against
+    the model's 3 outputs does so).  get(): float64 array [classes]."""
+
+    def __init__(self, name="Dice1D", input_index=0, target_index=0, classes=4):
+        super(Dice1D, self).__init__(name)
+        self.input_index = input_index
+        self.target_index = target_index
+        self.classes = classes
+
+    def update(self, ground, predict):
+        pred = predict[self.input_index].detach()
+        gr = ground[self.target_index].detach()
+        assert gr.shape == pred.shape
+        if self.classes > int(pred.shape[1]) or self.classes > 64:
+            raise IndexError("Dice1D: classes=%d, but the tensors have %d channels" % (self.classes, int(pred.shape[1])))
+        counts = ops.dice_counts(pred.cuda(), gr.cuda())                        # [N,C,2] int64 on the device
+        ops.dice1d_accumulate(counts, _acc(self, self.classes, counts.device), self.classes)
+        self.samples += 1
+
+    def get(self):
+        return _get_array(self)
+
+
+class RMSE(Metrics):
+    """metrics.py:54-73: sqrt(mean((pred - gr)^2)) over the whole tensor.  `data_parallel` (default False): Trainer.train sets it on its
+    train metrics when world > 1, and update() then all-reduces the two sums before the square root, so the value is the global batch's,
+    as the reference computes it on the gathered batch.  get(): a float64 scalar."""
+
+    def __init__(self, name="RMSE", input_index=0, target_index=0):
+        super(RMSE, self).__init__(name)
+        self.input_index = input_index
+        self.target_index = target_index
+        self.data_parallel = False
+
+    def update(self, ground, predict):
+        pred = predict[self.input_index].detach()
+        gr = ground[self.target_index].detach()
+        assert gr.shape == pred.shape
+        sums = ops.rmse_sums(pred.cuda(), gr.cuda())                            # [sum d^2, count] float64 on the device
+        if self.data_parallel:
+            from .loss import _all_reduce_sums
+            _all_reduce_sums(sums, self.data_parallel)
+        ops.rmse_accumulate(sums, _acc(self, 1, sums.device))
+        self.samples += 1
+
+    def get(self):
+        return _get_scalar(self)
+
+
+class RMSE_masked(Metrics):
+    """metrics.py:75-99 with plain torch ops on the device and the reference's broadcasting: the mask sum(mask, dim=(2, 3)) > 0 has the
+    shape [N, min(C, 2), W, 1] and is broadcast against [N, C, D, H, W], so the metric is defined only for degenerate shapes such as
+    [1, 2, 2, H, H] and raises (RuntimeError) where the reference raises.  get(): a float64 scalar."""
+
+    def __init__(self, name="RMSE_masked", input_index=0, target_index=0, target_index_mask=0):
+        super(RMSE_masked, self).__init__(name)
+        self.input_index = input_index
+        self.target_index = target_index
+        self.target_index_mask = target_index_mask
+
+    def update(self, ground, predict):
+        pred = predict[self.input_index].detach().cuda()
+        gr = ground[self.target_index].detach().cuda()
+        mask = ground[self.target_index_mask].detach().cuda()
+        assert gr.shape == pred.shape
+        mask = torch.unsqueeze((torch.sum(mask, dim=(2, 3)) > 0).float(), dim=3)[:, :2]
+        mse = torch.sum(mask * (pred - gr) ** 2) / (torch.sum(mask) + 1e-8)
+        _acc(self, 1, pred.device).add_(torch.sqrt(mse.mean()).to(torch.float64))
+        self.samples += 1
+
+    def get(self):
+        return _get_scalar(self)
+
+
+class DiceWT(Metrics):
+    """metrics.py:135-155: whole-tumour Dice of `argmax over dim 1 > 0` per sample, 2*I / (|P| + |G| + 1e-6) in float32 (both empty: 0),
+    the batch mean accumulated (float64 here; the reference's accumulator ends float32).  get(): a float64 scalar."""
+
+    def __init__(self, name="Dice_WT", input_index=0, target_index=0):
+        super(DiceWT, self).__init__(name)
+        self.input_index = input_index
+        self.target_index = target_index
+
+    def update(self, ground, predict):
+        pred = predict[self.input_index].detach()
+        gr = ground[self.target_index].detach()
+        assert gr.shape == pred.shape
+        conf = _confusion(pred.cuda(), gr.cuda())                               # [N,C,C] int64 on the device
+        ops.overlap_accumulate(conf, _acc(self, 1, conf.device), 1, "wt")
+        self.samples += 1
+
+    def get(self):
+        return _get_scalar(self)
+
+
+class Dice_ITK(Metrics):
+    """metrics.py:157-185: per sample and label i = 1..classes-1 of `argmax over dim 1`, the Dice of SimpleITK's
+    LabelOverlapMeasuresImageFilter on the two binary images (pred == i, gr == i): J = I/(P+G-I), 2J/(1+J) in float64, without
+    SimpleITK.  A label absent from both images -- always so for i >= C, e.g. columns 3 and 4 of the default classes=5 against 3
+    channels -- gives ops.OVERLAP_BOTH_EMPTY (NaN), and the column's mean with it.  That value was not checked against SimpleITK, whose
+    versions differ there.  get(): float64 array [classes-1]."""
+
+    def __init__(self, name="Dice_ITK", input_index=0, target_index=0, classes=5):
+        super(Dice_ITK, self).__init__(name)
+        self.input_index = input_index
+        self.target_index = target_index
+        self.classes = classes
+
+    def update(self, ground, predict):
+        pred = predict[self.input_index].detach()
+        gr = ground[self.target_index].detach()
+        assert gr.shape == pred.shape
+        nacc = self.classes - 1
+        if nacc < 1 or nacc > 64:
+            raise ValueError("Dice_ITK: classes=%d, 2..65" % self.classes)
+        conf = _confusion(pred.cuda(), gr.cuda())                               # [N,C,C] int64 on the device
+        ops.overlap_accumulate(conf, _acc(self, nacc, conf.device), nacc, "itk")
+        self.samples += 1
+
+    def get(self):
+        return _get_array(self)
+
+
+def print_metrics(writer, metric, prefix, epoch):
+    """metrics.py:273-280: an array value is logged as one scalar per entry, tagged prefix + name + index; any other value as one scalar
+    tagged prefix + name.  Then the line `Epoch <epoch>, <prefix> <name> <value>`."""
+    value = metric.get()
+    if isinstance(value, np.ndarray):
+        for i, v in enumerate(value):
+            writer.add_scalar("%s%s%d" % (prefix, metric.name, i), v, epoch)
+    else:
+        writer.add_scalar(prefix + metric.name, value, epoch)
+    print("Epoch %d, %s %s %s" % (epoch, prefix, metric.name, value))

@@ -433,6 +433,80 @@ def hausdorff_accumulate(sq, acc, nacc, mode=0):
     return acc
 
 
+OVERLAP_BOTH_EMPTY = float("nan")       # Dice_ITK for a label absent from both images (RU_OVERLAP_BOTH_EMPTY; not checked against SimpleITK)
+
+
+def label_confusion(pred, target):
+    """Per-sample confusion matrix of labels (metrics.py:135-185, validate.py:66-97) on the device, one pass, exact integer counts:
+    -> (conf int64 [N, L, L] with conf[n, a, b] = #voxels labelled a in `pred` and b in `target`, invalid int64 [N] or None).
+    float32 [N, C, ...] probabilities: label = argmax over C (torch's rules), L = C <= 8 (else ValueError).  uint8 [N, ...] label
+    volumes: 4 counts as 3, L = 4; invalid[n] counts the voxels where either value is outside 0..4 (they are in no bin)."""
+    if tuple(pred.shape) != tuple(target.shape) or pred.dtype != target.dtype or pred.dim() < 2:
+        raise ValueError("label_confusion: needs two tensors of one shape and dtype with a batch axis, got %s %s / %s %s"
+                         % (tuple(pred.shape), pred.dtype, tuple(target.shape), target.dtype))
+    n = int(pred.shape[0])
+    if pred.dtype == torch.uint8:
+        L.require_gpu()
+        pred, target = pred.contiguous(), target.contiguous()
+        kind, c, lab = L.CONF_LABEL, 1, 4
+        v = pred.numel() // max(n, 1)
+    else:
+        pred, target = _prep(pred), _prep(target)
+        kind, c = L.CONF_PROB, int(pred.shape[1])
+        if c > L.OVERLAP_MAX_LABELS:
+            raise ValueError("label_confusion: %d channels, the kernel counts at most %d" % (c, L.OVERLAP_MAX_LABELS))
+        lab = c
+        v = pred.numel() // max(n * c, 1)
+    conf = torch.empty((n, lab, lab), dtype=torch.int64, device=pred.device)
+    invalid = torch.empty(n, dtype=torch.int64, device=pred.device) if kind == L.CONF_LABEL else None
+    L.check(L.load().ru_label_confusion(L.ptr(pred), L.ptr(target), kind, n, c, v, L.ptr(conf), L.ptr(invalid, allow_none=True), L.stream()),
+            "ru_label_confusion")
+    return conf, invalid
+
+
+def overlap_accumulate(conf, acc, nacc, mode, out=None):
+    """From label_confusion's conf [N, L, L] (int64, device), one launch: mode "itk" (Dice_ITK: label i = 1..nacc -> acc[i-1] += batch
+    mean of ITK's Dice, float64; OVERLAP_BOTH_EMPTY for an absent label), "wt" (DiceWT: acc[0] += batch mean of the float32 whole-tumour
+    ratio), "validate" (validate.py: out[n] = [d1, d2, d3, dWT], acc += their sum over n).  `out`: float64 [N, nacc] or None."""
+    n, lab = int(conf.shape[0]), int(conf.shape[1])
+    assert conf.dtype == torch.int64 and conf.is_contiguous() and conf.shape == (n, lab, lab)
+    assert acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() >= nacc
+    assert out is None or (out.dtype == torch.float64 and out.is_contiguous() and out.numel() == n * nacc)
+    L.check(L.load().ru_overlap_accumulate(L.ptr(conf), n, lab, L.OVERLAP_MODES[mode], int(nacc), L.ptr(acc), L.ptr(out, allow_none=True),
+                                           L.stream()), "ru_overlap_accumulate")
+    return acc
+
+
+def dice1d_accumulate(counts, acc, classes):
+    """metrics.py:41-50 on the device from dice_counts' [N, C, 2]: acc[c] += batch mean of 2*I / (S + 1e-6) (float32 ratio), c < classes."""
+    n, c = int(counts.shape[0]), int(counts.shape[1])
+    assert counts.dtype == torch.int64 and counts.is_contiguous() and acc.dtype == torch.float64 and acc.numel() >= classes
+    L.check(L.load().ru_dice1d_accumulate(L.ptr(counts), L.ptr(acc), n, c, int(classes), L.stream()), "ru_dice1d_accumulate")
+    return acc
+
+
+def rmse_sums(pred, target):
+    """RMSE's two sums on the device: float64 [2] = (sum of (pred - target)^2, element count), from ru_crit_moments over the tensors taken as
+    one row -- the buffer a data-parallel RMSE all-reduces before the square root."""
+    pred, target = _prep(pred), _prep(target)
+    if pred.shape != target.shape:
+        raise AssertionError("prediction/target shape mismatch")
+    lib = L.load()
+    v = pred.numel()
+    buf = torch.empty(L.CRIT_MOMENTS + 1, dtype=torch.float64, device=pred.device)    # the 7 moments, then the count
+    ws = L.workspace(lib.ru_crit_moments_workspace_bytes(1, 1, v), pred.device)
+    L.check(lib.ru_crit_moments(L.f32(pred), L.f32(target), 1, 1, v, 0, L.ptr(buf), L.ptr(ws), ws.numel(), L.stream()), "ru_crit_moments")
+    buf[L.CRIT_MOMENTS:].fill_(float(v))
+    return buf[L.CRIT_M_D2:]
+
+
+def rmse_accumulate(sums, acc):
+    """acc[0] += sqrt(sums[0] / sums[1]) on the device (metrics.py:69-71)."""
+    assert sums.dtype == torch.float64 and sums.is_contiguous() and sums.numel() == 2 and acc.dtype == torch.float64
+    L.check(L.load().ru_rmse_accumulate(L.ptr(sums), L.ptr(acc), L.stream()), "ru_rmse_accumulate")
+    return acc
+
+
 # ---------------------------------------------------------------------- engine-internal voxel-major layout (tests / probes)
 def to_c16(x):
     """NCDHW [N,C,D,H,W] -> C16 storage [N,C/16,D,H,W,16] (device kernel ru_layout_convert)."""

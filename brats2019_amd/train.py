@@ -119,6 +119,9 @@ class Trainer(object):
                     raise RuntimeError("data-parallel training needs criteria that reduce over the global batch "
                                        "(brats2019_amd.loss modules); got %s" % type(c).__name__)
                 c.data_parallel = True
+            for m in train_metrics:
+                if hasattr(m, "data_parallel"):        # metrics.RMSE: the square root of the global batch's mean, not a mean of shard roots
+                    m.data_parallel = True
         if self.resume_training:
             self.load_latest()
         elif pretrained_weights is not None:

@@ -1,0 +1,77 @@
+"""Offline scorer with the reference's `validate.py --data_path --predictions_path` contract (validate.py:7-9,51-101): per case the
+Dice of labels 1, 2, 3 and of the whole tumour (labels > 0), label 4 counting as 3, and the mean over the cases.  The reference reads
+NIfTI through nibabel, which this image lacks; here a case is `<case>.npy` in `data_path` (uint8 ground-truth labels {0,1,2,4},
+[D,H,W]) and its prediction `<case>.npy` in `predictions_path`, as `python -m brats2019_amd.test --output DIR` writes it.
+
+Each case is uploaded as uint8 and scored on the device: one label confusion pass and one small launch (ru_label_confusion,
+ru_overlap_accumulate), the ratio of the float32-rounded counts in float32 (NaN -> 1) as validate.py forms it from float32 sums.
+
+    python -m brats2019_amd.validate --data_path ./labels --predictions_path ./predictions
+"""
+from __future__ import annotations
+
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from . import ops
+
+parser = argparse.ArgumentParser(description="PyTorch BraTS2019 Validate (MI355X HIP engine)")
+parser.add_argument("--data_path", default="", type=str, help="directory of <case>.npy ground-truth label volumes")
+parser.add_argument("--predictions_path", default="", type=str, help="directory of <case>.npy predicted label volumes")
+
+VALID_LABELS = (0, 1, 2, 3, 4)
+
+
+def _upload(arr, what):
+    arr = np.ascontiguousarray(arr)
+    if arr.dtype != np.uint8:
+        # the kernel counts values outside 0..4 of a uint8 volume; a wider type is checked here, before the cast could hide them
+        if arr.size and (arr.min() < 0 or arr.max() > 4 or not np.array_equal(arr, np.round(arr))):
+            raise ValueError("%s: labels outside {0,1,2,3,4}" % what)
+        arr = arr.astype(np.uint8)
+    return torch.from_numpy(arr).cuda()
+
+
+def score(cases):
+    """cases: iterable of (name, ground-truth labels, predicted labels), read one at a time.  -> (names, results float64 [cases, 4],
+    mean float64 [4]).  The values stay on the device until the end: one host copy for all cases."""
+    names, rows, invalid = [], [], []
+    total = torch.zeros(4, dtype=torch.float64, device="cuda")
+    for name, label, predict in cases:
+        if tuple(label.shape) != tuple(predict.shape):
+            raise ValueError("%s: prediction shape %s differs from the label shape %s" % (name, tuple(predict.shape), tuple(label.shape)))
+        g, p = _upload(label, name + " (labels)"), _upload(predict, name + " (prediction)")
+        conf, inv = ops.label_confusion(p.reshape(1, -1), g.reshape(1, -1))
+        row = torch.empty(4, dtype=torch.float64, device="cuda")
+        ops.overlap_accumulate(conf, total, 4, "validate", out=row)
+        names.append(name)
+        rows.append(row)
+        invalid.append(inv)
+    if not names:
+        raise ValueError("validate: no cases")
+    bad = torch.cat(invalid).cpu().numpy()
+    if bad.any():
+        k = int(np.argmax(bad > 0))
+        raise ValueError("%s: labels outside {0,1,2,3,4} in %d voxels" % (names[k], int(bad[k])))
+    return names, torch.stack(rows).cpu().numpy(), total.cpu().numpy() / len(names)
+
+
+def main(argv=None):
+    """-> (per-case results float64 [cases, 4] = [d1, d2, d3, dWT], their mean)."""
+    opt = parser.parse_args(argv)
+    print(torch.__version__)
+    print(opt)
+    series = sorted(f[:-4] for f in os.listdir(opt.data_path) if f.endswith(".npy") and os.path.isfile(os.path.join(opt.data_path, f)))
+    cases = ((f, np.load(os.path.join(opt.data_path, f + ".npy")), np.load(os.path.join(opt.predictions_path, f + ".npy"))) for f in series)
+    series, results, mean = score(cases)
+    for f, r in zip(series, results):
+        print(f, str(r))
+    print(mean)
+    return results, mean
+
+
+if __name__ == "__main__":
+    main()

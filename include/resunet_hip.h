@@ -416,6 +416,38 @@ int ru_hausdorff_sq(const float* p, const float* g, int N, int C, int D, int H, 
  * acc[i] += mean over the N samples (float64). */
 int ru_hausdorff_accumulate(const unsigned long long* sq, double* acc, int N, int K, int nacc, int mode, ru_stream_t stream);
 
+/* ---------------------------------------------------------------- evaluation metrics (metrics.py:22-185: `Dice1D`, `RMSE`, `DiceWT`, `Dice_ITK`;
+ * validate.py).  Label overlaps come from one per-sample confusion matrix of exact integer counts.
+ *   ru_label_confusion : conf[(n*L + a)*L + b] = #voxels of sample n with prediction label a and target label b (uint64), one pass that
+ *                        reads each input once; any V >= 1.  kind RU_CONF_PROB: pred, target = [N][C][V] float32, L = C in
+ *                        1..RU_OVERLAP_MAX_LABELS (more: RU_EINVAL), label = argmax over C with torch's rules (the first of equal maxima,
+ *                        a NaN is the maximum and the first NaN wins); `invalid` may be NULL.  kind RU_CONF_LABEL: pred, target = [N][V]
+ *                        uint8 label volumes, C = 1, L = 4, label 4 counts as 3 (validate.py:70); a voxel where either value is outside
+ *                        0..4 goes into invalid[n] (required) and into no bin.  conf and invalid are cleared by a kernel of the same call.
+ *   ru_overlap_accumulate : one launch from conf [N][L][L]; `out` (float64 [N][nacc]) receives the per-sample values when non-NULL.
+ *     RU_OVERLAP_ITK (Dice_ITK): column i-1 for label i = 1..nacc (<= 64): J = I/(P+G-I), dice = 2J/(1+J) in float64 (ITK's
+ *                        LabelOverlapMeasuresImageFilter: mean overlap from the union overlap of the one non-zero label of two binary
+ *                        images).  A label absent from both images (both counts 0, or i >= L) gives RU_OVERLAP_BOTH_EMPTY = NaN.  That
+ *                        value was NOT checked against SimpleITK, whose versions differ there.  acc[i-1] += batch mean.
+ *     RU_OVERLAP_WT (DiceWT): nacc = 1, labels > 0 on both sides: r = 2*I / (S + 1e-6) in float32 (both empty: 0), acc[0] += batch mean.
+ *     RU_OVERLAP_VALIDATE (validate.py): L = 4, nacc = 4, out required: per sample [d1, d2, d3, dWT], r = 2*num/den of the
+ *                        float32-rounded counts in float32, NaN -> 1; acc[k] += the SUM over the N samples (a running sum over cases).
+ *   ru_dice1d_accumulate : from ru_dice_counts' counts [N][C][2] = {I, |P|+|G|}: acc[c] += batch mean of 2*I / (S + 1e-6) formed in
+ *                        float32, c < classes (<= C, <= 64) (metrics.py:41-50).
+ *   ru_rmse_accumulate   : acc[0] += sqrt(sums[0] / sums[1]) in float64, sums = {sum (p-g)^2, count} on the device (metrics.py:66-71;
+ *                        the sum is ru_crit_moments' RU_CRIT_M_D2 moment of the tensor taken as one row). */
+#define RU_CONF_PROB 0
+#define RU_CONF_LABEL 1
+#define RU_OVERLAP_MAX_LABELS 8
+#define RU_OVERLAP_ITK 0
+#define RU_OVERLAP_WT 1
+#define RU_OVERLAP_VALIDATE 2
+int ru_label_confusion(const void* pred, const void* target, int kind, int N, int C, size_t V, unsigned long long* conf,
+                       unsigned long long* invalid, ru_stream_t stream);
+int ru_overlap_accumulate(const unsigned long long* conf, int N, int L, int mode, int nacc, double* acc, double* out, ru_stream_t stream);
+int ru_dice1d_accumulate(const unsigned long long* counts, double* acc, int N, int C, int classes, ru_stream_t stream);
+int ru_rmse_accumulate(const double* sums, double* acc, ru_stream_t stream);
+
 /* ---------------------------------------------------------------- training input pipeline (dataloader.py:100-216, SimpleReader)
  * ru_zscore_stats: per channel stats[c] = { #(x > 0), sum x, sum x^2 } over all V voxels in float64 -- the three numbers the
  *   reference's normalisation is made of (dataloader.py:124-130: the count is over positive voxels, the sums over all).
