@@ -94,6 +94,9 @@ SIGNATURES = {
     "ru_overlap_accumulate": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ru_dice1d_accumulate": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "ru_rmse_accumulate": (_i, [_vp, _vp, _vp]),
+    "ru_surface_workspace_bytes": (_sz, [_i] * 6),
+    "ru_surface_metrics": (_i, [_vp, _vp] + [_i] * 6 + [_d, _vp, _vp, _vp, _sz, _vp]),
+    "ru_surface_accumulate": (_i, [_vp, _vp] + [_i] * 4 + [_vp]),
     "ru_tile_gather": (_i, [_vp, _vp] + [_i] * 6 + [C.POINTER(_i), _i, _i, _i, _vp]),
     "ru_tile_scatter": (_i, [_vp, _vp] + [_i] * 6 + [C.POINTER(_i), _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
     "ru_case_bbox": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
@@ -125,6 +128,10 @@ CRIT_M_D2 = 6
 # ru_label_confusion / ru_overlap_accumulate (include/resunet_hip.h)
 CONF_PROB, CONF_LABEL, OVERLAP_MAX_LABELS = 0, 1, 8
 OVERLAP_MODES = {"itk": 0, "wt": 1, "validate": 2}
+
+# ru_surface_metrics / ru_surface_accumulate (include/resunet_hip.h)
+SURFACE_PROB, SURFACE_LABEL, SURFACE_REGIONS, SURFACE_COUNTS = 0, 1, 3, 6
+SURFACE_COLUMNS = {"dice": 0, "sensitivity": 1, "specificity": 2, "hd95": 3}
 
 
 class CritTerm(C.Structure):

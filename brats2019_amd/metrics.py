@@ -10,7 +10,11 @@ to the host.  `update(ground, predict)` keeps the reference's argument order (tr
 The rest of the reference's metrics.py: `Dice1D`, `RMSE`, `RMSE_masked`, `DiceWT`, `Dice_ITK` (metrics.py:22-185) and `print_metrics`
 (metrics.py:273-280).  DiceWT and Dice_ITK read one per-sample label confusion matrix (ru_label_confusion), Dice1D the Dice counts,
 RMSE the squared-difference moment; a small launch turns each into the batch mean on the device (ru_overlap_accumulate,
-ru_dice1d_accumulate, ru_rmse_accumulate)."""
+ru_dice1d_accumulate, ru_rmse_accumulate).
+
+Beyond the reference: the BraTS challenge's `Hausdorff95`, `Sensitivity` and `Specificity`, per channel on the `> 0.5` masks, from one
+pass sequence on the device (ru_surface_metrics: bit-packed masks and surfaces, an exact squared distance transform that fills a
+histogram of surface distances, an exact order statistic) and its accumulate launch (ru_surface_accumulate)."""
 from __future__ import annotations
 
 import numpy as np
@@ -284,6 +288,62 @@ class Dice_ITK(Metrics):
 
     def get(self):
         return _get_array(self)
+
+
+class _SurfaceMetric(Metrics):
+    """Per sample and channel i < classes-1 one column of ops.surface_metrics on `pred > 0.5` and `gr > 0.5`; update() adds the batch
+    mean to the float64 device accumulator and never synchronises.  get(): float64 array [classes-1]."""
+    column = None
+    empty_value = ops.HD95_EMPTY                                                   # HD95's value for one empty mask; not read by the others
+
+    def __init__(self, name, input_index, target_index, classes):
+        super(_SurfaceMetric, self).__init__(name)
+        self.input_index = input_index
+        self.target_index = target_index
+        self.classes = classes
+
+    def update(self, ground, predict):
+        pred = predict[self.input_index].detach()
+        gr = ground[self.target_index].detach()
+        assert gr.shape == pred.shape
+        nacc = self.classes - 1
+        if nacc < 1 or nacc > int(pred.shape[1]) or nacc > 64:
+            raise IndexError("%s: classes=%d needs 1 <= classes-1 <= %d channels" % (self.name, self.classes, min(int(pred.shape[1]), 64)))
+        values = ops.surface_metrics(pred.cuda(), gr.cuda(), self.empty_value)[0]      # [N,C,4] float64, stays on the device
+        ops.surface_accumulate(values, _acc(self, nacc, values.device), nacc, self.column)
+        self.samples += 1
+
+    def get(self):
+        return _get_array(self)
+
+
+class Hausdorff95(_SurfaceMetric):
+    """The 95th-percentile symmetric surface distance (HD95) of the BraTS challenge, in voxels at unit spacing: the surfaces are the
+    mask voxels with a face neighbour outside the mask or the grid, and the value is numpy.percentile of the distances from each surface
+    voxel to the other surface, both directions pooled (medpy.metric.binary.hd95 with connectivity=1; medpy itself was not run here).
+    Both masks empty: 0.  Exactly one empty: `empty_value`, by default 373.12866 = sqrt(240^2 + 240^2 + 155^2), the diagonal of a BraTS
+    volume -- a convention commonly used for BraTS leaderboards that was NOT checked against the official evaluation."""
+    column = "hd95"
+
+    def __init__(self, name="Hausdorff95", input_index=0, target_index=0, classes=4, empty_value=ops.HD95_EMPTY):
+        super(Hausdorff95, self).__init__(name, input_index, target_index, classes)
+        self.empty_value = empty_value
+
+
+class Sensitivity(_SurfaceMetric):
+    """TP / |G| per sample and channel (1 when G is empty), from exact voxel counts in float64."""
+    column = "sensitivity"
+
+    def __init__(self, name="Sensitivity", input_index=0, target_index=0, classes=4):
+        super(Sensitivity, self).__init__(name, input_index, target_index, classes)
+
+
+class Specificity(_SurfaceMetric):
+    """TN / (V - |G|) per sample and channel (1 when G fills the volume), from exact voxel counts in float64."""
+    column = "specificity"
+
+    def __init__(self, name="Specificity", input_index=0, target_index=0, classes=4):
+        super(Specificity, self).__init__(name, input_index, target_index, classes)
 
 
 def print_metrics(writer, metric, prefix, epoch):

@@ -508,6 +508,48 @@ def rmse_accumulate(sums, acc):
 
 
 # ---------------------------------------------------------------------- engine-internal voxel-major layout (tests / probes)
+HD95_EMPTY = 373.12866                  # sqrt(240^2 + 240^2 + 155^2): the diagonal of a BraTS volume
+
+
+def surface_metrics(pred, target, empty_value=HD95_EMPTY):
+    """The BraTS challenge numbers per sample and region on the device (include/resunet_hip.h, ru_surface_metrics):
+    -> (values float64 [N, K, 4] = (Dice, sensitivity, specificity, HD95), counts int64 [N, K, 6] = (|P|, |G|, TP, |dP|, |dG|, invalid)).
+    float32 [N, C, D, H, W]: P = pred > 0.5, G = target > 0.5 per channel, K = C.  uint8 label volumes [N, D, H, W]: K = 3 regions
+    WT = {1,2,3,4}, TC = {1,3,4}, ET = {3,4}; counts[n, :, 5] is the number of voxels of sample n where either value is above 4.
+    HD95 is numpy.percentile(surface distances, 95), 0 when both masks are empty and `empty_value` when one is.  Every extent must be
+    <= 512 (else RuntimeError).  Nothing is allocated but the outputs and the workspace; nothing synchronises."""
+    if tuple(pred.shape) != tuple(target.shape) or pred.dtype != target.dtype:
+        raise ValueError("surface_metrics: shapes or dtypes differ: %s %s / %s %s" % (tuple(pred.shape), pred.dtype, tuple(target.shape), target.dtype))
+    if pred.dtype == torch.uint8:
+        if pred.dim() != 4:
+            raise ValueError("surface_metrics: uint8 label volumes are [N, D, H, W], got %s" % (tuple(pred.shape),))
+        L.require_gpu()
+        pred, target = pred.contiguous(), target.contiguous()
+        kind, (n, d, h, w), c, k = L.SURFACE_LABEL, (int(v) for v in pred.shape), 1, L.SURFACE_REGIONS
+    else:
+        pred, target = _prep(pred), _prep(target)
+        kind, (n, c, d, h, w) = L.SURFACE_PROB, _dims5(pred)
+        k = c
+    lib = L.load()
+    values = torch.empty((n, k, 4), dtype=torch.float64, device=pred.device)
+    counts = torch.empty((n, k, L.SURFACE_COUNTS), dtype=torch.int64, device=pred.device)
+    ws = L.workspace(lib.ru_surface_workspace_bytes(kind, n, c, d, h, w), pred.device)
+    L.check(lib.ru_surface_metrics(L.ptr(pred), L.ptr(target), kind, n, c, d, h, w, float(empty_value), L.ptr(values), L.ptr(counts),
+                                   L.ptr(ws), ws.numel(), L.stream()), "ru_surface_metrics")
+    return values, counts
+
+
+def surface_accumulate(values, acc, nacc, column):
+    """acc[i] += batch mean of surface_metrics' values[:, i, column] (float64, on the device), i < nacc; column is one of
+    "dice", "sensitivity", "specificity", "hd95"."""
+    n, k = int(values.shape[0]), int(values.shape[1])
+    assert values.dtype == torch.float64 and values.is_contiguous() and values.shape == (n, k, 4)
+    assert acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() >= nacc
+    L.check(L.load().ru_surface_accumulate(L.ptr(values), L.ptr(acc), n, k, int(nacc), L.SURFACE_COLUMNS[column], L.stream()),
+            "ru_surface_accumulate")
+    return acc
+
+
 def to_c16(x):
     """NCDHW [N,C,D,H,W] -> C16 storage [N,C/16,D,H,W,16] (device kernel ru_layout_convert)."""
     x = _prep(x)

@@ -7,6 +7,9 @@ Each case is uploaded as uint8 and scored on the device: one label confusion pas
 ru_overlap_accumulate), the ratio of the float32-rounded counts in float32 (NaN -> 1) as validate.py forms it from float32 sums.
 
     python -m brats2019_amd.validate --data_path ./labels --predictions_path ./predictions
+
+`--regions` scores the BraTS challenge's way instead: per case the Dice, sensitivity, specificity and HD95 of the regions WT = {1,2,3,4},
+TC = {1,3,4} and ET = {3,4} (3 counts as 4), from one pass sequence of ru_surface_metrics per case (metrics.Hausdorff95 states HD95).
 """
 from __future__ import annotations
 
@@ -21,6 +24,12 @@ from . import ops
 parser = argparse.ArgumentParser(description="PyTorch BraTS2019 Validate (MI355X HIP engine)")
 parser.add_argument("--data_path", default="", type=str, help="directory of <case>.npy ground-truth label volumes")
 parser.add_argument("--predictions_path", default="", type=str, help="directory of <case>.npy predicted label volumes")
+# SUPPRESS: without the flag the namespace -- and so the printed output -- is the plain scorer's
+parser.add_argument("--regions", action="store_true", default=argparse.SUPPRESS,
+                    help="score Dice, sensitivity, specificity and HD95 of the regions WT, TC, ET")
+
+REGION_NAMES = ("WT", "TC", "ET")
+REGION_METRICS = ("Dice", "Sens", "Spec", "HD95")
 
 VALID_LABELS = (0, 1, 2, 3, 4)
 
@@ -59,13 +68,47 @@ def score(cases):
     return names, torch.stack(rows).cpu().numpy(), total.cpu().numpy() / len(names)
 
 
+def score_regions(cases):
+    """cases: iterable of (name, ground-truth labels, predicted labels), read one at a time.  -> (names, results float64 [cases, 4, 3],
+    mean float64 [4, 3]): rows Dice, sensitivity, specificity, HD95; columns WT, TC, ET.  The values stay on the device until the end:
+    one host copy for all cases."""
+    names, rows = [], []
+    for name, label, predict in cases:
+        if tuple(label.shape) != tuple(predict.shape) or np.ndim(label) != 3:
+            raise ValueError("%s: prediction shape %s and label shape %s must be one [D, H, W]" % (name, tuple(predict.shape), tuple(label.shape)))
+        g, p = _upload(label, name + " (labels)"), _upload(predict, name + " (prediction)")
+        values, counts = ops.surface_metrics(p[None], g[None])                  # [1, 3, 4], [1, 3, 6]
+        names.append(name)
+        rows.append(torch.cat([values.reshape(-1), counts[0, 0, 5:].to(torch.float64)]))
+    if not names:
+        raise ValueError("validate: no cases")
+    host = torch.stack(rows).cpu().numpy()
+    bad = host[:, -1]
+    if bad.any():
+        k = int(np.argmax(bad > 0))
+        raise ValueError("%s: labels outside {0,1,2,3,4} in %d voxels" % (names[k], int(bad[k])))
+    results = np.ascontiguousarray(host[:, :-1].reshape(len(names), 3, 4).transpose(0, 2, 1))
+    return names, results, results.mean(axis=0)
+
+
+def _region_row(r):
+    return "  ".join("%s %s" % (m, " ".join("%s %.4f" % (k, v) for k, v in zip(REGION_NAMES, row))) for m, row in zip(REGION_METRICS, r))
+
+
 def main(argv=None):
-    """-> (per-case results float64 [cases, 4] = [d1, d2, d3, dWT], their mean)."""
+    """-> (per-case results float64 [cases, 4] = [d1, d2, d3, dWT], their mean).  With --regions: (results float64 [cases, 4, 3], their
+    mean [4, 3]), rows Dice, sensitivity, specificity, HD95 and columns WT, TC, ET."""
     opt = parser.parse_args(argv)
     print(torch.__version__)
     print(opt)
     series = sorted(f[:-4] for f in os.listdir(opt.data_path) if f.endswith(".npy") and os.path.isfile(os.path.join(opt.data_path, f)))
     cases = ((f, np.load(os.path.join(opt.data_path, f + ".npy")), np.load(os.path.join(opt.predictions_path, f + ".npy"))) for f in series)
+    if getattr(opt, "regions", False):
+        series, results, mean = score_regions(cases)
+        for f, r in zip(series, results):
+            print(f, _region_row(r))
+        print("mean", _region_row(mean))
+        return results, mean
     series, results, mean = score(cases)
     for f, r in zip(series, results):
         print(f, str(r))

@@ -448,6 +448,39 @@ int ru_overlap_accumulate(const unsigned long long* conf, int N, int L, int mode
 int ru_dice1d_accumulate(const unsigned long long* counts, double* acc, int N, int C, int classes, ru_stream_t stream);
 int ru_rmse_accumulate(const double* sums, double* acc, ru_stream_t stream);
 
+/* ---------------------------------------------------------------- BraTS challenge metrics: Dice, sensitivity, specificity, HD95
+ * Per sample n and region k, P and G are binary masks on the D x H x W grid, every extent in [1, 512] (larger: RU_EINVAL).
+ *   kind RU_SURFACE_PROB : pred, target = [N][C][D][H][W] float32, P = pred > 0.5 and G = target > 0.5 per channel, K = C regions.
+ *   kind RU_SURFACE_LABEL: pred, target = [N][D][H][W] uint8 label volumes, C = 1, K = RU_SURFACE_REGIONS in the model's channel order:
+ *                          WT = {1, 2, 3, 4}, TC = {1, 3, 4}, ET = {3, 4}; a voxel where either value is above 4 is in no region and
+ *                          is counted in counts[.][RU_SURFACE_C_INVALID] (the caller reports it).
+ * Surface dA = the voxels of A with a face neighbour (6-connectivity) outside A or outside the grid.  S = the multiset of the squared
+ * distances from each voxel of dP to the nearest voxel of dG and from each voxel of dG to the nearest of dP (exact integers, voxel
+ * centres, unit spacing); HD95 = numpy.percentile(sqrt(S), 95) with numpy's default linear method reproduced exactly (x = (n-1)*0.95,
+ * i = floor(x), j = min(i+1, n-1), t = x - i, numpy's _lerp of sqrt(s_(i)) and sqrt(s_(j)) in float64).  HD95 = 0 when both masks are
+ * empty and `empty_value` when exactly one is.  From the exact counts, in float64: Dice = 2TP/(|P|+|G|) (1 when both are empty),
+ * sensitivity = TP/|G| (1 when |G| = 0), specificity = (V-|P|-|G|+TP)/(V-|G|) (1 when |G| = V).
+ *   ru_surface_metrics   : values [N][K][4] float64 = {RU_SURFACE_DICE, _SENS, _SPEC, _HD95}; counts [N][K][RU_SURFACE_COUNTS] uint64 =
+ *                          {|P|, |G|, TP, |dP|, |dG|, invalid voxels of sample n (kind RU_SURFACE_LABEL; 0 otherwise)}.  Both are written
+ *                          by the call (cleared by a kernel).  ws: ru_surface_workspace_bytes(kind, N, C, D, H, W) bytes (0 for a bad
+ *                          shape or kind): 8 B per voxel for two distance maps, the four bit masks, and one histogram of
+ *                          (D-1)^2 + (H-1)^2 + (W-1)^2 + 1 uint32 bins per (n, k).  RU_EINVAL for a bad kind, an extent outside
+ *                          [1, 512], 2 * N * K > 65535 (the launch grids) or an undersized workspace.
+ *   ru_surface_accumulate: acc[i] += mean over the N samples of values[n][i][column] in float64, i < nacc (<= K, <= 64). */
+#define RU_SURFACE_PROB 0
+#define RU_SURFACE_LABEL 1
+#define RU_SURFACE_REGIONS 3
+#define RU_SURFACE_DICE 0
+#define RU_SURFACE_SENS 1
+#define RU_SURFACE_SPEC 2
+#define RU_SURFACE_HD95 3
+#define RU_SURFACE_COUNTS 6
+#define RU_SURFACE_C_INVALID 5
+size_t ru_surface_workspace_bytes(int kind, int N, int C, int D, int H, int W);
+int ru_surface_metrics(const void* pred, const void* target, int kind, int N, int C, int D, int H, int W, double empty_value,
+                       double* values, unsigned long long* counts, void* ws, size_t ws_bytes, ru_stream_t stream);
+int ru_surface_accumulate(const double* values, double* acc, int N, int K, int nacc, int column, ru_stream_t stream);
+
 /* ---------------------------------------------------------------- training input pipeline (dataloader.py:100-216, SimpleReader)
  * ru_zscore_stats: per channel stats[c] = { #(x > 0), sum x, sum x^2 } over all V voxels in float64 -- the three numbers the
  *   reference's normalisation is made of (dataloader.py:124-130: the count is over positive voxels, the sums over all).
