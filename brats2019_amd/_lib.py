@@ -107,9 +107,15 @@ SIGNATURES = {
     "ru_cc_workspace_bytes": (_sz, [_i, _i, _i]),
     "ru_cc_reject": (_i, [_vp, _i, _i, _i, _d, _vp, _sz, _vp]),
     "ru_paste_labels": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
+    "ru_ens_accumulate": (_i, [_vp, _i, C.c_uint, _vp, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
+    "ru_ens_finalize": (_i, [_vp, _i, _vp, _vp, _vp, _i, _sz, _vp]),
+    "ru_ens_accumulate_finalize": (_i, [_vp, _i, C.c_uint, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
+    "ru_ens_argmax": (_i, [_vp, _i, _vp, _i, _sz, _vp]),
+    "ru_paste_probs": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
     "ru_zscore_workspace_bytes": (_sz, [_i, _sz]),
     "ru_zscore_stats": (_i, [_vp, _vp, _i, _sz, _vp, _sz, _vp]),
     "ru_augment_patch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ru_augment_patch_soft": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "ru_layout_convert": (_i, [_vp, _vp, _i, _i, _sz, _i, _vp]),
     "ru_upsample2x_trilinear_fwd_l": (_i, [_vp, _vp] + [_i] * 5 + [_f, _vp]),
     "ru_upsample2x_trilinear_bwd_l": (_i, [_vp, _vp] + [_i] * 5 + [_vp]),

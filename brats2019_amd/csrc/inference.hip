@@ -19,8 +19,6 @@
 
 namespace ru {
 
-struct Box3 { int lo[3], size[3]; };
-
 // ------------------------------------------------------------------ sliding-window tiles (loader_helper.py:34-97, train.py:158-174)
 constexpr int kMaxTiles = 64;
 struct TileOrigins { int o[kMaxTiles][3]; };
@@ -351,15 +349,6 @@ __global__ __launch_bounds__(256) void paste_labels_kernel(const unsigned char* 
         if (z >= 0 && z < b.size[0] && y >= 0 && y < b.size[1] && x >= 0 && x < b.size[2]) o = lab[((size_t)z * b.size[1] + y) * b.size[2] + x];
         full[v] = o;
     }
-}
-
-static int make_box(Box3& b, const int* lo, const int* size, int D, int H, int W, const char* who) {
-    const int dims[3] = {D, H, W};
-    for (int a = 0; a < 3; ++a) {
-        if (!(lo[a] >= 0 && size[a] > 0 && lo[a] + size[a] <= dims[a])) { set_error("%s: the box must lie inside the volume", who); return RU_EINVAL; }
-        b.lo[a] = lo[a]; b.size[a] = size[a];
-    }
-    return RU_OK;
 }
 
 }  // namespace ru

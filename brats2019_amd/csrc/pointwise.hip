@@ -1208,6 +1208,9 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {
     if (m < 0) m += 2 * n;
     return m < n ? m : 2 * n - 1 - m;
 }
+// SOFT: the three target channels are the SAME interpolation (corner offsets, weights, flips, transpose) of a.soft's float channels instead of
+// the one-hot label -- affine_transform(soft, (1, sx, sy, sz), order=1, mode='reflect'), dataloader.py:179 applied to a teacher's region maps.
+template <bool SOFT>
 __global__ __launch_bounds__(256) void augment_patch_kernel(const AugmentArgs a) {
     const int P0 = a.P[0], P1 = a.P[1], P2 = a.P[2];
     const bool tr = (a.flags & 8) != 0;
@@ -1246,22 +1249,35 @@ __global__ __launch_bounds__(256) void augment_patch_kernel(const AugmentArgs a)
 #pragma unroll
             for (int c = 0; c < RU_AUG_MAXC; ++c)
                 if (c < a.C) acc[c] += w * a.image[(size_t)c * DHW + v];
-            const int l = a.label[v];
-            cw1 += l == 1 ? w : 0.f;
-            cw2 += l == 2 ? w : 0.f;
-            cw3 += l == 3 ? w : 0.f;
+            if (SOFT) {                                            // cw1..3 hold WT, TC, ET
+                cw1 += w * a.soft[v];
+                cw2 += w * a.soft[DHW + v];
+                cw3 += w * a.soft[2 * DHW + v];
+            } else {
+                const int l = a.label[v];
+                cw1 += l == 1 ? w : 0.f;
+                cw2 += l == 2 ? w : 0.f;
+                cw3 += l == 3 ? w : 0.f;
+            }
         }
 #pragma unroll
         for (int c = 0; c < RU_AUG_MAXC; ++c)
             if (c < a.C) a.data[(size_t)c * total + o] = ((acc[c] - a.mean[c]) * a.istd[c]) * a.gain[c] + a.bias[c];
-        a.target[o] = (cw1 + cw2) + cw3;                           // WT = 1 + 2 + 3
-        a.target[total + o] = cw1 + cw3;                           // TC = 1 + 3
-        a.target[2 * total + o] = cw3;                             // ET = 3
+        if (SOFT) {
+            a.target[o] = cw1;
+            a.target[total + o] = cw2;
+            a.target[2 * total + o] = cw3;
+        } else {
+            a.target[o] = (cw1 + cw2) + cw3;                       // WT = 1 + 2 + 3
+            a.target[total + o] = cw1 + cw3;                       // TC = 1 + 3
+            a.target[2 * total + o] = cw3;                         // ET = 3
+        }
     }
 }
 int augment_patch_launch(const AugmentArgs& a, hipStream_t s) {
     const size_t total = (size_t)a.P[0] * a.P[1] * a.P[2];
-    hipLaunchKernelGGL(augment_patch_kernel, dim3(grid1d(total, 256, 4096)), dim3(256), 0, s, a);
+    if (a.soft) hipLaunchKernelGGL(augment_patch_kernel<true>, dim3(grid1d(total, 256, 4096)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(augment_patch_kernel<false>, dim3(grid1d(total, 256, 4096)), dim3(256), 0, s, a);
     RU_CHECK_LAUNCH("augment_patch_kernel");
     return RU_OK;
 }

@@ -114,6 +114,17 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return cdiv(a, b) * b; }
 
+// a box [lo, lo + size) inside a [D][H][W] volume (the crop of test.py:85-99), passed to kernels by value
+struct Box3 { int lo[3], size[3]; };
+static inline int make_box(Box3& b, const int* lo, const int* size, int D, int H, int W, const char* who) {
+    const int dims[3] = {D, H, W};
+    for (int a = 0; a < 3; ++a) {
+        if (!(lo[a] >= 0 && size[a] > 0 && lo[a] + size[a] <= dims[a])) { set_error("%s: the box must lie inside the volume", who); return RU_EINVAL; }
+        b.lo[a] = lo[a]; b.size[a] = size[a];
+    }
+    return RU_OK;
+}
+
 // ------------------------------------------------------------------ in-launch finalization of partial sums (fin_tail.hpp)
 // RU_FUSE_TAIL_FINALIZE: the kernel that writes the per-workgroup partial sums of a GroupNorm (forward statistics, or the two sums of its
 // backward) also finalizes them -- its LAST workgroup to finish (one integer ticket, agent scope, reset by the finisher so that the
@@ -442,7 +453,8 @@ constexpr int RU_AUG_MAXC = 8;
 struct AugmentArgs {
     const float* image;          // [C][D][H][W] raw modalities
     const unsigned char* label;  // [D][H][W] values 0..3
-    float* data;                 // [C][Q0][Q1][P2]
+    const float* soft;           // [3][D][H][W] teacher region probabilities (ru_augment_patch_soft), or null: targets from `label`
+    float* data;                // [C][Q0][Q1][P2]
     float* target;               // [3][Q0][Q1][P2]
     int C, D, H, W;
     int lo[3], P[3];

@@ -70,13 +70,23 @@ def remap_labels(label):
 
 class DeviceCase(object):
     """One multimodal case resident in HBM: raw modalities [C,D,H,W] float32, label [D,H,W] uint8 in {0,1,2,3} (raw BraTS 4 is
-    remapped to 3, see remap_labels), z-score constants, centre box."""
+    remapped to 3, see remap_labels), z-score constants, centre box.  `soft` (optional, keyword): [3,D,H,W] float32 WT/TC/ET
+    probabilities of a teacher (`inference.predict_case_ensemble(..., want_probs=True)`) -- the targets of `augment_patch` are then
+    interpolated from them instead of from the one-hot label; `label` still places the crops (`label_bbox`)."""
 
-    def __init__(self, image, label, patch_size, device="cuda"):
+    def __init__(self, image, label, patch_size, device="cuda", soft=None):
         L.require_gpu()
         label = remap_labels(label)
         self.image = torch.as_tensor(np.ascontiguousarray(image, dtype=np.float32)).to(device)
         self.label = torch.as_tensor(label).to(device)
+        self.soft = None
+        if soft is not None:
+            if isinstance(soft, torch.Tensor):
+                self.soft = soft.detach().to(device=device, dtype=torch.float32).contiguous()
+            else:
+                self.soft = torch.as_tensor(np.ascontiguousarray(soft, dtype=np.float32)).to(device)
+            if tuple(self.soft.shape) != (3,) + tuple(self.label.shape):
+                raise ValueError("soft targets must be [3,D,H,W] = %s, got %s" % ((3,) + tuple(self.label.shape), tuple(self.soft.shape)))
         self.patch_size = tuple(int(p) for p in patch_size)
         self.mean, self.std = zscore_stats(self.image)
         self.bbox = label_bbox(label, self.patch_size)
@@ -102,7 +112,9 @@ def _arr(ctype, values):
 
 
 def augment_patch(case, p, patch_size=None):
-    """(data [C,Q0,Q1,P2], target [3,Q0,Q1,P2]) float32 device tensors for explicit parameters `p` (see draw_augment_params)."""
+    """(data [C,Q0,Q1,P2], target [3,Q0,Q1,P2]) float32 device tensors for explicit parameters `p` (see draw_augment_params).  A case
+    with soft targets takes the same pass with the teacher's three channels interpolated in place of the one-hot label
+    (`ru_augment_patch_soft`: affine_transform(soft, (1, sx, sy, sz), order=1, mode='reflect'), dataloader.py:179 on float channels)."""
     patch = tuple(int(v) for v in (patch_size or case.patch_size))
     c, d, h, w = (int(v) for v in case.image.shape)
     flags = sum(1 << i for i, f in enumerate(p["flips"]) if f) | (8 if p["transpose"] else 0)
@@ -110,18 +122,24 @@ def augment_patch(case, p, patch_size=None):
     data = torch.empty((c,) + out_sp, dtype=torch.float32, device=case.image.device)
     target = torch.empty((3,) + out_sp, dtype=torch.float32, device=case.image.device)
     lib = L.load()
-    L.check(lib.ru_augment_patch(L.f32(case.image), L.ptr(case.label),
-                                 _arr(C.c_float, [float(v) for v in case.mean]), _arr(C.c_float, [float(1.0 / v) for v in case.std]),
-                                 c, d, h, w, _arr(C.c_int, [int(v) for v in p["crop_lo"]]), _arr(C.c_int, list(patch)),
-                                 _arr(C.c_double, [float(v) for v in p["scale"]]), flags,
-                                 _arr(C.c_float, [float(v) for v in p["gain"]]), _arr(C.c_float, [float(v) for v in p["bias"]]),
-                                 L.f32(data), L.f32(target), L.stream()), "ru_augment_patch")
+    soft = getattr(case, "soft", None)
+    tail = (_arr(C.c_float, [float(v) for v in case.mean]), _arr(C.c_float, [float(1.0 / v) for v in case.std]),
+            c, d, h, w, _arr(C.c_int, [int(v) for v in p["crop_lo"]]), _arr(C.c_int, list(patch)),
+            _arr(C.c_double, [float(v) for v in p["scale"]]), flags,
+            _arr(C.c_float, [float(v) for v in p["gain"]]), _arr(C.c_float, [float(v) for v in p["bias"]]),
+            L.f32(data), L.f32(target), L.stream())
+    if soft is None:
+        L.check(lib.ru_augment_patch(L.f32(case.image), L.ptr(case.label), *tail), "ru_augment_patch")
+    else:
+        L.check(lib.ru_augment_patch_soft(L.f32(case.image), L.ptr(case.label), L.f32(soft), *tail), "ru_augment_patch_soft")
     return data, target
 
 
 class SimpleReader(torch.utils.data.Dataset):
     """dataloader.py:67-216 over in-memory cases: `cases` is a list of (image [C,D,H,W], label [D,H,W]) arrays (or of callables
-    returning such a pair -- the place for a NIfTI reader).  Items are ([data], [target]) like the reference's, on the device."""
+    returning such a pair -- the place for a NIfTI reader).  Items are ([data], [target]) like the reference's, on the device.
+    A case may be (image, label, soft) with soft [3,D,H,W] float32 teacher probabilities: its targets are distilled from `soft`
+    (see DeviceCase); the draws are the same."""
 
     def __init__(self, cases, patch_size, images_in_epoch=4000, patches_from_single_image=1, device="cuda"):
         super(SimpleReader, self).__init__()
@@ -140,8 +158,9 @@ class SimpleReader(torch.utils.data.Dataset):
             self.patches_from_current_image = 0
             self.current_image_index = index
             src = self.cases[index]
-            image, label = src() if callable(src) else src
-            self.case = DeviceCase(image, label, self.patch_size, self.device)
+            item = src() if callable(src) else src
+            image, label = item[0], item[1]
+            self.case = DeviceCase(image, label, self.patch_size, self.device, soft=item[2] if len(item) > 2 else None)
         self.patches_from_current_image += 1
 
     def __getitem__(self, index):

@@ -1,0 +1,75 @@
+"""Ensemble of saved predictions: the reference's average_predicts.ipynb / emsemble_predicts.ipynb (`sum(data_files) / len(data_files)`,
+argmax, 3 -> 4) for `.npy` predictions.  Every `--predictions` directory holds one model's outputs under the same file names; the files
+found in the first directory are merged across all of them.
+
+    python -m brats2019_amd.ensemble --predictions runA runB runC --output merged [--rule class|regions]
+
+  --rule class    (default, the notebooks') [4,D,H,W] class probabilities -> uint8 labels {0,1,2,4}: argmax over the channels of the mean
+                  (first maximum wins), class 3 stored as 4;
+  --rule regions  [3,D,H,W] WT/TC/ET probabilities, e.g. what `python -m brats2019_amd.test --probs_output DIR` writes -> mean, 0.5
+                  threshold, label composition with the ET > 32 rule and 26-connected component rejection (test.py:144-164).
+
+The sums, the division, the threshold / argmax and the post-processing run on the device (csrc/ensemble.hip, csrc/inference.hip) with one
+upload per file and one download per case.  `--host` computes the same with numpy and scipy (`inference.ensemble_mean_host`, no GPU).
+NIfTI input is out of scope (no nibabel): predictions are arrays.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+
+import numpy as np
+
+from . import inference
+
+parser = argparse.ArgumentParser(description="Average saved predictions of several models (MI355X HIP engine)")
+parser.add_argument("--predictions", required=True, type=str, nargs="+", help="one directory of .npy predictions per model")
+parser.add_argument("--output", required=True, type=str, help="directory for the merged uint8 label volumes")
+parser.add_argument("--rule", default="class", choices=["class", "regions"])
+parser.add_argument("--host", action="store_true", help="numpy / scipy instead of the device kernels")
+
+CHANNELS = {"class": 4, "regions": 3}
+
+
+def merge_host(preds, rule):
+    if rule == "class":
+        return inference.ensemble_class_labels_host(preds)
+    return inference.postprocess_labels(inference.compose_labels_host(inference.ensemble_mean_host(preds)))
+
+
+def merge_device(preds, rule):
+    import torch
+    from . import ops
+    acc = None
+    for p in preds:                                               # one upload at a time: a prediction is folded in before the next arrives
+        acc = ops.ens_accumulate(torch.as_tensor(p, dtype=torch.float32).cuda(), acc=acc)
+    if rule == "class":
+        return ops.ens_argmax(acc, len(preds)).cpu().numpy()
+    mask, counts, _ = ops.ens_finalize(acc, len(preds))
+    labels = ops.compose_labels(mask, counts, et_min=32)
+    return ops.cc_reject(labels, 0.1).cpu().numpy()
+
+
+def main(argv=None):
+    opt = parser.parse_args(argv)
+    names = sorted(f for f in os.listdir(opt.predictions[0]) if f.endswith(".npy"))
+    if not names:
+        raise SystemExit("no .npy predictions in %s" % opt.predictions[0])
+    os.makedirs(opt.output, exist_ok=True)
+    for name in names:
+        preds = []
+        for d in opt.predictions:
+            path = os.path.join(d, name)
+            if not os.path.exists(path):
+                raise SystemExit("%s is missing from %s" % (name, d))
+            p = np.load(path)
+            if p.ndim != 4 or p.shape[0] != CHANNELS[opt.rule] or (preds and p.shape != preds[0].shape):
+                raise SystemExit("%s: expected [%d,D,H,W] arrays of one shape for --rule %s, got %s" % (path, CHANNELS[opt.rule], opt.rule, p.shape))
+            preds.append(p.astype(np.float32, copy=False))
+        labels = merge_host(preds, opt.rule) if opt.host else merge_device(preds, opt.rule)
+        np.save(os.path.join(opt.output, name), labels)
+        print(name, labels.shape, labels.dtype, len(preds), "models", {int(k): int(v) for k, v in zip(*np.unique(labels, return_counts=True))})
+
+
+if __name__ == "__main__":
+    main()

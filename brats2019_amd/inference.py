@@ -10,6 +10,12 @@ of the case to the download of its label volume (kernels in csrc
   ru_cc_reject      26-connected components (skimage.morphology.label) + rejection of regions below ratio 0.1 (:51-62,162-164);
   ru_paste_labels   paste into the full volume (:167-168).
 
+Ensembles (README.md:1-5 of the reference: an ensemble annotates the cases the small network is distilled from; average_predicts.ipynb /
+emsemble_predicts.ipynb average saved predictions on the host): `predict_case_ensemble*` prepares the case ONCE, runs each model on the
+shared batch and folds its prediction into a running float32 sum at once (csrc/ensemble.hip), so at most one model's output is alive;
+the mean probabilities -- the soft labels a student is trained on -- come back pasted into the case's frame when asked for.
+`ensemble_merge_host` / `ensemble_class_labels_host` restate the arithmetic in numpy.
+
 The numpy functions below (`get_bbox`, `prepare_case`, `reject_small_regions`, `postprocess_labels`) are the host restatement the
 device pipeline is tested against; `predict_case` does not call them.  NIfTI reading/writing (nibabel) is out of scope; `predict_case`
 takes and returns arrays.
@@ -141,3 +147,117 @@ def predict_case(model, image):
     img = torch.as_tensor(np.asarray(image) if not isinstance(image, torch.Tensor) else image, dtype=torch.float32).cuda()
     full, counts = predict_case_device(model, img)
     return full.cpu().numpy(), tuple(int(v) for v in counts.cpu().tolist())
+
+
+# ---------------------------------------------------------------------- ensembles of models and soft labels (csrc/ensemble.hip)
+def ensemble_mean_host(preds):
+    """`sum(data_files) / len(data_files)` of the reference's notebooks on float32 arrays: S_1 = p_1, S_m = S_(m-1) + p_m in list order,
+    one true division by the number of models."""
+    acc = np.asarray(preds[0], np.float32)
+    for p in preds[1:]:
+        acc = acc + np.asarray(p, np.float32)
+    return acc / np.float32(len(preds))
+
+
+def ensemble_merge_host(outs_list, pad_left=(0, 0, 0), size=None):
+    """Host restatement of `ensemble_merge`: outs_list[m] = the K = 4 flipped predictions [K,3,Dp,Hp,Wp] of model m.  Per model the
+    un-flipped float32 mean (((o0 + o1) + o2) + o3) / K of test.py:134-138 on the un-padded box, then `ensemble_mean_host` over the models,
+    the 0.5 threshold and the per-region counts (test.py:144).  Returns (mean float32 [3,*size], mask bool, (wt, tc, et))."""
+    per_model = []
+    for outs in outs_list:
+        un = [np.flip(np.asarray(o, np.float32), axis=ax) if ax else np.asarray(o, np.float32) for o, ax in zip(outs, TTA_FLIPS)]
+        acc = un[0]
+        for o in un[1:]:
+            acc = acc + o
+        p = acc / np.float32(len(un))
+        sz = p.shape[1:] if size is None else size
+        per_model.append(p[:, int(pad_left[0]):int(pad_left[0]) + int(sz[0]), int(pad_left[1]):int(pad_left[1]) + int(sz[1]),
+                           int(pad_left[2]):int(pad_left[2]) + int(sz[2])])
+    mean = ensemble_mean_host(per_model)
+    mask = mean > 0.5
+    return mean, mask, tuple(int(v) for v in mask.sum(axis=(1, 2, 3)))
+
+
+def ensemble_class_labels_host(preds):
+    """The notebooks' rule for saved class maps [4,D,H,W]: argmax over the channels of the mean, class 3 stored as 4."""
+    lab = np.argmax(ensemble_mean_host(preds), axis=0).astype(np.uint8)
+    lab[lab == 3] = 4
+    return lab
+
+
+def compose_labels_host(mean):
+    """test.py:144-159: labels {0,1,2,4} from region probabilities [3,D,H,W]; ET only with more than 32 ET voxels."""
+    m = np.asarray(mean) > 0.5
+    out = np.zeros(m.shape[1:], np.uint8)
+    out[m[0]] = 2
+    out[m[1]] = 1
+    if m[2].sum() > 32:
+        out[m[2]] = 4
+    return out
+
+
+def _merge_step(acc, probs, index, count, lo, size, want_mean):
+    """Fold model `index` of `count` into the running sum; the last one is fused with the finalize.  -> (acc, result or None)"""
+    if index + 1 < count:
+        return ops.ens_accumulate(probs, TTA_FLIPS, acc, lo, size), None
+    return acc, ops.ens_accumulate_finalize(probs, TTA_FLIPS, acc, count, lo, size, want_mean=want_mean)
+
+
+def ensemble_merge(probs_list, pad_left, size, want_mean=False):
+    """The merge of an ensemble alone: probs_list[m] = [4,3,Dp,Hp,Wp] device tensor, the four test-time flips predicted by model m.
+    Returns what `ops.tta_merge_box` returns for one model -- (mask uint8 [3,*size], counts int64 [3], mean float32 or None) -- for the
+    float32 mean over the models of their un-flipped, un-padded means."""
+    if not len(probs_list):
+        raise ValueError("ensemble_merge: empty list")
+    if any(tuple(p.shape) != tuple(probs_list[0].shape) for p in probs_list):
+        raise ValueError("ensemble_merge: predictions of different shapes: %s" % [tuple(p.shape) for p in probs_list])
+    acc, out = None, None
+    for i, p in enumerate(probs_list):
+        acc, out = _merge_step(acc, p, i, len(probs_list), pad_left, size, want_mean)
+    return out
+
+
+def _check_ensemble(models):
+    models = list(models)
+    if not models:
+        raise ValueError("predict_case_ensemble: no model given")
+    sig = [(int(m.conv_input.in_channels), int(m.number_of_outputs)) for m in models]
+    if any(s != sig[0] for s in sig):
+        raise ValueError("predict_case_ensemble: the models must agree on input channels and outputs, got (inputs, outputs) = %s" % sig)
+    return models
+
+
+def predict_case_ensemble_device(models, image, want_probs=False):
+    """`predict_case_device` for a list of models: the case is prepared once, every model runs on the same batch of four flips and its
+    prediction enters the running sum before the next forward starts; then labels, component rejection and paste as for one model.
+    Returns (labels, counts) and, with want_probs, the float32 [3,D,H,W] mean probabilities pasted into the case's frame (zero outside
+    the crop box).  An ensemble of one is `predict_case_device`."""
+    models = _check_ensemble(models)
+    image = image.contiguous().float()
+    if int(image.shape[0]) != int(models[0].conv_input.in_channels):
+        raise ValueError("predict_case_ensemble: the case has %d modalities, the models take %d" % (int(image.shape[0]), int(models[0].conv_input.in_channels)))
+    batch, lo, size, left, _padded = prepare_case_device(image)
+    acc, out = None, None
+    for i, model in enumerate(models):
+        model.eval()
+        if hasattr(model, "freeze_params"):
+            model.freeze_params(True)
+        with torch.no_grad():
+            probs = model([batch])[0]                                # [4,3,Dp,Hp,Wp]; merged below, released before the next forward
+        acc, out = _merge_step(acc, probs, i, len(models), left, size, want_probs)
+        del probs
+    mask, counts, mean = out
+    labels = ops.compose_labels(mask, counts, et_min=32)
+    ops.cc_reject(labels, 0.1)
+    full = ops.paste_labels(labels, image.shape[1:], lo)
+    if want_probs:
+        return full, counts, ops.paste_probs(mean, image.shape[1:], lo)
+    return full, counts
+
+
+def predict_case_ensemble(models, image, want_probs=False):
+    """`predict_case` for a list of models (numpy or tensor in, numpy out): one upload, `predict_case_ensemble_device`, one download."""
+    img = torch.as_tensor(np.asarray(image) if not isinstance(image, torch.Tensor) else image, dtype=torch.float32).cuda()
+    out = predict_case_ensemble_device(models, img, want_probs=want_probs)
+    res = (out[0].cpu().numpy(), tuple(int(v) for v in out[1].cpu().tolist()))
+    return res + (out[2].cpu().numpy(),) if want_probs else res

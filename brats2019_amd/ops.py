@@ -384,6 +384,83 @@ def paste_labels(lab, full_shape, lo):
     return full
 
 
+def _ens_box(probs, lo, size):
+    probs = _prep(probs)
+    if probs.dim() == 4:
+        probs = probs[None]                                            # an already merged prediction: one copy, no flips
+    k, c, d, h, w = [int(v) for v in probs.shape]
+    lo = (0, 0, 0) if lo is None else tuple(int(v) for v in lo)
+    size = (d, h, w) if size is None else tuple(int(v) for v in size)
+    return probs, (k, c, d, h, w), lo, size
+
+
+def ens_accumulate(probs, flip_axes=((),), acc=None, lo=None, size=None):
+    """One model of an ensemble (csrc/ensemble.hip): acc [C,*size] float32 takes S_m = S_(m-1) + p_m with p_m the un-flipped mean of
+    probs [K,C,D,H,W] on the box [lo, lo+size) (test.py:134-144), in float32 in call order.  acc=None starts a sum (S_1 = p_1, written
+    without a memset).  probs [C,D,H,W] with the defaults accumulates an already merged prediction.  Returns acc."""
+    probs, (k, c, d, h, w), lo, size = _ens_box(probs, lo, size)
+    first = acc is None
+    if first:
+        acc = torch.empty((c,) + size, dtype=torch.float32, device=probs.device)
+    elif tuple(acc.shape) != (c,) + size or acc.dtype != torch.float32:
+        raise ValueError("ens_accumulate: acc %s does not match %d channels of a %s box" % (tuple(acc.shape), c, size))
+    L.check(L.load().ru_ens_accumulate(L.f32(probs), k, _flip_bits(flip_axes), L.f32(acc), int(first), c, d, h, w, _ints(lo), _ints(size), L.stream()),
+            "ru_ens_accumulate")
+    return acc
+
+
+def _ens_outputs(c, size, device, want_mean):
+    mask = torch.empty((c,) + tuple(size), dtype=torch.uint8, device=device)
+    counts = torch.empty(c, dtype=torch.int64, device=device)
+    mean = torch.empty((c,) + tuple(size), dtype=torch.float32, device=device) if want_mean else None
+    return mask, counts, mean
+
+
+def ens_finalize(acc, m, want_mean=False):
+    """The sum of `m` models -> (mask uint8 = acc / m > 0.5, counts int64 [C], mean = acc / m or None): `sum(data_files) / len(data_files)`
+    of the reference's notebooks in float32 (a true division), then test.py:144."""
+    if not (acc.is_cuda and acc.is_contiguous() and acc.dtype == torch.float32 and acc.dim() >= 2):
+        raise ValueError("ens_finalize: contiguous float32 device tensor [C, ...]")
+    c = int(acc.shape[0])
+    mask, counts, mean = _ens_outputs(c, acc.shape[1:], acc.device, want_mean)
+    L.check(L.load().ru_ens_finalize(L.f32(acc), int(m), L.ptr(mean, True), L.ptr(mask), L.ptr(counts), c, acc.numel() // c, L.stream()), "ru_ens_finalize")
+    return mask, counts, mean
+
+
+def ens_accumulate_finalize(probs, flip_axes, acc, m, lo=None, size=None, want_mean=False):
+    """The LAST model's ens_accumulate fused with ens_finalize (one pass, acc is not written; acc=None: an ensemble of one): the same
+    (mask, counts, mean or None), bit for bit."""
+    probs, (k, c, d, h, w), lo, size = _ens_box(probs, lo, size)
+    if acc is not None and (tuple(acc.shape) != (c,) + size or acc.dtype != torch.float32):
+        raise ValueError("ens_accumulate_finalize: acc %s does not match %d channels of a %s box" % (tuple(acc.shape), c, size))
+    mask, counts, mean = _ens_outputs(c, size, probs.device, want_mean)
+    L.check(L.load().ru_ens_accumulate_finalize(L.f32(probs), k, _flip_bits(flip_axes), L.ptr(acc, True), int(acc is None), int(m), L.ptr(mean, True),
+                                                L.ptr(mask), L.ptr(counts), c, d, h, w, _ints(lo), _ints(size), L.stream()), "ru_ens_accumulate_finalize")
+    return mask, counts, mean
+
+
+def ens_argmax(acc, m):
+    """The class rule of the reference's notebooks on the sum of `m` class maps [C,D,H,W]: argmax over the channels of acc / m (first
+    maximum wins, as np.argmax), 3 -> 4; uint8 [D,H,W]."""
+    if not (acc.is_cuda and acc.is_contiguous() and acc.dtype == torch.float32 and acc.dim() >= 2):
+        raise ValueError("ens_argmax: contiguous float32 device tensor [C, ...]")
+    c = int(acc.shape[0])
+    labels = torch.empty(tuple(acc.shape[1:]), dtype=torch.uint8, device=acc.device)
+    L.check(L.load().ru_ens_argmax(L.f32(acc), int(m), L.ptr(labels), c, acc.numel() // c, L.stream()), "ru_ens_argmax")
+    return labels
+
+
+def paste_probs(mean, full_shape, lo):
+    """paste_labels for float channels: float32 device volume [C,*full_shape], zero except the box at `lo`, which holds mean [C,d,h,w]."""
+    if not (mean.is_cuda and mean.is_contiguous() and mean.dtype == torch.float32 and mean.dim() == 4):
+        raise ValueError("paste_probs: contiguous float32 device tensor [C,d,h,w]")
+    c = int(mean.shape[0])
+    full = torch.empty((c,) + tuple(int(v) for v in full_shape), dtype=torch.float32, device=mean.device)
+    d, h, w = (int(v) for v in full.shape[1:])
+    L.check(L.load().ru_paste_probs(L.f32(mean), L.f32(full), c, d, h, w, _ints(lo), _ints(mean.shape[1:]), L.stream()), "ru_paste_probs")
+    return full
+
+
 def dice_counts(pred, target):
     """metrics.Dice.update counting step (metrics.py:116-127): int64 device tensor [N,C,2] = (#(p>.5 & g>.5), #(p>.5) + #(g>.5))."""
     pred, target = _prep(pred), _prep(target)

@@ -4,6 +4,10 @@ and needs nibabel / skimage, which this image lacks; here a case is a `.npy` arr
 loader_helper.read_multimodal does) and the result a uint8 `.npy` label volume {0,1,2,4}.
 
     python -m brats2019_amd.test --name brain-tumor-segmentation-0002 --models_path ./models --input case.npy --output seg.npy
+
+`--ensemble B C ...` adds the best checkpoints of further experiments under the same `--models_path`: every case is segmented by the
+mean of all models' probabilities (`inference.predict_case_ensemble`).  `--probs_output DIR` also saves that mean -- the soft labels a
+student network is distilled from -- as float32 `NAME.npy` [3,D,H,W].
 """
 from __future__ import annotations
 
@@ -21,18 +25,26 @@ parser.add_argument("--models_path", default="/models", type=str, help="Path to 
 parser.add_argument("--input", default=None, type=str, nargs="+", help=".npy case(s) [4,D,H,W]; default: a synthetic 128^3 case")
 parser.add_argument("--output", default=None, type=str, help="output .npy (single case) or directory")
 parser.add_argument("--precision", default="bf16x3", choices=["bf16x3", "f32"])
+parser.add_argument("--ensemble", default=None, type=str, nargs="+", help="further experiment names under --models_path: segment with the mean of all models")
+parser.add_argument("--probs_output", default=None, type=str, help="directory for the mean region probabilities (soft labels), float32 NAME.npy [3,D,H,W]")
+
+
+def _load_net(name, opt):
+    trainer = train.Trainer(name=name, models_root=opt.models_path, rewrite=False, connect_tb=False)
+    trainer.load_best()
+    trainer.state.cuda = True
+    net = trainer.model.module if hasattr(trainer.model, "module") else trainer.model
+    net.set_precision(opt.precision)
+    net.cuda()
+    return net
 
 
 def main(argv=None):
     opt = parser.parse_args(argv)
     print(torch.__version__)
     print(opt)
-    trainer = train.Trainer(name=opt.name, models_root=opt.models_path, rewrite=False, connect_tb=False)
-    trainer.load_best()
-    trainer.state.cuda = True
-    net = trainer.model.module if hasattr(trainer.model, "module") else trainer.model
-    net.set_precision(opt.precision)
-    net.cuda()
+    net = _load_net(opt.name, opt)
+    others = [_load_net(name, opt) for name in (opt.ensemble or [])]
     cases = opt.input
     if not cases:
         rng = np.random.default_rng(0)
@@ -42,7 +54,14 @@ def main(argv=None):
     else:
         cases = [(os.path.splitext(os.path.basename(c))[0], np.load(c)) for c in cases]
     for name, image in cases:
-        labels, (wt, tc, et) = inference.predict_case(net, image)
+        if others or opt.probs_output:
+            out = inference.predict_case_ensemble([net] + others, image, want_probs=bool(opt.probs_output))
+            labels, (wt, tc, et) = out[0], out[1]
+            if opt.probs_output:
+                os.makedirs(opt.probs_output, exist_ok=True)
+                np.save(os.path.join(opt.probs_output, name + ".npy"), out[2])
+        else:
+            labels, (wt, tc, et) = inference.predict_case(net, image)
         if opt.output:
             dst = opt.output if opt.output.endswith(".npy") and len(cases) == 1 else os.path.join(opt.output, name + ".npy")
             os.makedirs(os.path.dirname(os.path.abspath(dst)), exist_ok=True)

@@ -365,6 +365,27 @@ size_t ru_cc_workspace_bytes(int D, int H, int W);
 int ru_cc_reject(unsigned char* labels, int D, int H, int W, double ratio, void* ws, size_t ws_bytes, ru_stream_t stream);
 int ru_paste_labels(const unsigned char* lab, unsigned char* full, int D, int H, int W, const int* lo, const int* size, ru_stream_t stream);
 
+/* ---------------------------------------------------------------- ensemble inference and soft labels (csrc/ensemble.hip)
+ * The reference's ensemble step (README.md:1-5; average_predicts.ipynb / emsemble_predicts.ipynb: `sum(data_files) / len(data_files)`,
+ * argmax, 3 -> 4) with the models' predictions resident on the device.  Fixed float32 arithmetic, comparable bit for bit with numpy:
+ *   per model  p_m = (((o0 + o1) + o2) + o3) / K, un-flipped, on the box [lo, lo + size) -- ru_tta_merge_box's mean (test.py:134-144);
+ *   across models  S_1 = p_1, S_m = S_(m-1) + p_m in call order;  mean = S_M / (float)M by a true division.
+ * ru_ens_accumulate: one pass per model over probs [K][C][D][H][W]; acc [C][size] takes S_m (first != 0: written, not read -- no memset).
+ *   K = 1, flips = 0 and the box equal to the volume accumulates an already merged prediction (a saved file).
+ * ru_ens_finalize: mean_out (may be NULL) = acc / M, mask = mean > 0.5 (test.py:144), counts[C] = exact voxels set per channel.
+ * ru_ens_accumulate_finalize: the LAST model's accumulate and the finalize in one pass (acc is read, not written; NULL when first != 0,
+ *   i.e. an ensemble of one, which is ru_tta_merge_box); identical results.
+ * ru_ens_argmax: the notebooks' class rule on acc [C][V] of saved class maps: argmax over c of acc / M (first maximum wins, as np.argmax),
+ *   class 3 written as 4, uint8.
+ * ru_paste_probs: the soft labels in the case's own frame: full [C][D][H][W] = 0 outside the box, mean [C][size] inside (test.py:167-168). */
+int ru_ens_accumulate(const float* probs, int K, unsigned flips, float* acc, int first, int C, int D, int H, int W, const int* lo, const int* size,
+                      ru_stream_t stream);
+int ru_ens_finalize(const float* acc, int M, float* mean_out, unsigned char* mask, unsigned long long* counts, int C, size_t Vbox, ru_stream_t stream);
+int ru_ens_accumulate_finalize(const float* probs, int K, unsigned flips, const float* acc, int first, int M, float* mean_out, unsigned char* mask,
+                               unsigned long long* counts, int C, int D, int H, int W, const int* lo, const int* size, ru_stream_t stream);
+int ru_ens_argmax(const float* acc, int M, unsigned char* labels, int C, size_t V, ru_stream_t stream);
+int ru_paste_probs(const float* mean, float* full, int C, int D, int H, int W, const int* lo, const int* size, ru_stream_t stream);
+
 /* ---------------------------------------------------------------- voxel-major working layout ("C16")
  * Between the first and the last convolution the split-bf16 engine keeps activations as [N][C/16][D][H][W][16]
  * (16 channels of a voxel contiguous; C % 16 == 0): a halo tile of a 3x3x3 convolution is then a few long contiguous
@@ -494,6 +515,13 @@ int ru_zscore_stats(const float* image, double* stats, int C, size_t V, void* ws
 int ru_augment_patch(const float* image, const unsigned char* label, const float* mean, const float* inv_std,
                      int C, int D, int H, int W, const int* crop_lo, const int* patch, const double* scale, int flags,
                      const float* gain, const float* bias, float* data_out, float* target_out, ru_stream_t stream);
+/* ru_augment_patch_soft: the same pass for distillation.  soft [3][D][H][W] = a teacher's WT/TC/ET probabilities in the case's frame
+ * (ru_paste_probs): the targets are affine_transform(soft, (1, sx, sy, sz), order=1, mode='reflect') of the crop -- the reference's call
+ * at dataloader.py:179 on three float channels -- with the same flips and transpose; `label` is not read then (may be NULL).
+ * soft = NULL: ru_augment_patch. */
+int ru_augment_patch_soft(const float* image, const unsigned char* label, const float* soft, const float* mean, const float* inv_std,
+                          int C, int D, int H, int W, const int* crop_lo, const int* patch, const double* scale, int flags,
+                          const float* gain, const float* bias, float* data_out, float* target_out, ru_stream_t stream);
 
 #ifdef __cplusplus
 }
