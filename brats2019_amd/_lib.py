@@ -116,6 +116,10 @@ SIGNATURES = {
     "ru_zscore_stats": (_i, [_vp, _vp, _i, _sz, _vp, _sz, _vp]),
     "ru_augment_patch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "ru_augment_patch_soft": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ru_elastic_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ru_elastic_noise": (_i, [C.c_ulonglong, _i, _i, _i, _vp, _vp]),
+    "ru_elastic_field": (_i, [_vp, _d, _d, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ru_elastic_warp": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "ru_layout_convert": (_i, [_vp, _vp, _i, _i, _sz, _i, _vp]),
     "ru_upsample2x_trilinear_fwd_l": (_i, [_vp, _vp] + [_i] * 5 + [_f, _vp]),
     "ru_upsample2x_trilinear_bwd_l": (_i, [_vp, _vp] + [_i] * 5 + [_vp]),

@@ -523,6 +523,28 @@ int ru_augment_patch_soft(const float* image, const unsigned char* label, const 
                           int C, int D, int H, int W, const int* crop_lo, const int* patch, const double* scale, int flags,
                           const float* gain, const float* bias, float* data_out, float* target_out, ru_stream_t stream);
 
+/* ---------------------------------------------------------------- elastic deformation of a training patch (dataloader.py:24-48 elastic_transform,
+ * the commented-out call sites :177 / :180 and the draws :166-168).  Opt-in; ru_augment_patch is not touched.  All three calls only enqueue.
+ * ru_elastic_noise: noise_out [3][P0][P1][P2] float64, uniform in [-1, 1): a counter-based generator (two rounds of splitmix64's finalizer), a pure
+ *   function of (seed, field, linear voxel index) -- the stand-in for `random_state.rand(*shape) * 2 - 1`; numpy's Mersenne Twister stream is not
+ *   reproduced, which is why ru_elastic_field takes the noise as an INPUT.
+ * ru_elastic_field: disp_out [3][P0][P1][P2] float64 = scipy.ndimage.gaussian_filter(noise[f], sigma, mode="constant", cval=0) times alpha, alpha,
+ *   alpha / 2.5: radius int(4 sigma + 0.5), weights exp(-0.5 x^2 / sigma^2) / sum, three separable passes along axis 0, 1, 2, zero outside the
+ *   volume, accumulated and stored in float64.  The radius may exceed an extent.  Refused (RU_EINVAL, before any launch): sigma <= 0 or not finite,
+ *   radius > 256, P2 > 512, P0 > 21845, noise == disp_out.  ws: ru_elastic_workspace_bytes(P0, P1, P2).
+ * ru_elastic_warp: every output voxel reads its source at (i + d0, j + d1, k + d2) in float64.  The C image channels take
+ *   map_coordinates(order=1, mode='reflect'): linear interpolation on the half-sample-symmetric extension (d c b a | a b c d | d c b a), periodic
+ *   beyond one reflection; the T target channels take order=0: the voxel at floor(c + 0.5) on the same extension.  The same pass applies what
+ *   ru_augment_patch applies last: flips (flags bit 0/1/2 = axes D/H/W), the D <-> H transpose (bit 3), gain and bias on the image channels
+ *   (dataloader.py:184-204).  data_out [C][Q0][Q1][P2], target_out [T][Q0][Q1][P2], (Q0, Q1) = (P1, P0) when transposed; not in place.  gain and
+ *   bias are HOST pointers read at launch.  C, T in 0..8 (a count of 0 skips that group and its pointers). */
+size_t ru_elastic_workspace_bytes(int P0, int P1, int P2);
+int ru_elastic_noise(unsigned long long seed, int P0, int P1, int P2, double* noise_out, ru_stream_t stream);
+int ru_elastic_field(const double* noise, double sigma, double alpha, int P0, int P1, int P2, double* disp_out, void* ws, size_t ws_bytes,
+                     ru_stream_t stream);
+int ru_elastic_warp(const float* data_in, int C, const float* target_in, int T, const double* disp, int P0, int P1, int P2, int flags,
+                    const float* gain, const float* bias, float* data_out, float* target_out, ru_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
