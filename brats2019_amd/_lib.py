@@ -112,6 +112,12 @@ SIGNATURES = {
     "ru_ens_accumulate_finalize": (_i, [_vp, _i, C.c_uint, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
     "ru_ens_argmax": (_i, [_vp, _i, _vp, _i, _sz, _vp]),
     "ru_paste_probs": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
+    "ru_unc_accumulate": (_i, [_vp, _i, C.c_uint, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
+    "ru_unc_accumulate_finalize": (_i, [_vp, _i, C.c_uint, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
+    "ru_unc_finalize": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _sz, _vp]),
+    "ru_unc_histogram": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "ru_unc_score": (_i, [_vp, C.POINTER(_i), _i, _vp, _vp, _vp]),
+    "ru_paste_u8c": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
     "ru_zscore_workspace_bytes": (_sz, [_i, _sz]),
     "ru_zscore_stats": (_i, [_vp, _vp, _i, _sz, _vp, _sz, _vp]),
     "ru_augment_patch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -138,6 +144,10 @@ CRIT_M_D2 = 6
 # ru_label_confusion / ru_overlap_accumulate (include/resunet_hip.h)
 CONF_PROB, CONF_LABEL, OVERLAP_MAX_LABELS = 0, 1, 8
 OVERLAP_MODES = {"itk": 0, "wt": 1, "validate": 2}
+
+# ru_unc_* (include/resunet_hip.h): measures, histogram extents [regions][levels][TP FP FN TN]
+UNC_MEASURES = {"std": 0, "entropy": 1}
+UNC_REGIONS, UNC_LEVELS, UNC_CLASSES = 3, 101, 4
 
 # ru_surface_metrics / ru_surface_accumulate (include/resunet_hip.h)
 SURFACE_PROB, SURFACE_LABEL, SURFACE_REGIONS, SURFACE_COUNTS = 0, 1, 3, 6

@@ -10,7 +10,9 @@ found in the first directory are merged across all of them.
                   threshold, label composition with the ET > 32 rule and 26-connected component rejection (test.py:144-164).
 
 The sums, the division, the threshold / argmax and the post-processing run on the device (csrc/ensemble.hip, csrc/inference.hip) with one
-upload per file and one download per case.  `--host` computes the same with numpy and scipy (`inference.ensemble_mean_host`, no GPU).
+upload per file and one download per case.  With `--rule regions`, `--uncertainty_output DIR [--uncertainty std|entropy]` also writes the
+BraTS uncertainty maps of the saved predictions, taken as members with one copy each (K = 1): uint8 `NAME_unc_whole.npy`, `NAME_unc_core.npy`,
+`NAME_unc_enhance.npy`, values 0 (certain) .. 100 (uncertain) (csrc/uncertainty.hip; `inference.uncertainty_*_host` with `--host`).  `--host` computes the same with numpy and scipy (`inference.ensemble_mean_host`, no GPU).
 NIfTI input is out of scope (no nibabel): predictions are arrays.
 """
 from __future__ import annotations
@@ -27,6 +29,10 @@ parser.add_argument("--predictions", required=True, type=str, nargs="+", help="o
 parser.add_argument("--output", required=True, type=str, help="directory for the merged uint8 label volumes")
 parser.add_argument("--rule", default="class", choices=["class", "regions"])
 parser.add_argument("--host", action="store_true", help="numpy / scipy instead of the device kernels")
+# SUPPRESS: without these flags the namespace does not change
+parser.add_argument("--uncertainty", default=argparse.SUPPRESS, choices=["std", "entropy"], help="uncertainty measure of the maps (default std)")
+parser.add_argument("--uncertainty_output", default=argparse.SUPPRESS, type=str,
+                    help="--rule regions: directory for the uint8 uncertainty maps NAME_unc_whole.npy, NAME_unc_core.npy, NAME_unc_enhance.npy")
 
 CHANNELS = {"class": 4, "regions": 3}
 
@@ -37,9 +43,22 @@ def merge_host(preds, rule):
     return inference.postprocess_labels(inference.compose_labels_host(inference.ensemble_mean_host(preds)))
 
 
-def merge_device(preds, rule):
+def uncertainty_host(preds, measure):
+    mean = inference.ensemble_mean_host(preds)
+    return inference.uncertainty_std_host([[p] for p in preds], mean) if measure == "std" else inference.uncertainty_entropy_host(mean)
+
+
+def merge_device(preds, rule, uncertainty=None):
+    """-> labels, or (labels, uint8 maps [3,D,H,W]) with `uncertainty` (rule "regions")"""
     import torch
     from . import ops
+    if uncertainty is not None:
+        acc, acc2 = None, None
+        for p in preds:
+            acc, acc2 = ops.unc_accumulate(torch.as_tensor(p, dtype=torch.float32).cuda(), acc=acc, acc2=acc2)
+        mask, counts, _, unc = ops.unc_finalize(acc, acc2, len(preds), 1, uncertainty)
+        labels = ops.compose_labels(mask, counts, et_min=32)
+        return ops.cc_reject(labels, 0.1).cpu().numpy(), unc.cpu().numpy()
     acc = None
     for p in preds:                                               # one upload at a time: a prediction is folded in before the next arrives
         acc = ops.ens_accumulate(torch.as_tensor(p, dtype=torch.float32).cuda(), acc=acc)
@@ -52,6 +71,10 @@ def merge_device(preds, rule):
 
 def main(argv=None):
     opt = parser.parse_args(argv)
+    unc_dir = getattr(opt, "uncertainty_output", None)
+    measure = getattr(opt, "uncertainty", "std") if unc_dir else None
+    if unc_dir and opt.rule != "regions":
+        parser.error("--uncertainty_output needs --rule regions: the maps are per region")
     names = sorted(f for f in os.listdir(opt.predictions[0]) if f.endswith(".npy"))
     if not names:
         raise SystemExit("no .npy predictions in %s" % opt.predictions[0])
@@ -66,7 +89,11 @@ def main(argv=None):
             if p.ndim != 4 or p.shape[0] != CHANNELS[opt.rule] or (preds and p.shape != preds[0].shape):
                 raise SystemExit("%s: expected [%d,D,H,W] arrays of one shape for --rule %s, got %s" % (path, CHANNELS[opt.rule], opt.rule, p.shape))
             preds.append(p.astype(np.float32, copy=False))
-        labels = merge_host(preds, opt.rule) if opt.host else merge_device(preds, opt.rule)
+        if measure:
+            labels, maps = (merge_host(preds, opt.rule), uncertainty_host(preds, measure)) if opt.host else merge_device(preds, opt.rule, measure)
+            inference.save_uncertainty(unc_dir, name[:-4], maps)
+        else:
+            labels = merge_host(preds, opt.rule) if opt.host else merge_device(preds, opt.rule)
         np.save(os.path.join(opt.output, name), labels)
         print(name, labels.shape, labels.dtype, len(preds), "models", {int(k): int(v) for k, v in zip(*np.unique(labels, return_counts=True))})
 

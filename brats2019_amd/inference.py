@@ -22,6 +22,8 @@ takes and returns arrays.
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 
@@ -125,9 +127,12 @@ def prepare_case_device(image):
     return batch, lo, size, left, padded
 
 
-def predict_case_device(model, image):
+def predict_case_device(model, image, uncertainty=None):
     """The per-case pipeline of test.py:82-168 with every array on the device: image [4,D,H,W] device tensor -> (uint8 device label volume
-    [D,H,W] with values {0,1,2,4}, int64 device tensor of the (wt, tc, et) voxel counts)."""
+    [D,H,W] with values {0,1,2,4}, int64 device tensor of the (wt, tc, et) voxel counts).  uncertainty="std" | "entropy": the model is
+    served as an ensemble of one and the uint8 [3,D,H,W] uncertainty maps of its four flips are appended."""
+    if uncertainty is not None:
+        return predict_case_ensemble_device([model], image, uncertainty=uncertainty)
     image = image.contiguous().float()
     batch, lo, size, left, _padded = prepare_case_device(image)
     model.eval()
@@ -141,9 +146,12 @@ def predict_case_device(model, image):
     return ops.paste_labels(labels, image.shape[1:], lo), counts
 
 
-def predict_case(model, image):
+def predict_case(model, image, uncertainty=None):
     """Full per-case pipeline of test.py:82-168 for one multimodal volume `image` [4,D,H,W] (numpy or tensor): one upload, the device
-    pipeline above, one download.  Returns (uint8 label volume [D,H,W] with values {0,1,2,4}, (wt, tc, et) voxel counts)."""
+    pipeline above, one download.  Returns (uint8 label volume [D,H,W] with values {0,1,2,4}, (wt, tc, et) voxel counts) and, with
+    uncertainty="std" | "entropy", the uint8 [3,D,H,W] uncertainty maps."""
+    if uncertainty is not None:
+        return predict_case_ensemble([model], image, uncertainty=uncertainty)
     img = torch.as_tensor(np.asarray(image) if not isinstance(image, torch.Tensor) else image, dtype=torch.float32).cuda()
     full, counts = predict_case_device(model, img)
     return full.cpu().numpy(), tuple(int(v) for v in counts.cpu().tolist())
@@ -196,24 +204,105 @@ def compose_labels_host(mean):
     return out
 
 
-def _merge_step(acc, probs, index, count, lo, size, want_mean):
-    """Fold model `index` of `count` into the running sum; the last one is fused with the finalize.  -> (acc, result or None)"""
+def _members_host(outs_list, pad_left=(0, 0, 0), size=None):
+    """The M x K un-flipped float32 members of an ensemble on the un-padded box: outs_list[m] = [K,3,Dp,Hp,Wp] as in `ensemble_merge_host`."""
+    members = []
+    for outs in outs_list:
+        un = [np.flip(np.asarray(o, np.float32), axis=ax) if ax else np.asarray(o, np.float32) for o, ax in zip(outs, TTA_FLIPS)]
+        sz = un[0].shape[1:] if size is None else size
+        members.append([o[:, int(pad_left[0]):int(pad_left[0]) + int(sz[0]), int(pad_left[1]):int(pad_left[1]) + int(sz[1]),
+                          int(pad_left[2]):int(pad_left[2]) + int(sz[2])] for o in un])
+    return members
+
+
+def second_moment_host(members):
+    """T_M of csrc/uncertainty.hip: members[m][k] float32 arrays; per model q_m = ((o0*o0 + o1*o1) + o2*o2) + o3*o3, every product and
+    sum rounded to float32, then T_1 = q_1, T_m = T_(m-1) + q_m in list order."""
+    total = None
+    for copies in members:
+        q = None
+        for o in copies:
+            o = np.asarray(o, np.float32)
+            q = o * o if q is None else q + o * o
+        total = q if total is None else total + q
+    return total
+
+
+def uncertainty_std_host(members, mean=None):
+    """The "std" map: members[m][k] = the M x K un-flipped float32 predictions of one shape, `mean` their float32 ensemble mean (formed as
+    `ensemble_merge_host` forms it when not given).  e2 = T_M / (M*K), var = max(e2 - mean^2, 0) and u = floor(min(200*sqrt(var), 100) +
+    0.5) in float64; uint8 in 0..100."""
+    m, k = len(members), len(members[0])
+    if mean is None:
+        per_model = []
+        for copies in members:
+            acc = np.asarray(copies[0], np.float32)
+            for o in copies[1:]:
+                acc = acc + np.asarray(o, np.float32)
+            per_model.append(acc / np.float32(k))
+        mean = ensemble_mean_host(per_model)
+    e2 = second_moment_host(members).astype(np.float64) / np.float64(m * k)
+    mu = np.asarray(mean, np.float32).astype(np.float64)
+    var = np.maximum(e2 - mu * mu, 0.0)
+    return np.floor(np.minimum(200.0 * np.sqrt(var), 100.0) + 0.5).astype(np.uint8)
+
+
+def uncertainty_entropy_host(mean):
+    """The "entropy" map of the float32 ensemble mean: H = -(mu*log2(mu) + (1-mu)*log2(1-mu)) in float64, a term being 0 unless its
+    argument lies inside (0, 1); u = floor(100*H + 0.5), uint8 in 0..100."""
+    mu = np.asarray(mean, np.float32).astype(np.float64)
+    nu = 1.0 - mu
+
+    def term(a):
+        inside = (a > 0.0) & (a < 1.0)
+        return np.where(inside, a * np.log2(np.where(inside, a, 0.5)), 0.0)
+
+    h = -(term(mu) + term(nu))
+    return np.minimum(np.floor(100.0 * h + 0.5), 100.0).astype(np.uint8)
+
+
+UNCERTAINTY_STEMS = ("whole", "core", "enhance")     # NAME_unc_<stem>: the challenge's file stems of the WT, TC and ET maps
+
+
+def save_uncertainty(directory, name, maps):
+    """The three files of one case, NAME_unc_whole.npy / _core / _enhance: maps uint8 [3,D,H,W] in the order WT, TC, ET."""
+    os.makedirs(directory, exist_ok=True)
+    for stem, m in zip(UNCERTAINTY_STEMS, maps):
+        np.save(os.path.join(directory, "%s_unc_%s.npy" % (name, stem)), np.ascontiguousarray(m, dtype=np.uint8))
+
+
+def _check_uncertainty(uncertainty):
+    if uncertainty not in (None, "std", "entropy"):
+        raise ValueError("uncertainty=%r: None, \"std\" or \"entropy\"" % (uncertainty,))
+    return uncertainty
+
+
+def _merge_step(acc, probs, index, count, lo, size, want_mean, uncertainty=None):
+    """Fold model `index` of `count` into the running sum; the last one is fused with the finalize.  -> (acc, result or None).  With
+    `uncertainty`, acc is the pair (sum, second-moment sum) of csrc/uncertainty.hip and the result gains the uint8 map."""
+    if uncertainty is None:
+        if index + 1 < count:
+            return ops.ens_accumulate(probs, TTA_FLIPS, acc, lo, size), None
+        return acc, ops.ens_accumulate_finalize(probs, TTA_FLIPS, acc, count, lo, size, want_mean=want_mean)
+    s1, s2 = acc if acc is not None else (None, None)
     if index + 1 < count:
-        return ops.ens_accumulate(probs, TTA_FLIPS, acc, lo, size), None
-    return acc, ops.ens_accumulate_finalize(probs, TTA_FLIPS, acc, count, lo, size, want_mean=want_mean)
+        return ops.unc_accumulate(probs, TTA_FLIPS, s1, s2, lo, size), None
+    return acc, ops.unc_accumulate_finalize(probs, TTA_FLIPS, s1, s2, count, uncertainty, lo, size, want_mean=want_mean)
 
 
-def ensemble_merge(probs_list, pad_left, size, want_mean=False):
+def ensemble_merge(probs_list, pad_left, size, want_mean=False, uncertainty=None):
     """The merge of an ensemble alone: probs_list[m] = [4,3,Dp,Hp,Wp] device tensor, the four test-time flips predicted by model m.
     Returns what `ops.tta_merge_box` returns for one model -- (mask uint8 [3,*size], counts int64 [3], mean float32 or None) -- for the
-    float32 mean over the models of their un-flipped, un-padded means."""
+    float32 mean over the models of their un-flipped, un-padded means.  uncertainty="std" | "entropy": the same three, bit for bit, plus
+    the uint8 [3,*size] uncertainty map of the M x 4 members (csrc/uncertainty.hip)."""
+    _check_uncertainty(uncertainty)
     if not len(probs_list):
         raise ValueError("ensemble_merge: empty list")
     if any(tuple(p.shape) != tuple(probs_list[0].shape) for p in probs_list):
         raise ValueError("ensemble_merge: predictions of different shapes: %s" % [tuple(p.shape) for p in probs_list])
     acc, out = None, None
     for i, p in enumerate(probs_list):
-        acc, out = _merge_step(acc, p, i, len(probs_list), pad_left, size, want_mean)
+        acc, out = _merge_step(acc, p, i, len(probs_list), pad_left, size, want_mean, uncertainty)
     return out
 
 
@@ -227,11 +316,14 @@ def _check_ensemble(models):
     return models
 
 
-def predict_case_ensemble_device(models, image, want_probs=False):
+def predict_case_ensemble_device(models, image, want_probs=False, uncertainty=None):
     """`predict_case_device` for a list of models: the case is prepared once, every model runs on the same batch of four flips and its
     prediction enters the running sum before the next forward starts; then labels, component rejection and paste as for one model.
     Returns (labels, counts) and, with want_probs, the float32 [3,D,H,W] mean probabilities pasted into the case's frame (zero outside
-    the crop box).  An ensemble of one is `predict_case_device`."""
+    the crop box).  An ensemble of one is `predict_case_device`.  uncertainty="std" | "entropy" appends the uint8 [3,D,H,W] uncertainty
+    maps (WT, TC, ET; 0 certain .. 100 uncertain, zero outside the crop box) of the models x flips members, made in the same passes; the
+    other results do not change."""
+    _check_uncertainty(uncertainty)
     models = _check_ensemble(models)
     image = image.contiguous().float()
     if int(image.shape[0]) != int(models[0].conv_input.in_channels):
@@ -244,20 +336,22 @@ def predict_case_ensemble_device(models, image, want_probs=False):
             model.freeze_params(True)
         with torch.no_grad():
             probs = model([batch])[0]                                # [4,3,Dp,Hp,Wp]; merged below, released before the next forward
-        acc, out = _merge_step(acc, probs, i, len(models), left, size, want_probs)
+        acc, out = _merge_step(acc, probs, i, len(models), left, size, want_probs, uncertainty)
         del probs
-    mask, counts, mean = out
+    mask, counts, mean = out[:3]
     labels = ops.compose_labels(mask, counts, et_min=32)
     ops.cc_reject(labels, 0.1)
-    full = ops.paste_labels(labels, image.shape[1:], lo)
+    res = (ops.paste_labels(labels, image.shape[1:], lo), counts)
     if want_probs:
-        return full, counts, ops.paste_probs(mean, image.shape[1:], lo)
-    return full, counts
+        res += (ops.paste_probs(mean, image.shape[1:], lo),)
+    if uncertainty is not None:
+        res += (ops.paste_u8c(out[3], image.shape[1:], lo),)
+    return res
 
 
-def predict_case_ensemble(models, image, want_probs=False):
-    """`predict_case` for a list of models (numpy or tensor in, numpy out): one upload, `predict_case_ensemble_device`, one download."""
+def predict_case_ensemble(models, image, want_probs=False, uncertainty=None):
+    """`predict_case` for a list of models (numpy or tensor in, numpy out): one upload, `predict_case_ensemble_device`, one download.
+    Returns (labels, counts), then the mean probabilities with want_probs, then the uncertainty maps with `uncertainty`."""
     img = torch.as_tensor(np.asarray(image) if not isinstance(image, torch.Tensor) else image, dtype=torch.float32).cuda()
-    out = predict_case_ensemble_device(models, img, want_probs=want_probs)
-    res = (out[0].cpu().numpy(), tuple(int(v) for v in out[1].cpu().tolist()))
-    return res + (out[2].cpu().numpy(),) if want_probs else res
+    out = predict_case_ensemble_device(models, img, want_probs=want_probs, uncertainty=uncertainty)
+    return (out[0].cpu().numpy(), tuple(int(v) for v in out[1].cpu().tolist())) + tuple(t.cpu().numpy() for t in out[2:])

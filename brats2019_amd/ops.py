@@ -461,6 +461,108 @@ def paste_probs(mean, full_shape, lo):
     return full
 
 
+def _unc_sums(who, acc, acc2, c, size):
+    for name, t in (("acc", acc), ("acc2", acc2)):
+        if t is not None and (tuple(t.shape) != (c,) + size or t.dtype != torch.float32):
+            raise ValueError("%s: %s %s does not match %d channels of a %s box" % (who, name, tuple(t.shape), c, size))
+
+
+def unc_accumulate(probs, flip_axes=((),), acc=None, acc2=None, lo=None, size=None):
+    """ens_accumulate plus the second-moment sum (csrc/uncertainty.hip), one pass over probs [K,C,D,H,W]: acc takes S_m exactly as
+    ens_accumulate writes it, acc2 [C,*size] takes T_m = T_(m-1) + q_m with q_m = ((o0*o0 + o1*o1) + o2*o2) + o3*o3 of the un-flipped
+    copies, float32 without fma.  acc=None (then acc2 too) starts both sums.  Returns (acc, acc2)."""
+    probs, (k, c, d, h, w), lo, size = _ens_box(probs, lo, size)
+    first = acc is None
+    if first != (acc2 is None):
+        raise ValueError("unc_accumulate: acc and acc2 start together")
+    if first:
+        acc = torch.empty((c,) + size, dtype=torch.float32, device=probs.device)
+        acc2 = torch.empty((c,) + size, dtype=torch.float32, device=probs.device)
+    _unc_sums("unc_accumulate", acc, acc2, c, size)
+    L.check(L.load().ru_unc_accumulate(L.f32(probs), k, _flip_bits(flip_axes), L.f32(acc), L.f32(acc2), int(first), c, d, h, w, _ints(lo), _ints(size),
+                                       L.stream()), "ru_unc_accumulate")
+    return acc, acc2
+
+
+def _unc_measure(measure):
+    if measure not in L.UNC_MEASURES:
+        raise ValueError("uncertainty measure %r: one of %s" % (measure, sorted(L.UNC_MEASURES)))
+    return L.UNC_MEASURES[measure]
+
+
+def unc_accumulate_finalize(probs, flip_axes, acc, acc2, m, measure="std", lo=None, size=None, want_mean=False):
+    """The LAST member's unc_accumulate fused with the finalize: ens_accumulate_finalize's (mask, counts, mean or None), bit for bit, plus
+    the uint8 uncertainty map [C,*size] (0 certain .. 100 uncertain) of `measure` "std" or "entropy".  acc = acc2 = None: an ensemble of
+    one; acc2 may also be None with "entropy"."""
+    probs, (k, c, d, h, w), lo, size = _ens_box(probs, lo, size)
+    kind = _unc_measure(measure)
+    if acc is None and acc2 is not None or acc is not None and acc2 is None and measure == "std":
+        raise ValueError("unc_accumulate_finalize: the std measure needs both running sums")
+    _unc_sums("unc_accumulate_finalize", acc, acc2, c, size)
+    mask, counts, mean = _ens_outputs(c, size, probs.device, want_mean)
+    unc = torch.empty((c,) + size, dtype=torch.uint8, device=probs.device)
+    L.check(L.load().ru_unc_accumulate_finalize(L.f32(probs), k, _flip_bits(flip_axes), L.ptr(acc, True), L.ptr(acc2, True), int(acc is None), int(m), kind,
+                                                L.ptr(mean, True), L.ptr(mask), L.ptr(counts), L.ptr(unc), c, d, h, w, _ints(lo), _ints(size), L.stream()),
+            "ru_unc_accumulate_finalize")
+    return mask, counts, mean, unc
+
+
+def unc_finalize(acc, acc2, m, k=1, measure="std", want_mean=False):
+    """ens_finalize plus the uncertainty map, from the stored sums of `m` members of `k` copies each (saved predictions: k = 1).
+    acc2 may be None with "entropy".  Returns (mask, counts, mean or None, unc uint8)."""
+    if not (acc.is_cuda and acc.is_contiguous() and acc.dtype == torch.float32 and acc.dim() >= 2):
+        raise ValueError("unc_finalize: contiguous float32 device tensor [C, ...]")
+    kind = _unc_measure(measure)
+    c = int(acc.shape[0])
+    if acc2 is None and measure == "std":
+        raise ValueError("unc_finalize: the std measure needs the second-moment sum")
+    _unc_sums("unc_finalize", None, acc2, c, tuple(acc.shape[1:]))
+    mask, counts, mean = _ens_outputs(c, acc.shape[1:], acc.device, want_mean)
+    unc = torch.empty(tuple(acc.shape), dtype=torch.uint8, device=acc.device)
+    L.check(L.load().ru_unc_finalize(L.f32(acc), L.ptr(acc2, True), int(m), int(k), kind, L.ptr(mean, True), L.ptr(mask), L.ptr(counts), L.ptr(unc), c,
+                                     acc.numel() // c, L.stream()), "ru_unc_finalize")
+    return mask, counts, mean, unc
+
+
+def paste_u8c(maps, full_shape, lo):
+    """paste_labels for uint8 channels: [C,*full_shape], zero except the box at `lo`, which holds maps [C,d,h,w]."""
+    if not (maps.is_cuda and maps.is_contiguous() and maps.dtype == torch.uint8 and maps.dim() == 4):
+        raise ValueError("paste_u8c: contiguous uint8 device tensor [C,d,h,w]")
+    c = int(maps.shape[0])
+    full = torch.empty((c,) + tuple(int(v) for v in full_shape), dtype=torch.uint8, device=maps.device)
+    d, h, w = (int(v) for v in full.shape[1:])
+    L.check(L.load().ru_paste_u8c(L.ptr(maps), L.ptr(full), c, d, h, w, _ints(lo), _ints(maps.shape[1:]), L.stream()), "ru_paste_u8c")
+    return full
+
+
+def unc_histogram(pred, target, unc):
+    """One pass over a case for the uncertainty score: pred, target uint8 label volumes [D,H,W] with values {0,1,2,3,4}, unc uint8
+    [3,D,H,W] -> (hist int64 [3,101,4]: exact voxel counts per region (WT, TC, ET), map value and class (TP, FP, FN, TN); invalid int64
+    [1]: voxels with a label outside 0..4 or a map value above 100, which are in no bin)."""
+    for name, t in (("pred", pred), ("target", target), ("unc", unc)):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.uint8):
+            raise ValueError("unc_histogram: %s must be a contiguous uint8 device tensor" % name)
+    if pred.dim() != 3 or tuple(target.shape) != tuple(pred.shape) or tuple(unc.shape) != (L.UNC_REGIONS,) + tuple(pred.shape):
+        raise ValueError("unc_histogram: shapes %s / %s / %s, expected [D,H,W], [D,H,W], [3,D,H,W]" % (tuple(pred.shape), tuple(target.shape), tuple(unc.shape)))
+    d, h, w = (int(v) for v in pred.shape)
+    hist = torch.empty((L.UNC_REGIONS, L.UNC_LEVELS, L.UNC_CLASSES), dtype=torch.int64, device=pred.device)
+    invalid = torch.empty(1, dtype=torch.int64, device=pred.device)
+    L.check(L.load().ru_unc_histogram(L.ptr(pred), L.ptr(target), L.ptr(unc), d, h, w, L.ptr(hist), L.ptr(invalid), L.stream()), "ru_unc_histogram")
+    return hist, invalid
+
+
+def unc_score(hist, thresholds=(25, 50, 75, 100), acc=None, out=None):
+    """The BraTS uncertainty score from unc_histogram's counts, one launch: float64 [3,4] = per region (score, AUC_Dice, AUC_FTP, AUC_FTN)
+    over the strictly rising integer `thresholds` (include/resunet_hip.h, ru_unc_score); acc (float64 [3,4] or None) += the result."""
+    assert hist.dtype == torch.int64 and hist.is_contiguous() and tuple(hist.shape) == (L.UNC_REGIONS, L.UNC_LEVELS, L.UNC_CLASSES)
+    assert acc is None or (acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() == L.UNC_REGIONS * 4)
+    if out is None:
+        out = torch.empty((L.UNC_REGIONS, 4), dtype=torch.float64, device=hist.device)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == L.UNC_REGIONS * 4
+    L.check(L.load().ru_unc_score(L.ptr(hist), _ints(thresholds), len(thresholds), L.ptr(out), L.ptr(acc, True), L.stream()), "ru_unc_score")
+    return out
+
+
 def dice_counts(pred, target):
     """metrics.Dice.update counting step (metrics.py:116-127): int64 device tensor [N,C,2] = (#(p>.5 & g>.5), #(p>.5) + #(g>.5))."""
     pred, target = _prep(pred), _prep(target)

@@ -8,6 +8,10 @@ loader_helper.read_multimodal does) and the result a uint8 `.npy` label volume {
 `--ensemble B C ...` adds the best checkpoints of further experiments under the same `--models_path`: every case is segmented by the
 mean of all models' probabilities (`inference.predict_case_ensemble`).  `--probs_output DIR` also saves that mean -- the soft labels a
 student network is distilled from -- as float32 `NAME.npy` [3,D,H,W].
+
+`--uncertainty std|entropy --uncertainty_output DIR` also writes the BraTS uncertainty task's three maps per case, uint8 [D,H,W] with
+values 0 (certain) .. 100 (uncertain): `NAME_unc_whole.npy`, `NAME_unc_core.npy`, `NAME_unc_enhance.npy`, made from the models x flips
+predictions in the passes that merge them (`inference.predict_case_ensemble(..., uncertainty=...)`, csrc/uncertainty.hip).
 """
 from __future__ import annotations
 
@@ -27,6 +31,10 @@ parser.add_argument("--output", default=None, type=str, help="output .npy (singl
 parser.add_argument("--precision", default="bf16x3", choices=["bf16x3", "f32"])
 parser.add_argument("--ensemble", default=None, type=str, nargs="+", help="further experiment names under --models_path: segment with the mean of all models")
 parser.add_argument("--probs_output", default=None, type=str, help="directory for the mean region probabilities (soft labels), float32 NAME.npy [3,D,H,W]")
+# SUPPRESS: without these flags the namespace -- and so the printed output -- does not change
+parser.add_argument("--uncertainty", default=argparse.SUPPRESS, choices=["std", "entropy"], help="uncertainty measure of the maps (with --uncertainty_output)")
+parser.add_argument("--uncertainty_output", default=argparse.SUPPRESS, type=str,
+                    help="directory for the uint8 uncertainty maps NAME_unc_whole.npy, NAME_unc_core.npy, NAME_unc_enhance.npy")
 
 
 def _load_net(name, opt):
@@ -41,6 +49,9 @@ def _load_net(name, opt):
 
 def main(argv=None):
     opt = parser.parse_args(argv)
+    measure, unc_dir = getattr(opt, "uncertainty", None), getattr(opt, "uncertainty_output", None)
+    if (measure is None) != (unc_dir is None):
+        parser.error("--uncertainty and --uncertainty_output go together")
     print(torch.__version__)
     print(opt)
     net = _load_net(opt.name, opt)
@@ -54,12 +65,14 @@ def main(argv=None):
     else:
         cases = [(os.path.splitext(os.path.basename(c))[0], np.load(c)) for c in cases]
     for name, image in cases:
-        if others or opt.probs_output:
-            out = inference.predict_case_ensemble([net] + others, image, want_probs=bool(opt.probs_output))
+        if others or opt.probs_output or measure:
+            out = inference.predict_case_ensemble([net] + others, image, want_probs=bool(opt.probs_output), uncertainty=measure)
             labels, (wt, tc, et) = out[0], out[1]
             if opt.probs_output:
                 os.makedirs(opt.probs_output, exist_ok=True)
                 np.save(os.path.join(opt.probs_output, name + ".npy"), out[2])
+            if measure:
+                inference.save_uncertainty(unc_dir, name, out[-1])
         else:
             labels, (wt, tc, et) = inference.predict_case(net, image)
         if opt.output:

@@ -10,6 +10,14 @@ ru_overlap_accumulate), the ratio of the float32-rounded counts in float32 (NaN 
 
 `--regions` scores the BraTS challenge's way instead: per case the Dice, sensitivity, specificity and HD95 of the regions WT = {1,2,3,4},
 TC = {1,3,4} and ET = {3,4} (3 counts as 4), from one pass sequence of ru_surface_metrics per case (metrics.Hausdorff95 states HD95).
+
+`--uncertainty_path DIR [--thresholds 25 50 75 100]` scores the BraTS uncertainty task instead: DIR holds `<case>_unc_whole.npy`,
+`<case>_unc_core.npy`, `<case>_unc_enhance.npy` (uint8 [D,H,W], 0 certain .. 100 uncertain) as `python -m brats2019_amd.test
+--uncertainty_output DIR` writes them.  At a threshold t the voxels with a map value above t are filtered out and TP, FP, FN, TN of the
+region are counted on the rest: Dice_t = 2TP/(2TP+FP+FN) (1 for an empty denominator), FTP_t = (TP_100 - TP_t)/TP_100 (0 for TP_100 = 0),
+FTN_t likewise; the AUCs are trapezoid sums over the thresholds divided by their span, score = (AUC_Dice + (1 - AUC_FTP) + (1 - AUC_FTN)) / 3.
+One histogram pass and one small launch per case (ru_unc_histogram, ru_unc_score).  Neither the default thresholds nor the
+empty-denominator values have been checked against the challenge's own evaluator.
 """
 from __future__ import annotations
 
@@ -27,6 +35,12 @@ parser.add_argument("--predictions_path", default="", type=str, help="directory 
 # SUPPRESS: without the flag the namespace -- and so the printed output -- is the plain scorer's
 parser.add_argument("--regions", action="store_true", default=argparse.SUPPRESS,
                     help="score Dice, sensitivity, specificity and HD95 of the regions WT, TC, ET")
+parser.add_argument("--uncertainty_path", default=argparse.SUPPRESS, type=str,
+                    help="directory of <case>_unc_whole.npy, _unc_core.npy, _unc_enhance.npy: score the uncertainty maps")
+parser.add_argument("--thresholds", default=argparse.SUPPRESS, type=int, nargs="+", help="uncertainty thresholds, rising, inside 0..100 (default 25 50 75 100)")
+
+UNCERTAINTY_THRESHOLDS = (25, 50, 75, 100)
+UNCERTAINTY_COLUMNS = ("score", "AUC_Dice", "AUC_FTP", "AUC_FTN")
 
 REGION_NAMES = ("WT", "TC", "ET")
 REGION_METRICS = ("Dice", "Sens", "Spec", "HD95")
@@ -91,17 +105,76 @@ def score_regions(cases):
     return names, results, results.mean(axis=0)
 
 
+def score_uncertainty(cases, thresholds=UNCERTAINTY_THRESHOLDS):
+    """cases: iterable of (name, ground-truth labels [D,H,W], predicted labels [D,H,W], uncertainty maps uint8 [3,D,H,W] in the order WT,
+    TC, ET), read one at a time.  -> (names, results float64 [cases, 3, 4], mean float64 [3, 4]): rows WT, TC, ET; columns score,
+    AUC_Dice, AUC_FTP, AUC_FTN over the rising integer `thresholds`.  The values stay on the device until the end: one host copy for
+    all cases."""
+    thresholds = [int(t) for t in thresholds]
+    if not thresholds or thresholds[0] < 0 or thresholds[-1] > 100 or any(b <= a for a, b in zip(thresholds, thresholds[1:])):
+        raise ValueError("validate: the thresholds must rise strictly inside 0..100, got %s" % (thresholds,))
+    names, rows, total = [], [], None
+    for name, label, predict, maps in cases:
+        if np.ndim(label) != 3 or tuple(predict.shape) != tuple(label.shape) or tuple(np.shape(maps)) != (3,) + tuple(label.shape):
+            raise ValueError("%s: label shape %s, prediction shape %s and uncertainty shape %s must be [D,H,W], [D,H,W], [3,D,H,W]"
+                             % (name, tuple(label.shape), tuple(predict.shape), tuple(np.shape(maps))))
+        maps = np.ascontiguousarray(maps)
+        if maps.dtype != np.uint8:
+            # the kernel counts values above 100 of a uint8 map; a wider type is checked here, before the cast could hide them
+            if maps.size and (maps.min() < 0 or maps.max() > 100 or not np.array_equal(maps, np.round(maps))):
+                raise ValueError("%s: uncertainty values outside the integers 0..100" % name)
+            maps = maps.astype(np.uint8)
+        g, p = _upload(label, name + " (labels)"), _upload(predict, name + " (prediction)")
+        if total is None:
+            total = torch.zeros((3, 4), dtype=torch.float64, device="cuda")
+        hist, inv = ops.unc_histogram(p, g, torch.from_numpy(maps).cuda())
+        row = torch.empty(13, dtype=torch.float64, device="cuda")
+        ops.unc_score(hist, thresholds, acc=total, out=row[:12])
+        row[12:] = inv
+        names.append(name)
+        rows.append(row)
+    if not names:
+        raise ValueError("validate: no cases")
+    rows.append(torch.cat([total.reshape(-1), total.new_zeros(1)]))                   # the sums travel with the rows: one copy
+    host = torch.stack(rows).cpu().numpy()
+    bad = host[:-1, 12]
+    if bad.any():
+        k = int(np.argmax(bad > 0))
+        raise ValueError("%s: labels outside {0,1,2,3,4} or uncertainty values above 100 in %d voxels" % (names[k], int(bad[k])))
+    return names, np.ascontiguousarray(host[:-1, :12].reshape(len(names), 3, 4)), host[-1, :12].reshape(3, 4) / len(names)
+
+
+def _uncertainty_row(r):
+    return "  ".join("%s %s" % (n, " ".join("%s %.4f" % (k, v) for k, v in zip(UNCERTAINTY_COLUMNS, row))) for n, row in zip(REGION_NAMES, r))
+
+
+def _uncertainty_cases(opt, series):
+    from .inference import UNCERTAINTY_STEMS
+    for f in series:
+        maps = [np.load(os.path.join(opt.uncertainty_path, "%s_unc_%s.npy" % (f, stem))) for stem in UNCERTAINTY_STEMS]
+        if any(m.shape != maps[0].shape for m in maps):
+            raise ValueError("%s: the three uncertainty maps have different shapes %s" % (f, [m.shape for m in maps]))
+        yield f, np.load(os.path.join(opt.data_path, f + ".npy")), np.load(os.path.join(opt.predictions_path, f + ".npy")), np.stack(maps)
+
+
 def _region_row(r):
     return "  ".join("%s %s" % (m, " ".join("%s %.4f" % (k, v) for k, v in zip(REGION_NAMES, row))) for m, row in zip(REGION_METRICS, r))
 
 
 def main(argv=None):
     """-> (per-case results float64 [cases, 4] = [d1, d2, d3, dWT], their mean).  With --regions: (results float64 [cases, 4, 3], their
-    mean [4, 3]), rows Dice, sensitivity, specificity, HD95 and columns WT, TC, ET."""
+    mean [4, 3]), rows Dice, sensitivity, specificity, HD95 and columns WT, TC, ET.  With --uncertainty_path: (results float64 [cases, 3, 4],
+    their mean [3, 4]), rows WT, TC, ET and columns score, AUC_Dice, AUC_FTP, AUC_FTN."""
     opt = parser.parse_args(argv)
     print(torch.__version__)
     print(opt)
     series = sorted(f[:-4] for f in os.listdir(opt.data_path) if f.endswith(".npy") and os.path.isfile(os.path.join(opt.data_path, f)))
+    if getattr(opt, "uncertainty_path", None):
+        series, results, mean = score_uncertainty(_uncertainty_cases(opt, series), getattr(opt, "thresholds", UNCERTAINTY_THRESHOLDS))
+        for f, r in zip(series, results):
+            print(f, _uncertainty_row(r))
+        print("mean", _uncertainty_row(mean))
+        return results, mean
     cases = ((f, np.load(os.path.join(opt.data_path, f + ".npy")), np.load(os.path.join(opt.predictions_path, f + ".npy"))) for f in series)
     if getattr(opt, "regions", False):
         series, results, mean = score_regions(cases)

@@ -386,6 +386,47 @@ int ru_ens_accumulate_finalize(const float* probs, int K, unsigned flips, const 
 int ru_ens_argmax(const float* acc, int M, unsigned char* labels, int C, size_t V, ru_stream_t stream);
 int ru_paste_probs(const float* mean, float* full, int C, int D, int H, int W, const int* lo, const int* size, ru_stream_t stream);
 
+/* ---------------------------------------------------------------- uncertainty maps and the BraTS uncertainty score (csrc/uncertainty.hip)
+ * BraTS 2019's third task: per case three uint8 maps (WT, TC, ET; 0 = certain .. 100 = uncertain) beside the label map.  The samples are
+ * the M x K un-flipped predictions o[m][k] an ensemble forms anyway, on the box [lo, lo + size); `mean` is ru_ens_*'s float32 mean.
+ *   second moment, float32, every product and sum rounded (no fma):  q_m = ((o0*o0 + o1*o1) + o2*o2) + o3*o3;  T_1 = q_1, T_m = T_(m-1) + q_m
+ *   RU_UNC_STD      e2 = (double)T_M / (double)(M*K), mu = (double)mean, var = max(e2 - mu*mu, 0), u = floor(min(200*sqrt(var), 100) + 0.5):
+ *                   IEEE + - * / sqrt only, no contraction -- equal to numpy exactly
+ *   RU_UNC_ENTROPY  H = -(mu*log2(mu) + (1-mu)*log2(1-mu)), a term is 0 unless its argument lies inside (0, 1); u = floor(100*H + 0.5)
+ *                   (the device's log2 may differ from numpy's in the last place)
+ * ru_unc_accumulate: ru_ens_accumulate plus acc2 [C][size] <- T_m in the same pass over probs; acc is bit-identical to ru_ens_accumulate's.
+ *   first != 0: both buffers are written, not read (no memset).
+ * ru_unc_accumulate_finalize: the LAST model's accumulate and the finalize in one pass, as ru_ens_accumulate_finalize (same mean_out, mask,
+ *   counts, bit for bit), plus unc [C][size] uint8.  acc / acc2 are read, not written; both may be NULL when first != 0, acc2 also with
+ *   RU_UNC_ENTROPY.
+ * ru_unc_finalize: the same from stored sums of M members-of-K (saved predictions: K = 1); acc2 may be NULL with RU_UNC_ENTROPY.
+ * ru_unc_histogram: pred, target = uint8 label volumes [D][H][W] with values {0,1,2,3,4}, unc = uint8 [3][D][H][W] -> hist [3][101][4] =
+ *   exact voxel counts per region (WT = {1,2,3,4}, TC = {1,3,4}, ET = {3,4}), map value and class {RU_UNC_TP, _FP, _FN, _TN}; invalid[0] = voxels
+ *   with a label outside 0..4 or a map value above 100 (they are in no bin).  Both outputs are written, not accumulated.
+ * ru_unc_score: from hist and T strictly rising thresholds (HOST array, values 0..100, T <= 101), filtering out the voxels whose map value
+ *   exceeds the threshold t:  Dice_t = 2TP/(2TP+FP+FN) (1 for an empty denominator), FTP_t = (TP_100 - TP_t)/TP_100 (0 for TP_100 = 0), FTN_t
+ *   likewise; AUC = trapezoid rule / (t_last - t_first) (T = 1: the curve's value); out [3][4] = {score = (AUC_Dice + (1 - AUC_FTP) +
+ *   (1 - AUC_FTN)) / 3, AUC_Dice, AUC_FTP, AUC_FTN} in float64; acc [3][4] (may be NULL) += out: the running sum over the cases.  Neither
+ *   the empty-denominator values nor any threshold list have been checked against the challenge's evaluator.
+ * ru_paste_u8c: ru_paste_labels for C channels: full [C][D][H][W] = 0 outside the box, src [C][size] inside. */
+#define RU_UNC_STD 0
+#define RU_UNC_ENTROPY 1
+#define RU_UNC_TP 0
+#define RU_UNC_FP 1
+#define RU_UNC_FN 2
+#define RU_UNC_TN 3
+int ru_unc_accumulate(const float* probs, int K, unsigned flips, float* acc, float* acc2, int first, int C, int D, int H, int W, const int* lo,
+                      const int* size, ru_stream_t stream);
+int ru_unc_accumulate_finalize(const float* probs, int K, unsigned flips, const float* acc, const float* acc2, int first, int M, int measure,
+                               float* mean_out, unsigned char* mask, unsigned long long* counts, unsigned char* unc, int C, int D, int H, int W,
+                               const int* lo, const int* size, ru_stream_t stream);
+int ru_unc_finalize(const float* acc, const float* acc2, int M, int K, int measure, float* mean_out, unsigned char* mask, unsigned long long* counts,
+                    unsigned char* unc, int C, size_t Vbox, ru_stream_t stream);
+int ru_unc_histogram(const unsigned char* pred, const unsigned char* target, const unsigned char* unc, int D, int H, int W, unsigned long long* hist,
+                     unsigned long long* invalid, ru_stream_t stream);
+int ru_unc_score(const unsigned long long* hist, const int* thresholds, int T, double* out, double* acc, ru_stream_t stream);
+int ru_paste_u8c(const unsigned char* src, unsigned char* full, int C, int D, int H, int W, const int* lo, const int* size, ru_stream_t stream);
+
 /* ---------------------------------------------------------------- voxel-major working layout ("C16")
  * Between the first and the last convolution the split-bf16 engine keeps activations as [N][C/16][D][H][W][16]
  * (16 channels of a voxel contiguous; C % 16 == 0): a halo tile of a 3x3x3 convolution is then a few long contiguous
