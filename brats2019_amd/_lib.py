@@ -97,6 +97,9 @@ SIGNATURES = {
     "ru_surface_workspace_bytes": (_sz, [_i] * 6),
     "ru_surface_metrics": (_i, [_vp, _vp] + [_i] * 6 + [_d, _vp, _vp, _vp, _sz, _vp]),
     "ru_surface_accumulate": (_i, [_vp, _vp] + [_i] * 4 + [_vp]),
+    "ru_lesion_workspace_bytes": (_sz, [_i] * 7),
+    "ru_lesion_metrics": (_i, [_vp, _vp] + [_i] * 7 + [C.c_longlong, _d, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "ru_lesion_accumulate": (_i, [_vp, _vp] + [_i] * 4 + [_vp]),
     "ru_tile_gather": (_i, [_vp, _vp] + [_i] * 6 + [C.POINTER(_i), _i, _i, _i, _vp]),
     "ru_tile_scatter": (_i, [_vp, _vp] + [_i] * 6 + [C.POINTER(_i), _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
     "ru_case_bbox": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
@@ -152,6 +155,10 @@ UNC_REGIONS, UNC_LEVELS, UNC_CLASSES = 3, 101, 4
 # ru_surface_metrics / ru_surface_accumulate (include/resunet_hip.h)
 SURFACE_PROB, SURFACE_LABEL, SURFACE_REGIONS, SURFACE_COUNTS = 0, 1, 3, 6
 SURFACE_COLUMNS = {"dice": 0, "sensitivity": 1, "specificity": 2, "hd95": 3}
+
+# ru_lesion_metrics / ru_lesion_accumulate (include/resunet_hip.h)
+LESION_COUNTS, LESION_TABLE_COLUMNS, LESION_CHUNK = 6, 5, 8
+LESION_COLUMNS = {"dice": 0, "hd95": 1}
 
 
 class CritTerm(C.Structure):

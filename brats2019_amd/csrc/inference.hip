@@ -14,6 +14,7 @@
 // float64 sums in a fixed two-stage order.
 #include "ru_common.h"
 #include "pw_helpers.hpp"
+#include "cc_unionfind.hpp"
 
 #include <limits.h>
 
@@ -200,22 +201,7 @@ __global__ __launch_bounds__(256) void tta_merge_box_kernel(const float* __restr
 // their component (atomicMin), then every voxel is pointed at its root and the roots count their members.  The reference numbers its
 // components differently (skimage.morphology.label), but only component SIZES enter test.py:51-62, so the result is identical:
 // a foreground voxel survives iff size(component) >= ratio * (V - max(size of any label, background included)).
-__device__ __forceinline__ int cc_find(const int* parent, int i) {
-    int p = __hip_atomic_load(parent + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // L2-served: other CUs' links are seen
-    while (p != i) { i = p; p = __hip_atomic_load(parent + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }      // parents only ever decrease: terminates
-    return i;
-}
-__device__ __forceinline__ void cc_unite(int* parent, int a, int b) {
-    for (;;) {
-        a = cc_find(parent, a);
-        b = cc_find(parent, b);
-        if (a == b) return;
-        if (a > b) { const int t = a; a = b; b = t; }     // a < b: hang b under a
-        const int old = atomicMin(parent + b, a);
-        if (old == b) return;                             // b was still a root: linked
-        b = old;                                          // somebody re-parented b meanwhile: continue from there (the atomic's value is never stale)
-    }
-}
+// cc_find / cc_unite / cc_earlier: cc_unionfind.hpp (shared with lesion.hip)
 // Three passes instead of one (round 5: the plain form -- every voxel united with its 13 earlier neighbours through uncompressed trees -- took 18 ms on the
 // 4-million-voxel noise prediction of a random-init network, bench.py's predict_case):
 //   init     : a foreground voxel points at the SMALLEST of its earlier foreground neighbours (itself if none): plain reads of the label volume, no
@@ -223,7 +209,6 @@ __device__ __forceinline__ void cc_unite(int* parent, int a, int b) {
 //   compress : every voxel points at the root of its tree (stale parents read on the way are still ancestors: the pass is race-tolerant);
 //   merge    : the remaining equivalences -- a voxel and an earlier neighbour whose trees still differ -- by cc_unite on one- or two-hop paths;
 //   compress : again, so that counting and the rejection pass find their root in one hop.
-__device__ __forceinline__ bool cc_earlier(int dz, int dy, int dx) { return dz < 0 || (dz == 0 && (dy < 0 || (dy == 0 && dx < 0))); }
 __global__ __launch_bounds__(256) void cc_init_kernel(const unsigned char* __restrict__ labels, int* __restrict__ parent, int* __restrict__ count, int D, int H, int W) {
     const size_t V = (size_t)D * H * W;
     for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < V; v += (size_t)gridDim.x * 256) {

@@ -21,6 +21,7 @@
 // sf_accumulate_kernel (a call of its own) adds the batch mean of one of the four columns to a float64 device accumulator.
 // Squared distances stay exact integers: the largest is 3 * 511^2 < 2^20; the "no site" sentinel 2^30 plus any (i - j)^2 stays below 2^31.
 #include "ru_common.h"
+#include "surface_packed.hpp"
 
 namespace ru {
 namespace {
@@ -337,7 +338,40 @@ size_t sf_workspace_bytes(int kind, int N, int C, int D, int H, int W) {
     return nk * (4 * s.words * sizeof(u64) + 2 * s.V * sizeof(unsigned) + s.bins * sizeof(unsigned));
 }
 
+// the passes after the masks are packed and the counts and histograms cleared
+int sf_passes(const SfGeom& s, int NK, u64* bits, unsigned* f, unsigned* hist, u64* counts, double empty_value, double* values, hipStream_t st) {
+    hipLaunchKernelGGL(sf_surface_w_kernel, dim3(s.D, NK), dim3(256), 0, st, s, bits, f, counts);
+    RU_CHECK_LAUNCH("sf_surface_w_kernel");
+    hipLaunchKernelGGL(sf_pass_line_kernel<false>, dim3(cdiv(s.W, SF_TW), s.D, NK * 2), dim3(SF_LINE_THREADS), (size_t)s.H * SF_TW * sizeof(unsigned), st,
+                       f, s, bits, hist);
+    RU_CHECK_LAUNCH("sf_pass_line_kernel<H>");
+    hipLaunchKernelGGL(sf_pass_line_kernel<true>, dim3(cdiv(s.W, SF_TW), s.H, NK * 2), dim3(SF_LINE_THREADS), (size_t)s.D * SF_TW * sizeof(unsigned), st,
+                       f, s, bits, hist);
+    RU_CHECK_LAUNCH("sf_pass_line_kernel<D>");
+    hipLaunchKernelGGL(sf_select_kernel, dim3(NK), dim3(SF_SELECT_THREADS), 0, st, hist, s, counts, empty_value, values);
+    RU_CHECK_LAUNCH("sf_select_kernel");
+    return RU_OK;
+}
+
 }  // namespace
+
+size_t sf_packed_workspace_bytes(int items, int D, int H, int W) { return sf_workspace_bytes(RU_SURFACE_PROB, 1, items, D, H, W); }
+
+unsigned long long* sf_packed_bits(void* ws) { return (u64*)ws; }
+
+int sf_packed_run(int items, int D, int H, int W, void* ws, unsigned long long* counts, double empty_value, double* values, hipStream_t st) {
+    RU_REQUIRE(ws && counts && values && items > 0 && (long long)items * 2 <= 65535 && sf_shape_ok(RU_SURFACE_PROB, 1, items, D, H, W),
+               "sf_packed_run: bad argument");
+    const SfGeom s = sf_geom(D, H, W);
+    u64* bits = (u64*)ws;
+    unsigned* f = (unsigned*)(bits + (size_t)items * 4 * s.words);
+    unsigned* hist = f + (size_t)items * 2 * s.V;
+    const size_t nhist = (size_t)items * s.bins;
+    hipLaunchKernelGGL(sf_zero_kernel, dim3((unsigned)std::min<size_t>(1024, (nhist + 255) / 256)), dim3(256), 0, st, counts, (size_t)0, hist, nhist);
+    RU_CHECK_LAUNCH("sf_zero_kernel");
+    return sf_passes(s, items, bits, f, hist, counts, empty_value, values, st);
+}
+
 }  // namespace ru
 
 using namespace ru;
@@ -368,17 +402,7 @@ extern "C" int ru_surface_metrics(const void* pred, const void* target, int kind
     else
         hipLaunchKernelGGL(sf_pack_kernel<1>, dim3(D, NK), dim3(256), 0, st, pred, target, C, K, s, bits, counts);
     RU_CHECK_LAUNCH("sf_pack_kernel");
-    hipLaunchKernelGGL(sf_surface_w_kernel, dim3(D, NK), dim3(256), 0, st, s, bits, f, counts);
-    RU_CHECK_LAUNCH("sf_surface_w_kernel");
-    hipLaunchKernelGGL(sf_pass_line_kernel<false>, dim3(cdiv(W, SF_TW), D, NK * 2), dim3(SF_LINE_THREADS), (size_t)H * SF_TW * sizeof(unsigned), st,
-                       f, s, bits, hist);
-    RU_CHECK_LAUNCH("sf_pass_line_kernel<H>");
-    hipLaunchKernelGGL(sf_pass_line_kernel<true>, dim3(cdiv(W, SF_TW), H, NK * 2), dim3(SF_LINE_THREADS), (size_t)D * SF_TW * sizeof(unsigned), st,
-                       f, s, bits, hist);
-    RU_CHECK_LAUNCH("sf_pass_line_kernel<D>");
-    hipLaunchKernelGGL(sf_select_kernel, dim3(NK), dim3(SF_SELECT_THREADS), 0, st, hist, s, counts, empty_value, values);
-    RU_CHECK_LAUNCH("sf_select_kernel");
-    return RU_OK;
+    return sf_passes(s, NK, bits, f, hist, counts, empty_value, values, st);
 }
 
 extern "C" int ru_surface_accumulate(const double* values, double* acc, int N, int K, int nacc, int column, ru_stream_t stream) {

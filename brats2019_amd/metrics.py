@@ -14,7 +14,8 @@ ru_dice1d_accumulate, ru_rmse_accumulate).
 
 Beyond the reference: the BraTS challenge's `Hausdorff95`, `Sensitivity` and `Specificity`, per channel on the `> 0.5` masks, from one
 pass sequence on the device (ru_surface_metrics: bit-packed masks and surfaces, an exact squared distance transform that fills a
-histogram of surface distances, an exact order statistic) and its accumulate launch (ru_surface_accumulate)."""
+histogram of surface distances, an exact order statistic) and its accumulate launch (ru_surface_accumulate); and the challenge's
+lesion-wise ranking numbers `LesionWiseDice` and `LesionWiseHausdorff95` (ru_lesion_metrics, ru_lesion_accumulate)."""
 from __future__ import annotations
 
 import numpy as np
@@ -344,6 +345,55 @@ class Specificity(_SurfaceMetric):
 
     def __init__(self, name="Specificity", input_index=0, target_index=0, classes=4):
         super(Specificity, self).__init__(name, input_index, target_index, classes)
+
+
+class _LesionMetric(Metrics):
+    """Per sample and channel i < classes-1 one column of ops.lesion_metrics on `pred > 0.5` and `gr > 0.5`; update() adds the batch mean
+    to the float64 device accumulator.  get(): float64 array [classes-1]."""
+    column = None
+
+    def __init__(self, name, input_index, target_index, classes, empty_value, dilation, min_volume):
+        super(_LesionMetric, self).__init__(name)
+        self.input_index = input_index
+        self.target_index = target_index
+        self.classes = classes
+        self.empty_value = empty_value
+        self.dilation = dilation
+        self.min_volume = min_volume
+
+    def update(self, ground, predict):
+        pred = predict[self.input_index].detach()
+        gr = ground[self.target_index].detach()
+        assert gr.shape == pred.shape
+        nacc = self.classes - 1
+        if nacc < 1 or nacc > int(pred.shape[1]) or nacc > 64:
+            raise IndexError("%s: classes=%d needs 1 <= classes-1 <= %d channels" % (self.name, self.classes, min(int(pred.shape[1]), 64)))
+        summary = ops.lesion_metrics(pred.cuda(), gr.cuda(), self.dilation, self.min_volume, self.empty_value)[0]      # [N,C,2] float64, on the device
+        ops.lesion_accumulate(summary, _acc(self, nacc, summary.device), nacc, self.column)
+        self.samples += 1
+
+    def get(self):
+        return _get_array(self)
+
+
+class LesionWiseDice(_LesionMetric):
+    """The BraTS challenge's lesion-wise Dice (its ranking number since 2023): the ground-truth lesions are the 26-connected components of
+    the mask dilated `dilation` times (18-neighbour structure), each is scored against the union of the predicted components that meet
+    its dilated component, every predicted component that meets none counts as a lesion of Dice 0, and lesions of at most `min_volume`
+    voxels are not scored (include/resunet_hip.h, ru_lesion_metrics).  NOT checked against the official evaluator."""
+    column = "dice"
+
+    def __init__(self, name="LesionWiseDice", input_index=0, target_index=0, classes=4, empty_value=ops.HD95_EMPTY, dilation=3, min_volume=50):
+        super(LesionWiseDice, self).__init__(name, input_index, target_index, classes, empty_value, dilation, min_volume)
+
+
+class LesionWiseHausdorff95(_LesionMetric):
+    """The lesion-wise HD95 of the same matching: Hausdorff95's value per lesion, `empty_value` for a missed lesion and for every false
+    positive component.  NOT checked against the official evaluator (its penalty is a constant near 374)."""
+    column = "hd95"
+
+    def __init__(self, name="LesionWiseHausdorff95", input_index=0, target_index=0, classes=4, empty_value=ops.HD95_EMPTY, dilation=3, min_volume=50):
+        super(LesionWiseHausdorff95, self).__init__(name, input_index, target_index, classes, empty_value, dilation, min_volume)
 
 
 def print_metrics(writer, metric, prefix, epoch):

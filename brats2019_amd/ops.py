@@ -729,6 +729,52 @@ def surface_accumulate(values, acc, nacc, column):
     return acc
 
 
+LESION_MAX = 1024                       # default capacity of the per-lesion arrays (ground-truth lesions per sample and region)
+
+
+def lesion_metrics(pred, target, dilation=3, min_volume=50, empty_value=HD95_EMPTY, want_table=False, max_lesions=LESION_MAX):
+    """Lesion-wise Dice and HD95 per sample and region on the device (include/resunet_hip.h, ru_lesion_metrics, states the definition):
+    -> (summary float64 [N, K, 2] = (LesionDice, LesionHD95), counts int64 [N, K, 6] = (n_gt, n_kept, n_tp, n_fn, n_fp, invalid)), and
+    with want_table a third tensor float64 [N, K, max_lesions, 5] = (vol_i, |M_i|, tp_i, Dice_i, HD95_i), rows from n_gt on zero.
+    Inputs as for surface_metrics: float32 [N, C, D, H, W] (masks `> 0.5`, K = C) or uint8 label volumes [N, D, H, W] (K = 3 regions WT,
+    TC, ET).  Ground-truth lesions are the 26-connected components of the mask dilated `dilation` times by the 18-neighbour structure;
+    those of at most `min_volume` voxels are not scored.  More than `max_lesions` lesions in one (sample, region) raises RuntimeError.
+    The call synchronises once (the lesion counts size the HD95 batches)."""
+    if tuple(pred.shape) != tuple(target.shape) or pred.dtype != target.dtype:
+        raise ValueError("lesion_metrics: shapes or dtypes differ: %s %s / %s %s" % (tuple(pred.shape), pred.dtype, tuple(target.shape), target.dtype))
+    if int(dilation) < 0 or int(min_volume) < 0 or int(max_lesions) < 1:
+        raise ValueError("lesion_metrics: dilation %s and min_volume %s must be >= 0, max_lesions %s >= 1" % (dilation, min_volume, max_lesions))
+    if pred.dtype == torch.uint8:
+        if pred.dim() != 4:
+            raise ValueError("lesion_metrics: uint8 label volumes are [N, D, H, W], got %s" % (tuple(pred.shape),))
+        L.require_gpu()
+        pred, target = pred.contiguous(), target.contiguous()
+        kind, (n, d, h, w), c, k = L.SURFACE_LABEL, (int(v) for v in pred.shape), 1, L.SURFACE_REGIONS
+    else:
+        pred, target = _prep(pred), _prep(target)
+        kind, (n, c, d, h, w) = L.SURFACE_PROB, _dims5(pred)
+        k = c
+    lib = L.load()
+    summary = torch.empty((n, k, 2), dtype=torch.float64, device=pred.device)
+    counts = torch.empty((n, k, L.LESION_COUNTS), dtype=torch.int64, device=pred.device)
+    table = torch.zeros((n, k, int(max_lesions), L.LESION_TABLE_COLUMNS), dtype=torch.float64, device=pred.device) if want_table else None
+    ws = L.workspace(lib.ru_lesion_workspace_bytes(kind, n, c, d, h, w, int(max_lesions)), pred.device)
+    L.check(lib.ru_lesion_metrics(L.ptr(pred), L.ptr(target), kind, n, c, d, h, w, int(dilation), int(min_volume), float(empty_value),
+                                  L.ptr(summary), L.ptr(counts), L.ptr(table, allow_none=True), int(max_lesions), L.ptr(ws), ws.numel(),
+                                  L.stream()), "ru_lesion_metrics")
+    return (summary, counts, table) if want_table else (summary, counts)
+
+
+def lesion_accumulate(summary, acc, nacc, column):
+    """acc[i] += batch mean of lesion_metrics' summary[:, i, column] (float64, on the device), i < nacc; column is "dice" or "hd95"."""
+    n, k = int(summary.shape[0]), int(summary.shape[1])
+    assert summary.dtype == torch.float64 and summary.is_contiguous() and summary.shape == (n, k, 2)
+    assert acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() >= nacc
+    L.check(L.load().ru_lesion_accumulate(L.ptr(summary), L.ptr(acc), n, k, int(nacc), L.LESION_COLUMNS[column], L.stream()),
+            "ru_lesion_accumulate")
+    return acc
+
+
 def to_c16(x):
     """NCDHW [N,C,D,H,W] -> C16 storage [N,C/16,D,H,W,16] (device kernel ru_layout_convert)."""
     x = _prep(x)

@@ -11,6 +11,10 @@ ru_overlap_accumulate), the ratio of the float32-rounded counts in float32 (NaN 
 `--regions` scores the BraTS challenge's way instead: per case the Dice, sensitivity, specificity and HD95 of the regions WT = {1,2,3,4},
 TC = {1,3,4} and ET = {3,4} (3 counts as 4), from one pass sequence of ru_surface_metrics per case (metrics.Hausdorff95 states HD95).
 
+`--lesionwise [--dilation 3] [--min_volume 50]` scores the challenge's lesion-wise ranking numbers instead: per case and region the
+lesion-wise Dice and HD95 and the counts of ground-truth, kept, found, missed and false-positive lesions (ru_lesion_metrics; INTEGRATION.md
+states the definition).  Not checked against the challenge's own evaluator.
+
 `--uncertainty_path DIR [--thresholds 25 50 75 100]` scores the BraTS uncertainty task instead: DIR holds `<case>_unc_whole.npy`,
 `<case>_unc_core.npy`, `<case>_unc_enhance.npy` (uint8 [D,H,W], 0 certain .. 100 uncertain) as `python -m brats2019_amd.test
 --uncertainty_output DIR` writes them.  At a threshold t the voxels with a map value above t are filtered out and TP, FP, FN, TN of the
@@ -38,12 +42,18 @@ parser.add_argument("--regions", action="store_true", default=argparse.SUPPRESS,
 parser.add_argument("--uncertainty_path", default=argparse.SUPPRESS, type=str,
                     help="directory of <case>_unc_whole.npy, _unc_core.npy, _unc_enhance.npy: score the uncertainty maps")
 parser.add_argument("--thresholds", default=argparse.SUPPRESS, type=int, nargs="+", help="uncertainty thresholds, rising, inside 0..100 (default 25 50 75 100)")
+parser.add_argument("--lesionwise", action="store_true", default=argparse.SUPPRESS,
+                    help="score the lesion-wise Dice and HD95 of the regions WT, TC, ET")
+parser.add_argument("--dilation", default=argparse.SUPPRESS, type=int, help="lesion-wise: dilation iterations that join ground-truth fragments (default 3)")
+parser.add_argument("--min_volume", default=argparse.SUPPRESS, type=int, help="lesion-wise: ground-truth lesions of at most this many voxels are not scored (default 50)")
 
 UNCERTAINTY_THRESHOLDS = (25, 50, 75, 100)
 UNCERTAINTY_COLUMNS = ("score", "AUC_Dice", "AUC_FTP", "AUC_FTN")
 
 REGION_NAMES = ("WT", "TC", "ET")
 REGION_METRICS = ("Dice", "Sens", "Spec", "HD95")
+LESION_METRICS = ("LesionDice", "LesionHD95")
+LESION_COUNTS = ("gt", "kept", "tp", "fn", "fp")
 
 VALID_LABELS = (0, 1, 2, 3, 4)
 
@@ -105,6 +115,32 @@ def score_regions(cases):
     return names, results, results.mean(axis=0)
 
 
+def score_lesionwise(cases, dilation=3, min_volume=50):
+    """cases: iterable of (name, ground-truth labels, predicted labels), read one at a time.  -> (names, results float64 [cases, 2, 3],
+    mean float64 [2, 3], counts int64 [cases, 3, 5]): rows lesion-wise Dice and HD95; columns WT, TC, ET; counts n_gt, n_kept, n_tp, n_fn,
+    n_fp per region.  The values stay on the device until the end: one host copy for all cases."""
+    if int(dilation) < 0 or int(min_volume) < 0:
+        raise ValueError("validate: dilation %s and min_volume %s must be >= 0" % (dilation, min_volume))
+    names, rows = [], []
+    for name, label, predict in cases:
+        if tuple(label.shape) != tuple(predict.shape) or np.ndim(label) != 3:
+            raise ValueError("%s: prediction shape %s and label shape %s must be one [D, H, W]" % (name, tuple(predict.shape), tuple(label.shape)))
+        g, p = _upload(label, name + " (labels)"), _upload(predict, name + " (prediction)")
+        summary, counts = ops.lesion_metrics(p[None], g[None], dilation=dilation, min_volume=min_volume)     # [1, 3, 2], [1, 3, 6]
+        names.append(name)
+        rows.append(torch.cat([summary.reshape(-1), counts.reshape(-1).to(torch.float64)]))
+    if not names:
+        raise ValueError("validate: no cases")
+    host = torch.stack(rows).cpu().numpy()
+    counts = host[:, 6:].reshape(len(names), 3, 6).astype(np.int64)
+    bad = counts[:, 0, 5]
+    if bad.any():
+        k = int(np.argmax(bad > 0))
+        raise ValueError("%s: labels outside {0,1,2,3,4} in %d voxels" % (names[k], int(bad[k])))
+    results = np.ascontiguousarray(host[:, :6].reshape(len(names), 3, 2).transpose(0, 2, 1))
+    return names, results, results.mean(axis=0), np.ascontiguousarray(counts[:, :, :5])
+
+
 def score_uncertainty(cases, thresholds=UNCERTAINTY_THRESHOLDS):
     """cases: iterable of (name, ground-truth labels [D,H,W], predicted labels [D,H,W], uncertainty maps uint8 [3,D,H,W] in the order WT,
     TC, ET), read one at a time.  -> (names, results float64 [cases, 3, 4], mean float64 [3, 4]): rows WT, TC, ET; columns score,
@@ -161,10 +197,18 @@ def _region_row(r):
     return "  ".join("%s %s" % (m, " ".join("%s %.4f" % (k, v) for k, v in zip(REGION_NAMES, row))) for m, row in zip(REGION_METRICS, r))
 
 
+def _lesion_row(r, counts=None):
+    row = "  ".join("%s %s" % (m, " ".join("%s %.4f" % (k, v) for k, v in zip(REGION_NAMES, vals))) for m, vals in zip(LESION_METRICS, r))
+    if counts is None:
+        return row
+    return row + "  " + "  ".join("%s %s" % (n, " ".join("%s %d" % (k, v) for k, v in zip(LESION_COUNTS, c))) for n, c in zip(REGION_NAMES, counts))
+
+
 def main(argv=None):
     """-> (per-case results float64 [cases, 4] = [d1, d2, d3, dWT], their mean).  With --regions: (results float64 [cases, 4, 3], their
     mean [4, 3]), rows Dice, sensitivity, specificity, HD95 and columns WT, TC, ET.  With --uncertainty_path: (results float64 [cases, 3, 4],
-    their mean [3, 4]), rows WT, TC, ET and columns score, AUC_Dice, AUC_FTP, AUC_FTN."""
+    their mean [3, 4]), rows WT, TC, ET and columns score, AUC_Dice, AUC_FTP, AUC_FTN.  With --lesionwise: (results float64 [cases, 2, 3],
+    their mean [2, 3]), rows lesion-wise Dice and HD95 and columns WT, TC, ET."""
     opt = parser.parse_args(argv)
     print(torch.__version__)
     print(opt)
@@ -176,6 +220,12 @@ def main(argv=None):
         print("mean", _uncertainty_row(mean))
         return results, mean
     cases = ((f, np.load(os.path.join(opt.data_path, f + ".npy")), np.load(os.path.join(opt.predictions_path, f + ".npy"))) for f in series)
+    if getattr(opt, "lesionwise", False):
+        series, results, mean, counts = score_lesionwise(cases, getattr(opt, "dilation", 3), getattr(opt, "min_volume", 50))
+        for f, r, c in zip(series, results, counts):
+            print(f, _lesion_row(r, c))
+        print("mean", _lesion_row(mean))
+        return results, mean
     if getattr(opt, "regions", False):
         series, results, mean = score_regions(cases)
         for f, r in zip(series, results):

@@ -543,6 +543,45 @@ int ru_surface_metrics(const void* pred, const void* target, int kind, int N, in
                        double* values, unsigned long long* counts, void* ws, size_t ws_bytes, ru_stream_t stream);
 int ru_surface_accumulate(const double* values, double* acc, int N, int K, int nacc, int column, ru_stream_t stream);
 
+/* ---------------------------------------------------------------- lesion-wise Dice and HD95 (csrc/lesion.hip)
+ * Per sample n and region k, P and G are the masks of ru_surface_metrics (same kinds, same regions, every extent in [1, 512], and
+ * D * H * W < 2^31).  Parameters: dilation >= 0, min_volume >= 0, empty_value.
+ *   1. Dil(A) = `dilation` iterations of the binary dilation by the voxel, its 6 face and its 12 edge neighbours
+ *      (scipy.ndimage.binary_dilation(A, generate_binary_structure(3, 2), iterations=dilation)); outside the grid is background.
+ *   2. Z_1..Z_n = the 26-connected components of Dil(G), numbered by ascending smallest linear voxel index (scipy.ndimage.label with a
+ *      3 x 3 x 3 structure of ones).  Lesion L_i = G & Z_i (never empty), vol_i = |L_i|.
+ *   3. Q_1..Q_m = the 26-connected components of P.
+ *   4. M_i = the union of the Q_j that meet Z_i; one Q_j may belong to several M_i.  A Q_j that meets no Z_i is a false positive,
+ *      whatever the volumes of the lesions; n_fp is their number.
+ *   5. tp_i = |M_i & L_i| = |P & L_i|; Dice_i = 2 tp_i / (|M_i| + |L_i|) in float64; HD95_i = ru_surface_metrics' HD95 of the pair
+ *      (M_i, L_i): `empty_value` when M_i is empty.
+ *   6. Kept lesions: vol_i > min_volume; n_kept of them.  A dropped lesion leaves the sums; what it matched is still no false positive.
+ *   7. den = n_kept + n_fp; LesionDice = sum_kept Dice_i / den; LesionHD95 = (sum_kept HD95_i + n_fp * empty_value) / den, float64 sums
+ *      in ascending lesion order; den = 0: LesionDice = 1, LesionHD95 = 0.
+ * ru_lesion_metrics: summary [N][K][2] float64 = {RU_LESION_DICE, RU_LESION_HD95}; counts [N][K][RU_LESION_COUNTS] uint64 = {n_gt, n_kept,
+ *   n_tp (kept with M_i non-empty), n_fn (kept with M_i empty), n_fp, invalid voxels of sample n (kind RU_SURFACE_LABEL; 0 otherwise)};
+ *   table, optional (NULL): [N][K][max_lesions][RU_LESION_COLUMNS] float64 = {vol_i, |M_i|, tp_i, Dice_i, HD95_i} for the n_gt lesions
+ *   of (n, k), the dropped ones included; rows from n_gt on are not written.  More than max_lesions (1..65536) lesions in one (n, k):
+ *   RU_EINVAL, nothing is truncated; the number of predicted components is not limited.
+ *   The pairs (M_i, L_i) go through the surface passes of ru_surface_metrics as bit masks of the whole grid, RU_LESION_CHUNK at a time:
+ *   the workspace holds one chunk, it does not grow with the number of lesions beyond 52 B per lesion of max_lesions and (n, k).  The call
+ *   synchronises the stream ONCE, to read the lesion counts back (they size the chunk loop): it cannot be captured into a graph.
+ *   ws: ru_lesion_workspace_bytes(kind, N, C, D, H, W, max_lesions) bytes (0 for a bad shape, kind or max_lesions).
+ * ru_lesion_accumulate: acc[i] += mean over the N samples of summary[n][i][column] in float64, i < nacc (<= K, <= 64).
+ * None of this was checked against the challenge's own evaluator: the penalty value (the public evaluator uses a constant near 374),
+ * the absence of a size threshold on false positives and the 50-voxel default of the callers are open. */
+#define RU_LESION_DICE 0
+#define RU_LESION_HD95 1
+#define RU_LESION_COUNTS 6
+#define RU_LESION_C_INVALID 5
+#define RU_LESION_COLUMNS 5
+#define RU_LESION_CHUNK 8
+size_t ru_lesion_workspace_bytes(int kind, int N, int C, int D, int H, int W, int max_lesions);
+int ru_lesion_metrics(const void* pred, const void* target, int kind, int N, int C, int D, int H, int W, int dilation, long long min_volume,
+                      double empty_value, double* summary, unsigned long long* counts, double* table, int max_lesions, void* ws,
+                      size_t ws_bytes, ru_stream_t stream);
+int ru_lesion_accumulate(const double* summary, double* acc, int N, int K, int nacc, int column, ru_stream_t stream);
+
 /* ---------------------------------------------------------------- training input pipeline (dataloader.py:100-216, SimpleReader)
  * ru_zscore_stats: per channel stats[c] = { #(x > 0), sum x, sum x^2 } over all V voxels in float64 -- the three numbers the
  *   reference's normalisation is made of (dataloader.py:124-130: the count is over positive voxels, the sums over all).
