@@ -13,22 +13,11 @@
 // wave), 32-bit index arithmetic, integer counts reduced per wave and per workgroup before ONE global atomic.
 #include "ru_common.h"
 #include "pw_helpers.hpp"
+#include "mask_bits.hpp"
 
 #include <limits.h>
 
 namespace ru {
-
-// counts[c] += the workgroup's number of set voxels: wave shuffle, four partials through LDS, one atomic
-__device__ __forceinline__ void ens_count_add(unsigned local, unsigned* sm, unsigned long long* dst) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long n = (unsigned long long)sm[0] + sm[1] + sm[2] + sm[3];
-        if (n) atomicAdd(dst, n);
-    }
-}
 
 // One streaming pass per model.  S = FIRST ? p_m : acc + p_m.  !FINAL: acc = S.  FINAL (the last model of the list): mean = S / M goes
 // straight to mean_out / mask / counts and acc is not written -- the same values ens_finalize_kernel would produce from the stored S.
@@ -65,7 +54,7 @@ __global__ __launch_bounds__(256) void ens_accumulate_kernel(const float* __rest
             local += on ? 1u : 0u;
         }
     }
-    if (FINAL) ens_count_add(local, sm, counts + c);
+    if (FINAL) wg_count_add(local, sm, counts + c);
 }
 
 // mean = S_M / (float)M, mask = mean > 0.5, counts: acc is contiguous, so a lane takes 4 voxels (16-byte load, 16-byte + 4-byte stores) when
@@ -99,7 +88,7 @@ __global__ __launch_bounds__(256) void ens_finalize_kernel(const float* __restri
             local += on ? 1u : 0u;
         }
     }
-    ens_count_add(local, sm, counts + c);
+    wg_count_add(local, sm, counts + c);
 }
 
 // labels[v] = argmax_c (acc[c][v] / M), first maximum wins and a NaN counts as a maximum (np.argmax); class 3 is written as 4

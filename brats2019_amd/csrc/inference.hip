@@ -196,100 +196,16 @@ __global__ __launch_bounds__(256) void tta_merge_box_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------ 26-connected components + small-region rejection (test.py:51-62,162-164)
-// Label equivalence by union-find on the voxel indices: parent[v] = v for every foreground voxel, each voxel is united with its 13
-// "earlier" neighbours of the 26-neighbourhood (the other 13 are covered from the neighbour's side), roots are the smallest index of
-// their component (atomicMin), then every voxel is pointed at its root and the roots count their members.  The reference numbers its
-// components differently (skimage.morphology.label), but only component SIZES enter test.py:51-62, so the result is identical:
+// The labelling is cc_unionfind.hpp's (shared with lesion.hip): union-find on the voxel indices, roots count their members.  The reference
+// numbers its components differently (skimage.morphology.label), but only component SIZES enter test.py:51-62, so the result is identical:
 // a foreground voxel survives iff size(component) >= ratio * (V - max(size of any label, background included)).
-// cc_find / cc_unite / cc_earlier: cc_unionfind.hpp (shared with lesion.hip)
-// Three passes instead of one (round 5: the plain form -- every voxel united with its 13 earlier neighbours through uncompressed trees -- took 18 ms on the
-// 4-million-voxel noise prediction of a random-init network, bench.py's predict_case):
-//   init     : a foreground voxel points at the SMALLEST of its earlier foreground neighbours (itself if none): plain reads of the label volume, no
-//              atomics -- most of the component's links exist after this pass, as a forest with decreasing indices;
-//   compress : every voxel points at the root of its tree (stale parents read on the way are still ancestors: the pass is race-tolerant);
-//   merge    : the remaining equivalences -- a voxel and an earlier neighbour whose trees still differ -- by cc_unite on one- or two-hop paths;
-//   compress : again, so that counting and the rejection pass find their root in one hop.
-__global__ __launch_bounds__(256) void cc_init_kernel(const unsigned char* __restrict__ labels, int* __restrict__ parent, int* __restrict__ count, int D, int H, int W) {
-    const size_t V = (size_t)D * H * W;
-    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < V; v += (size_t)gridDim.x * 256) {
-        count[v] = 0;
-        if (!labels[v]) { parent[v] = -1; continue; }
-        const int x = (int)(v % W);
-        const size_t r = v / W;
-        const int y = (int)(r % H), z = (int)(r / H);
-        int m = (int)v;
-#pragma unroll
-        for (int dz = -1; dz <= 0; ++dz)
-#pragma unroll
-            for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-                for (int dx = -1; dx <= 1; ++dx) {
-                    if (!cc_earlier(dz, dy, dx)) continue;
-                    const int zz = z + dz, yy = y + dy, xx = x + dx;
-                    if (zz < 0 || yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
-                    const size_t u = ((size_t)zz * H + yy) * W + xx;
-                    if (labels[u] && (int)u < m) m = (int)u;
-                }
-        parent[v] = m;
-    }
-}
-__global__ __launch_bounds__(256) void cc_compress_kernel(int* parent, size_t V) {
-    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < V; v += (size_t)gridDim.x * 256) {
-        if (parent[v] < 0) continue;
-        const int root = cc_find(parent, (int)v);
-        __hip_atomic_store(parent + v, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // (an ancestor whatever the other threads do meanwhile)
-    }
-}
-__global__ __launch_bounds__(256) void cc_merge_kernel(int* parent, int D, int H, int W) {
-    const size_t V = (size_t)D * H * W;
-    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < V; v += (size_t)gridDim.x * 256) {
-        const int pv = parent[v];
-        if (pv < 0) continue;
-        const int x = (int)(v % W);
-        const size_t r = v / W;
-        const int y = (int)(r % H), z = (int)(r / H);
-        // the 13 neighbours that precede v in linear order: (dz, dy, dx) with dz = -1, or dz = 0 and dy = -1, or dz = dy = 0 and dx = -1
-#pragma unroll
-        for (int dz = -1; dz <= 0; ++dz)
-#pragma unroll
-            for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-                for (int dx = -1; dx <= 1; ++dx) {
-                    if (!cc_earlier(dz, dy, dx)) continue;
-                    const int zz = z + dz, yy = y + dy, xx = x + dx;
-                    if (zz < 0 || yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
-                    const size_t u = ((size_t)zz * H + yy) * W + xx;
-                    const int pu = parent[u];
-                    if (pu >= 0 && pu != pv) cc_unite(parent, (int)v, (int)u);       // (equal parents: one tree already; a stale read only costs a redundant unite)
-                }
-    }
-}
-// wave-aggregated counting: consecutive voxels mostly share their root, and atomics on one address serialise (~12 ns each: a 100 000-voxel
-// tumour counted voxel by voxel would take over a millisecond) -- the lanes of a wave that hold the same root elect one to add their number
-__global__ __launch_bounds__(256) void cc_count_kernel(const int* parent, int* count, size_t V) {
-    const size_t vend = (V + 255) / 256 * 256;                 // whole waves stay in the loop (the ballots need every lane)
-    // ... and a wave carries the (root, number) of its last group across its iterations (wave-uniform), adding it when the root changes: a component
-    // that fills the volume -- the noise prediction of a random-init network -- costs one atomic per wave instead of one per 64 voxels (0.72 -> ~0.15 ms)
-    int run_root = -1, run_cnt = 0;
-    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < vend; v += (size_t)gridDim.x * 256) {
-        int root = -1;
-        if (v < V && parent[v] >= 0) root = cc_find(parent, (int)v);
-        unsigned long long todo = __ballot(root >= 0);
-        while (todo) {
-            const int leader = __builtin_ctzll(todo);
-            const int lroot = __shfl(root, leader);
-            const unsigned long long same = __ballot(root == lroot) & todo;
-            const int n = (int)__builtin_popcountll(same);
-            if (lroot == run_root) run_cnt += n;
-            else {
-                if (run_cnt && (threadIdx.x & 63) == 0) atomicAdd(count + run_root, run_cnt);
-                run_root = lroot; run_cnt = n;
-            }
-            todo &= ~same;
-        }
-    }
-    if (run_cnt && (threadIdx.x & 63) == 0) atomicAdd(count + run_root, run_cnt);
-}
+struct CcLabels {                                              // the foreground of the one volume: labels != 0
+    const unsigned char* labels;
+    int W;
+    __device__ void select(int, int) {}
+    __device__ bool operator()(size_t row, int x) const { return labels[row * W + x] != 0; }
+};
+__global__ __launch_bounds__(256) void cc_count_kernel(const int* parent, int* count, size_t V) { cc_count_members(parent, count, V); }
 // scal[0] = largest component, scal[1] = number of foreground voxels: one atomic pair per workgroup, at most 256 workgroups
 __global__ __launch_bounds__(256) void cc_max_kernel(const int* __restrict__ count, int* __restrict__ scal, size_t V) {
     __shared__ int sm[4][2];
@@ -446,14 +362,9 @@ extern "C" int ru_cc_reject(unsigned char* labels, int D, int H, int W, double r
     hipError_t e = hipMemsetAsync(scal, 0, 256, s);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(cc)");
     const unsigned g = grid1d(V, 256 * 4, 4096);
-    hipLaunchKernelGGL(cc_init_kernel, dim3(g), dim3(256), 0, s, labels, parent, count, D, H, W);
-    RU_CHECK_LAUNCH("cc_init_kernel");
-    hipLaunchKernelGGL(cc_compress_kernel, dim3(g), dim3(256), 0, s, parent, V);
-    RU_CHECK_LAUNCH("cc_compress_kernel");
-    hipLaunchKernelGGL(cc_merge_kernel, dim3(g), dim3(256), 0, s, parent, D, H, W);
-    RU_CHECK_LAUNCH("cc_merge_kernel");
-    hipLaunchKernelGGL(cc_compress_kernel, dim3(g), dim3(256), 0, s, parent, V);
-    RU_CHECK_LAUNCH("cc_compress_kernel");
+    const CcLabels fg = {labels, W};
+    const int rl = cc_label(fg, parent, 0, count, D, H, W, dim3(g), s);
+    if (rl) return rl;
     hipLaunchKernelGGL(cc_count_kernel, dim3(g), dim3(256), 0, s, parent, count, V);
     RU_CHECK_LAUNCH("cc_count_kernel");
     hipLaunchKernelGGL(cc_max_kernel, dim3(g < 256 ? g : 256), dim3(256), 0, s, count, scal, V);

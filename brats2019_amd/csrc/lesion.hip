@@ -1,14 +1,14 @@
 // Lesion-wise Dice and HD95 on the device (the BraTS ranking since 2023; include/resunet_hip.h states the definition).  Per (sample n,
-// region k), P and G are bit-packed along x like surface.hip's masks: one 64-bit word per 64 voxels, bits >= W of a row zero.
+// region k), P and G are bit-packed along x (mask_bits.hpp): one 64-bit word per 64 voxels, bits >= W of a row zero.
 //
 //   ls_clear_kernel      : clears the outputs, the per-lesion counters and the pair table.
-//   ls_pack_kernel<KIND> : one wave per row: the masks P and G from wave ballots, and the invalid label voxels.
+//   ls_pack_kernel<KIND> : the masks P and G, and the invalid label voxels (mask_bits.hpp, mask_pack_rows).
 //   ls_dilate_kernel     : one thread per word, one launch per iteration, ping-pong between two planes: the rows (dz, dy) = (0, 0) and
 //                          the four face rows contribute themselves and their x +- 1 shifts (carries cross word boundaries), the four
 //                          diagonal rows themselves only -- the 18-neighbour structure.  Z = Dil(G).
-//   ls_cc_*_kernel       : inference.hip's union-find passes (init, compress, merge, compress), here from bit planes and for Z and P of
+//   cc_*_kernel<LsPlanes>: the union-find labelling of cc_unionfind.hpp (init, compress, merge, compress) from bit planes, for Z and P of
 //                          every (n, k) in one launch.  Roots are smallest indices.
-//   ls_count_kernel      : |Q_j| at every root of P (wave-aggregated, as cc_count_kernel); the roots of Z are appended to a list.
+//   ls_count_kernel      : the roots of Z are appended to a list; |Q_j| at every root of P (cc_count_members).
 //   ls_rank_kernel       : sorts the list: lesion i = the component of Z with the i-th smallest root, scipy.ndimage.label's order.
 //   ls_pair_kernel       : one wave per row: vol_i and tp_i by popcount, and every run start of P & Z inserts its pair (root of P,
 //                          lesion) into an open-addressing table.  Distinct pairs <= components of P & Z <= ceil(D/2) ceil(H/2)
@@ -24,38 +24,23 @@
 #include "pw_helpers.hpp"
 #include "cc_unionfind.hpp"
 #include "surface_packed.hpp"
+#include "mask_bits.hpp"
 
 #include <limits.h>
 
 namespace ru {
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int LS_MAX_EXTENT = 512;
 constexpr int LS_MAX_LESIONS = 1 << 16;
 constexpr u64 LS_FREE = ~0ull;                      // an unused table slot
 constexpr unsigned LS_MATCHED = 0x80000000u;        // high bit of |Q_j|: some lesion matched the component
 
-struct LsGeom {
-    int D, H, W, WW;
-    size_t V, words;
-    unsigned slots;                                 // power of two >= 2 * ceil(D/2) * ceil(H/2) * ceil(W/2)
-};
-
-LsGeom ls_geom(int D, int H, int W) {
-    LsGeom g;
-    g.D = D;
-    g.H = H;
-    g.W = W;
-    g.WW = (W + 63) / 64;
-    g.V = (size_t)D * H * W;
-    g.words = (size_t)D * H * g.WW;
+// slots of the pair table of one (n, k): a power of two >= 2 * ceil(D/2) * ceil(H/2) * ceil(W/2)
+unsigned ls_slots(int D, int H, int W) {
     const size_t need = 2 * (size_t)((D + 1) / 2) * ((H + 1) / 2) * ((W + 1) / 2);
     unsigned s = 64;
     while (s < need) s <<= 1;
-    g.slots = s;
-    return g;
+    return s;
 }
 
 // workspace slices; planes per (n, k): 0 = P, 1 = G, 2 and 3 = the dilation's ping-pong
@@ -68,12 +53,12 @@ struct LsWs {
     size_t bytes;
 };
 
-LsWs ls_layout(char* base, size_t NK, const LsGeom& g, size_t max_lesions) {
+LsWs ls_layout(char* base, size_t NK, const MaskGeom& g, unsigned slots, size_t max_lesions) {
     LsWs w;
     size_t off = 0;
     auto take = [&](size_t bytes) { char* p = base + off; off += align_up(bytes, 256); return p; };
     w.bits = (u64*)take(NK * 4 * g.words * sizeof(u64));
-    w.tab = (u64*)take(NK * g.slots * sizeof(u64));
+    w.tab = (u64*)take(NK * slots * sizeof(u64));
     w.vals = (double*)take(NK * max_lesions * 4 * sizeof(double));
     w.icounts = (u64*)take((size_t)RU_LESION_CHUNK * RU_SURFACE_COUNTS * sizeof(u64));
     w.pz = (int*)take(NK * g.V * sizeof(int));
@@ -92,16 +77,7 @@ LsWs ls_layout(char* base, size_t NK, const LsGeom& g, size_t max_lesions) {
 }
 
 bool ls_shape_ok(int kind, int N, int C, int D, int H, int W, int max_lesions) {
-    return (kind == RU_SURFACE_PROB || (kind == RU_SURFACE_LABEL && C == 1)) && N > 0 && C > 0 && D >= 1 && H >= 1 && W >= 1 &&
-           D <= LS_MAX_EXTENT && H <= LS_MAX_EXTENT && W <= LS_MAX_EXTENT && max_lesions >= 1 && max_lesions <= LS_MAX_LESIONS;
-}
-
-int ls_regions(int kind, int C) { return kind == RU_SURFACE_LABEL ? RU_SURFACE_REGIONS : C; }
-
-__device__ __forceinline__ bool ls_region(unsigned v, int k) {
-    if (k == 0) return v >= 1u && v <= 4u;
-    if (k == 1) return v == 1u || v == 3u || v == 4u;
-    return v == 3u || v == 4u;
+    return mask_shape_ok(kind, N, C, D, H, W) && max_lesions >= 1 && max_lesions <= LS_MAX_LESIONS;
 }
 
 __global__ void ls_clear_kernel(LsWs w, size_t NK, size_t max_lesions, unsigned slots, double* __restrict__ summary, u64* __restrict__ counts) {
@@ -115,56 +91,27 @@ __global__ void ls_clear_kernel(LsWs w, size_t NK, size_t max_lesions, unsigned 
     }
 }
 
-// grid (D, N*K), 256 threads: wave q takes the rows h = q, q + 4, ... of plane d.  counts[nk*6 + 5] += invalid voxels
+// grid (D, N*K), 256 threads.  counts[nk*6 + 5] += invalid voxels
 template <int KIND>
-__global__ __launch_bounds__(256) void ls_pack_kernel(const void* __restrict__ pv, const void* __restrict__ gv, int C, int K, LsGeom s,
+__global__ __launch_bounds__(256) void ls_pack_kernel(const void* __restrict__ pv, const void* __restrict__ gv, int C, int K, MaskGeom s,
                                                       u64* __restrict__ bits, u64* __restrict__ counts) {
-    const int d = blockIdx.x, nk = blockIdx.y, n = nk / K, k = nk % K;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64* __restrict__ bp = bits + (size_t)nk * 4 * s.words;
-    u64* __restrict__ bg = bp + s.words;
-    const size_t base = KIND == 0 ? ((size_t)n * C + k) * s.V : (size_t)n * s.V;
-    u64 ci = 0;
-    for (int h = wave; h < s.H; h += 4) {
-        const size_t row = (size_t)d * s.H + h;
-        for (int c = 0; c < s.WW; ++c) {
-            const int w = c * 64 + lane;
-            bool pm = false, gm = false, bad = false;
-            if (w < s.W) {
-                const size_t v = base + row * s.W + w;
-                if (KIND == 0) {
-                    pm = static_cast<const float*>(pv)[v] > 0.5f;
-                    gm = static_cast<const float*>(gv)[v] > 0.5f;
-                } else {
-                    const unsigned a = static_cast<const unsigned char*>(pv)[v], b = static_cast<const unsigned char*>(gv)[v];
-                    pm = ls_region(a, k);
-                    gm = ls_region(b, k);
-                    bad = a > 4u || b > 4u;
-                }
-            }
-            const u64 mp = __ballot(pm), mg = __ballot(gm);
-            if (KIND == 1) ci += __popcll(__ballot(bad));
-            if (lane == 0) {
-                bp[row * s.WW + c] = mp;
-                bg[row * s.WW + c] = mg;
-            }
-        }
-    }
-    if (lane == 0 && ci) atomicAdd(counts + (size_t)nk * RU_LESION_COUNTS + RU_LESION_C_INVALID, ci);
+    u64 c[4];
+    mask_pack_rows<KIND, false>(pv, gv, C, K, s, bits, c);
+    if ((threadIdx.x & 63) == 0 && c[3]) atomicAdd(counts + (size_t)blockIdx.y * RU_LESION_COUNTS + RU_LESION_C_INVALID, c[3]);
 }
 
-__device__ __forceinline__ u64 ls_word(const u64* __restrict__ b, const LsGeom& s, int d, int h, int c) {
+__device__ __forceinline__ u64 ls_word(const u64* __restrict__ b, const MaskGeom& s, int d, int h, int c) {
     return (d < 0 || d >= s.D || h < 0 || h >= s.H || c < 0 || c >= s.WW) ? 0ull : b[((size_t)d * s.H + h) * s.WW + c];
 }
 // word c of row (d, h) or-ed with its shifts by one voxel along x, the carries taken from the neighbouring words
-__device__ __forceinline__ u64 ls_row3(const u64* __restrict__ b, const LsGeom& s, int d, int h, int c) {
+__device__ __forceinline__ u64 ls_row3(const u64* __restrict__ b, const MaskGeom& s, int d, int h, int c) {
     if (d < 0 || d >= s.D || h < 0 || h >= s.H) return 0ull;
     const u64 m = ls_word(b, s, d, h, c), prev = ls_word(b, s, d, h, c - 1), next = ls_word(b, s, d, h, c + 1);
     return m | (m << 1) | (prev >> 63) | (m >> 1) | (next << 63);
 }
 
 // grid (blocks, N*K): one iteration, plane `src` -> plane `dst` of every (n, k)
-__global__ __launch_bounds__(256) void ls_dilate_kernel(LsGeom s, u64* __restrict__ bits, int src, int dst) {
+__global__ __launch_bounds__(256) void ls_dilate_kernel(MaskGeom s, u64* __restrict__ bits, int src, int dst) {
     const int nk = blockIdx.y;
     const u64* __restrict__ a = bits + ((size_t)nk * 4 + src) * s.words;
     u64* __restrict__ o = bits + ((size_t)nk * 4 + dst) * s.words;
@@ -179,106 +126,26 @@ __global__ __launch_bounds__(256) void ls_dilate_kernel(LsGeom s, u64* __restric
     }
 }
 
-__device__ __forceinline__ bool ls_bit(const u64* __restrict__ plane, const LsGeom& s, size_t row, int x) {
-    return (plane[row * s.WW + (x >> 6)] >> (x & 63)) & 1ull;
-}
+// the labelling's foreground: block (., nk, z) labels plane `zplane` (Z) of (n, k) = nk for z = 0, plane 0 (P) for z = 1
+struct LsPlanes {
+    const u64* plane;
+    size_t words;
+    int WW, zplane;
+    __device__ void select(int nk, int z) { plane += ((size_t)nk * 4 + (z ? 0 : zplane)) * words; }
+    __device__ bool operator()(size_t row, int x) const { return mask_bit(plane, WW, row, x); }
+};
 
-// grid (blocks, N*K, 2): z = 0 labels plane `zplane` (Z) into pz, z = 1 plane 0 (P) into pp and clears cnt
-__global__ __launch_bounds__(256) void ls_cc_init_kernel(LsGeom s, const u64* __restrict__ bits, int zplane, int* __restrict__ pz, int* __restrict__ pp,
-                                                         int* __restrict__ cnt) {
-    const int nk = blockIdx.y, which = blockIdx.z;
-    const u64* __restrict__ plane = bits + ((size_t)nk * 4 + (which ? 0 : zplane)) * s.words;
-    int* __restrict__ parent = (which ? pp : pz) + (size_t)nk * s.V;
-    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < s.V; v += (size_t)gridDim.x * 256) {
-        if (which) cnt[(size_t)nk * s.V + v] = 0;
-        const int x = (int)(v % s.W);
-        const size_t r = v / s.W;
-        if (!ls_bit(plane, s, r, x)) { parent[v] = -1; continue; }
-        const int y = (int)(r % s.H), z = (int)(r / s.H);
-        int m = (int)v;
-#pragma unroll
-        for (int dz = -1; dz <= 0; ++dz)
-#pragma unroll
-            for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-                for (int dx = -1; dx <= 1; ++dx) {
-                    if (!cc_earlier(dz, dy, dx)) continue;
-                    const int zz = z + dz, yy = y + dy, xx = x + dx;
-                    if (zz < 0 || yy < 0 || yy >= s.H || xx < 0 || xx >= s.W) continue;
-                    const size_t rr = (size_t)zz * s.H + yy;
-                    const int u = (int)(rr * s.W + xx);
-                    if (u < m && ls_bit(plane, s, rr, xx)) m = u;
-                }
-        parent[v] = m;
-    }
-}
-
-__global__ __launch_bounds__(256) void ls_cc_compress_kernel(LsGeom s, int* __restrict__ pz, int* __restrict__ pp) {
-    int* parent = (blockIdx.z ? pp : pz) + (size_t)blockIdx.y * s.V;
-    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < s.V; v += (size_t)gridDim.x * 256) {
-        if (parent[v] < 0) continue;
-        const int root = cc_find(parent, (int)v);
-        __hip_atomic_store(parent + v, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-__global__ __launch_bounds__(256) void ls_cc_merge_kernel(LsGeom s, int* __restrict__ pz, int* __restrict__ pp) {
-    int* parent = (blockIdx.z ? pp : pz) + (size_t)blockIdx.y * s.V;
-    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < s.V; v += (size_t)gridDim.x * 256) {
-        const int pv = parent[v];
-        if (pv < 0) continue;
-        const int x = (int)(v % s.W);
-        const size_t r = v / s.W;
-        const int y = (int)(r % s.H), z = (int)(r / s.H);
-#pragma unroll
-        for (int dz = -1; dz <= 0; ++dz)
-#pragma unroll
-            for (int dy = -1; dy <= 1; ++dy)
-#pragma unroll
-                for (int dx = -1; dx <= 1; ++dx) {
-                    if (!cc_earlier(dz, dy, dx)) continue;
-                    const int zz = z + dz, yy = y + dy, xx = x + dx;
-                    if (zz < 0 || yy < 0 || yy >= s.H || xx < 0 || xx >= s.W) continue;
-                    const size_t u = ((size_t)zz * s.H + yy) * s.W + xx;
-                    const int pu = parent[u];
-                    if (pu >= 0 && pu != pv) cc_unite(parent, (int)v, (int)u);
-                }
-    }
-}
-
-// grid (blocks, N*K): cnt[root of P] += members (cc_count_kernel's wave aggregation with a carried run); roots of Z join the list
-__global__ __launch_bounds__(256) void ls_count_kernel(LsGeom s, const int* __restrict__ pz, const int* __restrict__ pp, int* __restrict__ cnt,
+// grid (blocks, N*K): the roots of Z join the list; cnt[root of P] += members
+__global__ __launch_bounds__(256) void ls_count_kernel(size_t V, const int* __restrict__ pz, const int* __restrict__ pp, int* __restrict__ cnt,
                                                        int* __restrict__ roots, int* __restrict__ nles, int max_lesions) {
     const int nk = blockIdx.y;
-    const int* __restrict__ parent = pp + (size_t)nk * s.V;
-    const int* __restrict__ zparent = pz + (size_t)nk * s.V;
-    int* __restrict__ count = cnt + (size_t)nk * s.V;
-    const size_t vend = (s.V + 255) / 256 * 256;               // whole waves stay in the loop (the ballots need every lane)
-    int run_root = -1, run_cnt = 0;
-    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < vend; v += (size_t)gridDim.x * 256) {
-        int root = -1;
-        if (v < s.V) {
-            if (parent[v] >= 0) root = cc_find(parent, (int)v);
-            if (zparent[v] == (int)v) {
-                const int at = atomicAdd(nles + nk, 1);
-                if (at < max_lesions) roots[(size_t)nk * max_lesions + at] = (int)v;
-            }
-        }
-        unsigned long long todo = __ballot(root >= 0);
-        while (todo) {
-            const int leader = __builtin_ctzll(todo);
-            const int lroot = __shfl(root, leader);
-            const unsigned long long same = __ballot(root == lroot) & todo;
-            const int n = (int)__builtin_popcountll(same);
-            if (lroot == run_root) run_cnt += n;
-            else {
-                if (run_cnt && (threadIdx.x & 63) == 0) atomicAdd(count + run_root, run_cnt);
-                run_root = lroot; run_cnt = n;
-            }
-            todo &= ~same;
-        }
+    const int* __restrict__ zparent = pz + (size_t)nk * V;
+    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < V; v += (size_t)gridDim.x * 256) {
+        if (zparent[v] != (int)v) continue;
+        const int at = atomicAdd(nles + nk, 1);
+        if (at < max_lesions) roots[(size_t)nk * max_lesions + at] = (int)v;
     }
-    if (run_cnt && (threadIdx.x & 63) == 0) atomicAdd(count + run_root, run_cnt);
+    cc_count_members(pp + (size_t)nk * V, cnt + (size_t)nk * V, V);
 }
 
 // grid (N*K), 256 threads: sorted[rank] = root, the rank by counting the smaller roots (the roots are distinct)
@@ -329,7 +196,7 @@ __device__ __forceinline__ bool ls_contains(const u64* __restrict__ tab, unsigne
 __device__ __forceinline__ u64 ls_key(int proot, int lesion) { return ((u64)(unsigned)proot << 32) | (u64)(unsigned)lesion; }
 
 // grid (D, N*K), 256 threads, one wave per row.  vol[i] += |G & Z_i|, tp[i] += |P & G & Z_i|; pairs from the run starts of P & Z
-__global__ __launch_bounds__(256) void ls_pair_kernel(LsGeom s, const u64* __restrict__ bits, int zplane, const int* __restrict__ pz, const int* __restrict__ pp,
+__global__ __launch_bounds__(256) void ls_pair_kernel(MaskGeom s, unsigned slots, const u64* __restrict__ bits, int zplane, const int* __restrict__ pz, const int* __restrict__ pp,
                                                       const int* __restrict__ sorted, const int* __restrict__ nles, int max_lesions,
                                                       unsigned* __restrict__ vol, unsigned* __restrict__ tp, u64* __restrict__ tab) {
     const int d = blockIdx.x, nk = blockIdx.y;
@@ -343,7 +210,7 @@ __global__ __launch_bounds__(256) void ls_pair_kernel(LsGeom s, const u64* __res
     const int n = min(nles[nk], max_lesions);
     unsigned* __restrict__ voln = vol + (size_t)nk * max_lesions;
     unsigned* __restrict__ tpn = tp + (size_t)nk * max_lesions;
-    u64* __restrict__ tabn = tab + (size_t)nk * s.slots;
+    u64* __restrict__ tabn = tab + (size_t)nk * slots;
     for (int h = wave; h < s.H; h += 4) {
         const size_t row = (size_t)d * s.H + h;
         u64 carry = 0;                                          // bit 63 of P & Z of the previous word
@@ -367,17 +234,17 @@ __global__ __launch_bounds__(256) void ls_pair_kernel(LsGeom s, const u64* __res
                 }
                 todo &= ~same;
             }
-            if (les >= 0 && ((start >> lane) & 1ull)) ls_insert(tabn, s.slots, ls_key(cc_find(parent, v), les));
+            if (les >= 0 && ((start >> lane) & 1ull)) ls_insert(tabn, slots, ls_key(cc_find(parent, v), les));
         }
     }
 }
 
 // grid (blocks, N*K): every pair (j, i): |M_i| += |Q_j|, Q_j is matched
-__global__ __launch_bounds__(256) void ls_table_kernel(LsGeom s, const u64* __restrict__ tab, int* __restrict__ cnt, unsigned* __restrict__ msz, int max_lesions) {
+__global__ __launch_bounds__(256) void ls_table_kernel(size_t V, unsigned slots, const u64* __restrict__ tab, int* __restrict__ cnt, unsigned* __restrict__ msz, int max_lesions) {
     const int nk = blockIdx.y;
-    unsigned* __restrict__ count = (unsigned*)(cnt + (size_t)nk * s.V);
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < s.slots; i += (size_t)gridDim.x * 256) {
-        const u64 key = tab[(size_t)nk * s.slots + i];
+    unsigned* __restrict__ count = (unsigned*)(cnt + (size_t)nk * V);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < slots; i += (size_t)gridDim.x * 256) {
+        const u64 key = tab[(size_t)nk * slots + i];
         if (key == LS_FREE) continue;
         const unsigned j = (unsigned)(key >> 32), les = (unsigned)key;
         const unsigned size = __hip_atomic_load(count + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ~LS_MATCHED;
@@ -387,7 +254,7 @@ __global__ __launch_bounds__(256) void ls_table_kernel(LsGeom s, const u64* __re
 }
 
 // grid (blocks, N*K): nfp += roots of P without the mark
-__global__ __launch_bounds__(256) void ls_fp_kernel(LsGeom s, const int* __restrict__ pp, const int* __restrict__ cnt, int* __restrict__ nfp) {
+__global__ __launch_bounds__(256) void ls_fp_kernel(MaskGeom s, const int* __restrict__ pp, const int* __restrict__ cnt, int* __restrict__ nfp) {
     const int nk = blockIdx.y;
     const int* __restrict__ parent = pp + (size_t)nk * s.V;
     const unsigned* __restrict__ count = (const unsigned*)(cnt + (size_t)nk * s.V);
@@ -400,7 +267,7 @@ __global__ __launch_bounds__(256) void ls_fp_kernel(LsGeom s, const int* __restr
 }
 
 // grid (D, items), 256 threads, one wave per row: item t is lesion i0 + t of (n, k) = nk.  Plane 0 of the item = M_i, plane 1 = L_i.
-__global__ __launch_bounds__(256) void ls_item_kernel(LsGeom s, const u64* __restrict__ bits, const int* __restrict__ pz, const int* __restrict__ pp,
+__global__ __launch_bounds__(256) void ls_item_kernel(MaskGeom s, unsigned slots, const u64* __restrict__ bits, const int* __restrict__ pz, const int* __restrict__ pp,
                                                       const int* __restrict__ sorted, const u64* __restrict__ tab, const unsigned* __restrict__ vol,
                                                       const unsigned* __restrict__ msz, const unsigned* __restrict__ tp, int max_lesions, int nk, int i0,
                                                       u64* __restrict__ ibits, u64* __restrict__ icounts) {
@@ -410,7 +277,7 @@ __global__ __launch_bounds__(256) void ls_item_kernel(LsGeom s, const u64* __res
     const u64* __restrict__ bg = bp + s.words;
     const int* __restrict__ zparent = pz + (size_t)nk * s.V;
     const int* __restrict__ parent = pp + (size_t)nk * s.V;
-    const u64* __restrict__ tabn = tab + (size_t)nk * s.slots;
+    const u64* __restrict__ tabn = tab + (size_t)nk * slots;
     const int root = sorted[(size_t)nk * max_lesions + i];
     u64* __restrict__ im = ibits + (size_t)t * 4 * s.words;
     u64* __restrict__ il = im + s.words;
@@ -421,7 +288,7 @@ __global__ __launch_bounds__(256) void ls_item_kernel(LsGeom s, const u64* __res
             const int v = (int)(row * s.W + c * 64 + lane);
             bool inl = false, inm = false;
             if ((gw >> lane) & 1ull) inl = cc_find(zparent, v) == root;
-            if ((pw >> lane) & 1ull) inm = ls_contains(tabn, s.slots, ls_key(cc_find(parent, v), i));
+            if ((pw >> lane) & 1ull) inm = ls_contains(tabn, slots, ls_key(cc_find(parent, v), i));
             const u64 ml = __ballot(inl), mm = __ballot(inm);
             if (lane == 0) {
                 im[row * s.WW + c] = mm;
@@ -478,15 +345,6 @@ __global__ void ls_summary_kernel(int NK, int max_lesions, const int* __restrict
     q[4] = (u64)fp;
 }
 
-// acc[i] += mean over the N samples of summary[n][i][column], i < nacc; samples summed in order
-__global__ void ls_accumulate_kernel(const double* __restrict__ summary, double* __restrict__ acc, int N, int K, int nacc, int column) {
-    const int i = threadIdx.x;
-    if (i >= nacc) return;
-    double sum = 0.0;
-    for (int n = 0; n < N; ++n) sum += summary[((size_t)n * K + i) * 2 + column];
-    acc[i] += sum / (double)N;
-}
-
 }  // namespace
 }  // namespace ru
 
@@ -494,7 +352,7 @@ using namespace ru;
 
 extern "C" size_t ru_lesion_workspace_bytes(int kind, int N, int C, int D, int H, int W, int max_lesions) {
     if (!ls_shape_ok(kind, N, C, D, H, W, max_lesions) || (size_t)D * H * W >= (size_t)INT_MAX) return 0;
-    return ls_layout(nullptr, (size_t)N * ls_regions(kind, C), ls_geom(D, H, W), (size_t)max_lesions).bytes;
+    return ls_layout(nullptr, (size_t)N * mask_regions(kind, C), mask_geom(D, H, W), ls_slots(D, H, W), (size_t)max_lesions).bytes;
 }
 
 extern "C" int ru_lesion_metrics(const void* pred, const void* target, int kind, int N, int C, int D, int H, int W, int dilation, long long min_volume,
@@ -502,22 +360,23 @@ extern "C" int ru_lesion_metrics(const void* pred, const void* target, int kind,
                                  size_t ws_bytes, ru_stream_t stream) {
     RU_REQUIRE(pred && target && summary && counts && N > 0 && C > 0, "ru_lesion_metrics: bad argument");
     RU_REQUIRE(kind == RU_SURFACE_PROB || (kind == RU_SURFACE_LABEL && C == 1), "ru_lesion_metrics: bad kind %d (C = %d)", kind, C);
-    RU_REQUIRE(D >= 1 && H >= 1 && W >= 1 && D <= LS_MAX_EXTENT && H <= LS_MAX_EXTENT && W <= LS_MAX_EXTENT,
-               "ru_lesion_metrics: extents %d x %d x %d: every axis must be in [1, %d]", D, H, W, LS_MAX_EXTENT);
+    RU_REQUIRE(D >= 1 && H >= 1 && W >= 1 && D <= MAX_EXTENT && H <= MAX_EXTENT && W <= MAX_EXTENT,
+               "ru_lesion_metrics: extents %d x %d x %d: every axis must be in [1, %d]", D, H, W, MAX_EXTENT);
     RU_REQUIRE((size_t)D * H * W < (size_t)INT_MAX, "ru_lesion_metrics: volume too large for 32-bit voxel indices");
-    RU_REQUIRE(dilation >= 0 && dilation <= LS_MAX_EXTENT && min_volume >= 0, "ru_lesion_metrics: dilation %d, min_volume %lld: both must be >= 0", dilation,
+    RU_REQUIRE(dilation >= 0 && dilation <= MAX_EXTENT && min_volume >= 0, "ru_lesion_metrics: dilation %d, min_volume %lld: both must be >= 0", dilation,
                min_volume);
     RU_REQUIRE(max_lesions >= 1 && max_lesions <= LS_MAX_LESIONS, "ru_lesion_metrics: max_lesions %d: must be in [1, %d]", max_lesions, LS_MAX_LESIONS);
-    const int K = ls_regions(kind, C);
+    const int K = mask_regions(kind, C);
     RU_REQUIRE((long long)N * K <= 65535, "ru_lesion_metrics: N * regions = %lld: the grid needs N * regions <= 65535", (long long)N * K);
     const size_t need = ru_lesion_workspace_bytes(kind, N, C, D, H, W, max_lesions);
     RU_REQUIRE(ws && need && ws_bytes >= need, "ru_lesion_metrics: workspace too small");
     hipStream_t st = (hipStream_t)stream;
-    const LsGeom s = ls_geom(D, H, W);
+    const MaskGeom s = mask_geom(D, H, W);
+    const unsigned slots = ls_slots(D, H, W);
     const int NK = N * K;
-    const LsWs w = ls_layout((char*)ws, (size_t)NK, s, (size_t)max_lesions);
-    const size_t nclear = std::max((size_t)NK * s.slots, (size_t)NK * max_lesions);
-    hipLaunchKernelGGL(ls_clear_kernel, dim3(grid1d(nclear, 256, 4096)), dim3(256), 0, st, w, (size_t)NK, (size_t)max_lesions, s.slots, summary, counts);
+    const LsWs w = ls_layout((char*)ws, (size_t)NK, s, slots, (size_t)max_lesions);
+    const size_t nclear = std::max((size_t)NK * slots, (size_t)NK * max_lesions);
+    hipLaunchKernelGGL(ls_clear_kernel, dim3(grid1d(nclear, 256, 4096)), dim3(256), 0, st, w, (size_t)NK, (size_t)max_lesions, slots, summary, counts);
     RU_CHECK_LAUNCH("ls_clear_kernel");
     if (kind == RU_SURFACE_PROB)
         hipLaunchKernelGGL(ls_pack_kernel<0>, dim3(D, NK), dim3(256), 0, st, pred, target, C, K, s, w.bits, counts);
@@ -532,21 +391,16 @@ extern "C" int ru_lesion_metrics(const void* pred, const void* target, int kind,
         RU_CHECK_LAUNCH("ls_dilate_kernel");
         zplane = dst;
     }
-    hipLaunchKernelGGL(ls_cc_init_kernel, dim3(gv, NK, 2), dim3(256), 0, st, s, w.bits, zplane, w.pz, w.pp, w.cnt);
-    RU_CHECK_LAUNCH("ls_cc_init_kernel");
-    hipLaunchKernelGGL(ls_cc_compress_kernel, dim3(gv, NK, 2), dim3(256), 0, st, s, w.pz, w.pp);
-    RU_CHECK_LAUNCH("ls_cc_compress_kernel");
-    hipLaunchKernelGGL(ls_cc_merge_kernel, dim3(gv, NK, 2), dim3(256), 0, st, s, w.pz, w.pp);
-    RU_CHECK_LAUNCH("ls_cc_merge_kernel");
-    hipLaunchKernelGGL(ls_cc_compress_kernel, dim3(gv, NK, 2), dim3(256), 0, st, s, w.pz, w.pp);
-    RU_CHECK_LAUNCH("ls_cc_compress_kernel");
-    hipLaunchKernelGGL(ls_count_kernel, dim3(gv, NK), dim3(256), 0, st, s, w.pz, w.pp, w.cnt, w.roots, w.nles, max_lesions);
+    const LsPlanes planes = {w.bits, s.words, s.WW, zplane};
+    const int rl = cc_label(planes, w.pz, (size_t)(w.pp - w.pz), w.cnt, D, H, W, dim3(gv, NK, 2), st);       // z = 0: Z into pz, z = 1: P into pp
+    if (rl) return rl;
+    hipLaunchKernelGGL(ls_count_kernel, dim3(gv, NK), dim3(256), 0, st, s.V, w.pz, w.pp, w.cnt, w.roots, w.nles, max_lesions);
     RU_CHECK_LAUNCH("ls_count_kernel");
     hipLaunchKernelGGL(ls_rank_kernel, dim3(NK), dim3(256), 0, st, w.roots, w.sorted, w.nles, max_lesions);
     RU_CHECK_LAUNCH("ls_rank_kernel");
-    hipLaunchKernelGGL(ls_pair_kernel, dim3(D, NK), dim3(256), 0, st, s, w.bits, zplane, w.pz, w.pp, w.sorted, w.nles, max_lesions, w.vol, w.tp, w.tab);
+    hipLaunchKernelGGL(ls_pair_kernel, dim3(D, NK), dim3(256), 0, st, s, slots, w.bits, zplane, w.pz, w.pp, w.sorted, w.nles, max_lesions, w.vol, w.tp, w.tab);
     RU_CHECK_LAUNCH("ls_pair_kernel");
-    hipLaunchKernelGGL(ls_table_kernel, dim3(grid1d(s.slots, 256, 4096), NK), dim3(256), 0, st, s, w.tab, w.cnt, w.msz, max_lesions);
+    hipLaunchKernelGGL(ls_table_kernel, dim3(grid1d(slots, 256, 4096), NK), dim3(256), 0, st, s.V, slots, w.tab, w.cnt, w.msz, max_lesions);
     RU_CHECK_LAUNCH("ls_table_kernel");
     hipLaunchKernelGGL(ls_fp_kernel, dim3(gv, NK), dim3(256), 0, st, s, w.pp, w.cnt, w.nfp);
     RU_CHECK_LAUNCH("ls_fp_kernel");
@@ -562,7 +416,7 @@ extern "C" int ru_lesion_metrics(const void* pred, const void* target, int kind,
     for (int nk = 0; nk < NK; ++nk)
         for (int i0 = 0; i0 < nles[nk]; i0 += RU_LESION_CHUNK) {
             const int items = std::min(RU_LESION_CHUNK, nles[nk] - i0);
-            hipLaunchKernelGGL(ls_item_kernel, dim3(D, items), dim3(256), 0, st, s, w.bits, w.pz, w.pp, w.sorted, w.tab, w.vol, w.msz, w.tp, max_lesions, nk,
+            hipLaunchKernelGGL(ls_item_kernel, dim3(D, items), dim3(256), 0, st, s, slots, w.bits, w.pz, w.pp, w.sorted, w.tab, w.vol, w.msz, w.tp, max_lesions, nk,
                                i0, sf_packed_bits(w.sf), w.icounts);
             RU_CHECK_LAUNCH("ls_item_kernel");
             const int rc = sf_packed_run(items, D, H, W, w.sf, w.icounts, empty_value, w.vals + ((size_t)nk * max_lesions + i0) * 4, st);
@@ -576,7 +430,7 @@ extern "C" int ru_lesion_metrics(const void* pred, const void* target, int kind,
 
 extern "C" int ru_lesion_accumulate(const double* summary, double* acc, int N, int K, int nacc, int column, ru_stream_t stream) {
     RU_REQUIRE(summary && acc && N > 0 && K > 0 && nacc > 0 && nacc <= K && nacc <= 64 && column >= 0 && column < 2, "ru_lesion_accumulate: bad argument");
-    hipLaunchKernelGGL(ls_accumulate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, summary, acc, N, K, nacc, column);
-    RU_CHECK_LAUNCH("ls_accumulate_kernel");
+    hipLaunchKernelGGL(column_mean_kernel<2>, dim3(1), dim3(64), 0, (hipStream_t)stream, summary, acc, N, K, nacc, column);
+    RU_CHECK_LAUNCH("column_mean_kernel");
     return RU_OK;
 }

@@ -2,25 +2,17 @@
 // (metrics.py:188-271, SimpleITK's HausdorffDistanceImageFilter at unit spacing on the (D, H, W) axes).
 //
 // HD(P, G) = max(directed(P, G), directed(G, P)), directed(A, B) = max over a in A of min over b in B of |a - b| (voxel centres).
-// Per (sample n, channel k) two exact squared Euclidean distance transforms run in integer arithmetic, separable over the axes:
-//   pass W  (hd_pass_w_kernel):    thresholds both masks on the fly, counts their voxels and writes the 1-D squared distance to the
-//                                  nearest site of each row, for the transform to G and the one to P;
-//   pass H  (hd_pass_line_kernel<false>): f(i) = min_j f(j) + (i - j)^2 over the H line, in place;
-//   pass D  (hd_pass_line_kernel<true>):  the same over the D line, fused with the reduction: it writes no distance map, it takes the
-//                                  max of d^2 over the voxels of the OTHER mask (P for the transform to G, G for the one to P).
-// The H / D passes stage a tile of 32 neighbouring W columns over the whole line in LDS (coalesced 128-B row segments, at most
-// 32 x 512 x 4 B = 64 KiB) and take the minimum by brute force over the line.  Squared distances stay exact integers: the largest is
-// 3 * 511^2 < 2^20, and the "no site" sentinel 2^30 plus any (i - j)^2 stays below 2^31.
+// Per (sample n, channel k) two exact squared Euclidean distance transforms run in integer arithmetic (edt_exact.hpp), to G and to P:
+//   pass W  (hd_pass_w_kernel): thresholds both masks on the fly, counts their voxels and hands each row's ballots to edt_row_pass;
+//   pass H  (edt_line_kernel<false>): in place;
+//   pass D  (edt_line_kernel<true, HdMax>): writes no distance map, it takes the max of d^2 over the voxels of the OTHER mask (P for the
+//           transform to G, G for the one to P).
 // hd_accumulate_kernel then applies the reference's bookkeeping (empty masks, the i-1 quirk), the float64 sqrt and the batch mean.
 #include "ru_common.h"
+#include "edt_exact.hpp"
 
 namespace ru {
 namespace {
-
-constexpr int HD_MAX_EXTENT = 512;       // every axis; the W pass holds a row in 8 ballots of 64
-constexpr unsigned HD_INF = 1u << 30;    // "no site"
-constexpr int HD_TW = 32;                // W columns per tile of the line passes
-constexpr int HD_LINE_THREADS = 256;     // 32 columns x 8 line positions
 
 // mask of sample n, channel k at voxel v.  mode 0: x > 0.5 (metrics.py:205-206).  mode 1: argmax over the channels > 0 (metrics.py:245-246);
 // torch's argmax takes the first of equal maxima, so this is max(x[1:]) > x[0]
@@ -33,21 +25,6 @@ __device__ __forceinline__ bool hd_mask(const float* __restrict__ x, int mode, i
     return any;
 }
 
-__device__ __forceinline__ unsigned hd_row_sq(unsigned long long m, unsigned long long below, int w, int c, int lane, int prev, int next) {
-    // nearest site at or left of w: in this chunk (bits <= lane) or the last site of an earlier chunk; at or right of w likewise
-    const int left = below ? c * 64 + 63 - __clzll((long long)below) : prev;
-    const unsigned long long above = m >> lane;
-    const int right = above ? w + __ffsll((long long)above) - 1 : next;
-    const int best = min(w - left, right - w);
-    return best < HD_MAX_EXTENT ? (unsigned)(best * best) : HD_INF;
-}
-
-// out = 0 as a kernel node rather than a hipMemsetAsync: captured into a hipGraph, the memset was seen to leave these slots uncleared on replay
-__global__ void hd_zero_kernel(unsigned long long* __restrict__ out, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = 0;
-}
-
 // grid (D, N*K), 256 threads: wave q takes the rows h = q, q + 4, ... of plane d.  f = [N*K][2][V]: transform 0 = to G, 1 = to P.
 // out[nk*4 + 2] / [nk*4 + 3] += #P / #G.
 __global__ __launch_bounds__(256) void hd_pass_w_kernel(const float* __restrict__ p, const float* __restrict__ g, int mode, int C, int K,
@@ -57,13 +34,12 @@ __global__ __launch_bounds__(256) void hd_pass_w_kernel(const float* __restrict_
     const size_t V = (size_t)D * H * W;
     unsigned* __restrict__ fg = f + ((size_t)nk * 2) * V;
     unsigned* __restrict__ fp = fg + V;
-    const unsigned long long upto = lane == 63 ? ~0ull : (2ull << lane) - 1;
     unsigned long long cp = 0, cg = 0;
     for (int h = wave; h < H; h += 4) {
         const size_t row = ((size_t)d * H + h) * W;
-        unsigned long long mp[8], mg[8];
+        u64 mp[MAX_WORDS], mg[MAX_WORDS];
 #pragma unroll
-        for (int c = 0; c < 8; ++c) {
+        for (int c = 0; c < MAX_WORDS; ++c) {
             const int w = c * 64 + lane;
             const bool in = w < W;
             mp[c] = __ballot(in && hd_mask(p, mode, C, V, n, k, row + w));
@@ -71,28 +47,8 @@ __global__ __launch_bounds__(256) void hd_pass_w_kernel(const float* __restrict_
             cp += __popcll(mp[c]);
             cg += __popcll(mg[c]);
         }
-        // first site after each chunk (wave-uniform), then a forward sweep with the last site before it
-        int nextp[8], nextg[8];
-        int np_ = 1 << 20, ng_ = 1 << 20;
-#pragma unroll
-        for (int c = 7; c >= 0; --c) {
-            nextp[c] = np_;
-            nextg[c] = ng_;
-            if (mp[c]) np_ = c * 64 + __ffsll((long long)mp[c]) - 1;
-            if (mg[c]) ng_ = c * 64 + __ffsll((long long)mg[c]) - 1;
-        }
-        int prevp = -(1 << 20), prevg = -(1 << 20);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            if (c * 64 >= W) break;
-            const int w = c * 64 + lane;
-            if (w < W) {
-                fg[row + w] = hd_row_sq(mg[c], mg[c] & upto, w, c, lane, prevg, nextg[c]);
-                fp[row + w] = hd_row_sq(mp[c], mp[c] & upto, w, c, lane, prevp, nextp[c]);
-            }
-            if (mp[c]) prevp = c * 64 + 63 - __clzll((long long)mp[c]);
-            if (mg[c]) prevg = c * 64 + 63 - __clzll((long long)mg[c]);
-        }
+        edt_row_pass(mg, W, fg + row);
+        edt_row_pass(mp, W, fp + row);
     }
     if (lane == 0) {
         if (cp) atomicAdd(out + (size_t)nk * 4 + 2, cp);
@@ -100,57 +56,27 @@ __global__ __launch_bounds__(256) void hd_pass_w_kernel(const float* __restrict_
     }
 }
 
-// grid (cdiv(W, 32), lines, N*K*2), 256 threads, dynamic LDS L x 32 x 4 B.  FINAL = false: the H pass (lines = D planes, L = H, in place).
-// FINAL = true: the D pass (lines = H rows, L = D): max of d^2 over the sample mask's voxels -> out[nk*4 + t], one atomicMax per wave.
-template <bool FINAL>
-__global__ __launch_bounds__(HD_LINE_THREADS) void hd_pass_line_kernel(unsigned* __restrict__ f, const float* __restrict__ p, const float* __restrict__ g,
-                                                                       int mode, int C, int K, int D, int H, int W, unsigned long long* __restrict__ out) {
-    extern __shared__ unsigned s[];
-    const int x = threadIdx.x % HD_TW, r = threadIdx.x / HD_TW;
-    constexpr int R = HD_LINE_THREADS / HD_TW;
-    const int w = blockIdx.x * HD_TW + x, a = blockIdx.y, t = blockIdx.z & 1, nk = blockIdx.z >> 1;
-    const size_t V = (size_t)D * H * W;
-    const int L = FINAL ? D : H;
-    const size_t stride = FINAL ? (size_t)H * W : (size_t)W;
-    const size_t off = FINAL ? (size_t)a * W + w : (size_t)a * H * W + w;          // voxel index of line element 0
-    unsigned* __restrict__ fl = f + ((size_t)nk * 2 + t) * V;
-    const bool col = w < W;
-    for (int i = r; i < L; i += R) s[i * HD_TW + x] = col ? fl[off + i * stride] : HD_INF;
-    __syncthreads();
-    const float* __restrict__ smp = t == 0 ? p : g;                                 // transform to G is sampled on P and vice versa
-    const int n = nk / K, k = nk % K;
-    unsigned best = 0;
-    for (int i0 = r; i0 < L; i0 += 4 * R) {
-        bool on[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int i = i0 + u * R;
-            on[u] = col && i < L;
-            if (FINAL && on[u]) on[u] = hd_mask(smp, mode, C, V, n, k, off + i * stride);
-        }
-        if (FINAL && !__any(on[0] || on[1] || on[2] || on[3])) continue;           // no voxel of the sample mask here: nothing to reduce
-        unsigned acc[4] = {HD_INF, HD_INF, HD_INF, HD_INF};
-        for (int j = 0; j < L; ++j) {
-            const unsigned fj = s[j * HD_TW + x];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int dd = i0 + u * R - j;
-                acc[u] = min(acc[u], fj + (unsigned)__mul24(dd, dd));
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (!on[u]) continue;
-            if (FINAL) best = max(best, acc[u]);
-            else fl[off + (size_t)(i0 + u * R) * stride] = acc[u];                // the block owns its lines: in place after the barrier
-        }
+// the D pass's query: the transform to G (t = 0) is sampled on P and vice versa; out[nk*4 + t] = max of d^2, one atomicMax per wave
+struct HdMax {
+    const float *p, *g, *smp;
+    int mode, C, K, n, k;
+    unsigned long long* out;
+    unsigned best;
+    __device__ void begin(const MaskGeom&, int nk, int t) {
+        smp = t == 0 ? p : g;
+        n = nk / K;
+        k = nk % K;
+        out += (size_t)nk * 4 + t;
+        best = 0;
     }
-    if (FINAL) {
+    __device__ bool query(const MaskGeom& s, int d, int h, int w) const { return hd_mask(smp, mode, C, s.V, n, k, ((size_t)d * s.H + h) * s.W + w); }
+    __device__ void consume(unsigned sq) { best = max(best, sq); }
+    __device__ void finish() {
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) best = max(best, (unsigned)__shfl_xor((int)best, m));
-        if ((threadIdx.x & 63) == 0 && best) atomicMax(out + (size_t)nk * 4 + t, (unsigned long long)best);
+        if ((threadIdx.x & 63) == 0 && best) atomicMax(out, (unsigned long long)best);
     }
-}
+};
 
 // metrics.py:208-228 (mode 0) / 248-263 (mode 1) from the squared maxima and counts, then metrics.py:230 / 265: acc += the batch mean.
 // One thread per result column, samples in order (numpy's axis-0 sum is sequential; its 1-D pairwise sum is too below 8 samples).
@@ -196,24 +122,19 @@ extern "C" size_t ru_hausdorff_workspace_bytes(int N, int C, int D, int H, int W
 extern "C" int ru_hausdorff_sq(const float* p, const float* g, int N, int C, int D, int H, int W, int mode, unsigned long long* out,
                                void* ws, size_t ws_bytes, ru_stream_t stream) {
     RU_REQUIRE(p && g && out && N > 0 && C > 0 && (mode == 0 || mode == 1), "ru_hausdorff_sq: bad argument");
-    RU_REQUIRE(D > 0 && H > 0 && W > 0 && D <= HD_MAX_EXTENT && H <= HD_MAX_EXTENT && W <= HD_MAX_EXTENT,
-               "ru_hausdorff_sq: extents %d x %d x %d: every axis must be in [1, %d]", D, H, W, HD_MAX_EXTENT);
+    RU_REQUIRE(D > 0 && H > 0 && W > 0 && D <= MAX_EXTENT && H <= MAX_EXTENT && W <= MAX_EXTENT,
+               "ru_hausdorff_sq: extents %d x %d x %d: every axis must be in [1, %d]", D, H, W, MAX_EXTENT);
     const int K = mode == 0 ? C : 1;
     RU_REQUIRE((long long)N * K * 2 <= 65535, "ru_hausdorff_sq: N * channels too large");
     RU_REQUIRE(ws && ws_bytes >= hd_workspace_bytes(N, C, D, H, W, mode), "ru_hausdorff_sq: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     unsigned* f = (unsigned*)ws;
-    hipLaunchKernelGGL(hd_zero_kernel, dim3(cdiv(4 * N * K, 256)), dim3(256), 0, s, out, 4 * N * K);
-    RU_CHECK_LAUNCH("hd_zero_kernel");
+    hipLaunchKernelGGL((zero2_kernel<u64, u64>), dim3(cdiv(4 * N * K, 256)), dim3(256), 0, s, out, (size_t)4 * N * K, (u64*)nullptr, (size_t)0);
+    RU_CHECK_LAUNCH("zero2_kernel");
     hipLaunchKernelGGL(hd_pass_w_kernel, dim3(D, N * K), dim3(256), 0, s, p, g, mode, C, K, D, H, W, f, out);
     RU_CHECK_LAUNCH("hd_pass_w_kernel");
-    hipLaunchKernelGGL(hd_pass_line_kernel<false>, dim3(cdiv(W, HD_TW), D, N * K * 2), dim3(HD_LINE_THREADS), (size_t)H * HD_TW * sizeof(unsigned), s,
-                       f, p, g, mode, C, K, D, H, W, out);
-    RU_CHECK_LAUNCH("hd_pass_line_kernel<H>");
-    hipLaunchKernelGGL(hd_pass_line_kernel<true>, dim3(cdiv(W, HD_TW), H, N * K * 2), dim3(HD_LINE_THREADS), (size_t)D * HD_TW * sizeof(unsigned), s,
-                       f, p, g, mode, C, K, D, H, W, out);
-    RU_CHECK_LAUNCH("hd_pass_line_kernel<D>");
-    return RU_OK;
+    const HdMax q = {p, g, nullptr, mode, C, K, 0, 0, out, 0u};
+    return edt_line_passes(f, mask_geom(D, H, W), N * K, q, s);
 }
 
 extern "C" int ru_hausdorff_accumulate(const unsigned long long* sq, double* acc, int N, int K, int nacc, int mode, ru_stream_t stream) {

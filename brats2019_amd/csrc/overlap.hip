@@ -10,8 +10,9 @@
 //                          label Dice from the matrix, then the batch mean into the float64 accumulator.
 //   ov_dice1d_kernel     : Dice1D from ru_dice_counts' {I, |P|+|G|}.
 //   ov_rmse_kernel       : RMSE's sqrt(sum d^2 / count) from ru_crit_moments' RU_CRIT_M_D2 moment.
-// The outputs are cleared by a kernel, not by hipMemsetAsync, so the calls capture into a hipGraph (metrics.hip, hd_zero_kernel).
+// The outputs are cleared by a kernel, not by hipMemsetAsync, so the calls capture into a hipGraph (mask_bits.hpp, zero2_kernel).
 #include "ru_common.h"
+#include "mask_bits.hpp"
 
 namespace ru {
 namespace {
@@ -141,12 +142,6 @@ __global__ __launch_bounds__(OV_THREADS) void ov_confusion_label_kernel(const un
     ov_publish<NB>(cnt, conf + n * (L * L), invalid + n, L * L);
 }
 
-__global__ void ov_zero_kernel(unsigned long long* __restrict__ a, int na, unsigned long long* __restrict__ b, int nb) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < na) a[i] = 0;
-    else if (b && i < na + nb) b[i - na] = 0;
-}
-
 int ov_blocks(size_t V, int N, int per_block) {
     const size_t need = (V + per_block - 1) / per_block;
     int want = (OV_TARGET_BLOCKS + N - 1) / N;
@@ -258,8 +253,8 @@ extern "C" int ru_label_confusion(const void* pred, const void* target, int kind
     hipStream_t s = (hipStream_t)stream;
     const int L = kind == RU_CONF_PROB ? C : OV_LABEL_LABELS;
     const int nconf = N * L * L, ninv = invalid ? N : 0;
-    hipLaunchKernelGGL(ov_zero_kernel, dim3(cdiv(nconf + ninv, 256)), dim3(256), 0, s, conf, nconf, invalid, ninv);
-    RU_CHECK_LAUNCH("ov_zero_kernel");
+    hipLaunchKernelGGL((zero2_kernel<u64, u64>), dim3(cdiv(nconf + ninv, 256)), dim3(256), 0, s, conf, (size_t)nconf, invalid, (size_t)ninv);
+    RU_CHECK_LAUNCH("zero2_kernel");
     if (kind == RU_CONF_LABEL) {
         const unsigned char* p = (const unsigned char*)pred;
         const unsigned char* g = (const unsigned char*)target;

@@ -18,6 +18,7 @@
 // voxels of the box (16-byte loads and stores; the hardware takes them at dword alignment, which a box row at an odd offset needs).
 #include "ru_common.h"
 #include "pw_helpers.hpp"
+#include "mask_bits.hpp"
 
 #include <limits.h>
 
@@ -31,7 +32,7 @@ constexpr int UNC_BINS = UNC_REGIONS * UNC_LEVELS * UNC_CLASSES;
 constexpr int UNC_HIST_THREADS = 256, UNC_HIST_WAVES = UNC_HIST_THREADS / 64;
 constexpr int UNC_HIST_MAX_BLOCKS = 512;                                   // bounds the same-address atomics: <= 512 per bin
 constexpr int UNC_MAX_THRESHOLDS = 101;
-// labels of the three regions as bit sets over the label value: WT = {1,2,3,4}, TC = {1,3,4}, ET = {3,4} (validate --regions)
+// labels of the three regions as bit sets over the label value: WT = {1,2,3,4}, TC = {1,3,4}, ET = {3,4} (mask_bits.hpp, brats_region)
 constexpr unsigned UNC_REGION_BITS[UNC_REGIONS] = {0x1eu, 0x1au, 0x18u};
 
 struct UncThresholds { int t[UNC_MAX_THRESHOLDS]; };
@@ -67,18 +68,6 @@ __device__ __forceinline__ void unc_store_u8x4(unsigned char* p, const unsigned 
     } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j) p[j] = (unsigned char)b[j];
-    }
-}
-
-// counts[c] += the workgroup's number of set voxels: wave shuffle, four partials through LDS, one atomic (ensemble.hip, ens_count_add)
-__device__ __forceinline__ void unc_count_add(unsigned local, unsigned* sm, unsigned long long* dst) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long n = (unsigned long long)sm[0] + sm[1] + sm[2] + sm[3];
-        if (n) atomicAdd(dst, n);
     }
 }
 
@@ -189,7 +178,7 @@ __global__ __launch_bounds__(256) void unc_accumulate_kernel(const float* __rest
             }
         }
     }
-    if (FINAL) unc_count_add(local, sm, counts + c);
+    if (FINAL) wg_count_add(local, sm, counts + c);
 }
 
 // stored sums -> mean = S_M / (float)M, mask, counts and the map; acc2 may be null with the entropy measure
@@ -243,7 +232,7 @@ __global__ __launch_bounds__(256) void unc_finalize_kernel(const float* __restri
             }
         }
     }
-    unc_count_add(local, sm, counts + c);
+    wg_count_add(local, sm, counts + c);
 }
 
 // ---------------------------------------------------------------- the score: histogram pass
@@ -312,12 +301,6 @@ __global__ __launch_bounds__(UNC_HIST_THREADS) void unc_histogram_kernel(const u
         for (int w = 0; w < UNC_HIST_WAVES; ++w) t += s[w][i];
         if (t) atomicAdd(i < UNC_BINS ? hist + i : invalid, t);
     }
-}
-
-__global__ void unc_zero_kernel(unsigned long long* __restrict__ a, int na, unsigned long long* __restrict__ b, int nb) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < na) a[i] = 0;
-    else if (b && i < na + nb) b[i - na] = 0;
 }
 
 // ---------------------------------------------------------------- the score: curves and AUCs, one thread per region
@@ -396,8 +379,8 @@ int unc_accumulate_impl(const float* probs, int K, unsigned flips, float* acc, f
     const dim3 grid(grid1d(((size_t)size[0] * size[1] * size[2] + 3) / 4, 256 * 2, 2048), (unsigned)C), block(256);
     const double MK = (double)M * (double)K;
     if (M > 0) {
-        hipLaunchKernelGGL(unc_zero_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, counts, C, nullptr, 0);
-        RU_CHECK_LAUNCH("unc_zero_kernel");
+        hipLaunchKernelGGL((zero2_kernel<u64, u64>), dim3(cdiv(C, 256)), dim3(256), 0, s, counts, (size_t)C, (u64*)nullptr, (size_t)0);
+        RU_CHECK_LAUNCH("zero2_kernel");
         if (first) hipLaunchKernelGGL((unc_accumulate_kernel<true, true>), grid, block, 0, s, probs, K, flips, acc, acc2, (float)M, MK, measure, mean_out, mask, counts, unc, C, D, H, W, b);
         else hipLaunchKernelGGL((unc_accumulate_kernel<false, true>), grid, block, 0, s, probs, K, flips, acc, acc2, (float)M, MK, measure, mean_out, mask, counts, unc, C, D, H, W, b);
     } else {
@@ -439,8 +422,8 @@ extern "C" int ru_unc_finalize(const float* acc, const float* acc2, int M, int K
     RU_REQUIRE(acc2 || measure == RU_UNC_ENTROPY, "ru_unc_finalize: RU_UNC_STD needs the second-moment sum");
     RU_REQUIRE(Vbox < (size_t)INT_MAX, "ru_unc_finalize: volume too large for 32-bit voxel indices");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(unc_zero_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, counts, C, nullptr, 0);
-    RU_CHECK_LAUNCH("unc_zero_kernel");
+    hipLaunchKernelGGL((zero2_kernel<u64, u64>), dim3(cdiv(C, 256)), dim3(256), 0, s, counts, (size_t)C, (u64*)nullptr, (size_t)0);
+    RU_CHECK_LAUNCH("zero2_kernel");
     hipLaunchKernelGGL(unc_finalize_kernel, dim3(grid1d((Vbox + 3) / 4, 256 * 2, 2048), (unsigned)C), dim3(256), 0, s, acc, acc2, (float)M, (double)M * (double)K,
                        measure, mean_out, mask, counts, unc, (unsigned)Vbox);
     RU_CHECK_LAUNCH("unc_finalize_kernel");
@@ -453,8 +436,8 @@ extern "C" int ru_unc_histogram(const unsigned char* pred, const unsigned char* 
     const size_t V = (size_t)D * H * W;
     RU_REQUIRE(V < (1ull << 32), "ru_unc_histogram: volume too large for 32-bit counters per workgroup");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(unc_zero_kernel, dim3(cdiv(UNC_BINS + 1, 256)), dim3(256), 0, s, hist, UNC_BINS, invalid, 1);
-    RU_CHECK_LAUNCH("unc_zero_kernel");
+    hipLaunchKernelGGL((zero2_kernel<u64, u64>), dim3(cdiv(UNC_BINS + 1, 256)), dim3(256), 0, s, hist, (size_t)UNC_BINS, invalid, (size_t)1);
+    RU_CHECK_LAUNCH("zero2_kernel");
     const bool vec = V % 16 == 0 && (((uintptr_t)pred | (uintptr_t)target | (uintptr_t)unc) & 15) == 0;
     if (vec) hipLaunchKernelGGL(unc_histogram_kernel<true>, dim3(grid1d(V / 16, UNC_HIST_THREADS, UNC_HIST_MAX_BLOCKS)), dim3(UNC_HIST_THREADS), 0, s, pred, target,
                                 unc, V, hist, invalid);

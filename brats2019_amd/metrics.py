@@ -291,14 +291,14 @@ class Dice_ITK(Metrics):
         return _get_array(self)
 
 
-class _SurfaceMetric(Metrics):
-    """Per sample and channel i < classes-1 one column of ops.surface_metrics on `pred > 0.5` and `gr > 0.5`; update() adds the batch
-    mean to the float64 device accumulator and never synchronises.  get(): float64 array [classes-1]."""
+class _ColumnMetric(Metrics):
+    """One column of a per-(sample, channel) device scorer on `pred > 0.5` and `gr > 0.5`, channels i < classes-1; update() adds the batch
+    mean to the float64 device accumulator and never reads it back.  A subclass supplies _score (the op: a float64 device tensor
+    [N,C,columns]) and _accumulate (its column-mean op).  get(): float64 array [classes-1]."""
     column = None
-    empty_value = ops.HD95_EMPTY                                                   # HD95's value for one empty mask; not read by the others
 
     def __init__(self, name, input_index, target_index, classes):
-        super(_SurfaceMetric, self).__init__(name)
+        super(_ColumnMetric, self).__init__(name)
         self.input_index = input_index
         self.target_index = target_index
         self.classes = classes
@@ -310,12 +310,21 @@ class _SurfaceMetric(Metrics):
         nacc = self.classes - 1
         if nacc < 1 or nacc > int(pred.shape[1]) or nacc > 64:
             raise IndexError("%s: classes=%d needs 1 <= classes-1 <= %d channels" % (self.name, self.classes, min(int(pred.shape[1]), 64)))
-        values = ops.surface_metrics(pred.cuda(), gr.cuda(), self.empty_value)[0]      # [N,C,4] float64, stays on the device
-        ops.surface_accumulate(values, _acc(self, nacc, values.device), nacc, self.column)
+        values = self._score(pred.cuda(), gr.cuda())                                   # stays on the device
+        self._accumulate(values, _acc(self, nacc, values.device), nacc, self.column)
         self.samples += 1
 
     def get(self):
         return _get_array(self)
+
+
+class _SurfaceMetric(_ColumnMetric):
+    """A column of ops.surface_metrics ([N,C,4])."""
+    empty_value = ops.HD95_EMPTY                                                   # HD95's value for one empty mask; not read by the others
+    _accumulate = staticmethod(ops.surface_accumulate)
+
+    def _score(self, pred, gr):
+        return ops.surface_metrics(pred, gr, self.empty_value)[0]
 
 
 class Hausdorff95(_SurfaceMetric):
@@ -347,33 +356,18 @@ class Specificity(_SurfaceMetric):
         super(Specificity, self).__init__(name, input_index, target_index, classes)
 
 
-class _LesionMetric(Metrics):
-    """Per sample and channel i < classes-1 one column of ops.lesion_metrics on `pred > 0.5` and `gr > 0.5`; update() adds the batch mean
-    to the float64 device accumulator.  get(): float64 array [classes-1]."""
-    column = None
+class _LesionMetric(_ColumnMetric):
+    """A column of ops.lesion_metrics' summary ([N,C,2]); this op reads the lesion counts back, so update() synchronises."""
+    _accumulate = staticmethod(ops.lesion_accumulate)
 
     def __init__(self, name, input_index, target_index, classes, empty_value, dilation, min_volume):
-        super(_LesionMetric, self).__init__(name)
-        self.input_index = input_index
-        self.target_index = target_index
-        self.classes = classes
+        super(_LesionMetric, self).__init__(name, input_index, target_index, classes)
         self.empty_value = empty_value
         self.dilation = dilation
         self.min_volume = min_volume
 
-    def update(self, ground, predict):
-        pred = predict[self.input_index].detach()
-        gr = ground[self.target_index].detach()
-        assert gr.shape == pred.shape
-        nacc = self.classes - 1
-        if nacc < 1 or nacc > int(pred.shape[1]) or nacc > 64:
-            raise IndexError("%s: classes=%d needs 1 <= classes-1 <= %d channels" % (self.name, self.classes, min(int(pred.shape[1]), 64)))
-        summary = ops.lesion_metrics(pred.cuda(), gr.cuda(), self.dilation, self.min_volume, self.empty_value)[0]      # [N,C,2] float64, on the device
-        ops.lesion_accumulate(summary, _acc(self, nacc, summary.device), nacc, self.column)
-        self.samples += 1
-
-    def get(self):
-        return _get_array(self)
+    def _score(self, pred, gr):
+        return ops.lesion_metrics(pred, gr, self.dilation, self.min_volume, self.empty_value)[0]
 
 
 class LesionWiseDice(_LesionMetric):

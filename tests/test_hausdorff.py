@@ -73,7 +73,7 @@ def blob_masks(rng, shape, count, nblobs=3):
     for m in out:
         for _ in range(nblobs):
             c = [rng.uniform(0, s) for s in shape]
-            r = rng.uniform(1.0, 0.3 * min(shape))
+            r = rng.uniform(1.0, max(1.5, 0.3 * min(shape)))                     # (1.5: shapes with an axis of 1)
             m |= (zz - c[0]) ** 2 + (yy - c[1]) ** 2 + (xx - c[2]) ** 2 <= r * r
     return out
 
@@ -163,14 +163,15 @@ def _check_exact(pred, gr, mode, what):
 @pytest.mark.gpu
 def test_hausdorff_sq_is_exact_on_blobs_and_ragged_shapes():
     rng = np.random.default_rng(11)
-    for n, c, shape in [(2, 3, (128, 128, 128)), (2, 2, (5, 6, 7)), (1, 3, (37, 41, 29))]:
+    wide = [(5, 37, 129), (1, 1, 65), (3, 4, 500), (64, 1, 300)]              # rows of more than one 64-voxel word, D = 1, H = 1
+    for n, c, shape in [(2, 3, (128, 128, 128)), (2, 2, (5, 6, 7)), (1, 3, (37, 41, 29))] + [(1, 2, shape) for shape in wide]:
         pm, gm = blob_masks(rng, shape, n * c), blob_masks(rng, shape, n * c)
         pred = soft(rng, pm).reshape((n, c) + shape)
         gr = soft(rng, gm).reshape((n, c) + shape)
         _check_exact(pred, gr, 0, "blobs %s" % (shape,))
         _check_exact(pred, gr, 1, "blobs %s WT" % (shape,))
     # sparse speckle: long gaps in every pass
-    for shape in [(37, 41, 29), (5, 6, 7)]:
+    for shape in [(37, 41, 29), (5, 6, 7)] + wide:
         pred = (rng.random((2, 2) + shape) < 0.004).astype(np.float32)
         gr = (rng.random((2, 2) + shape) < 0.004).astype(np.float32)
         pred[:, :, 0, 0, 0] = gr[:, :, -1, -1, -1] = 1.0
