@@ -102,6 +102,8 @@ SIGNATURES = {
     "ru_lesion_accumulate": (_i, [_vp, _vp] + [_i] * 4 + [_vp]),
     "ru_tile_gather": (_i, [_vp, _vp] + [_i] * 6 + [C.POINTER(_i), _i, _i, _i, _vp]),
     "ru_tile_scatter": (_i, [_vp, _vp] + [_i] * 6 + [C.POINTER(_i), _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
+    "ru_blend_accumulate": (_i, [_vp, _vp, _vp] + [_i] * 8 + [C.POINTER(_i), _i, C.POINTER(_i), _i, C.POINTER(_i), _i, _i, _i, _vp]),
+    "ru_blend_finalize": (_i, [_vp, _vp, _vp] + [_i] * 8 + [C.POINTER(_i), _i, C.POINTER(_i), _i, C.POINTER(_i), _i, _vp]),
     "ru_case_bbox": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "ru_case_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ru_case_stats": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp, _sz, _vp]),

@@ -27,7 +27,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, tiling
 
 TTA_FLIPS = ((), (1,), (2,), (1, 2))          # test.py:117-120, axes of the [C,D,H,W] volume
 
@@ -127,33 +127,50 @@ def prepare_case_device(image):
     return batch, lo, size, left, padded
 
 
-def predict_case_device(model, image, uncertainty=None):
+def _forward(model, batch, tile, overlap, window):
+    """The forward of the batch of flips: whole, or with `tile` set through overlapping tiles blended with `window` (tiling.predict_blended)."""
+    if tile is None:
+        return model([batch])[0]
+    return tiling.predict_blended(model, batch, tile, overlap=overlap, window=window)
+
+
+def _check_tiled(model, tile, overlap, window):
+    if tile is not None:
+        tiling._check_blend(overlap, window)
+        tiling._check_tile(model, tile)
+
+
+def predict_case_device(model, image, uncertainty=None, tile=None, overlap=0.5, window="gaussian"):
     """The per-case pipeline of test.py:82-168 with every array on the device: image [4,D,H,W] device tensor -> (uint8 device label volume
     [D,H,W] with values {0,1,2,4}, int64 device tensor of the (wt, tc, et) voxel counts).  uncertainty="std" | "entropy": the model is
-    served as an ensemble of one and the uint8 [3,D,H,W] uncertainty maps of its four flips are appended."""
+    served as an ensemble of one and the uint8 [3,D,H,W] uncertainty maps of its four flips are appended.  tile=(td, th, tw): the padded
+    crop does not go through the network whole but in tiles overlapping by `overlap`, blended with `window` ("gaussian" | "constant");
+    everything behind the forward is the same."""
     if uncertainty is not None:
-        return predict_case_ensemble_device([model], image, uncertainty=uncertainty)
+        return predict_case_ensemble_device([model], image, uncertainty=uncertainty, tile=tile, overlap=overlap, window=window)
+    _check_tiled(model, tile, overlap, window)
     image = image.contiguous().float()
     batch, lo, size, left, _padded = prepare_case_device(image)
     model.eval()
     if hasattr(model, "freeze_params"):
         model.freeze_params(True)
     with torch.no_grad():
-        probs = model([batch])[0]                                    # [4,3,Dp,Hp,Wp]
+        probs = _forward(model, batch, tile, overlap, window)        # [4,3,Dp,Hp,Wp]
     mask, counts, _ = ops.tta_merge_box(probs, TTA_FLIPS, left, size)
     labels = ops.compose_labels(mask, counts, et_min=32)
     ops.cc_reject(labels, 0.1)
     return ops.paste_labels(labels, image.shape[1:], lo), counts
 
 
-def predict_case(model, image, uncertainty=None):
+def predict_case(model, image, uncertainty=None, tile=None, overlap=0.5, window="gaussian"):
     """Full per-case pipeline of test.py:82-168 for one multimodal volume `image` [4,D,H,W] (numpy or tensor): one upload, the device
     pipeline above, one download.  Returns (uint8 label volume [D,H,W] with values {0,1,2,4}, (wt, tc, et) voxel counts) and, with
-    uncertainty="std" | "entropy", the uint8 [3,D,H,W] uncertainty maps."""
+    uncertainty="std" | "entropy", the uint8 [3,D,H,W] uncertainty maps.  `tile`, `overlap`, `window`: as `predict_case_device`."""
     if uncertainty is not None:
-        return predict_case_ensemble([model], image, uncertainty=uncertainty)
+        return predict_case_ensemble([model], image, uncertainty=uncertainty, tile=tile, overlap=overlap, window=window)
+    _check_tiled(model, tile, overlap, window)
     img = torch.as_tensor(np.asarray(image) if not isinstance(image, torch.Tensor) else image, dtype=torch.float32).cuda()
-    full, counts = predict_case_device(model, img)
+    full, counts = predict_case_device(model, img, tile=tile, overlap=overlap, window=window)
     return full.cpu().numpy(), tuple(int(v) for v in counts.cpu().tolist())
 
 
@@ -316,15 +333,17 @@ def _check_ensemble(models):
     return models
 
 
-def predict_case_ensemble_device(models, image, want_probs=False, uncertainty=None):
+def predict_case_ensemble_device(models, image, want_probs=False, uncertainty=None, tile=None, overlap=0.5, window="gaussian"):
     """`predict_case_device` for a list of models: the case is prepared once, every model runs on the same batch of four flips and its
     prediction enters the running sum before the next forward starts; then labels, component rejection and paste as for one model.
     Returns (labels, counts) and, with want_probs, the float32 [3,D,H,W] mean probabilities pasted into the case's frame (zero outside
     the crop box).  An ensemble of one is `predict_case_device`.  uncertainty="std" | "entropy" appends the uint8 [3,D,H,W] uncertainty
     maps (WT, TC, ET; 0 certain .. 100 uncertain, zero outside the crop box) of the models x flips members, made in the same passes; the
-    other results do not change."""
+    other results do not change.  `tile`, `overlap`, `window`: every model's forward runs as in `predict_case_device`."""
     _check_uncertainty(uncertainty)
     models = _check_ensemble(models)
+    for model in models:
+        _check_tiled(model, tile, overlap, window)
     image = image.contiguous().float()
     if int(image.shape[0]) != int(models[0].conv_input.in_channels):
         raise ValueError("predict_case_ensemble: the case has %d modalities, the models take %d" % (int(image.shape[0]), int(models[0].conv_input.in_channels)))
@@ -335,7 +354,7 @@ def predict_case_ensemble_device(models, image, want_probs=False, uncertainty=No
         if hasattr(model, "freeze_params"):
             model.freeze_params(True)
         with torch.no_grad():
-            probs = model([batch])[0]                                # [4,3,Dp,Hp,Wp]; merged below, released before the next forward
+            probs = _forward(model, batch, tile, overlap, window)    # [4,3,Dp,Hp,Wp]; merged below, released before the next forward
         acc, out = _merge_step(acc, probs, i, len(models), left, size, want_probs, uncertainty)
         del probs
     mask, counts, mean = out[:3]
@@ -349,9 +368,13 @@ def predict_case_ensemble_device(models, image, want_probs=False, uncertainty=No
     return res
 
 
-def predict_case_ensemble(models, image, want_probs=False, uncertainty=None):
+def predict_case_ensemble(models, image, want_probs=False, uncertainty=None, tile=None, overlap=0.5, window="gaussian"):
     """`predict_case` for a list of models (numpy or tensor in, numpy out): one upload, `predict_case_ensemble_device`, one download.
     Returns (labels, counts), then the mean probabilities with want_probs, then the uncertainty maps with `uncertainty`."""
+    _check_uncertainty(uncertainty)
+    models = _check_ensemble(models)
+    for model in models:
+        _check_tiled(model, tile, overlap, window)
     img = torch.as_tensor(np.asarray(image) if not isinstance(image, torch.Tensor) else image, dtype=torch.float32).cuda()
-    out = predict_case_ensemble_device(models, img, want_probs=want_probs, uncertainty=uncertainty)
+    out = predict_case_ensemble_device(models, img, want_probs=want_probs, uncertainty=uncertainty, tile=tile, overlap=overlap, window=window)
     return (out[0].cpu().numpy(), tuple(int(v) for v in out[1].cpu().tolist())) + tuple(t.cpu().numpy() for t in out[2:])

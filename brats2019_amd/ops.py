@@ -312,6 +312,58 @@ def tile_scatter(out, tiles, origins, border, center):
     return out
 
 
+def _blend_geometry(who, volume_shape, tile_shape, starts, profiles):
+    """Host-side checks of the blend entries (before the library is loaded) -> (per-axis start lists, tile extents)."""
+    tile = [int(v) for v in tile_shape]
+    starts = [[int(v) for v in s] for s in starts]
+    if len(tile) != 3 or len(starts) != 3 or any(t <= 0 for t in tile) or any(not s for s in starts):
+        raise ValueError("%s: three positive tile extents and three non-empty start lists are needed" % who)
+    if tile[2] % 4:
+        raise ValueError("%s: the tile width %d is not a multiple of 4" % (who, tile[2]))
+    for s, t, n in zip(starts, tile, volume_shape):
+        if s[0] != 0 or any(b <= a or b > a + t for a, b in zip(s, s[1:])) or s[-1] >= int(n) or s[-1] + t < int(n):
+            raise ValueError("%s: tile starts %s do not cover an axis of %d voxels with tiles of %d (start at 0, strictly increasing, no gap)" % (who, s, int(n), t))
+    if not (isinstance(profiles, torch.Tensor) and profiles.dim() == 1 and int(profiles.numel()) == sum(tile) and profiles.dtype == torch.float32):
+        raise ValueError("%s: `profiles` must be a float32 tensor of td + th + tw = %d values" % (who, sum(tile)))
+    return starts, tile
+
+
+def blend_accumulate(acc, tiles, starts, profiles, t0=0):
+    """Fold the predictions of the tiles t0 .. t0+T-1 (`tiles` [T*N, C, td, th, tw], the layout of `tile_gather`) into the running
+    window-weighted sum `acc` [N,C,D,H,W] in place (csrc/blend.hip).  `starts` = the three per-axis start lists, tile index =
+    (iz*ny + iy)*nx + ix; `profiles` = device float32 [td+th+tw].  The calls of one volume come in rising t0 and cover every tile once;
+    the first touch of a voxel is written, so `acc` needs no memset."""
+    if not (isinstance(acc, torch.Tensor) and acc.dim() == 5 and acc.dtype == torch.float32 and acc.is_contiguous()):
+        raise ValueError("blend_accumulate: `acc` must be a contiguous float32 [N,C,D,H,W] tensor (it is written in place)")
+    n, c, d, h, w = _dims5(acc)
+    if tiles.dim() != 5 or int(tiles.shape[1]) != c or int(tiles.shape[0]) % n:
+        raise ValueError("blend_accumulate: tiles %s do not match a %s volume" % (tuple(tiles.shape), tuple(acc.shape)))
+    starts, (td, th, tw) = _blend_geometry("blend_accumulate", (d, h, w), tiles.shape[2:], starts, profiles)
+    t = int(tiles.shape[0]) // n
+    ntiles = len(starts[0]) * len(starts[1]) * len(starts[2])
+    if not (0 <= int(t0) and t >= 1 and int(t0) + t <= ntiles):
+        raise ValueError("blend_accumulate: tiles %d .. %d of %d" % (int(t0), int(t0) + t - 1, ntiles))
+    tiles = _prep(tiles)
+    L.check(L.load().ru_blend_accumulate(L.f32(tiles), L.f32(acc), L.f32(profiles), n, c, d, h, w, td, th, tw, _ints(starts[0]), len(starts[0]),
+                                         _ints(starts[1]), len(starts[1]), _ints(starts[2]), len(starts[2]), int(t0), t, L.stream()), "ru_blend_accumulate")
+    return acc
+
+
+def blend_finalize(acc, tile_shape, starts, profiles, out=None):
+    """`acc` / Wn with the summed window Wn recomputed from the geometry (csrc/blend.hip) -> `out` (default: in place)."""
+    if not (isinstance(acc, torch.Tensor) and acc.dim() == 5 and acc.dtype == torch.float32 and acc.is_contiguous()):
+        raise ValueError("blend_finalize: `acc` must be a contiguous float32 [N,C,D,H,W] tensor")
+    out = acc if out is None else out
+    if tuple(out.shape) != tuple(acc.shape) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("blend_finalize: `out` must be a contiguous float32 tensor of acc's shape")
+    n, c, d, h, w = _dims5(acc)
+    starts, (td, th, tw) = _blend_geometry("blend_finalize", (d, h, w), tile_shape, starts, profiles)
+    L.require_gpu()
+    L.check(L.load().ru_blend_finalize(L.f32(acc), L.f32(out), L.f32(profiles), n, c, d, h, w, td, th, tw, _ints(starts[0]), len(starts[0]),
+                                       _ints(starts[1]), len(starts[1]), _ints(starts[2]), len(starts[2]), L.stream()), "ru_blend_finalize")
+    return out
+
+
 def case_bbox(image):
     """test.py:47-49 on the device: per modality {min z, y, x, max z, y, x} of the non-zero voxels -> int64 numpy [C,6] (one small copy to
     the host: the crop extents fix the shapes of everything downstream); all-zero modality: {-1,-1,-1, 0,0,0} as loader_helper.bbox3."""

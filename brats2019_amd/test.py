@@ -12,6 +12,10 @@ student network is distilled from -- as float32 `NAME.npy` [3,D,H,W].
 `--uncertainty std|entropy --uncertainty_output DIR` also writes the BraTS uncertainty task's three maps per case, uint8 [D,H,W] with
 values 0 (certain) .. 100 (uncertain): `NAME_unc_whole.npy`, `NAME_unc_core.npy`, `NAME_unc_enhance.npy`, made from the models x flips
 predictions in the passes that merge them (`inference.predict_case_ensemble(..., uncertainty=...)`, csrc/uncertainty.hip).
+
+`--tile D H W [--overlap F] [--window gaussian|constant]` runs every forward as a sliding window over the padded crop: tiles of D x H x W
+overlapping by the fraction F (default 0.5), every predicted voxel used and weighted by the window (`tiling.predict_blended`,
+csrc/blend.hip) -- for a case whose padded crop does not fit the device whole.
 """
 from __future__ import annotations
 
@@ -35,6 +39,9 @@ parser.add_argument("--probs_output", default=None, type=str, help="directory fo
 parser.add_argument("--uncertainty", default=argparse.SUPPRESS, choices=["std", "entropy"], help="uncertainty measure of the maps (with --uncertainty_output)")
 parser.add_argument("--uncertainty_output", default=argparse.SUPPRESS, type=str,
                     help="directory for the uint8 uncertainty maps NAME_unc_whole.npy, NAME_unc_core.npy, NAME_unc_enhance.npy")
+parser.add_argument("--tile", default=argparse.SUPPRESS, type=int, nargs=3, metavar=("D", "H", "W"), help="blended sliding-window forward with tiles of this size")
+parser.add_argument("--overlap", default=argparse.SUPPRESS, type=float, help="overlap of neighbouring tiles as a fraction of the tile, 0 .. 0.75 (with --tile; default 0.5)")
+parser.add_argument("--window", default=argparse.SUPPRESS, choices=["gaussian", "constant"], help="blend window (with --tile; default gaussian)")
 
 
 def _load_net(name, opt):
@@ -52,6 +59,9 @@ def main(argv=None):
     measure, unc_dir = getattr(opt, "uncertainty", None), getattr(opt, "uncertainty_output", None)
     if (measure is None) != (unc_dir is None):
         parser.error("--uncertainty and --uncertainty_output go together")
+    if not hasattr(opt, "tile") and (hasattr(opt, "overlap") or hasattr(opt, "window")):
+        parser.error("--overlap and --window need --tile")
+    tiled = dict(tile=tuple(opt.tile), overlap=getattr(opt, "overlap", 0.5), window=getattr(opt, "window", "gaussian")) if hasattr(opt, "tile") else {}
     print(torch.__version__)
     print(opt)
     net = _load_net(opt.name, opt)
@@ -66,7 +76,7 @@ def main(argv=None):
         cases = [(os.path.splitext(os.path.basename(c))[0], np.load(c)) for c in cases]
     for name, image in cases:
         if others or opt.probs_output or measure:
-            out = inference.predict_case_ensemble([net] + others, image, want_probs=bool(opt.probs_output), uncertainty=measure)
+            out = inference.predict_case_ensemble([net] + others, image, want_probs=bool(opt.probs_output), uncertainty=measure, **tiled)
             labels, (wt, tc, et) = out[0], out[1]
             if opt.probs_output:
                 os.makedirs(opt.probs_output, exist_ok=True)
@@ -74,7 +84,7 @@ def main(argv=None):
             if measure:
                 inference.save_uncertainty(unc_dir, name, out[-1])
         else:
-            labels, (wt, tc, et) = inference.predict_case(net, image)
+            labels, (wt, tc, et) = inference.predict_case(net, image, **tiled)
         if opt.output:
             dst = opt.output if opt.output.endswith(".npy") and len(cases) == 1 else os.path.join(opt.output, name + ".npy")
             os.makedirs(os.path.dirname(os.path.abspath(dst)), exist_ok=True)

@@ -68,3 +68,135 @@ def copy_back(data, tile, center_shape, index_min, index_max, border):
 def grid_for(shape, center_shape):
     """train.py:158: number of centre blocks per axis."""
     return [int(math.ceil(s / c)) for s, c in zip(shape, center_shape)]
+
+
+def auto_batch_tiles(model, tile_shape, nvol, cap=8):
+    """Tiles per forward: as many as fit in a third of the free device memory (the inference arena keeps every activation of a
+    forward: ~5.7 GiB per 192^3 tile in bf16x3, 7.6 GiB in f32), at most `cap`; 1 for a callable without the engine."""
+    net = model.module if hasattr(model, "module") else model
+    if not (torch.cuda.is_available() and hasattr(net, "_get_engine")):
+        return 1
+    from . import _lib as L
+    eng = net._get_engine()
+    per = L.load().ru_unet_workspace_bytes(eng.h, int(nvol), int(tile_shape[0]), int(tile_shape[1]), int(tile_shape[2]), 0)
+    if per == 0:
+        return 1
+    free, _total = torch.cuda.mem_get_info()
+    return int(max(1, min(cap, (free // 3) // per)))
+
+
+# ---------------------------------------------------------------------- overlap-and-blend sliding window (csrc/blend.hip)
+# Tiles overlap, every predicted voxel is used and weighted by a window that falls off towards the tile's edge, where the network saw
+# the least context (the sliding window of nnU-Net / MONAI; the reference pastes centre blocks only).  The arithmetic is fixed --
+# INTEGRATION.md, "Blended sliding window" -- and `blend_host` restates it in numpy float32.
+BLEND_WINDOWS = ("gaussian", "constant")
+BLEND_MAX_OVERLAP = 0.75
+
+
+def _check_blend(overlap, window, sigma_scale=0.125):
+    if not (isinstance(overlap, (int, float)) and 0.0 <= float(overlap) <= BLEND_MAX_OVERLAP):
+        raise ValueError("overlap=%r: a fraction in [0, %g]" % (overlap, BLEND_MAX_OVERLAP))
+    if window not in BLEND_WINDOWS:
+        raise ValueError("window=%r: one of %s" % (window, ", ".join(BLEND_WINDOWS)))
+    if not float(sigma_scale) > 0.0:
+        raise ValueError("sigma_scale=%r must be positive" % (sigma_scale,))
+
+
+def blend_starts(n, tile, overlap=0.5):
+    """Tile starts along an axis of `n` voxels: 0, step, 2*step, ... (step = tile - int(overlap*tile)) while the tile ends before the
+    volume does, then n - tile, so the last tile ends at the volume's end; [0] when one tile holds the axis (it may stick out)."""
+    _check_blend(overlap, "constant")
+    n, tile = int(n), int(tile)
+    if n < 1 or tile < 1:
+        raise ValueError("blend_starts: extents must be positive, got n=%d tile=%d" % (n, tile))
+    if n <= tile:
+        return [0]
+    step = tile - int(overlap * tile)
+    starts, s = [], 0
+    while s + tile < n:
+        starts.append(s)
+        s += step
+    return starts + [n - tile]
+
+
+def blend_profile(tile, window="gaussian", sigma_scale=0.125):
+    """Window profile of one axis, float32 [tile]: exp(-0.5*((i - (tile-1)/2) / (sigma_scale*tile))^2) in float64, rounded; or ones."""
+    _check_blend(0.0, window, sigma_scale)
+    import numpy as np
+    tile = int(tile)
+    if window == "constant":
+        return np.ones(tile, np.float32)
+    i = np.arange(tile, dtype=np.float64)
+    return np.exp(-0.5 * np.square((i - (tile - 1) / 2.0) / (float(sigma_scale) * tile))).astype(np.float32)
+
+
+def blend_origins(starts):
+    """The tiles of a call: the Cartesian product of the three start lists, tile index = (iz*ny + iy)*nx + ix."""
+    return [(int(z), int(y), int(x)) for z in starts[0] for y in starts[1] for x in starts[2]]
+
+
+def blend_host(tiles, shape, tile_shape, starts, profiles):
+    """numpy float32 restatement of csrc/blend.hip: tiles [(t*N + n), C, td, th, tw] of a volume with the spatial extents shape[-3:]
+    -> [N, C, D, H, W].  w = fl32(fl32(gz*gy)*gx); per voxel over its covering tiles in rising tile index S <- S + w*p, Wn <- Wn + w,
+    every product and sum rounded to float32; result S / Wn.  What a tile holds outside the volume is dropped."""
+    import numpy as np
+    tiles = np.asarray(tiles, np.float32)
+    d, h, w = (int(v) for v in tuple(shape)[-3:])
+    td, th, tw = (int(v) for v in tile_shape)
+    origins = blend_origins(starts)
+    n = tiles.shape[0] // len(origins)
+    if tiles.shape[0] != n * len(origins) or tuple(tiles.shape[2:]) != (td, th, tw):
+        raise ValueError("blend_host: tiles %s do not match %d tiles of %s" % (tiles.shape, len(origins), (td, th, tw)))
+    gz, gy, gx = (np.asarray(p, np.float32) for p in profiles)
+    weight = (gz[:, None, None] * gy[None, :, None]) * gx[None, None, :]            # float32 throughout: two roundings
+    total = np.zeros((n, tiles.shape[1], d, h, w), np.float32)
+    norm = np.zeros((d, h, w), np.float32)
+    for t, (oz, oy, ox) in enumerate(origins):
+        ez, ey, ex = min(td, d - oz), min(th, h - oy), min(tw, w - ox)
+        wt = weight[:ez, :ey, :ex]
+        vol = (slice(oz, oz + ez), slice(oy, oy + ey), slice(ox, ox + ex))
+        total[(slice(None), slice(None)) + vol] = total[(slice(None), slice(None)) + vol] + wt * tiles[t * n:(t + 1) * n, :, :ez, :ey, :ex]
+        norm[vol] = norm[vol] + wt
+    return total / norm
+
+
+def _check_tile(model, tile_shape):
+    tile = tuple(int(v) for v in tile_shape)
+    if len(tile) != 3 or any(t <= 0 for t in tile):
+        raise ValueError("tile=%r: three positive extents" % (tile_shape,))
+    if tile[2] % 4:
+        raise ValueError("tile=%r: the tile width must be a multiple of 4 (16-byte rows of the tile kernels)" % (tile,))
+    net = model.module if hasattr(model, "module") else model
+    depth = getattr(net, "depth", None)
+    if isinstance(depth, int) and depth > 1 and any(t % (1 << (depth - 1)) for t in tile):
+        raise ValueError("tile=%r: a network of depth %d takes extents divisible by %d" % (tile, depth, 1 << (depth - 1)))
+    return tile
+
+
+def predict_blended(model, x, tile_shape, overlap=0.5, window="gaussian", sigma_scale=0.125, batch_tiles=None):
+    """Sliding-window forward of `model` (any callable with the `model([tiles])[0]` convention) over x [N,C,D,H,W] on the device with
+    tiles that overlap by `overlap` and are blended with `window` -> [N,C_out,D,H,W] on the device.  Per batch of tiles: `copy_tiles`
+    -> forward -> ops.blend_accumulate; then ops.blend_finalize in place.  The result does not depend on `batch_tiles` (None: sized
+    from the free device memory, at most 8)."""
+    _check_blend(overlap, window, sigma_scale)
+    tile = _check_tile(model, tile_shape)
+    if not (isinstance(x, torch.Tensor) and x.dim() == 5):
+        raise ValueError("predict_blended: x must be an [N,C,D,H,W] tensor")
+    if not x.is_cuda:
+        raise RuntimeError("predict_blended: expected a ROCm device tensor, got a %s tensor (HIP-only path)" % x.device)
+    import numpy as np
+    x = x.contiguous().float()
+    nvol = int(x.shape[0])
+    starts = [blend_starts(n, t, overlap) for n, t in zip(x.shape[2:], tile)]
+    origins = blend_origins(starts)
+    profiles = torch.from_numpy(np.concatenate([blend_profile(t, window, sigma_scale) for t in tile])).to(x.device)
+    per = max(1, int(batch_tiles if batch_tiles is not None else auto_batch_tiles(model, tile, nvol)))
+    acc = None
+    with torch.no_grad():
+        for t0 in range(0, len(origins), per):
+            out = model([copy_tiles(x, tile, origins[t0:t0 + per])])[0]
+            if acc is None:                                                   # the first touch of a voxel is written: no memset
+                acc = torch.empty((nvol, int(out.shape[1])) + tuple(int(v) for v in x.shape[2:]), dtype=torch.float32, device=x.device)
+            ops.blend_accumulate(acc, out, starts, profiles, t0=t0)
+            del out
+    return ops.blend_finalize(acc, tile, starts, profiles)

@@ -275,25 +275,18 @@ class Trainer(object):
             return self.model(self._to_device(batch[0]))
 
     def _auto_batch_tiles(self, tile_shape, nvol, cap=8):
-        """Tiles per forward: as many as fit in a third of the free device memory (the inference arena keeps every activation of a
-        forward: ~5.7 GiB per 192^3 tile in bf16x3, 7.6 GiB in f32), at most `cap`."""
-        net = self.model.module if hasattr(self.model, "module") else self.model
-        if not (torch.cuda.is_available() and hasattr(net, "_get_engine")):
-            return 1
-        from . import _lib as L
-        eng = net._get_engine()
-        per = L.load().ru_unet_workspace_bytes(eng.h, int(nvol), int(tile_shape[0]), int(tile_shape[1]), int(tile_shape[2]), 0)
-        if per == 0:
-            return 1
-        free, _total = torch.cuda.mem_get_info()
-        return int(max(1, min(cap, (free // 3) // per)))
+        """Tiles per forward: as many as fit in a third of the free device memory, at most `cap` (tiling.auto_batch_tiles)."""
+        return tiling.auto_batch_tiles(self.model, tile_shape, nvol, cap)
 
-    def predict_tiled(self, batch, output_shape, tile_shape=None, center_shape=None, border=None, batch_tiles=None):
+    def predict_tiled(self, batch, output_shape, tile_shape=None, center_shape=None, border=None, batch_tiles=None, blend=None, overlap=0.5):
         """train.py:145-176: per centre block, run the model on the zero-padded tile and paste the centre back.
         The volume goes to the device once, tiles are cut there and `batch_tiles` of them share one forward (every op of
         the network is per-sample, so batching tiles does not change a single value); the pasted result stays on the
         device until the end (the reference does .cuda()/.cpu() per tile).  `batch_tiles=None`: sized from the free device
-        memory (at most 8)."""
+        memory (at most 8).  blend="gaussian" | "constant": tiles of `tile_shape` overlapping by `overlap`, every predicted voxel used
+        and weighted by that window (tiling.predict_blended); `center_shape` and `border` are ignored."""
+        if blend is not None:
+            tiling._check_blend(overlap, blend)
         tile_shape = tuple(tile_shape or self.tile_shape)
         center_shape = tuple(center_shape or self.center_shape)
         border = tuple(border or self.border)
@@ -312,6 +305,8 @@ class Trainer(object):
                 dist.all_reduce(t, op=dist.ReduceOp.MIN)
                 batch_tiles = int(t.item())
         inp = inp.contiguous().float()
+        if blend is not None:
+            return [tiling.predict_blended(self.model, inp, tile_shape, overlap=overlap, window=blend, batch_tiles=batch_tiles).cpu()]
         output = torch.zeros(output_shape, dtype=torch.float32, device=inp.device)
         grid = tiling.grid_for(inp.shape[2:], center_shape)
         positions = [(i, j, k) for i in range(grid[0]) for j in range(grid[1]) for k in range(grid[2])]

@@ -341,6 +341,24 @@ int ru_tile_gather(const float* data, float* tiles, int N, int C, int D, int H, 
                    int td, int th, int tw, ru_stream_t stream);
 int ru_tile_scatter(const float* tiles, float* out, int N, int C, int D, int H, int W, int T, const int* origins,
                     int td, int th, int tw, const int* border, const int* center, ru_stream_t stream);
+/* Blended sliding window (csrc/blend.hip): overlapping tiles, every predicted voxel used, weighted by a window that falls off towards the
+ * tile's edge.  Geometry: per axis a HOST list of tile starts, beginning at 0, strictly increasing, without gaps, the last tile reaching
+ * the volume's end (a tile may stick out of the volume: ru_tile_gather reads zeros there, what is predicted there is dropped); the tiles
+ * are the Cartesian product of the three lists, tile index = (iz*ny + iy)*nx + ix.  `profiles` = DEVICE float32 [td + th + tw], the window
+ * profiles gz, gy, gx one behind the other.  Fixed float32 arithmetic, comparable bit for bit with numpy:
+ *   weight of tile voxel (z, y, x)   w = fl32(fl32(gz[z] * gy[y]) * gx[x])
+ *   per volume voxel and channel, over the tiles that cover it IN RISING TILE INDEX:  S <- fl32(S + fl32(w*p)),  Wn <- fl32(Wn + w), from 0
+ *   result = fl32(S / Wn) by a true division; no fma contraction, no atomics: two calls give identical bytes.
+ * ru_blend_accumulate: folds tiles [t0, t0 + T) -- `tiles` holds these T only, in ru_tile_gather's layout [(t*N + n), C, td, th, tw] -- into
+ *   acc [N][C][D][H][W].  A gather over the volume voxels inside the bounding box of the launch's tiles, so overlapping tiles of one call do
+ *   not race and the result does not depend on how the tiles are split into calls.  The calls of one volume must come in rising t0 and cover
+ *   every tile once: a voxel whose smallest covering tile index is >= t0 is WRITTEN (S starts from 0, acc is not read -- no memset), every
+ *   other one continues from acc.  tw % 4 == 0; tile rows are read 16 bytes at a time where (x - start_x) % 4 == 0, by dwords elsewhere.
+ * ru_blend_finalize: out = acc / Wn with Wn recomputed from the start lists and the profiles (no second volume); out may alias acc.  */
+int ru_blend_accumulate(const float* tiles, float* acc, const float* profiles, int N, int C, int D, int H, int W, int td, int th, int tw,
+                        const int* starts_z, int nz, const int* starts_y, int ny, const int* starts_x, int nx, int t0, int T, ru_stream_t stream);
+int ru_blend_finalize(const float* acc, float* out, const float* profiles, int N, int C, int D, int H, int W, int td, int th, int tw,
+                      const int* starts_z, int nz, const int* starts_y, int ny, const int* starts_x, int nx, ru_stream_t stream);
 /* Case preparation (test.py:47-49,85-120).  ru_case_bbox: box[c*6 .. c*6+5] (DEVICE ints) = {min z, y, x, max z, y, x} of the non-zero
  * voxels of modality c of image [C][D][H][W]; {INT_MAX x3, -1 x3} for an all-zero modality (the host applies test.py:47-49's union and
  * its rule for empty modalities).  ru_case_stats: per channel over the crop box [lo, lo + size): stats[c*3..] = count(x > 0), sum x,
