@@ -112,6 +112,8 @@ SIGNATURES = {
     "ru_cc_workspace_bytes": (_sz, [_i, _i, _i]),
     "ru_cc_reject": (_i, [_vp, _i, _i, _i, _d, _vp, _sz, _vp]),
     "ru_paste_labels": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
+    "ru_postprocess_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ru_postprocess_regions": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_longlong), C.POINTER(C.c_ulonglong), C.c_uint, C.c_uint, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ru_ens_accumulate": (_i, [_vp, _i, C.c_uint, _vp, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
     "ru_ens_finalize": (_i, [_vp, _i, _vp, _vp, _vp, _i, _sz, _vp]),
     "ru_ens_accumulate_finalize": (_i, [_vp, _i, C.c_uint, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
@@ -161,6 +163,9 @@ SURFACE_COLUMNS = {"dice": 0, "sensitivity": 1, "specificity": 2, "hd95": 3}
 # ru_lesion_metrics / ru_lesion_accumulate (include/resunet_hip.h)
 LESION_COUNTS, LESION_TABLE_COLUMNS, LESION_CHUNK = 6, 5, 8
 LESION_COLUMNS = {"dice": 0, "hd95": 1}
+
+# ru_postprocess_regions (include/resunet_hip.h)
+POSTPROCESS_MASKS, POSTPROCESS_LABELS, POSTPROCESS_REGIONS, POSTPROCESS_STATS = 0, 1, 3, 6
 
 
 class CritTerm(C.Structure):

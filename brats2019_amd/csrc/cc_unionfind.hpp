@@ -1,4 +1,5 @@
-// 26-connected component labelling by union-find on voxel indices (inference.hip: ru_cc_reject; lesion.hip: ru_lesion_metrics).
+// 26-connected component labelling by union-find on voxel indices (inference.hip: ru_cc_reject; lesion.hip: ru_lesion_metrics;
+// postprocess.hip: ru_postprocess_regions, which also labels the background 6-connected -- CONN = 6 below, 3 earlier neighbours instead of 13).
 // parent[v] = v for a root, a smaller index of the same component otherwise, -1 for background; roots are the smallest index of their
 // component (atomicMin), which is also the order in which scipy.ndimage.label numbers components.  Each voxel is united with its 13
 // "earlier" neighbours of the 26-neighbourhood (the other 13 are covered from the neighbour's side), in three passes instead of one
@@ -35,12 +36,20 @@ __device__ __forceinline__ void cc_unite(int* parent, int a, int b) {
 // the 13 neighbours that precede a voxel in linear order: (dz, dy, dx) with dz = -1, or dz = 0 and dy = -1, or dz = dy = 0 and dx = -1
 __device__ __forceinline__ bool cc_earlier(int dz, int dy, int dx) { return dz < 0 || (dz == 0 && (dy < 0 || (dy == 0 && dx < 0))); }
 
-// visit(u, row, x) for every earlier neighbour u = row * W + x of voxel v that lies inside the grid
-template <class Visit>
+// visit(u, row, x) for every earlier neighbour u = row * W + x of voxel v that lies inside the grid; CONN = 6: the three face neighbours
+// (z - 1), (y - 1), (x - 1) only, in the same (ascending) order
+template <int CONN = 26, class Visit>
 __device__ __forceinline__ void cc_for_earlier(size_t v, int H, int W, Visit visit) {
+    static_assert(CONN == 26 || CONN == 6, "cc_for_earlier: 26- or 6-connected");
     const int x = (int)(v % W);
     const size_t r = v / W;
     const int y = (int)(r % H), z = (int)(r / H);
+    if constexpr (CONN == 6) {
+        if (z > 0) visit(v - (size_t)H * W, r - H, x);
+        if (y > 0) visit(v - W, r - 1, x);
+        if (x > 0) visit(v - 1, r, x - 1);
+        return;
+    }
 #pragma unroll
     for (int dz = -1; dz <= 0; ++dz)
 #pragma unroll
@@ -59,7 +68,7 @@ namespace {
 
 // Fg: void select(int y, int z) once per block, then bool operator()(size_t row, int x): is voxel x of row (z * H + y) foreground?
 // `count` (may be null) holds one array of V per y; the last z clears it.
-template <class Fg>
+template <class Fg, int CONN = 26>
 __global__ __launch_bounds__(256) void cc_init_kernel(Fg fg, int* __restrict__ parent, size_t zpitch, int* __restrict__ count, int D, int H, int W) {
     const size_t V = (size_t)D * H * W;
     fg.select(blockIdx.y, blockIdx.z);
@@ -69,7 +78,7 @@ __global__ __launch_bounds__(256) void cc_init_kernel(Fg fg, int* __restrict__ p
         if (clear) count[blockIdx.y * V + v] = 0;
         if (!fg(v / W, (int)(v % W))) { parent[v] = -1; continue; }
         int m = (int)v;
-        cc_for_earlier(v, H, W, [&](size_t u, size_t row, int x) {
+        cc_for_earlier<CONN>(v, H, W, [&](size_t u, size_t row, int x) {
             if ((int)u < m && fg(row, x)) m = (int)u;
         });
         parent[v] = m;
@@ -85,13 +94,14 @@ __global__ __launch_bounds__(256) void cc_compress_kernel(int* parent, size_t zp
     }
 }
 
+template <int CONN = 26>
 __global__ __launch_bounds__(256) void cc_merge_kernel(int* parent, size_t zpitch, int D, int H, int W) {
     const size_t V = (size_t)D * H * W;
     parent += blockIdx.z * zpitch + blockIdx.y * V;
     for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < V; v += (size_t)gridDim.x * 256) {
         const int pv = parent[v];
         if (pv < 0) continue;
-        cc_for_earlier(v, H, W, [&](size_t u, size_t, int) {
+        cc_for_earlier<CONN>(v, H, W, [&](size_t u, size_t, int) {
             const int pu = parent[u];
             if (pu >= 0 && pu != pv) cc_unite(parent, (int)v, (int)u);       // (equal parents: one tree already; a stale read only costs a redundant unite)
         });
@@ -126,15 +136,15 @@ __device__ __forceinline__ void cc_count_members(const int* parent, int* count, 
     if (run_cnt && (threadIdx.x & 63) == 0) atomicAdd(count + run_root, run_cnt);
 }
 
-// init, compress, merge, compress on stream st; grid = (blocks over V, volumes per z, z)
-template <class Fg>
+// init, compress, merge, compress on stream st; grid = (blocks over V, volumes per z, z); cc_label<6>(...) labels 6-connected
+template <int CONN = 26, class Fg>
 inline int cc_label(const Fg& fg, int* parent, size_t zpitch, int* count, int D, int H, int W, dim3 grid, hipStream_t st) {
     const size_t V = (size_t)D * H * W;
-    hipLaunchKernelGGL(cc_init_kernel<Fg>, grid, dim3(256), 0, st, fg, parent, zpitch, count, D, H, W);
+    hipLaunchKernelGGL((cc_init_kernel<Fg, CONN>), grid, dim3(256), 0, st, fg, parent, zpitch, count, D, H, W);
     RU_CHECK_LAUNCH("cc_init_kernel");
     hipLaunchKernelGGL(cc_compress_kernel, grid, dim3(256), 0, st, parent, zpitch, V);
     RU_CHECK_LAUNCH("cc_compress_kernel");
-    hipLaunchKernelGGL(cc_merge_kernel, grid, dim3(256), 0, st, parent, zpitch, D, H, W);
+    hipLaunchKernelGGL(cc_merge_kernel<CONN>, grid, dim3(256), 0, st, parent, zpitch, D, H, W);
     RU_CHECK_LAUNCH("cc_merge_kernel");
     hipLaunchKernelGGL(cc_compress_kernel, grid, dim3(256), 0, st, parent, zpitch, V);
     RU_CHECK_LAUNCH("cc_compress_kernel");

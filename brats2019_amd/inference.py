@@ -7,6 +7,8 @@ of the case to the download of its label volume (kernels in csrc
   ru_case_prepare   crop + zero-pad to x16 (test.py:92-99) + z-score (:113) + the FOUR test-time flips (:115-120) written as ONE batch;
   model             one batch-4 forward instead of four forward calls with host round trips (:124-132);
   ru_tta_merge_box  un-flip + average + un-pad + threshold + per-class counts (:134-144); ru_compose_labels (:146-159);
+  ru_postprocess_regions  opt-in (`postprocess=PostProcess(...)`): per region, components below a volume or a mean probability go, only the
+                    largest stays, holes are filled, the regions are nested -- between the merge and the label composition (csrc/postprocess.hip);
   ru_cc_reject      26-connected components (skimage.morphology.label) + rejection of regions below ratio 0.1 (:51-62,162-164);
   ru_paste_labels   paste into the full volume (:167-168).
 
@@ -22,6 +24,7 @@ takes and returns arrays.
 """
 from __future__ import annotations
 
+import collections
 import os
 
 import numpy as np
@@ -101,14 +104,133 @@ def predict_tta(model, x, pad_left=(0, 0, 0), pad_right=(0, 0, 0), want_mean=Fal
     return labels, counts, mean
 
 
-def postprocess_labels(labels):
+def postprocess_labels(labels, ratio=0.1):
     """test.py:162-164 on the host (26-connected components, ratio 0.1)."""
     import scipy.ndimage as ndi
     comp, _ = ndi.label(labels > 0, structure=np.ones((3, 3, 3), dtype=bool))
-    clusters = reject_small_regions(comp, 0.1)
+    clusters = reject_small_regions(comp, ratio)
     labels = labels.copy()
     labels[clusters == 0] = 0
     return labels
+
+
+# ---------------------------------------------------------------------- region-wise post-processing (csrc/postprocess.hip)
+class PostProcess(collections.namedtuple("PostProcess", "min_volume min_confidence keep_largest fill_holes nest reject_ratio")):
+    """The post-processing of one case, the `postprocess=` keyword of `predict_case*`: the parameters of `ops.postprocess_regions` (a scalar
+    or a triple WT, TC, ET each; INTEGRATION.md states the definition) and `reject_ratio`, the reference's own step on the union of all
+    labels (test.py:162-164, `ops.cc_reject`), which stays by default; None switches it off.  `PostProcess()` changes nothing."""
+    __slots__ = ()
+
+    def __new__(cls, min_volume=0, min_confidence=0.0, keep_largest=False, fill_holes=False, nest=False, reject_ratio=0.1):
+        mv, _, kl, fh = ops.postprocess_params(min_volume, min_confidence, keep_largest, fill_holes)           # (raises on a bad value)
+        if reject_ratio is not None and not float(reject_ratio) >= 0.0:
+            raise ValueError("PostProcess: reject_ratio %r: a ratio >= 0 or None" % (reject_ratio,))
+        mc = tuple(float(c) for c in min_confidence) if hasattr(min_confidence, "__len__") else (float(min_confidence),) * 3
+        return super().__new__(cls, tuple(mv), mc, tuple(bool((kl >> k) & 1) for k in range(3)), tuple(bool((fh >> k) & 1) for k in range(3)), bool(nest),
+                               None if reject_ratio is None else float(reject_ratio))        # every per-region field is stored as a triple WT, TC, ET
+
+    @property
+    def needs_probs(self):
+        """the confidence rule of some region is on: the merge passes must return the mean probabilities"""
+        return any(ops.postprocess_params(self.min_volume, self.min_confidence)[1])
+
+    def regions(self):
+        """the keywords of `ops.postprocess_regions` / `postprocess_regions_host`"""
+        return dict(min_volume=self.min_volume, min_confidence=self.min_confidence, keep_largest=self.keep_largest, fill_holes=self.fill_holes,
+                    nest=self.nest)
+
+
+def _check_postprocess(postprocess):
+    if postprocess is not None and not isinstance(postprocess, PostProcess):
+        raise ValueError("postprocess=%r: None or an inference.PostProcess" % (postprocess,))
+    return postprocess
+
+
+def postprocess_regions_host(x, probs=None, min_volume=0, min_confidence=0.0, keep_largest=False, fill_holes=False, nest=False, want_stats=False):
+    """`ops.postprocess_regions` restated with numpy and scipy (INTEGRATION.md states the definition): the oracle of the device tests and the
+    `--host` path of `python -m brats2019_amd.postprocess`.  x: masks [3, D, H, W] (non-zero = foreground) -> (uint8 masks, int64 counts
+    [3]), or a uint8 label volume [D, H, W] -> (uint8 labels, counts); want_stats appends the int64 statistics [3, 5] / [3, 6]."""
+    import scipy.ndimage as ndi
+    mv, thr, kl, fh = ops.postprocess_params(min_volume, min_confidence, keep_largest, fill_holes)
+    x = np.asarray(x)
+    labels_in = x.ndim == 3
+    if not (labels_in or (x.ndim == 4 and x.shape[0] == 3)):
+        raise ValueError("postprocess_regions_host: masks [3, D, H, W] or a label volume [D, H, W], got %s" % (x.shape,))
+    if any(thr) and probs is None:
+        raise ValueError("postprocess_regions_host: min_confidence > 0 needs the probabilities")
+    if probs is not None and (labels_in or tuple(np.shape(probs)) != x.shape):
+        raise ValueError("postprocess_regions_host: probabilities go with masks and have their shape")
+    if labels_in:
+        regions = [(x >= 1) & (x <= 4), (x == 1) | (x == 3) | (x == 4), (x == 3) | (x == 4)]
+    else:
+        regions = [x[k] != 0 for k in range(3)]
+    q = None
+    if any(thr):                                                     # q(p): an exact float32 product by 2^16, truncated
+        q = np.floor(np.clip(np.asarray(probs, np.float32), np.float32(0), np.float32(1)) * np.float32(65536.0)).astype(np.int64)
+    stats = np.zeros((3, 6 if labels_in else 5), np.int64)
+    out = []
+    for k, r in enumerate(regions):
+        comp, n = ndi.label(r, structure=np.ones((3, 3, 3), dtype=bool))          # numbered by ascending smallest linear index
+        vol = np.bincount(comp.ravel(), minlength=n + 1).astype(np.int64)
+        keep = np.ones(n + 1, bool)
+        keep[0] = False
+        small = keep & (vol < mv[k])
+        keep &= ~small
+        stats[k, 0], stats[k, 1] = n, small.sum()
+        if thr[k] > 0:
+            conf = np.bincount(comp.ravel(), weights=q[k].ravel(), minlength=n + 1).astype(np.int64)    # (sums below 2^53: exact in float64)
+            low = keep & (conf < thr[k] * vol)
+            keep &= ~low
+            stats[k, 2] = low.sum()
+        if (kl >> k) & 1 and keep.any():
+            alive = np.flatnonzero(keep)
+            best = alive[np.argmax(vol[alive])]                      # the first maximum: the smallest label, the smallest linear index
+            stats[k, 3] = alive.size - 1
+            keep[:] = False
+            keep[best] = True
+        r = keep[comp]
+        if (fh >> k) & 1:
+            filled = ndi.binary_fill_holes(r)
+            stats[k, 4] = int(filled.sum()) - int(r.sum())
+            r = filled
+        out.append(r)
+    if nest:
+        out[1] = out[1] & out[0]
+        out[2] = out[2] & out[1]
+    counts = np.array([int(r.sum()) for r in out], np.int64)
+    if labels_in:
+        stats[:, 5] = int((x > 4).sum())
+        res = np.zeros(x.shape, np.uint8)
+        res[out[0]] = 2
+        res[out[1]] = 1
+        res[out[2]] = 4
+    else:
+        res = np.stack(out).astype(np.uint8)
+    return (res, counts, stats) if want_stats else (res, counts)
+
+
+def compose_masks_host(mask, counts, et_min=32):
+    """test.py:153-159 from the three masks and their counts (`ops.compose_labels`): ET only with more than `et_min` ET voxels."""
+    m = np.asarray(mask) != 0
+    out = np.zeros(m.shape[1:], np.uint8)
+    out[m[0]] = 2
+    out[m[1]] = 1
+    if int(counts[2]) > et_min:
+        out[m[2]] = 4
+    return out
+
+
+def _labels_from_masks(mask, counts, mean, postprocess):
+    """masks of the merge -> (label volume in the crop frame, counts): the region pass of `postprocess` (if any), test.py:153-159, and the
+    reference's rejection on the union of all labels unless `postprocess` switches it off"""
+    ratio = 0.1
+    if postprocess is not None:
+        mask, counts = ops.postprocess_regions(mask, probs=mean if postprocess.needs_probs else None, **postprocess.regions())
+        ratio = postprocess.reject_ratio
+    labels = ops.compose_labels(mask, counts, et_min=32)
+    if ratio is not None:
+        ops.cc_reject(labels, ratio)
+    return labels, counts
 
 
 def prepare_case_device(image):
@@ -140,14 +262,17 @@ def _check_tiled(model, tile, overlap, window):
         tiling._check_tile(model, tile)
 
 
-def predict_case_device(model, image, uncertainty=None, tile=None, overlap=0.5, window="gaussian"):
+def predict_case_device(model, image, uncertainty=None, tile=None, overlap=0.5, window="gaussian", postprocess=None):
     """The per-case pipeline of test.py:82-168 with every array on the device: image [4,D,H,W] device tensor -> (uint8 device label volume
     [D,H,W] with values {0,1,2,4}, int64 device tensor of the (wt, tc, et) voxel counts).  uncertainty="std" | "entropy": the model is
     served as an ensemble of one and the uint8 [3,D,H,W] uncertainty maps of its four flips are appended.  tile=(td, th, tw): the padded
     crop does not go through the network whole but in tiles overlapping by `overlap`, blended with `window` ("gaussian" | "constant");
-    everything behind the forward is the same."""
+    everything behind the forward is the same.  postprocess=PostProcess(...): the region pass (`ops.postprocess_regions`) runs on the merged
+    masks in the crop frame before the labels are composed, so the ET > 32 rule and the returned counts are those of the post-processed
+    masks; the uncertainty maps are not touched."""
+    _check_postprocess(postprocess)
     if uncertainty is not None:
-        return predict_case_ensemble_device([model], image, uncertainty=uncertainty, tile=tile, overlap=overlap, window=window)
+        return predict_case_ensemble_device([model], image, uncertainty=uncertainty, tile=tile, overlap=overlap, window=window, postprocess=postprocess)
     _check_tiled(model, tile, overlap, window)
     image = image.contiguous().float()
     batch, lo, size, left, _padded = prepare_case_device(image)
@@ -156,21 +281,21 @@ def predict_case_device(model, image, uncertainty=None, tile=None, overlap=0.5, 
         model.freeze_params(True)
     with torch.no_grad():
         probs = _forward(model, batch, tile, overlap, window)        # [4,3,Dp,Hp,Wp]
-    mask, counts, _ = ops.tta_merge_box(probs, TTA_FLIPS, left, size)
-    labels = ops.compose_labels(mask, counts, et_min=32)
-    ops.cc_reject(labels, 0.1)
+    mask, counts, mean = ops.tta_merge_box(probs, TTA_FLIPS, left, size, want_mean=postprocess is not None and postprocess.needs_probs)
+    labels, counts = _labels_from_masks(mask, counts, mean, postprocess)
     return ops.paste_labels(labels, image.shape[1:], lo), counts
 
 
-def predict_case(model, image, uncertainty=None, tile=None, overlap=0.5, window="gaussian"):
+def predict_case(model, image, uncertainty=None, tile=None, overlap=0.5, window="gaussian", postprocess=None):
     """Full per-case pipeline of test.py:82-168 for one multimodal volume `image` [4,D,H,W] (numpy or tensor): one upload, the device
     pipeline above, one download.  Returns (uint8 label volume [D,H,W] with values {0,1,2,4}, (wt, tc, et) voxel counts) and, with
-    uncertainty="std" | "entropy", the uint8 [3,D,H,W] uncertainty maps.  `tile`, `overlap`, `window`: as `predict_case_device`."""
+    uncertainty="std" | "entropy", the uint8 [3,D,H,W] uncertainty maps.  `tile`, `overlap`, `window`, `postprocess`: as `predict_case_device`."""
+    _check_postprocess(postprocess)
     if uncertainty is not None:
-        return predict_case_ensemble([model], image, uncertainty=uncertainty, tile=tile, overlap=overlap, window=window)
+        return predict_case_ensemble([model], image, uncertainty=uncertainty, tile=tile, overlap=overlap, window=window, postprocess=postprocess)
     _check_tiled(model, tile, overlap, window)
     img = torch.as_tensor(np.asarray(image) if not isinstance(image, torch.Tensor) else image, dtype=torch.float32).cuda()
-    full, counts = predict_case_device(model, img, tile=tile, overlap=overlap, window=window)
+    full, counts = predict_case_device(model, img, tile=tile, overlap=overlap, window=window, postprocess=postprocess)
     return full.cpu().numpy(), tuple(int(v) for v in counts.cpu().tolist())
 
 
@@ -333,14 +458,16 @@ def _check_ensemble(models):
     return models
 
 
-def predict_case_ensemble_device(models, image, want_probs=False, uncertainty=None, tile=None, overlap=0.5, window="gaussian"):
+def predict_case_ensemble_device(models, image, want_probs=False, uncertainty=None, tile=None, overlap=0.5, window="gaussian", postprocess=None):
     """`predict_case_device` for a list of models: the case is prepared once, every model runs on the same batch of four flips and its
     prediction enters the running sum before the next forward starts; then labels, component rejection and paste as for one model.
     Returns (labels, counts) and, with want_probs, the float32 [3,D,H,W] mean probabilities pasted into the case's frame (zero outside
     the crop box).  An ensemble of one is `predict_case_device`.  uncertainty="std" | "entropy" appends the uint8 [3,D,H,W] uncertainty
     maps (WT, TC, ET; 0 certain .. 100 uncertain, zero outside the crop box) of the models x flips members, made in the same passes; the
-    other results do not change.  `tile`, `overlap`, `window`: every model's forward runs as in `predict_case_device`."""
+    other results do not change.  `tile`, `overlap`, `window`: every model's forward runs as in `predict_case_device`.  `postprocess`: as
+    there, on the masks of the ensemble mean; the soft labels and the uncertainty maps are those of the merge, not post-processed."""
     _check_uncertainty(uncertainty)
+    _check_postprocess(postprocess)
     models = _check_ensemble(models)
     for model in models:
         _check_tiled(model, tile, overlap, window)
@@ -355,11 +482,10 @@ def predict_case_ensemble_device(models, image, want_probs=False, uncertainty=No
             model.freeze_params(True)
         with torch.no_grad():
             probs = _forward(model, batch, tile, overlap, window)    # [4,3,Dp,Hp,Wp]; merged below, released before the next forward
-        acc, out = _merge_step(acc, probs, i, len(models), left, size, want_probs, uncertainty)
+        acc, out = _merge_step(acc, probs, i, len(models), left, size, want_probs or (postprocess is not None and postprocess.needs_probs), uncertainty)
         del probs
     mask, counts, mean = out[:3]
-    labels = ops.compose_labels(mask, counts, et_min=32)
-    ops.cc_reject(labels, 0.1)
+    labels, counts = _labels_from_masks(mask, counts, mean, postprocess)
     res = (ops.paste_labels(labels, image.shape[1:], lo), counts)
     if want_probs:
         res += (ops.paste_probs(mean, image.shape[1:], lo),)
@@ -368,13 +494,42 @@ def predict_case_ensemble_device(models, image, want_probs=False, uncertainty=No
     return res
 
 
-def predict_case_ensemble(models, image, want_probs=False, uncertainty=None, tile=None, overlap=0.5, window="gaussian"):
+def predict_case_ensemble(models, image, want_probs=False, uncertainty=None, tile=None, overlap=0.5, window="gaussian", postprocess=None):
     """`predict_case` for a list of models (numpy or tensor in, numpy out): one upload, `predict_case_ensemble_device`, one download.
     Returns (labels, counts), then the mean probabilities with want_probs, then the uncertainty maps with `uncertainty`."""
     _check_uncertainty(uncertainty)
+    _check_postprocess(postprocess)
     models = _check_ensemble(models)
     for model in models:
         _check_tiled(model, tile, overlap, window)
     img = torch.as_tensor(np.asarray(image) if not isinstance(image, torch.Tensor) else image, dtype=torch.float32).cuda()
-    out = predict_case_ensemble_device(models, img, want_probs=want_probs, uncertainty=uncertainty, tile=tile, overlap=overlap, window=window)
+    out = predict_case_ensemble_device(models, img, want_probs=want_probs, uncertainty=uncertainty, tile=tile, overlap=overlap, window=window,
+                                       postprocess=postprocess)
     return (out[0].cpu().numpy(), tuple(int(v) for v in out[1].cpu().tolist())) + tuple(t.cpu().numpy() for t in out[2:])
+
+
+# ---------------------------------------------------------------------- the post-processing flags of test, ensemble and postprocess
+def add_postprocess_arguments(parser):
+    """--min_volume, --min_confidence, --keep_largest, --fill_holes, --nest, --no_reject.  SUPPRESS: without them the namespace does not change."""
+    import argparse
+    names = list(ops.REGION_NAMES)
+    parser.add_argument("--min_volume", default=argparse.SUPPRESS, type=int, nargs=3, metavar=("WT", "TC", "ET"),
+                        help="drop the 26-connected components of a region with fewer voxels")
+    parser.add_argument("--min_confidence", default=argparse.SUPPRESS, type=float, nargs=3, metavar=("WT", "TC", "ET"),
+                        help="drop the components of a region whose mean probability is lower (0 .. 1)")
+    parser.add_argument("--keep_largest", default=argparse.SUPPRESS, nargs="+", choices=names, help="regions of which only the largest component stays")
+    parser.add_argument("--fill_holes", default=argparse.SUPPRESS, nargs="+", choices=names, help="regions whose enclosed holes are filled")
+    parser.add_argument("--nest", default=argparse.SUPPRESS, action="store_true", help="cut TC to WT and ET to TC")
+    parser.add_argument("--no_reject", default=argparse.SUPPRESS, action="store_true",
+                        help="without the reference's rejection of small components of the union of all labels (ratio 0.1)")
+
+
+def postprocess_from_args(opt):
+    """The `PostProcess` of a parsed namespace; None when none of the flags of `add_postprocess_arguments` was given."""
+    flags = ("min_volume", "min_confidence", "keep_largest", "fill_holes", "nest", "no_reject")
+    if not any(hasattr(opt, f) for f in flags):
+        return None
+    which = lambda f: tuple(n in getattr(opt, f, ()) for n in ops.REGION_NAMES)
+    return PostProcess(min_volume=tuple(getattr(opt, "min_volume", (0, 0, 0))), min_confidence=tuple(getattr(opt, "min_confidence", (0.0, 0.0, 0.0))),
+                       keep_largest=which("keep_largest"), fill_holes=which("fill_holes"), nest=getattr(opt, "nest", False),
+                       reject_ratio=None if getattr(opt, "no_reject", False) else 0.1)

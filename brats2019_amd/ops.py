@@ -426,6 +426,65 @@ def cc_reject(labels, ratio=0.1):
     return labels
 
 
+REGION_NAMES = ("wt", "tc", "et")      # the order of the model's channels and of every per-region parameter
+
+
+def postprocess_params(min_volume=0, min_confidence=0.0, keep_largest=False, fill_holes=False):
+    """The per-region parameters of `postprocess_regions` (a scalar or a triple WT, TC, ET each) as the integers the kernels and the host
+    restatement compare: (min_volume [3], T [3] = floor(min_confidence * 65536.0) in float64, keep_largest bits, fill_holes bits)."""
+    import math
+
+    def triple(v, name):
+        if isinstance(v, (str, bytes)) or not hasattr(v, "__len__"):
+            return (v, v, v)
+        if len(v) != 3:
+            raise ValueError("postprocess_regions: %s takes a scalar or one value per region (WT, TC, ET), got %r" % (name, v))
+        return tuple(v)
+
+    mv = [int(v) for v in triple(min_volume, "min_volume")]
+    mc = [float(v) for v in triple(min_confidence, "min_confidence")]
+    if any(v < 0 for v in mv) or any(int(a) != a for a in triple(min_volume, "min_volume")):
+        raise ValueError("postprocess_regions: min_volume %r: integers >= 0" % (min_volume,))
+    if any(not 0.0 <= c <= 1.0 for c in mc):
+        raise ValueError("postprocess_regions: min_confidence %r: values in [0, 1]" % (min_confidence,))
+    thr = [int(math.floor(c * 65536.0)) for c in mc]
+    bits = lambda v, name: sum(1 << k for k, b in enumerate(triple(v, name)) if bool(b))
+    return mv, thr, bits(keep_largest, "keep_largest"), bits(fill_holes, "fill_holes")
+
+
+def postprocess_regions(x, probs=None, min_volume=0, min_confidence=0.0, keep_largest=False, fill_holes=False, nest=False, want_stats=False):
+    """Region-wise post-processing on the device (include/resunet_hip.h, ru_postprocess_regions; INTEGRATION.md states the definition).
+    x: uint8 device masks [3, D, H, W] (WT, TC, ET; non-zero = foreground) -> (masks uint8 [3, D, H, W] of 0 / 1, counts int64 [3]), or a
+    uint8 device label volume [D, H, W] with values {0, 1, 2, 4} (3 read as 4, above 4 background) -> (labels, counts of WT, TC, ET).
+    Per region, a scalar or a triple each: 26-connected components below `min_volume` voxels go; with `probs` (float32 [3, D, H, W], masks
+    only) those whose mean probability is below `min_confidence`; with `keep_largest` all but the largest survivor; `fill_holes` fills
+    the enclosed 6-connected background; `nest` cuts TC to WT and ET to TC.  want_stats appends int64 [3, 5] = (components found, removed
+    by volume, by confidence only, by keep_largest, voxels filled), for a label volume [3, 6] with the invalid voxels (above 4) last.
+    `x` is not written; nothing synchronises; two calls give identical bytes."""
+    mv, thr, kl, fh = postprocess_params(min_volume, min_confidence, keep_largest, fill_holes)
+    if not (isinstance(x, torch.Tensor) and x.dtype == torch.uint8 and (x.dim() == 3 or (x.dim() == 4 and int(x.shape[0]) == L.POSTPROCESS_REGIONS))):
+        raise ValueError("postprocess_regions: uint8 masks [3, D, H, W] or a uint8 label volume [D, H, W]")
+    kind = L.POSTPROCESS_LABELS if x.dim() == 3 else L.POSTPROCESS_MASKS
+    if any(thr) and probs is None:
+        raise ValueError("postprocess_regions: min_confidence > 0 needs the probabilities")
+    if probs is not None and (kind == L.POSTPROCESS_LABELS or tuple(probs.shape) != tuple(x.shape)):
+        raise ValueError("postprocess_regions: probabilities go with masks and have their shape, got %s for %s" % (tuple(probs.shape), tuple(x.shape)))
+    L.require_gpu()
+    x = x.contiguous()
+    d, h, w = (int(v) for v in x.shape[-3:])
+    lib = L.load()
+    out = torch.empty_like(x)
+    counts = torch.empty(L.POSTPROCESS_REGIONS, dtype=torch.int64, device=x.device)
+    stats = torch.empty((L.POSTPROCESS_REGIONS, L.POSTPROCESS_STATS), dtype=torch.int64, device=x.device)
+    ws = L.workspace(lib.ru_postprocess_workspace_bytes(kind, d, h, w), x.device)
+    L.check(lib.ru_postprocess_regions(L.ptr(x), L.f32(_prep(probs)) if probs is not None and any(thr) else None, kind, d, h, w,
+                                       (C.c_longlong * 3)(*mv), (C.c_ulonglong * 3)(*thr), kl, fh, int(bool(nest)), L.ptr(out), L.ptr(counts),
+                                       L.ptr(stats), L.ptr(ws), ws.numel(), L.stream()), "ru_postprocess_regions")
+    if not want_stats:
+        return out, counts
+    return out, counts, (stats if kind == L.POSTPROCESS_LABELS else stats[:, :5].contiguous())
+
+
 def paste_labels(lab, full_shape, lo):
     """test.py:167-168: uint8 device volume `full_shape`, zero except the box at `lo`, which holds `lab`."""
     if not (lab.is_cuda and lab.is_contiguous() and lab.dtype == torch.uint8 and lab.dim() == 3):

@@ -16,6 +16,10 @@ predictions in the passes that merge them (`inference.predict_case_ensemble(...,
 `--tile D H W [--overlap F] [--window gaussian|constant]` runs every forward as a sliding window over the padded crop: tiles of D x H x W
 overlapping by the fraction F (default 0.5), every predicted voxel used and weighted by the window (`tiling.predict_blended`,
 csrc/blend.hip) -- for a case whose padded crop does not fit the device whole.
+
+`--min_volume WT TC ET`, `--min_confidence WT TC ET`, `--keep_largest wt|tc|et ...`, `--fill_holes wt|tc|et ...`, `--nest`, `--no_reject`
+post-process the merged masks per region on the device before the labels are composed (`inference.PostProcess`, csrc/postprocess.hip;
+INTEGRATION.md states the definition); `--no_reject` drops the reference's rejection on the union of all labels.
 """
 from __future__ import annotations
 
@@ -42,6 +46,7 @@ parser.add_argument("--uncertainty_output", default=argparse.SUPPRESS, type=str,
 parser.add_argument("--tile", default=argparse.SUPPRESS, type=int, nargs=3, metavar=("D", "H", "W"), help="blended sliding-window forward with tiles of this size")
 parser.add_argument("--overlap", default=argparse.SUPPRESS, type=float, help="overlap of neighbouring tiles as a fraction of the tile, 0 .. 0.75 (with --tile; default 0.5)")
 parser.add_argument("--window", default=argparse.SUPPRESS, choices=["gaussian", "constant"], help="blend window (with --tile; default gaussian)")
+inference.add_postprocess_arguments(parser)
 
 
 def _load_net(name, opt):
@@ -62,6 +67,9 @@ def main(argv=None):
     if not hasattr(opt, "tile") and (hasattr(opt, "overlap") or hasattr(opt, "window")):
         parser.error("--overlap and --window need --tile")
     tiled = dict(tile=tuple(opt.tile), overlap=getattr(opt, "overlap", 0.5), window=getattr(opt, "window", "gaussian")) if hasattr(opt, "tile") else {}
+    post = inference.postprocess_from_args(opt)
+    if post is not None:
+        tiled["postprocess"] = post
     print(torch.__version__)
     print(opt)
     net = _load_net(opt.name, opt)

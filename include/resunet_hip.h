@@ -383,6 +383,42 @@ size_t ru_cc_workspace_bytes(int D, int H, int W);
 int ru_cc_reject(unsigned char* labels, int D, int H, int W, double ratio, void* ws, size_t ws_bytes, ru_stream_t stream);
 int ru_paste_labels(const unsigned char* lab, unsigned char* full, int D, int H, int W, const int* lo, const int* size, ru_stream_t stream);
 
+/* ---------------------------------------------------------------- region-wise post-processing (csrc/postprocess.hip)
+ * Between ru_tta_merge_box / the ensemble finalize and ru_compose_labels.  Per region k of R_0 = WT, R_1 = TC, R_2 = ET on a grid [D][H][W]
+ * (D * H * W < 2^31), in this order (INTEGRATION.md states the same with its reasons):
+ *   1. the 26-connected components of R_k (scipy.ndimage.label with a 3 x 3 x 3 structure of ones; ru_cc_reject's connectivity);
+ *   2. per component vol = its voxels and, with probabilities, conf = the sum over its voxels of q(p) = (uint32) floor(clamp(p, 0, 1) *
+ *      65536.0f) -- an exact float32 product, truncated -- in 64-bit integers;
+ *   3. a component is removed if vol < min_volume[k]; or if conf_thr[k] > 0 and conf < conf_thr[k] * vol (integers; conf_thr[k] = T_k =
+ *      floor(min_confidence[k] * 65536.0) formed by the caller, <= 65536); or if bit k of keep_largest_bits is set and it is not the
+ *      component of largest vol among the survivors of the two rules, ties to the one holding the smallest linear voxel index;
+ *   4. bit k of fill_holes_bits: every 6-connected component of the background of the filtered mask that touches no face of the grid
+ *      becomes foreground (scipy.ndimage.binary_fill_holes, default structure; an extent of 1 leaves no holes);
+ *   5. nest != 0: R_1 &= R_0, then R_2 &= R_1.
+ * kind RU_POSTPROCESS_MASKS:  in = uint8 [3][D][H][W], non-zero = foreground; probs = float32 [3][D][H][W] or NULL (then every conf_thr
+ *                             must be 0); out = uint8 [3][D][H][W] of 0 / 1.
+ * kind RU_POSTPROCESS_LABELS: in = uint8 [D][H][W] BraTS labels, regions as ru_surface_metrics (WT = {1,2,3,4}, TC = {1,3,4}, ET = {3,4};
+ *                             above 4: background); probs NULL; out = uint8 [D][H][W]: 2 where WT, 1 where TC, 4 where ET, in that order.
+ * counts [3] uint64 = the voxels of the three output regions (what ru_compose_labels takes).  stats [3][RU_POSTPROCESS_STATS] int64 =
+ * {components found, removed by volume, removed by confidence only, removed by keep_largest, voxels filled, invalid label voxels
+ * (kind LABELS: bytes above 4, the same in every row; 0 otherwise)}.  `in` is not written and must not be `out`.  Integer atomics only:
+ * two calls give identical bytes.  The call only enqueues; ws: ru_postprocess_workspace_bytes(kind, D, H, W) bytes (0 for a bad kind or
+ * shape).  min_volume, conf_thr: HOST arrays of 3. */
+#define RU_POSTPROCESS_MASKS 0
+#define RU_POSTPROCESS_LABELS 1
+#define RU_POSTPROCESS_REGIONS 3
+#define RU_POSTPROCESS_STATS 6
+#define RU_POSTPROCESS_S_FOUND 0
+#define RU_POSTPROCESS_S_VOLUME 1
+#define RU_POSTPROCESS_S_CONFIDENCE 2
+#define RU_POSTPROCESS_S_LARGEST 3
+#define RU_POSTPROCESS_S_FILLED 4
+#define RU_POSTPROCESS_S_INVALID 5
+size_t ru_postprocess_workspace_bytes(int kind, int D, int H, int W);
+int ru_postprocess_regions(const void* in, const float* probs, int kind, int D, int H, int W, const long long* min_volume,
+                           const unsigned long long* conf_thr, unsigned keep_largest_bits, unsigned fill_holes_bits, int nest,
+                           unsigned char* out, unsigned long long* counts, long long* stats, void* ws, size_t ws_bytes, ru_stream_t stream);
+
 /* ---------------------------------------------------------------- ensemble inference and soft labels (csrc/ensemble.hip)
  * The reference's ensemble step (README.md:1-5; average_predicts.ipynb / emsemble_predicts.ipynb: `sum(data_files) / len(data_files)`,
  * argmax, 3 -> 4) with the models' predictions resident on the device.  Fixed float32 arithmetic, comparable bit for bit with numpy:
