@@ -574,7 +574,7 @@ static int conv3_gn(ru_unet* h, Arena& A, hipStream_t s, const float* x, const f
         h->probe_used += 2;
     }
     if (!tail) RU_RUN(gn_finalize_launch(partials, nblk, gamma, beta, out_gn.mean, out_gn.rstd, out_gn.scale, out_gn.shift, N, Cout,
-                                         (size_t)D * H * W, kGroups, kEps, s, out_gn.k));
+                                         (size_t)D * H * W, kGroups, kEps, s, out_gn.k, ksplit > 1));
     h->gn_order.push_back(out_gn);
     return RU_OK;
 }
@@ -1625,7 +1625,7 @@ extern "C" int ru_groupnorm_fwd(const float* x, const float* gamma, const float*
     RU_WS_OK(Cw);
     int rc = gn_stats_launch(x, part, N, C, V, s);
     if (rc) return rc;
-    rc = gn_finalize_launch(part, nblk, gamma, beta, mean, rstd, scale, shift, N, C, V, G, eps, s);
+    rc = gn_finalize_launch(part, nblk, gamma, beta, mean, rstd, scale, shift, N, C, V, G, eps, s, nullptr, true);
     if (rc) return rc;
     return gn_apply_launch(x, scale, shift, residual, y, N, C, V, slope, s);
 }

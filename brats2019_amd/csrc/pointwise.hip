@@ -232,23 +232,49 @@ constexpr int GN_CHUNK = 8192;   // elements of one (n,c) row reduced by one wor
 int gn_stats_tiles(size_t V) { return (int)((V + GN_CHUNK - 1) / GN_CHUNK); }
 int gn_bwd_tiles(size_t V) { return gn_stats_tiles(V); }
 
+// One workgroup per (row, chunk) publishes (sum, M2): M2 = sum (x - c)^2 about the chunk's own float32 mean c = sum / count.  The chunk is held in registers
+// between the two sums (GN_CHUNK / 256 = 32 values per thread), so x is read once.  (sum, sum x^2) partials lose (mean / std)^2 * 2^-24 of the variance when the
+// finalize forms sumsq / m - mean^2; centred partials combined with Chan's formula (gn_finalize_kernel<true>) stay at float32 rounding whatever the mean is.
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ x, float* __restrict__ partials, size_t V, int nblk) {
     __shared__ float buf[4];
     const size_t row = blockIdx.y;              // n*C + c
     const size_t v0 = (size_t)blockIdx.x * GN_CHUNK;
     const size_t v1 = v0 + GN_CHUNK < V ? v0 + GN_CHUNK : V;
+    const float inv = 1.f / (float)(v1 - v0);
     const float* xp = x + row * V;
     float s1 = 0.f, s2 = 0.f;
     if ((V & 3) == 0) {
-        for (size_t v = v0 + threadIdx.x * 4; v < v1; v += 1024) {
-            const float4 t = *reinterpret_cast<const float4*>(xp + v);
-            s1 += (t.x + t.y) + (t.z + t.w);
-            s2 += (t.x * t.x + t.y * t.y) + (t.z * t.z + t.w * t.w);
+        float4 r[GN_CHUNK / 1024];
+#pragma unroll
+        for (int k = 0; k < GN_CHUNK / 1024; ++k) {
+            const size_t v = v0 + threadIdx.x * 4 + (size_t)k * 1024;
+            r[k] = v < v1 ? *reinterpret_cast<const float4*>(xp + v) : make_float4(0.f, 0.f, 0.f, 0.f);
+            s1 += (r[k].x + r[k].y) + (r[k].z + r[k].w);
+        }
+        s1 = block_sum(s1, buf);
+        const float c = s1 * inv;
+#pragma unroll
+        for (int k = 0; k < GN_CHUNK / 1024; ++k) {
+            if (v0 + threadIdx.x * 4 + (size_t)k * 1024 < v1) {
+                const float a = r[k].x - c, b = r[k].y - c, d = r[k].z - c, e = r[k].w - c;
+                s2 += (a * a + b * b) + (d * d + e * e);
+            }
         }
     } else {
-        for (size_t v = v0 + threadIdx.x; v < v1; v += 256) { const float t = xp[v]; s1 += t; s2 += t * t; }
+        float r[GN_CHUNK / 256];
+#pragma unroll
+        for (int k = 0; k < GN_CHUNK / 256; ++k) {
+            const size_t v = v0 + threadIdx.x + (size_t)k * 256;
+            r[k] = v < v1 ? xp[v] : 0.f;
+            s1 += r[k];
+        }
+        s1 = block_sum(s1, buf);
+        const float c = s1 * inv;
+#pragma unroll
+        for (int k = 0; k < GN_CHUNK / 256; ++k) {
+            if (v0 + threadIdx.x + (size_t)k * 256 < v1) { const float a = r[k] - c; s2 += a * a; }
+        }
     }
-    s1 = block_sum(s1, buf);
     s2 = block_sum(s2, buf);
     if (threadIdx.x == 0) {
         float* p = partials + (row * nblk + blockIdx.x) * 2;
@@ -262,7 +288,11 @@ int gn_stats_launch(const float* x, float* partials, int N, int C, size_t V, hip
     return RU_OK;
 }
 
-// one workgroup per (n, g): float64 combine of the per-tile float32 (sum, sumsq) partials
+// one workgroup per (n, g): float64 combine of the per-tile float32 partials.  CENTRED = false: (sum, sumsq) pairs of the convolution epilogues, var = sumsq / m - mean^2.
+// CENTRED = true: the (sum, M2) pairs of gn_stats_kernel, chunk b of a row holding min(GN_CHUNK, V - b * GN_CHUNK) elements, combined with Chan's formula:
+// m * var = sum_b [M2_b + count_b * (sum_b / count_b - mean)^2].  (M2_b is taken about the float32-rounded chunk mean: that adds count_b * (2^-24 * mean_b)^2 at the
+// most, below 1e-14 * (mean / std)^2 of the variance.)
+template <bool CENTRED>
 __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ partials, int nblk, const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, float* __restrict__ mean, float* __restrict__ rstd,
                                                           float* __restrict__ scale, float* __restrict__ shift, int C, size_t V, int G, float eps,
@@ -273,18 +303,32 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
     const int cpg = C / G;
     const float* p = partials + ((size_t)n * C + (size_t)g * cpg) * nblk * 2;   // cpg*nblk contiguous (sum,sumsq) pairs
     const int cnt = cpg * nblk;
+    const double m = (double)cpg * (double)V;
     double s1 = 0.0, s2 = 0.0;
     for (int i = threadIdx.x; i < cnt; i += 256) { s1 += (double)p[2 * i]; s2 += (double)p[2 * i + 1]; }
     s1 = wave_sum_d(s1);
     s2 = wave_sum_d(s2);
     if ((threadIdx.x & 63) == 0) { buf[threadIdx.x >> 6][0] = s1; buf[threadIdx.x >> 6][1] = s2; }
     __syncthreads();
+    s1 = (buf[0][0] + buf[1][0]) + (buf[2][0] + buf[3][0]);
+    s2 = (buf[0][1] + buf[1][1]) + (buf[2][1] + buf[3][1]);
+    const double mu = s1 / m;
+    if (CENTRED) {                               // second pass over the pairs: the spread of the chunk means about the group mean
+        double sb = 0.0;
+        for (int i = threadIdx.x; i < cnt; i += 256) {
+            const size_t b0 = (size_t)(i % nblk) * GN_CHUNK;
+            const double nb = (double)(b0 + GN_CHUNK < V ? (size_t)GN_CHUNK : V - b0);
+            const double d = (double)p[2 * i] / nb - mu;
+            sb += nb * d * d;
+        }
+        sb = wave_sum_d(sb);
+        __syncthreads();
+        if ((threadIdx.x & 63) == 0) buf[threadIdx.x >> 6][0] = sb;
+        __syncthreads();
+        s2 += (buf[0][0] + buf[1][0]) + (buf[2][0] + buf[3][0]);
+    }
     if (threadIdx.x == 0) {
-        s1 = (buf[0][0] + buf[1][0]) + (buf[2][0] + buf[3][0]);
-        s2 = (buf[0][1] + buf[1][1]) + (buf[2][1] + buf[3][1]);
-        const double m = (double)cpg * (double)V;
-        const double mu = s1 / m;
-        double var = s2 / m - mu * mu;
+        double var = CENTRED ? s2 / m : s2 / m - mu * mu;
         if (var < 0.0) var = 0.0;
         const double rs = 1.0 / sqrt(var + (double)eps);
         sh[0] = (float)mu; sh[1] = (float)rs;
@@ -307,9 +351,11 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
     }
 }
 int gn_finalize_launch(const float* partials, int nblk, const float* gamma, const float* beta, float* mean, float* rstd,
-                       float* scale, float* shift, int N, int C, size_t V, int G, float eps, hipStream_t s, float* bst_k) {
+                       float* scale, float* shift, int N, int C, size_t V, int G, float eps, hipStream_t s, float* bst_k, bool centred) {
     RU_REQUIRE(C % G == 0 && C / G <= 256, "groupnorm: C must be divisible by G (and C/G <= 256)");
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3(N * G), dim3(256), 0, s, partials, nblk, gamma, beta, mean, rstd, scale, shift, C, V, G, eps, bst_k);
+    RU_REQUIRE(!centred || nblk == gn_stats_tiles(V), "groupnorm: centred partials come from gn_stats_launch (%d chunks per row)", gn_stats_tiles(V));
+    if (centred) hipLaunchKernelGGL(gn_finalize_kernel<true>, dim3(N * G), dim3(256), 0, s, partials, nblk, gamma, beta, mean, rstd, scale, shift, C, V, G, eps, bst_k);
+    else hipLaunchKernelGGL(gn_finalize_kernel<false>, dim3(N * G), dim3(256), 0, s, partials, nblk, gamma, beta, mean, rstd, scale, shift, C, V, G, eps, bst_k);
     RU_CHECK_LAUNCH("gn_finalize_kernel");
     return RU_OK;
 }

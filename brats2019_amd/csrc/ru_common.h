@@ -387,10 +387,11 @@ int d2s_launch(const float* y, float* x, int N, int C, int D, int H, int W, hipS
 
 // GroupNorm pieces
 int gn_stats_tiles(size_t V);                                                    // nblk used by gn_stats_launch
-int gn_stats_launch(const float* x, float* partials, int N, int C, size_t V, hipStream_t s);   // [N][C][nblk][2]
-// partials -> mean,rstd [N][G]; scale,shift [N][C] (y = x*scale+shift)
+int gn_stats_launch(const float* x, float* partials, int N, int C, size_t V, hipStream_t s);   // [N][C][nblk][2]: per chunk (sum, M2 about the chunk's mean)
+// partials -> mean,rstd [N][G]; scale,shift [N][C] (y = x*scale+shift).  centred: the partials are gn_stats_launch's (sum, M2) pairs, not (sum, sumsq)
 int gn_finalize_launch(const float* partials, int nblk, const float* gamma, const float* beta, float* mean, float* rstd,
-                       float* scale, float* shift, int N, int C, size_t V, int G, float eps, hipStream_t s, float* bst_k = nullptr);   // bst_k: optional [N][3][C] constants for Conv3Args::bst_k
+                       float* scale, float* shift, int N, int C, size_t V, int G, float eps, hipStream_t s, float* bst_k = nullptr,   // bst_k: optional [N][3][C] constants for Conv3Args::bst_k
+                       bool centred = false);
 // y = (res ? res : 0) + lrelu(x*scale[n,c]+shift[n,c], slope)
 int gn_apply_launch(const float* x, const float* scale, const float* shift, const float* res, float* y,
                     int N, int C, size_t V, float slope, hipStream_t s);
