@@ -1784,6 +1784,62 @@ extern "C" int ru_conv3d_bwd_weight_l(const float* x, const float* dy, float* dw
     return wgrad3_launch(a, (hipStream_t)stream);
 }
 
+// The voxel-major pointwise family, one launch at a time: thin fillers of Conv1Args / Wgrad1Args (no kernels, no arithmetic of their own).
+extern "C" size_t ru_conv1_l_workspace_bytes(int C0, int Cout, int s2d) {
+    return 4096 + (s2d ? 2 * align_up((size_t)C0 * Cout * sizeof(float), 256) : 0);      // both packs of the 2x2x2 weight
+}
+extern "C" int ru_conv1_l(const float* x0, int C0, const float* x1, int C1, const float* w, int ldw, float* y, float* y1, int Cout0,
+                          const float* add, float out_slope, const float* mask, float mask_slope, int N, int Cout, size_t V,
+                          int s2d, int Dc, int Hc, int Wc, const float* bst_y, const float* bst_k, float bst_slope,
+                          float* stat_partials, size_t stat_floats, int* nblk, int* inst, void* ws, size_t ws_bytes, ru_stream_t stream) {
+    RU_REQUIRE(x0 && w && y, "ru_conv1_l: null argument");
+    RU_REQUIRE(s2d >= 0 && s2d <= 2, "ru_conv1_l: s2d is 0 (plain), 1 (gather) or 2 (scatter)");
+    hipStream_t s = (hipStream_t)stream;
+    WsCarver C(ws, ws_bytes);
+    Conv1Args a{};
+    a.x0 = x0; a.C0 = C0; a.x1 = x1; a.C1 = C1; a.wT = w; a.ldw = ldw; a.y = y; a.add = add; a.out_slope = out_slope;
+    a.N = N; a.Cout = Cout; a.V = V; a.s2d = s2d; a.Dc = Dc; a.Hc = Hc; a.Wc = Wc; a.mask = mask; a.mask_slope = mask_slope;
+    a.y1 = y1; a.Cout0 = Cout0; a.bst_y = bst_y; a.bst_k = bst_k; a.bst_slope = bst_slope; a.stat_partials = stat_partials;
+    if (s2d) {
+        // w is the reference's [Cconv_out][Cconv_in][2][2][2]; the engine's pack gives the gather its [Cout][tap*Cin + c] and the scatter its [tap*Cin + c][C0]
+        RU_REQUIRE(C0 > 0 && Cout > 0 && (s2d == 1 ? C0 : Cout) % 8 == 0, "ru_conv1_l: stride-2 modes need 8 x channels on the gathered side");
+        const int co = s2d == 1 ? Cout : C0, ci = (s2d == 1 ? C0 : Cout) / 8;
+        float* wd = C.take((size_t)8 * ci * co);
+        float* wdT = C.take((size_t)8 * ci * co);
+        RU_WS_OK(C);
+        int rc = pack_down16_launch(w, wd, wdT, co, ci, s);
+        if (rc) return rc;
+        a.wT = s2d == 1 ? wd : wdT;
+        a.ldw = C0;
+    }
+    if (inst) *inst = conv1_16_choose(a).packed();
+    if (nblk) *nblk = 0;
+    if (bst_y) {
+        const int nb = conv1_16_bst_nblk(a);             // 0: no fused form -- conv1_16_launch refuses below, with its own message
+        RU_REQUIRE(nb == 0 || (stat_partials && stat_floats >= (size_t)N * (s2d == 2 ? Cout / 8 : Cout) * nb * 2), "ru_conv1_l: statistics buffer too small");
+        if (nblk) *nblk = nb;
+    }
+    return conv1_16_launch(a, s);
+}
+
+extern "C" size_t ru_wgrad1_l_workspace_bytes(int N, int Cin, int Cout, size_t V) { return 4096 + align_up(wgrad1_workspace_bytes(N, Cin, Cout, V), 256); }
+extern "C" int ru_wgrad1_l(const float* x, const float* x1, int C0, const float* dy, float* dw, int ldw, int N, int Cin, int Cout, size_t V,
+                           int c16, int s2d, int Dc, int Hc, int Wc, int tap_split, const float* dg_w, int dg_ldw, float* dg_y0, float* dg_y1,
+                           float dg_mask_slope, int* inst, void* ws, size_t ws_bytes, ru_stream_t stream) {
+    RU_REQUIRE(x && dy && dw, "ru_wgrad1_l: null argument");
+    WsCarver C(ws, ws_bytes);
+    Wgrad1Args a{};
+    a.x = x; a.x1 = x1; a.C0 = C0; a.dy = dy; a.dw = dw; a.ldw = ldw; a.N = N; a.Cin = Cin; a.Cout = Cout; a.V = V;
+    a.c16 = c16; a.s2d = s2d; a.Dc = Dc; a.Hc = Hc; a.Wc = Wc; a.tap_split = tap_split;
+    a.dg_w = dg_w; a.dg_ldw = dg_ldw; a.dg_y0 = dg_y0; a.dg_y1 = dg_y1; a.dg_mask_slope = dg_mask_slope;
+    RU_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && V > 0, "ru_wgrad1_l: bad shape");
+    a.ws_bytes = wgrad1_workspace_bytes(N, Cin, Cout, V);
+    a.ws = C.take(a.ws_bytes / 4);
+    RU_WS_OK(C);
+    if (inst) *inst = wgrad1_inst(a);
+    return wgrad1_launch(a, (hipStream_t)stream);
+}
+
 // ====================================================================== training input pipeline (dataloader.py)
 extern "C" size_t ru_zscore_workspace_bytes(int C, size_t V) { return zscore_workspace_bytes(C, V) + 256; }
 extern "C" int ru_zscore_stats(const float* image, double* stats, int C, size_t V, void* ws, size_t ws_bytes, ru_stream_t stream) {

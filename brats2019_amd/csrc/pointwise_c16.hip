@@ -722,21 +722,27 @@ __global__ __launch_bounds__(256, (PAIR || NSLOT > 0) ? 2 : 1) void conv1_16_ker
         }
     }
 }
-// output channel blocks per workgroup.  Scatter mode (the transposed stride-2 conv: a streaming kernel whose 16-byte stores land 128 bytes
-// apart): RU_C1_SCATTER_COB (env, tools only) overrides the default for A/B runs
-static int conv1_16_cob(const Conv1Args& a) {
+// The one dispatch predicate: which conv1_16_kernel<cob, s2d, nslot, pair> a launch takes.
+// cob: output channel blocks per workgroup.  Scatter mode (the transposed stride-2 conv: a streaming kernel whose 16-byte stores land 128 bytes
+// apart): RU_C1_SCATTER_COB (env, tools only) overrides the default for A/B runs.
+// nslot: distinct 16-channel blocks of the output tensor a workgroup touches when the GroupNorm-backward statistics are fused (0: no statistics).
+// pair (the scatter mode's two x taps in one whole-line instruction): 8 consecutive coarse voxels of a 64-voxel wave tile must share a row; RU_C1_PAIR=0: off (A/B)
+Conv1Inst conv1_16_choose(const Conv1Args& a) {
     const int CBo = a.Cout / 16;
-    int cob = CBo >= 4 ? 4 : (CBo >= 2 ? 2 : 1);
+    Conv1Inst c{CBo >= 4 ? 4 : (CBo >= 2 ? 2 : 1), a.s2d, 0, 0};
     if (a.s2d == 2) {
         static const int forced = [] { const char* e = getenv("RU_C1_SCATTER_COB"); return e ? atoi(e) : 0; }();
-        if ((forced == 2 || forced == 4 || forced == 1) && forced <= CBo) cob = forced;
+        if ((forced == 2 || forced == 4 || forced == 1) && forced <= CBo) c.cob = forced;
     }
-    return cob;
+    if (a.bst_y) c.nslot = a.s2d == 2 ? (CBo >> 3) : c.cob;
+    static const bool pair_off = [] { const char* e = getenv("RU_C1_PAIR"); return e && *e == '0'; }();
+    c.pair = a.s2d == 2 && a.bst_y && !pair_off && a.Wc % 8 == 0 && c.cob == 4 && !a.mask && (c.nslot == 1 || c.nslot == 2);
+    return c;
 }
 int conv1_16_bst_nblk(const Conv1Args& a) {
     if (a.s2d == 1 || a.y1 || a.Cout % 16 || a.V == 0) return 0;
     const int nvt = (int)((a.V + 63) / 64), CBo = a.Cout / 16;
-    const int cob = conv1_16_cob(a);
+    const int cob = conv1_16_choose(a).cob;
     const int gx = cdiv(nvt, 4), gy = cdiv(CBo, cob);
     if (a.s2d == 2) {
         const int cbf = CBo >> 3;                        // every workgroup must carry whole groups of taps of the same fine channel blocks
@@ -756,30 +762,27 @@ int conv1_16_launch(const Conv1Args& a, hipStream_t s) {
         RU_REQUIRE(a.s2d == 1 ? a.C0 % 128 == 0 : a.Cout % 128 == 0, "conv1_16: stride-2 modes need 8 x (multiple of 16) channels");
     }
     const int nvt = (int)((a.V + 63) / 64), CBo = a.Cout / 16;
-    const int cob = conv1_16_cob(a);
+    const Conv1Inst c = conv1_16_choose(a);
     const bool bst = a.bst_y != nullptr;
     RU_REQUIRE(!bst || (a.bst_k && a.stat_partials && a.s2d != 1 && !a.y1 && conv1_16_bst_nblk(a) > 0), "conv1_16: fused GroupNorm-backward statistics need the plain or scatter mode with whole channel blocks per workgroup");
-    dim3 grid((unsigned)cdiv(nvt, 4), (unsigned)cdiv(CBo, cob), (unsigned)a.N);
-    const int nslot = !bst ? 0 : (a.s2d == 2 ? (CBo >> 3) : cob);          // distinct output channel blocks per workgroup (conv1_16_bst_nblk checked the shape)
-    // paired stores (the scatter mode's two x taps in one whole-line instruction): 8 consecutive coarse voxels of a 64-voxel wave tile must share a row; RU_C1_PAIR=0: off (A/B)
-    static const bool pair_off = [] { const char* e = getenv("RU_C1_PAIR"); return e && *e == '0'; }();
-    const bool pair = a.s2d == 2 && bst && !pair_off && a.Wc % 8 == 0 && cob == 4 && !a.mask;
-#define RU_C1_LAUNCH(COB_)                                                                                          \
-    do {                                                                                                           \
-        if (a.s2d == 1) hipLaunchKernelGGL((conv1_16_kernel<COB_, 1, 0>), grid, dim3(256), 0, s, a, nvt);           \
-        else if (a.s2d == 2 && nslot == 1 && pair && COB_ == 4) hipLaunchKernelGGL((conv1_16_kernel<4, 2, 1, true>), grid, dim3(256), 0, s, a, nvt);  \
-        else if (a.s2d == 2 && nslot == 2 && pair && COB_ == 4) hipLaunchKernelGGL((conv1_16_kernel<4, 2, 2, true>), grid, dim3(256), 0, s, a, nvt);  \
-        else if (a.s2d == 2 && nslot == 1) hipLaunchKernelGGL((conv1_16_kernel<COB_, 2, 1>), grid, dim3(256), 0, s, a, nvt);  \
-        else if (a.s2d == 2 && nslot == 2) hipLaunchKernelGGL((conv1_16_kernel<COB_, 2, (COB_ >= 2 ? 2 : 1)>), grid, dim3(256), 0, s, a, nvt);  \
-        else if (a.s2d == 2 && nslot == 4) hipLaunchKernelGGL((conv1_16_kernel<COB_, 2, (COB_ >= 4 ? 4 : 1)>), grid, dim3(256), 0, s, a, nvt);  \
-        else if (a.s2d == 2) hipLaunchKernelGGL((conv1_16_kernel<COB_, 2, 0>), grid, dim3(256), 0, s, a, nvt);      \
-        else if (bst) hipLaunchKernelGGL((conv1_16_kernel<COB_, 0, COB_>), grid, dim3(256), 0, s, a, nvt);          \
-        else hipLaunchKernelGGL((conv1_16_kernel<COB_, 0, 0>), grid, dim3(256), 0, s, a, nvt);                      \
-    } while (0)
-    if (cob == 4) RU_C1_LAUNCH(4);
-    else if (cob == 2) RU_C1_LAUNCH(2);
-    else RU_C1_LAUNCH(1);
-#undef RU_C1_LAUNCH
+    dim3 grid((unsigned)cdiv(nvt, 4), (unsigned)cdiv(CBo, c.cob), (unsigned)a.N);
+    switch (c.packed()) {
+#define RU_C1_CASE(COB_, S2D_, NSLOT_, PAIR_)                                                                      \
+    case COB_ | (S2D_ << 4) | (NSLOT_ << 8) | (PAIR_ << 12):                                                        \
+        hipLaunchKernelGGL((conv1_16_kernel<COB_, S2D_, NSLOT_, PAIR_ != 0>), grid, dim3(256), 0, s, a, nvt);       \
+        break
+        RU_C1_CASE(4, 0, 0, 0); RU_C1_CASE(2, 0, 0, 0); RU_C1_CASE(1, 0, 0, 0);      // plain
+        RU_C1_CASE(4, 0, 4, 0); RU_C1_CASE(2, 0, 2, 0); RU_C1_CASE(1, 0, 1, 0);      // plain + statistics: one slot per block
+        RU_C1_CASE(4, 1, 0, 0); RU_C1_CASE(2, 1, 0, 0); RU_C1_CASE(1, 1, 0, 0);      // gather
+        RU_C1_CASE(4, 2, 0, 0); RU_C1_CASE(2, 2, 0, 0); RU_C1_CASE(1, 2, 0, 0);      // scatter (cob 2 / 1: RU_C1_SCATTER_COB only)
+        RU_C1_CASE(4, 2, 1, 1); RU_C1_CASE(4, 2, 2, 1);                              // scatter + statistics, paired stores
+        RU_C1_CASE(4, 2, 1, 0); RU_C1_CASE(4, 2, 2, 0); RU_C1_CASE(4, 2, 4, 0);      // scatter + statistics, slots = fine channel blocks
+        RU_C1_CASE(2, 2, 1, 0); RU_C1_CASE(2, 2, 2, 0); RU_C1_CASE(1, 2, 1, 0);
+#undef RU_C1_CASE
+    default:
+        set_error("conv1_16: no kernel for cob %d, mode %d, %d statistic slots", c.cob, c.s2d, c.nslot);
+        return RU_EINVAL;
+    }
     RU_CHECK_LAUNCH("conv1_16_kernel");
     return RU_OK;
 }

@@ -337,6 +337,8 @@ struct Wgrad1Args {
 };
 size_t wgrad1_workspace_bytes(int N, int Cin, int Cout, size_t V);
 int wgrad1_launch(const Wgrad1Args& a, hipStream_t s);
+// the kernel wgrad1_launch takes for `a`: ot | ct << 4 (wgrad1_f32_kernel<ot, ct>) | 1 << 8 (wgrad1_s2d_kernel instead) | 1 << 9 (fused data gradient)
+int wgrad1_inst(const Wgrad1Args& a);
 
 // ------------------------------------------------------------------ pointwise / small kernels (pointwise.hip)
 // y[n][o][v] = act( sum_c wT[c*ldw + o] * xcat[n][c][v] ) (+ add), xcat = concat(x0[C0], x1[C1]) on channels.
@@ -439,6 +441,10 @@ int up2_bwd16_launch(const float* dy, float* dx, int N, int C, int D, int H, int
 int pack_down16_launch(const float* w, float* wd, float* wdT, int Cout, int Cin, hipStream_t s);       // [Cout][Cin][8] -> [Cout][8*Cin], [8*Cin][Cout]
 // Conv1Args on C16 tensors; a.wT is read as wm[Cout][C0 + C1] (row-major out x in, pitch a.ldw)
 int conv1_16_launch(const Conv1Args& a, hipStream_t s);
+// the instantiation conv1_16_kernel<cob, s2d, nslot, pair> conv1_16_launch takes for `a` (the one place that decides; conv1_16_bst_nblk and the
+// launcher both read it); packed() = cob | s2d << 4 | nslot << 8 | pair << 12 is what ru_conv1_l reports
+struct Conv1Inst { int cob, s2d, nslot, pair; int packed() const { return cob | (s2d << 4) | (nslot << 8) | (pair << 12); } };
+Conv1Inst conv1_16_choose(const Conv1Args& a);
 
 int crit_tiles(size_t total);
 int crit_sums_launch(const float* p, const float* g, double* sums, int N, int C, size_t V, float bgw, void* ws, size_t ws_bytes, hipStream_t s);

@@ -490,18 +490,19 @@ __global__ __launch_bounds__(256, 2) void wgrad1_f32_kernel(const Wgrad1Args a, 
 #pragma unroll
             for (int j = 0; j < ND; ++j) {
                 const int e4 = tid + j * 256, q = e4 & 3, r = (e4 >> 2) % W1_VC, p = e4 / (4 * W1_VC);
-                const bool ok = v0 + r < V;
-                const float4 t4 = *reinterpret_cast<const float4*>(a.dy + (((size_t)n * (a.Cout >> 4) + (o0 >> 4) + p) * V + (ok ? v0 + r : 0)) * 16 + 4 * q);
+                const int ob = (o0 >> 4) + p;
+                const bool ok = v0 + r < V && ob < (a.Cout >> 4);    // (an odd number of channel blocks: the last tile's second block is not in the tensor)
+                const float4 t4 = *reinterpret_cast<const float4*>(a.dy + (ok ? (((size_t)n * (a.Cout >> 4) + ob) * V + v0 + r) * 16 + 4 * q : 0));
                 dv[j] = ok ? t4 : make_float4(0.f, 0.f, 0.f, 0.f);
             }
 #pragma unroll
             for (int j = 0; j < NX; ++j) {
                 const int e4 = tid + j * 256, q = e4 & 3, r = (e4 >> 2) % W1_VC, p = e4 / (4 * W1_VC);
-                const bool ok = v0 + r < V;
+                const bool ok = v0 + r < V && (c0 >> 4) + p < (a.Cin >> 4);   // (as for dy: a block beyond the tensor is zeros, read from a valid address)
                 const size_t vv = ok ? v0 + r : 0;
                 size_t off;
                 if (a.s2d) {                             // x = fine tensor of a 2x2x2 stride-2 conv: channel block (tap, cbf) at the fine voxel
-                    const int CBf = a.Cin >> 7, kb = (c0 >> 4) + p, tap = kb / CBf, cbf = kb - tap * CBf;
+                    const int CBf = a.Cin >> 7, kb = ok ? (c0 >> 4) + p : 0, tap = kb / CBf, cbf = kb - tap * CBf;
                     const int xc = (int)(vv % a.Wc);
                     const size_t rr = vv / a.Wc;
                     const int yc = (int)(rr % a.Hc), zc = (int)(rr / a.Hc);
@@ -511,7 +512,7 @@ __global__ __launch_bounds__(256, 2) void wgrad1_f32_kernel(const Wgrad1Args a, 
                     off = (((size_t)n * (a.Cin >> 4) + (c0 >> 4) + p) * V + vv) * 16 + 4 * q;
                 }
                 // optional second input tensor (channel blocks >= xCB0): selects of base and block index, no branch around the load
-                const int kbx = (c0 >> 4) + p;
+                const int kbx = ok ? (c0 >> 4) + p : 0;
                 const bool second = kbx >= xCB0;
                 const float* xsrc = second ? xsecond : a.x;
                 if (!a.s2d) off = (((size_t)n * (second ? xCB1 : xCB0) + (second ? kbx - xCB0 : kbx)) * V + vv) * 16 + 4 * q;
@@ -811,6 +812,11 @@ static int wgrad1_cfg(const Wgrad1Args& a, const W1Choice& c, hipStream_t s) {
     return wgrad_reduce_launch((const float*)a.ws, c.nbx, 1, CoP, CiP, a.Cout, a.Cin, a.dw, a.ldw, 1, a.tap_split, s, 0, a.defer);
 }
 
+int wgrad1_inst(const Wgrad1Args& a) {
+    const W1Choice c = wgrad1_choose(a.N, a.Cin, a.Cout, a.V);
+    return c.ot | (c.ct << 4) | ((a.s2d && wgrad1_s2d_usable(a.Cin, a.Cout)) ? 256 : 0) | (a.dg_w ? 512 : 0);
+}
+
 int wgrad1_launch(const Wgrad1Args& a, hipStream_t s) {
     RU_REQUIRE(a.N > 0 && a.Cin > 0 && a.Cout > 0 && a.V > 0 && a.ldw >= a.Cin, "wgrad1: bad shape");
     RU_REQUIRE(!a.c16 || (a.Cin % 16 == 0 && a.Cout % 16 == 0), "wgrad1: C16 tensors need channel counts that are multiples of 16");
@@ -823,7 +829,8 @@ int wgrad1_launch(const Wgrad1Args& a, hipStream_t s) {
         set_error("wgrad1: workspace too small");
         return RU_ENOMEM;
     }
-    if (a.s2d && wgrad1_s2d_usable(a.Cin, a.Cout)) {
+    const int inst = wgrad1_inst(a);
+    if (inst & 256) {
         static PerDevice attr_done;
         const size_t lds = (size_t)4 * 16 * W1_RS * sizeof(float);
         if (!attr_done.get()) {
@@ -836,10 +843,12 @@ int wgrad1_launch(const Wgrad1Args& a, hipStream_t s) {
         RU_CHECK_LAUNCH("wgrad1_s2d_kernel");
         return wgrad_reduce_launch((const float*)a.ws, nbx, 1, a.Cout, a.Cin, a.Cout, a.Cin, a.dw, a.ldw, 1, a.tap_split, s, 0, a.defer);
     }
-    if (c.ot == 2 && c.ct == 2) return wgrad1_cfg<2, 2>(a, c, s);
-    if (c.ot == 2) return wgrad1_cfg<2, 1>(a, c, s);
-    if (c.ct == 2) return wgrad1_cfg<1, 2>(a, c, s);
-    return wgrad1_cfg<1, 1>(a, c, s);
+    switch (inst & 255) {
+    case 2 | (2 << 4): return wgrad1_cfg<2, 2>(a, c, s);
+    case 2 | (1 << 4): return wgrad1_cfg<2, 1>(a, c, s);
+    case 1 | (2 << 4): return wgrad1_cfg<1, 2>(a, c, s);
+    default: return wgrad1_cfg<1, 1>(a, c, s);
+    }
 }
 
 }  // namespace ru

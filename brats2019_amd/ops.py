@@ -4,6 +4,7 @@ documents the reference call site it stands in for.  Used by loss.py / train.py 
 tests; the network itself goes through engine.py (one C call per forward/backward)."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import torch
@@ -967,3 +968,83 @@ def conv3d_bwd_weight_layout(x, dy, x_c16=False, dy_c16=False):
     L.check(lib.ru_conv3d_bwd_weight_l(L.f32(x), L.f32(dy), L.f32(dw), n, cin, cout, d, h, wd, int(x_c16) | (int(dy_c16) << 1),
                                        L.ptr(ws), ws.numel(), L.stream()), "ru_conv3d_bwd_weight_l")
     return dw
+
+
+Conv1Result = collections.namedtuple("Conv1Result", "y y1 partials nblk inst")
+Wgrad1Result = collections.namedtuple("Wgrad1Result", "dw dx0 dx1 inst")
+
+
+def conv1_inst(packed):
+    """ru_conv1_l's kernel report -> (COB, S2D, NSLOT, PAIR) of conv1_16_kernel."""
+    return packed & 15, (packed >> 4) & 15, (packed >> 8) & 15, bool((packed >> 12) & 1)
+
+
+def wgrad1_inst(packed):
+    """ru_wgrad1_l's kernel report -> (OT, CT, stride-2 kernel, fused data gradient)."""
+    return packed & 15, (packed >> 4) & 15, bool(packed & 256), bool(packed & 512)
+
+
+def conv1x1_c16(x0, w, x1=None, add=None, out_slope=1.0, mask=None, mask_slope=LEAKY_SLOPE, cout0=0, s2d=0,
+                bst_y=None, bst_k=None, bst_slope=LEAKY_SLOPE):
+    """One launch of the voxel-major pointwise convolution (ru_conv1_l; model.py:393,401,424 and the 2x2x2 stride-2 conv of model.py:361-363
+    with its transpose).  s2d = 0: w is [Cout, ldw] as the kernel reads it, x1 the second half of a concat, cout0 > 0 splits the output in (y, y1);
+    s2d = 1 (gather): x0 is the fine tensor, w the reference's [Cout, Cin, 2, 2, 2]; s2d = 2 (scatter): x0 is the coarse tensor, w the reference's
+    [C0, Cfine, 2, 2, 2], y the fine tensor.  bst_*: fused GroupNorm-backward sums, returned as partials [N, C, nblk, 2]."""
+    x0, w, x1, add, mask, bst_y, bst_k = (_prep(t) for t in (x0, w, x1, add, mask, bst_y, bst_k))
+    lib = L.load()
+    n, cb0, d, h, wd, _ = (int(v) for v in x0.shape)
+    c0, c1 = cb0 * 16, (int(x1.shape[1]) * 16 if x1 is not None else 0)
+    dc, hc, wc, ldw = d, h, wd, 0
+    if s2d == 0:
+        cout, ldw = int(w.shape[0]), int(w.shape[1])
+        out_sp, cstat = (d, h, wd), cout
+    elif s2d == 1:
+        cout, c0 = int(w.shape[0]), 8 * c0
+        dc, hc, wc = d // 2, h // 2, wd // 2
+        out_sp, cstat = (dc, hc, wc), cout
+    else:
+        cout = 8 * int(w.shape[1])
+        out_sp, cstat = (2 * d, 2 * h, 2 * wd), cout // 8
+    v = dc * hc * wc
+    dev = x0.device
+    y1 = None
+    if cout0:
+        y = torch.empty((n, cout0 // 16) + (d, h, wd) + (16,), dtype=torch.float32, device=dev)
+        y1 = torch.empty((n, (cout - cout0) // 16) + (d, h, wd) + (16,), dtype=torch.float32, device=dev)
+    else:
+        y = torch.empty((n, cstat // 16) + out_sp + (16,), dtype=torch.float32, device=dev)
+    part, cap = None, 0
+    if bst_y is not None:
+        cap = n * cstat * ((v + 255) // 256) * max(cout // 16, 1) * 2          # nblk <= voxel groups x channel groups
+        part = torch.zeros(cap, dtype=torch.float32, device=dev)
+    ws = L.workspace(lib.ru_conv1_l_workspace_bytes(c0, cout, s2d), dev)
+    nblk, inst = C.c_int(0), C.c_int(0)
+    L.check(lib.ru_conv1_l(L.f32(x0), c0, L.ptr(x1, True), c1, L.f32(w), ldw, L.f32(y), L.ptr(y1, True), cout0, L.ptr(add, True), float(out_slope),
+                           L.ptr(mask, True), float(mask_slope), n, cout, v, s2d, dc, hc, wc, L.ptr(bst_y, True), L.ptr(bst_k, True), float(bst_slope),
+                           L.ptr(part, True), cap, C.byref(nblk), C.byref(inst), L.ptr(ws), ws.numel(), L.stream()), "ru_conv1_l")
+    if part is not None:
+        part = part[:n * cstat * nblk.value * 2].view(n, cstat, nblk.value, 2)
+    return Conv1Result(y, y1, part, nblk.value, inst.value)
+
+
+def conv1x1_bwd_weight_c16(x, dy, x1=None, ldw=None, s2d=False, tap_split=False, dg_w=None, dg_mask_slope=LEAKY_SLOPE):
+    """One launch of the voxel-major 1x1x1 weight gradient (ru_wgrad1_l): dw [Cout, ldw] (tap_split: the reference's [Cout, Cin/8, 2, 2, 2]).  x1: the
+    second half of a concat; s2d: x is the FINE tensor of a stride-2 conv; dg_w [Cout, dg_ldw]: the fused data gradient (dx0 like x, dx1 like x1,
+    the latter through the LeakyReLU-backward mask of x1)."""
+    x, dy, x1, dg_w = (_prep(t) for t in (x, dy, x1, dg_w))
+    lib = L.load()
+    n, cbo, d, h, wd, _ = (int(v) for v in dy.shape)
+    c0 = int(x.shape[1]) * 16
+    cin = 8 * c0 if s2d else c0 + (int(x1.shape[1]) * 16 if x1 is not None else 0)
+    cout, v = cbo * 16, d * h * wd
+    ldw = cin if ldw is None else int(ldw)
+    dev = x.device
+    dw = torch.zeros((cout, cin // 8, 2, 2, 2) if tap_split else (cout, ldw), dtype=torch.float32, device=dev)
+    dx0 = torch.empty_like(x) if dg_w is not None else None
+    dx1 = torch.empty_like(x1) if dg_w is not None and x1 is not None else None
+    ws = L.workspace(lib.ru_wgrad1_l_workspace_bytes(n, cin, cout, v), dev)
+    inst = C.c_int(0)
+    L.check(lib.ru_wgrad1_l(L.f32(x), L.ptr(x1, True), c0 if x1 is not None else 0, L.f32(dy), L.f32(dw), ldw, n, cin, cout, v, 1, int(bool(s2d)), d, h, wd,
+                            cin // 8 if tap_split else 0, L.ptr(dg_w, True), int(dg_w.shape[1]) if dg_w is not None else 0, L.ptr(dx0, True), L.ptr(dx1, True),
+                            float(dg_mask_slope), C.byref(inst), L.ptr(ws), ws.numel(), L.stream()), "ru_wgrad1_l")
+    return Wgrad1Result(dw, dx0, dx1, inst.value)

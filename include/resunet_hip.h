@@ -503,6 +503,32 @@ int ru_conv3d_bwd_weight_l(const float* x, const float* dy, float* dw,
                            int N, int Cin, int Cout, int D, int H, int W, int flags,
                            void* ws, size_t ws_bytes, ru_stream_t stream);
 
+/* The voxel-major pointwise family, one launch at a time (all tensors C16).
+ * ru_conv1_l: y[v][o] = lrelu_out_slope( sum_c w[o][c] * cat(x0, x1)[v][c] ), then the LeakyReLU-backward mask (y * (mask > 0 ? 1 : mask_slope)), then + add.
+ *   s2d = 0: w is [Cout][ldw] (ldw >= C0 + C1, a multiple of 4); x1 / C1 optional (a channel concat that is never made); y1 / Cout0 optional: output
+ *            channels Cout0.. go to y1, and the mask then applies to (and is laid out like) y1 only.
+ *   s2d = 1: the 2x2x2 stride-2 convolution read straight from the FINE tensor x0 (C0 / 8 channels, extents 2Dc x 2Hc x 2Wc), V = Dc*Hc*Wc coarse voxels;
+ *            w is the reference's [Cout][C0/8][2][2][2] and is packed here (ldw is ignored).
+ *   s2d = 2: its transpose written straight into the FINE tensor y (Cout / 8 channels); w is the reference's [C0][Cout/8][2][2][2] (ldw is ignored).
+ *   bst_y / bst_k[N][3][C] (k1, k2, thr) / bst_slope (optional; plain and scatter modes): the GroupNorm-backward sums of the stored output d,
+ *            u = bst_y*k1 + k2, dh = u > thr ? d : d*bst_slope, S1 = sum dh, S2' = sum dh*u, as partials [N][C][*nblk][2] in stat_partials (capacity stat_floats);
+ *            *nblk = 0 where the shape has no fused form (the launch is then refused).
+ *   *inst (optional): the kernel instantiation taken, COB | S2D << 4 | NSLOT << 8 | PAIR << 12.
+ * ru_wgrad1_l: dw[o*ldw + c] = sum_{n,v} dy[n][v][o] * x[n][v][c]; c16 = 0: NCDHW operands.  x1 / C0: input channels C0.. live in x1.  s2d = 1: x is the FINE tensor
+ *   of a stride-2 conv (Cin = 8 x its channels, channel tap*(Cin/8) + c at fine voxel (2z+i, 2y+j, 2x+k), tap = 4i + 2j + k); tap_split = Cin/8 writes
+ *   dw[o*ldw + c*8 + tap], the reference's [Cout][Cin/8][2][2][2].  dg_w (optional, [Cout][dg_ldw], Cout <= 32): the data gradient in the same pass,
+ *   dx[v][c] = sum_o dg_w[o][c] * dy[v][o], channels < C0 (or all) to dg_y0, the others to dg_y1 times (x1 > 0 ? 1 : dg_mask_slope).
+ *   *inst (optional): OT | CT << 4 of wgrad1_f32_kernel<OT, CT>, bit 8 = the stride-2 kernel instead, bit 9 = fused data gradient. */
+size_t ru_conv1_l_workspace_bytes(int C0, int Cout, int s2d);
+int ru_conv1_l(const float* x0, int C0, const float* x1, int C1, const float* w, int ldw, float* y, float* y1, int Cout0,
+               const float* add, float out_slope, const float* mask, float mask_slope, int N, int Cout, size_t V,
+               int s2d, int Dc, int Hc, int Wc, const float* bst_y, const float* bst_k, float bst_slope,
+               float* stat_partials, size_t stat_floats, int* nblk, int* inst, void* ws, size_t ws_bytes, ru_stream_t stream);
+size_t ru_wgrad1_l_workspace_bytes(int N, int Cin, int Cout, size_t V);
+int ru_wgrad1_l(const float* x, const float* x1, int C0, const float* dy, float* dw, int ldw, int N, int Cin, int Cout, size_t V,
+                int c16, int s2d, int Dc, int Hc, int Wc, int tap_split, const float* dg_w, int dg_ldw, float* dg_y0, float* dg_y1,
+                float dg_mask_slope, int* inst, void* ws, size_t ws_bytes, ru_stream_t stream);
+
 /* trilinear x2 and its transpose on C16 tensors (C % 16 == 0; D,H,W = extents of the COARSE side, as in
  * ru_upsample2x_trilinear_*).  out_slope: LeakyReLU slope applied to the interpolated value (the decoder fuses model.py:401-402
  * into the up-sampling; 1 = none). */
