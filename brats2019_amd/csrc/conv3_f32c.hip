@@ -446,6 +446,14 @@ bool conv3_f32c_head_takes_residual(int Cin, int Cout, int W) {
     return !(e && *e == '0') && f32c_head_form(Cin, Cout) && Cin % 16 == 0 && (W & 3) == 0;
 }
 
+// the kernel conv3_f32c_launch takes for `a` (ru_common.h: c3r_*): tile, IN16 / OUT16, HEAD.  Pure; the tile is f32c_choose's whether or not a kernel exists for it.  (An NCDHW input always writes
+// voxel-major output: the launcher has no <false, false> form and its RU_REQUIREs refuse that pair.)
+int conv3_f32c_route(const Conv3Args& a) {
+    const F32CChoice c = f32c_choose(a.N, a.Cout, a.D, a.H, a.W);
+    const bool i16 = a.in_c16 != 0, o16 = a.out_c16 != 0 || !i16;
+    return c3r_make(C3F_F32C, c.tz, c.ty, i16, o16, false, false, false, i16 && !o16 && f32c_head_form(a.Cin, a.Cout));
+}
+
 int conv3_f32c_launch(const Conv3Args& a, const void* wfr, hipStream_t s) {
     RU_REQUIRE(a.in_c16 || a.out_c16, "conv3_f32c: at least one voxel-major side (the NCDHW kernel is conv3_f32_kernel)");
     RU_REQUIRE(!a.in_res || (a.in_c16 && !a.out_c16 && a.in_scale && !a.in_sum_out && f32c_head_form(a.Cin, a.Cout)),
@@ -458,18 +466,18 @@ int conv3_f32c_launch(const Conv3Args& a, const void* wfr, hipStream_t s) {
     RU_REQUIRE(a.out_c16 || (a.W & 3) == 0, "conv3_f32c: NCDHW output needs W %% 4 == 0");
     RU_REQUIRE(!a.in_c16 || (size_t)a.D * a.H * a.W * 64 < ((size_t)1 << 31), "conv3_f32c: a 16-channel block of the voxel-major input must be smaller than 2 GiB");
     RU_REQUIRE(a.N <= 32 || !a.stat_partials, "conv3_f32c: at most 32 samples per call when statistics are requested");
-    const F32CChoice c = f32c_choose(a.N, a.Cout, a.D, a.H, a.W);
+    const int r = conv3_f32c_route(a);
 #define RU_F32C_CASE(TZ, TY)                                                                                   \
-    if (c.tz == TZ && c.ty == TY) {                                                                            \
-        if (a.in_c16 && a.out_c16) return f32c_cfg<TZ, TY, true, true>(a, wfr, s);                             \
-        if (a.in_c16) return f32c_head_form(a.Cin, a.Cout) ? f32c_cfg<TZ, TY, true, false, true>(a, wfr, s) : f32c_cfg<TZ, TY, true, false>(a, wfr, s); \
+    if (c3r_tz(r) == TZ && c3r_ty(r) == TY) {                                                                  \
+        if (c3r_in16(r) && c3r_out16(r)) return f32c_cfg<TZ, TY, true, true>(a, wfr, s);                       \
+        if (c3r_in16(r)) return c3r_head(r) ? f32c_cfg<TZ, TY, true, false, true>(a, wfr, s) : f32c_cfg<TZ, TY, true, false>(a, wfr, s); \
         return f32c_cfg<TZ, TY, false, true>(a, wfr, s);                                                       \
     }
     RU_F32C_CASE(4, 8)
     RU_F32C_CASE(2, 8)
     RU_F32C_CASE(2, 4)
 #undef RU_F32C_CASE
-    set_error("conv3_f32c: no kernel for tile (%d, %d)", c.tz, c.ty);
+    set_error("conv3_f32c: no kernel for tile (%d, %d)", c3r_tz(r), c3r_ty(r));
     return RU_EINVAL;
 }
 

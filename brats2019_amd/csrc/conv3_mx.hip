@@ -47,16 +47,16 @@ static int mx_cfg(const Conv3Args& a, const void* mxfrag, hipStream_t s) {
     return RU_OK;
 }
 
-int conv3_mx_launch(const Conv3Args& a, const void* mxfrag, hipStream_t s) {
+int conv3_mx_launch(const Conv3Args& a, const void* mxfrag, int r, hipStream_t s) {       // r = conv3_sb_route(a): <GRAD, BST, ADD>
     RU_REQUIRE(a.in_c16 && a.out_c16 && !a.in_c4 && !a.bias && !a.sigmoid && !a.in_res && conv3_mx_shape_ok(a.N, a.Cin, a.Cout, a.D, a.H, a.W),
                "conv3_mx: voxel-major tensors, 16 input channels, whole 16-channel output blocks, no bias / input residual");
     RU_REQUIRE(a.N <= 32 || !a.stat_partials, "conv3_mx: at most 32 samples per call when statistics are requested");
     RU_REQUIRE((size_t)a.D * a.H * a.W * 64 < ((size_t)1 << 31), "conv3_mx: a 16-channel block of the voxel-major input must be smaller than 2 GiB (buffer addressing)");
-    if (a.in_g16) {                                       // a gradient in the operand form of the scheme: the data-gradient convolutions of the 16-channel level
+    if (c3r_grad(r)) {                                    // a gradient in the operand form of the scheme: the data-gradient convolutions of the 16-channel level
         RU_REQUIRE(a.in_s16 && !a.in_scale && a.Cout == 16 && (!a.bst_y || (a.bst_k && a.stat_partials)),
                    "conv3_mx: the gradient form -- operand-form input, no input transform, 16 output channels");
-        if (a.bst_y) return a.add ? mx_cfg<true, true, true>(a, mxfrag, s) : mx_cfg<true, true, false>(a, mxfrag, s);
-        return a.add ? mx_cfg<true, false, true>(a, mxfrag, s) : mx_cfg<true, false, false>(a, mxfrag, s);
+        if (c3r_bst(r)) return c3r_add(r) ? mx_cfg<true, true, true>(a, mxfrag, s) : mx_cfg<true, true, false>(a, mxfrag, s);
+        return c3r_add(r) ? mx_cfg<true, false, true>(a, mxfrag, s) : mx_cfg<true, false, false>(a, mxfrag, s);
     }
     RU_REQUIRE(!a.in_s16 && !a.add && !a.bst_y, "conv3_mx: the forward form -- plain float32 activations in, no residual, no GroupNorm-backward sums");
     return mx_cfg<false, false, false>(a, mxfrag, s);

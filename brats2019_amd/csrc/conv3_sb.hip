@@ -786,6 +786,49 @@ static int sb2c4_cfg(const Conv3Args& a, hipStream_t s) {
     return RU_OK;
 }
 
+// The kernel conv3_sb_launch takes for `a` (ru_common.h: Conv3Family, c3r_*): the ONE place that decides.  Pure: it reads the arguments and the RU_* switches and
+// judges nothing -- an argument set the launcher refuses still gets the value of the branch it would have reached.
+int conv3_sb_route(const Conv3Args& a) {
+    if (a.in_c4) return c3r_make(C3F_SB2C4, 4, 8, false, a.bst_y || a.out_c16, false, a.bst_y != nullptr);
+    SBChoice c = sb_choose(a.N, a.Cout, a.D, a.H, a.W);
+    if (sb_use_v2(c) && a.bias && a.out_c16) c = SBChoice{2, 8};
+#ifdef RU_SB2_DBG
+    if ((RU_SB2_DBG & 2048) && !a.stat_partials) c = SBChoice{2, 8};      // tools: time the one-stage kernel on a shape the persistent kernel would take
+    if ((RU_SB2_DBG & 4096) && !a.stat_partials) c = SBChoice{2, 4};
+#endif      // (no engine path: the persistent kernel has the bias for NCDHW output only)
+    if (a.in_c16 && a.out_c16 && !a.in_s16 && !a.bias && !a.sigmoid && !a.bst_y && !a.add && conv3_sb_uses_wz(a.N, a.Cin, a.Cout, a.D, a.H, a.W, a.products)) {
+        if (a.products == 2 && conv3_mx_wz_enabled()) return c3r_make(C3F_WZ32MX, 2, 8, true, true, true);      // an activation tensor: fp16 + MX-fp8 products (conv3_wz32mx.hpp)
+#ifdef RU_SB2_DBG
+        if (!conv3_wz32_enabled()) return c3r_make(C3F_WZ16, 2, 8, true, true, true);
+#endif
+        return c3r_make(C3F_WZ32, 2, 8, true, true, true);                                                      // matrix waves on 32x32x16 MFMAs (conv3_wz32.hpp)
+    }
+    if (a.in_g16) return c3r_make(C3F_MX, 4, 8, true, true, false, a.bst_y != nullptr, a.add != nullptr, false, true);
+    // Conv3Args::products == 2: the caller's input is an ACTIVATION tensor and it asks for the fp16 + MX-fp8 product scheme where a kernel for the shape exists
+    // (conv3_mx.hpp: the 16-channel level); everywhere else the request means three products
+    if (a.products == 2 && a.in_c16 && a.out_c16 && !a.in_s16 && !a.bias && !a.sigmoid && !a.add && !a.bst_y && !a.in_res && conv3_mx_enabled() &&
+        conv3_mx_shape_ok(a.N, a.Cin, a.Cout, a.D, a.H, a.W))
+        return c3r_make(C3F_MX, 4, 8, true, true);
+    const bool i16 = a.in_c16 != 0, o16 = a.out_c16 != 0;
+    if (!sb_use_v2(c)) return c3r_make(C3F_SB, c.tz, c.ty, i16, o16);
+    const int np = (i16 && o16 && a.products == 1) ? 1 : 3;
+    const bool multi = a.Cin > 16;
+    if (i16 && o16 && a.bst_y) return c3r_make(C3F_SB2, 4, 8, i16, o16, multi, true, a.add != nullptr, false, false, np);
+    if (a.add) return c3r_make(C3F_SB2, 4, 8, i16, o16, multi, false, true, false, false, np);
+    if (i16 && !o16 && sb_head_shape(a.Cin, a.Cout) && conv3_sb_head_form_enabled()) return c3r_make(C3F_SB2, 4, 8, i16, o16, false, false, false, true, false, np);
+    return c3r_make(C3F_SB2, 4, 8, i16, o16, multi, false, false, false, false, np);
+}
+
+// partials per (sample, channel) the kernel of route r writes (== the x extent of its grid): the count follows the route, so a launch that conv3_sb_uses_wz would
+// accept but whose operands (residual, GroupNorm-backward sums, split-form input) keep it on a direct kernel counts as that kernel does
+int conv3_sb_route_nblk(int r, int N, int Cout, int D, int H, int W) {
+    switch (c3r_family(r)) {
+    case C3F_WZ32: case C3F_WZ32MX: case C3F_WZ16: return (int)wz_grid_x(N, Cout, D, H, W);
+    case C3F_SB: return cdiv(D, c3r_tz(r)) * cdiv(H, c3r_ty(r)) * cdiv(W, 16);      // one-stage kernel: one per tile
+    default: return (int)sb2_grid_x(N, Cout, D, H, W);                              // persistent kernels: one per workgroup
+    }
+}
+
 int conv3_sb_launch(const Conv3Args& a, hipStream_t s) {
     RU_REQUIRE(!(a.sigmoid && a.out_c16), "conv3_sb: the fused sigmoid exists for NCDHW output only");
     RU_REQUIRE(!a.bst_y || (a.bst_k && a.stat_partials && (a.in_c16 || a.in_c4) && a.out_c16 && !a.bias && !a.sigmoid && (!a.add || !a.in_c4) &&
@@ -798,47 +841,42 @@ int conv3_sb_launch(const Conv3Args& a, hipStream_t s) {
         RU_REQUIRE(!a.out_c16 || a.Cout % 16 == 0, "conv3_sb: C16 output needs Cout %% 16 == 0");
         const SBChoice c4 = sb_choose(a.N, a.Cout, a.D, a.H, a.W);
         RU_REQUIRE(sb_use_v2(c4), "conv3_sb: the 4-channel kernel needs at least 256 (4,8,16) tiles x cout groups");
-        if (a.bst_y) return sb2c4_cfg<true, true>(a, s);
-        return a.out_c16 ? sb2c4_cfg<true>(a, s) : sb2c4_cfg<false>(a, s);
+        const int r4 = conv3_sb_route(a);
+        if (c3r_bst(r4)) return sb2c4_cfg<true, true>(a, s);
+        return c3r_out16(r4) ? sb2c4_cfg<true>(a, s) : sb2c4_cfg<false>(a, s);
     }
     RU_REQUIRE((a.W & 3) == 0 || (a.in_c16 && a.out_c16), "conv3_sb: W must be a multiple of 4 for NCDHW tensors");
     RU_REQUIRE(!a.in_c16 || a.Cin % 16 == 0, "conv3_sb: C16 input needs Cin %% 16 == 0");
     RU_REQUIRE(!a.in_s16 || (a.in_c16 && !a.in_scale), "conv3_sb: a split-form input is voxel-major and has no fused transform");
     RU_REQUIRE(!a.out_c16 || a.Cout % 16 == 0, "conv3_sb: C16 output needs Cout %% 16 == 0");
-    SBChoice c = sb_choose(a.N, a.Cout, a.D, a.H, a.W);
     RU_REQUIRE(!(a.bias && a.out_c16 && a.stat_partials), "conv3_sb: bias + voxel-major output + statistics is not a path of the network");
-    if (sb_use_v2(c) && a.bias && a.out_c16) c = SBChoice{2, 8};
-#ifdef RU_SB2_DBG
-    if ((RU_SB2_DBG & 2048) && !a.stat_partials) c = SBChoice{2, 8};      // tools: time the one-stage kernel on a shape the persistent kernel would take
-    if ((RU_SB2_DBG & 4096) && !a.stat_partials) c = SBChoice{2, 4};
-#endif      // (no engine path: the persistent kernel has the bias for NCDHW output only)
-    if (a.in_c16 && a.out_c16 && !a.in_s16 && !a.bias && !a.sigmoid && !a.bst_y && !a.add && conv3_sb_uses_wz(a.N, a.Cin, a.Cout, a.D, a.H, a.W, a.products))
-        return conv3_wz_launch(a, static_cast<const char*>(a.wfrag) + conv3_sb_frag_bytes_direct(a.Cin, a.Cout), s);
-    // Conv3Args::in_g16: the input is a gradient in the operand form of the MX scheme (the caller asked conv3_mxg_usable before it wrote the tensor that way)
-    if (a.in_g16) {
-        RU_REQUIRE(a.in_s16 && a.out_c16 && !a.bias && !a.sigmoid && !a.in_res && conv3_mxg_usable(a.N, a.Cin, a.Cout, a.D, a.H, a.W),
-                   "conv3_sb: a gradient-operand input is taken by conv3_mx_kernel<GRAD> only (16 -> 16 channels, persistent-kernel shapes)");
-        return conv3_mx_launch(a, static_cast<const char*>(a.wfrag) + conv3_sb_frag_bytes_direct(a.Cin, a.Cout), s);
+    const int r = conv3_sb_route(a);
+    const void* behind = static_cast<const char*>(a.wfrag) + conv3_sb_frag_bytes_direct(a.Cin, a.Cout);     // the non-direct fragments of the same weight
+    switch (c3r_family(r)) {
+    case C3F_WZ32: case C3F_WZ32MX: case C3F_WZ16:
+        return conv3_wz_launch(a, behind, r, s);
+    case C3F_MX:
+        // Conv3Args::in_g16: the input is a gradient in the operand form of the MX scheme (the caller asked conv3_mxg_usable before it wrote the tensor that way)
+        if (c3r_grad(r))
+            RU_REQUIRE(a.in_s16 && a.out_c16 && !a.bias && !a.sigmoid && !a.in_res && conv3_mxg_usable(a.N, a.Cin, a.Cout, a.D, a.H, a.W),
+                       "conv3_sb: a gradient-operand input is taken by conv3_mx_kernel<GRAD> only (16 -> 16 channels, persistent-kernel shapes)");
+        return conv3_mx_launch(a, behind, r, s);
+    case C3F_SB2:
+        if (c3r_in16(r) && c3r_out16(r)) return c3r_np(r) == 1 ? conv3_sb2_launch_c16_p1(a, r, s) : conv3_sb2_launch_c16(a, r, s);
+        return conv3_sb2_launch_mixed(a, r, s);          // (three products whatever a.products says: the NCDHW-side variants have no one-product form)
+    default: break;
     }
-    // Conv3Args::products == 2: the caller's input is an ACTIVATION tensor and it asks for the fp16 + MX-fp8 product scheme where a kernel for the shape exists
-    // (conv3_mx.hpp: the 16-channel level); everywhere else the request means three products
-    if (a.products == 2 && a.in_c16 && a.out_c16 && !a.in_s16 && !a.bias && !a.sigmoid && !a.add && !a.bst_y && !a.in_res && conv3_mx_enabled() &&
-        conv3_mx_shape_ok(a.N, a.Cin, a.Cout, a.D, a.H, a.W))
-        return conv3_mx_launch(a, static_cast<const char*>(a.wfrag) + conv3_sb_frag_bytes_direct(a.Cin, a.Cout), s);
-    if (sb_use_v2(c)) {
-        if (a.in_c16 && a.out_c16) return a.products == 1 ? conv3_sb2_launch_c16_p1(a, s) : conv3_sb2_launch_c16(a, s);
-        return conv3_sb2_launch_mixed(a, s);             // (three products whatever a.products says: the NCDHW-side variants have no one-product form)
+    const bool i16 = c3r_in16(r), o16 = c3r_out16(r);
+    if (c3r_ty(r) == 8) {
+        if (i16) return o16 ? sb_cfg<2, 8, true, true>(a, s) : sb_cfg<2, 8, true, false>(a, s);
+        return o16 ? sb_cfg<2, 8, false, true>(a, s) : sb_cfg<2, 8, false, false>(a, s);
     }
-    if (c.ty == 8) {
-        if (a.in_c16) return a.out_c16 ? sb_cfg<2, 8, true, true>(a, s) : sb_cfg<2, 8, true, false>(a, s);
-        return a.out_c16 ? sb_cfg<2, 8, false, true>(a, s) : sb_cfg<2, 8, false, false>(a, s);
+    if (c3r_ty(r) == 2) {
+        if (i16) return o16 ? sb_cfg<2, 2, true, true>(a, s) : sb_cfg<2, 2, true, false>(a, s);
+        return o16 ? sb_cfg<2, 2, false, true>(a, s) : sb_cfg<2, 2, false, false>(a, s);
     }
-    if (c.ty == 2) {
-        if (a.in_c16) return a.out_c16 ? sb_cfg<2, 2, true, true>(a, s) : sb_cfg<2, 2, true, false>(a, s);
-        return a.out_c16 ? sb_cfg<2, 2, false, true>(a, s) : sb_cfg<2, 2, false, false>(a, s);
-    }
-    if (a.in_c16) return a.out_c16 ? sb_cfg<2, 4, true, true>(a, s) : sb_cfg<2, 4, true, false>(a, s);
-    return a.out_c16 ? sb_cfg<2, 4, false, true>(a, s) : sb_cfg<2, 4, false, false>(a, s);
+    if (i16) return o16 ? sb_cfg<2, 4, true, true>(a, s) : sb_cfg<2, 4, true, false>(a, s);
+    return o16 ? sb_cfg<2, 4, false, true>(a, s) : sb_cfg<2, 4, false, false>(a, s);
 }
 
 }  // namespace ru

@@ -4,7 +4,7 @@
 
 namespace ru {
 
-int conv3_sb2_launch_c16(const Conv3Args& a, hipStream_t s) { return sb2_cfg<4, 8, true, true>(a, s); }
+int conv3_sb2_launch_c16(const Conv3Args& a, int r, hipStream_t s) { return sb2_cfg<4, 8, true, true>(a, r, s); }
 
 }  // namespace ru
 

@@ -5,6 +5,6 @@
 
 namespace ru {
 
-int conv3_sb2_launch_c16_p1(const Conv3Args& a, hipStream_t s) { return sb2_cfg<4, 8, true, true, 1>(a, s); }
+int conv3_sb2_launch_c16_p1(const Conv3Args& a, int r, hipStream_t s) { return sb2_cfg<4, 8, true, true, 1>(a, r, s); }
 
 }  // namespace ru

@@ -4,9 +4,9 @@
 
 namespace ru {
 
-int conv3_sb2_launch_mixed(const Conv3Args& a, hipStream_t s) {
-    if (a.in_c16) return sb2_cfg<4, 8, true, false>(a, s);
-    return a.out_c16 ? sb2_cfg<4, 8, false, true>(a, s) : sb2_cfg<4, 8, false, false>(a, s);
+int conv3_sb2_launch_mixed(const Conv3Args& a, int r, hipStream_t s) {
+    if (c3r_in16(r)) return sb2_cfg<4, 8, true, false>(a, r, s);
+    return c3r_out16(r) ? sb2_cfg<4, 8, false, true>(a, r, s) : sb2_cfg<4, 8, false, false>(a, r, s);
 }
 
 }  // namespace ru

@@ -1091,22 +1091,24 @@ static int sb2_cfg_m(const Conv3Args& a, hipStream_t s) {
     RU_CHECK_LAUNCH("conv3_sb2_kernel");
     return RU_OK;
 }
+// dispatch on the route conv3_sb_route decided (family C3F_SB2: its MULTI / BST / ADD / HEAD bits are the template arguments)
 template <int TZ, int TY, bool IN16, bool OUT16, int NP = 3>
-static int sb2_cfg(const Conv3Args& a, hipStream_t s) {
+static int sb2_cfg(const Conv3Args& a, int r, hipStream_t s) {
+    const bool multi = c3r_multi(r);
     if constexpr (IN16 && OUT16) {
-        if (a.bst_y && a.add) return a.Cin > 16 ? sb2_cfg_m<TZ, TY, IN16, OUT16, true, true, true, NP>(a, s) : sb2_cfg_m<TZ, TY, IN16, OUT16, false, true, true, NP>(a, s);
-        if (a.bst_y) return a.Cin > 16 ? sb2_cfg_m<TZ, TY, IN16, OUT16, true, true, false, NP>(a, s) : sb2_cfg_m<TZ, TY, IN16, OUT16, false, true, false, NP>(a, s);
+        if (c3r_bst(r) && c3r_add(r)) return multi ? sb2_cfg_m<TZ, TY, IN16, OUT16, true, true, true, NP>(a, s) : sb2_cfg_m<TZ, TY, IN16, OUT16, false, true, true, NP>(a, s);
+        if (c3r_bst(r)) return multi ? sb2_cfg_m<TZ, TY, IN16, OUT16, true, true, false, NP>(a, s) : sb2_cfg_m<TZ, TY, IN16, OUT16, false, true, false, NP>(a, s);
     }
-    if (a.add) return a.Cin > 16 ? sb2_cfg_m<TZ, TY, IN16, OUT16, true, false, true, NP>(a, s) : sb2_cfg_m<TZ, TY, IN16, OUT16, false, false, true, NP>(a, s);
+    if (c3r_add(r)) return multi ? sb2_cfg_m<TZ, TY, IN16, OUT16, true, false, true, NP>(a, s) : sb2_cfg_m<TZ, TY, IN16, OUT16, false, false, true, NP>(a, s);
     if constexpr (IN16 && !OUT16) {
-        if (sb_head_shape(a.Cin, a.Cout) && conv3_sb_head_form_enabled()) return sb2_cfg_m<TZ, TY, IN16, OUT16, false, false, false, NP, true>(a, s);
+        if (c3r_head(r)) return sb2_cfg_m<TZ, TY, IN16, OUT16, false, false, false, NP, true>(a, s);
     }
-    return a.Cin > 16 ? sb2_cfg_m<TZ, TY, IN16, OUT16, true, false, false, NP>(a, s) : sb2_cfg_m<TZ, TY, IN16, OUT16, false, false, false, NP>(a, s);
+    return multi ? sb2_cfg_m<TZ, TY, IN16, OUT16, true, false, false, NP>(a, s) : sb2_cfg_m<TZ, TY, IN16, OUT16, false, false, false, NP>(a, s);
 }
 
-// defined in conv3_sb2_c16.hip / conv3_sb2_c16_p1.hip (one product) / conv3_sb2_mixed.hip
-int conv3_sb2_launch_c16(const Conv3Args& a, hipStream_t s);
-int conv3_sb2_launch_c16_p1(const Conv3Args& a, hipStream_t s);
-int conv3_sb2_launch_mixed(const Conv3Args& a, hipStream_t s);
+// defined in conv3_sb2_c16.hip / conv3_sb2_c16_p1.hip (one product) / conv3_sb2_mixed.hip; r = conv3_sb_route(a)
+int conv3_sb2_launch_c16(const Conv3Args& a, int r, hipStream_t s);
+int conv3_sb2_launch_c16_p1(const Conv3Args& a, int r, hipStream_t s);
+int conv3_sb2_launch_mixed(const Conv3Args& a, int r, hipStream_t s);
 
 }  // namespace ru

@@ -1822,6 +1822,68 @@ extern "C" int ru_conv1_l(const float* x0, int C0, const float* x1, int C1, cons
     return conv1_16_launch(a, s);
 }
 
+// The 3x3x3 family, one launch at a time with every fused operand of Conv3Args (except the tail finalize `fin`, whose ticket is the engine's, and ksplit): a thin
+// filler like ru_conv1_l.  Weights are packed as ru_conv3d_fwd_l packs them; weight_mode = 1 packs the data-gradient form of w = [Cout][Cin][3][3][3] OF THE FORWARD
+// CONVOLUTION (channels swapped, taps mirrored), so that the launch maps x's Cin channels (the forward's outputs) to y's Cout channels as the engine's backward does.
+static size_t c3l_frag_bytes(int Cin, int Cout) { const size_t sb = conv3_sb_frag_bytes(Cin, Cout), f = conv3_f32c_frag_bytes(Cin, Cout); return sb > f ? sb : f; }
+extern "C" size_t ru_conv3_l_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W, int flags) {
+    const size_t nvox = (size_t)N * D * H * W;
+    return 4096 + align_up(c3l_frag_bytes(Cin, Cout) + 256, 256) + ((flags & 4) ? align_up(nvox * 16, 256) + align_up(conv3_sb4_frag_bytes(Cout) + 256, 256) : 0) +
+           ((flags & 64) ? align_up(nvox * 64, 256) : 0);
+}
+extern "C" int ru_conv3_l(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Cout, int D, int H, int W, int flags, int weight_mode,
+                          const float* add, const float* in_scale, const float* in_shift, float in_slope, const float* in_res, float* in_sum_out,
+                          int sigmoid, int products, const float* bst_y, const float* bst_k, float bst_slope, float* stat_partials, size_t stat_floats,
+                          int* nblk, int* route, void* ws, size_t ws_bytes, ru_stream_t stream) {
+    RU_REQUIRE(x && w && y, "ru_conv3_l: null argument");
+    RU_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, "ru_conv3_l: bad shape");
+    RU_REQUIRE(weight_mode == 0 || weight_mode == 1, "ru_conv3_l: weight_mode is 0 (forward packing) or 1 (data-gradient packing)");
+    hipStream_t s = (hipStream_t)stream;
+    WsCarver C(ws, ws_bytes);
+    Conv3Args a{};
+    void* wf = C.take(c3l_frag_bytes(Cin, Cout) / 4 + 64);
+    RU_WS_OK(C);
+    const bool f32 = (flags & 16) != 0;
+    a.products = (flags & 32) ? 2 : products;
+    RU_REQUIRE(!f32 || ((flags & 3) != 0 && !(flags & (4 | 8))), "ru_conv3_l: the exact-f32 form needs a voxel-major side and takes neither the 4-channel copy nor a split-form input");
+    const bool gop = (flags & 64) && !f32 && (flags & 3) == 3 && !(flags & (4 | 8)) && !bias && conv3_mxg_usable(N, Cin, Cout, D, H, W);
+    const int Cin_f = weight_mode ? Cout : Cin, Cout_f = weight_mode ? Cin : Cout;       // w's own extents [Cout_f][Cin_f][27]
+    int rc = f32 ? conv3_f32c_pack_weights(w, wf, Cin_f, Cout_f, weight_mode, s) : conv3_sb_pack_weights(w, wf, Cin_f, Cout_f, weight_mode, s, gop);
+    if (rc) return rc;
+    a.mode = f32 ? RU_PREC_F32 : RU_PREC_BF16X3; a.wfrag = wf;
+    a.in_c16 = flags & 1; a.out_c16 = (flags >> 1) & 1; a.in_s16 = (flags >> 3) & 1;
+    RU_REQUIRE(!a.in_s16 || a.in_c16, "ru_conv3_l: the split form is a voxel-major layout");
+    a.x = x; a.bias = bias; a.y = y; a.N = N; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W;
+    a.add = add; a.in_scale = in_scale; a.in_shift = in_shift; a.in_slope = in_slope; a.in_res = in_res; a.in_sum_out = in_sum_out; a.sigmoid = sigmoid;
+    a.bst_y = bst_y; a.bst_k = bst_k; a.bst_slope = bst_slope; a.stat_partials = stat_partials;
+    if (gop) {
+        const size_t nvox = (size_t)N * D * H * W;
+        float* g16 = C.take(nvox * 16);
+        RU_WS_OK(C);
+        rc = conv3_mxg_split_launch(x, g16, nvox, s);
+        if (rc) return rc;
+        a.x = g16; a.in_s16 = 1; a.in_g16 = 1; a.products = 0;
+    }
+    if (flags & 4) {                                             // x NCDHW with Cin <= 4: 4-channel copy + tap-pair kernel
+        RU_REQUIRE(!(flags & 1) && conv3_sb4_usable(N, Cin, Cout, D, H, W), "ru_conv3_l: shape does not fit the 4-channel kernel");
+        const size_t V = (size_t)D * H * W;
+        float* x4 = C.take((size_t)N * 4 * V);
+        void* wf4 = C.take(conv3_sb4_frag_bytes(Cout) / 4 + 64);
+        RU_WS_OK(C);
+        rc = pad_to_c4_launch(x, x4, N, Cin, V, s);
+        if (rc) return rc;
+        rc = conv3_sb4_pack_weights(w, wf4, Cin_f, Cout_f, weight_mode, s);
+        if (rc) return rc;
+        a.x = x4; a.wfrag = wf4; a.in_c4 = 1;
+    }
+    const int r = f32 ? conv3_f32c_route(a) : conv3_sb_route(a);
+    if (route) *route = r;
+    const int nb = f32 ? conv3_f32c_tiles_per_sample(N, Cin, Cout, D, H, W) : conv3_sb_route_nblk(r, N, Cout, D, H, W);     // partials per (sample, channel)
+    if (nblk) *nblk = nb;
+    RU_REQUIRE(!stat_partials || stat_floats >= (size_t)N * Cout * nb * 2, "ru_conv3_l: statistics buffer too small");
+    return f32 ? conv3_launch(a, s) : conv3_sb_launch(a, s);
+}
+
 extern "C" size_t ru_wgrad1_l_workspace_bytes(int N, int Cin, int Cout, size_t V) { return 4096 + align_up(wgrad1_workspace_bytes(N, Cin, Cout, V), 256); }
 extern "C" int ru_wgrad1_l(const float* x, const float* x1, int C0, const float* dy, float* dw, int ldw, int N, int Cin, int Cout, size_t V,
                            int c16, int s2d, int Dc, int Hc, int Wc, int tap_split, const float* dg_w, int dg_ldw, float* dg_y0, float* dg_y1,

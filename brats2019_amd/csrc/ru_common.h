@@ -219,6 +219,29 @@ int conv3_f32c_pack_weights(const float* w, void* wfr, int Cin_f, int Cout_f, in
 int conv3_f32c_tiles_per_sample(int N, int Cin, int Cout, int D, int H, int W);
 int conv3_f32c_launch(const Conv3Args& a, const void* wfr, hipStream_t s);
 bool conv3_f32c_head_takes_residual(int Cin, int Cout, int W);
+// The kernel a launch of the 3x3x3 family takes, as ONE packed value: conv3_sb_route / conv3_f32c_route are the only places that decide (pure host functions of the
+// arguments and the RU_* switches; no RU_REQUIRE -- those stay with the launchers, which dispatch on the value), and ru_conv3_l reports it.
+//   bits 0-3 family | 4-7 TZ | 8-11 TY | 12 IN16 | 13 OUT16 | 14 MULTI | 15 BST | 16 ADD | 17 HEAD | 18 GRAD | 20-21 NP (MFMA products per operand pair: 1 / 3)
+// IN16 / OUT16: voxel-major input / output; MULTI: more than one 16-channel input chunk; BST: GroupNorm-backward sums instead of (sum, sumsq); ADD: residual operand;
+// HEAD: the <= 4-output-channel head form; GRAD (conv3_mx_kernel only): gradient-operand input.  Flags a family has no template parameter for are 0.
+enum Conv3Family { C3F_SB = 1, C3F_SB2 = 2, C3F_SB2C4 = 3, C3F_WZ32 = 4, C3F_WZ32MX = 5, C3F_MX = 6, C3F_F32C = 7, C3F_WZ16 = 8 /* builds with RU_SB2_DBG only */ };
+static inline int c3r_make(int family, int tz, int ty, bool in16, bool out16, bool multi = false, bool bst = false, bool add = false, bool head = false, bool grad = false, int np = 3) {
+    return family | (tz << 4) | (ty << 8) | (in16 << 12) | (out16 << 13) | (multi << 14) | (bst << 15) | (add << 16) | (head << 17) | (grad << 18) | (np << 20);
+}
+static inline int c3r_family(int r) { return r & 15; }
+static inline int c3r_tz(int r) { return (r >> 4) & 15; }
+static inline int c3r_ty(int r) { return (r >> 8) & 15; }
+static inline bool c3r_in16(int r) { return (r >> 12) & 1; }
+static inline bool c3r_out16(int r) { return (r >> 13) & 1; }
+static inline bool c3r_multi(int r) { return (r >> 14) & 1; }
+static inline bool c3r_bst(int r) { return (r >> 15) & 1; }
+static inline bool c3r_add(int r) { return (r >> 16) & 1; }
+static inline bool c3r_head(int r) { return (r >> 17) & 1; }
+static inline bool c3r_grad(int r) { return (r >> 18) & 1; }
+static inline int c3r_np(int r) { return (r >> 20) & 3; }
+int conv3_sb_route(const Conv3Args& a);
+int conv3_f32c_route(const Conv3Args& a);         // always carries f32c_choose's tile: the launcher reports one no kernel exists for
+int conv3_sb_route_nblk(int r, int N, int Cout, int D, int H, int W);     // partials per (sample, channel) the kernel of route r = conv3_sb_route(a) writes
 // split-bf16 path (conv3_sb.hip)
 int conv3_sb_tiles_per_sample(int N, int Cin, int Cout, int D, int H, int W, int products = 3);    // products: Conv3Args::products of the launch
 bool conv3_sb_head_form_enabled();                // RU_HEAD_FORM=0 keeps the <= 4-output-channel convolutions on the 16-column kernel (A/B runs, parity tests)

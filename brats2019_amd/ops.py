@@ -1048,3 +1048,54 @@ def conv1x1_bwd_weight_c16(x, dy, x1=None, ldw=None, s2d=False, tap_split=False,
                             cin // 8 if tap_split else 0, L.ptr(dg_w, True), int(dg_w.shape[1]) if dg_w is not None else 0, L.ptr(dx0, True), L.ptr(dx1, True),
                             float(dg_mask_slope), C.byref(inst), L.ptr(ws), ws.numel(), L.stream()), "ru_wgrad1_l")
     return Wgrad1Result(dw, dx0, dx1, inst.value)
+
+
+Conv3Result = collections.namedtuple("Conv3Result", "y in_sum partials nblk route")
+Conv3Route = collections.namedtuple("Conv3Route", "family tz ty in16 out16 multi bst add np head grad")
+CONV3_FAMILIES = {1: "sb", 2: "sb2", 3: "sb2c4", 4: "wz32", 5: "wz32mx", 6: "mx", 7: "f32c", 8: "wz16"}
+
+
+def conv3_route(packed):
+    """ru_conv3_l's kernel report (conv3_sb_route / conv3_f32c_route) -> (family, TZ, TY, IN16, OUT16, MULTI, BST, ADD, NP, HEAD, GRAD)."""
+    bit = lambda b: bool((packed >> b) & 1)
+    return Conv3Route(CONV3_FAMILIES.get(packed & 15, "none"), (packed >> 4) & 15, (packed >> 8) & 15, bit(12), bit(13), bit(14), bit(15), bit(16),
+                      (packed >> 20) & 3, bit(17), bit(18))
+
+
+def conv3_fused(x, w, bias=None, in_c16=False, out_c16=False, few_channels=False, in_split=False, exact_f32=False, activations=False, gradient=False,
+                add=None, in_scale=None, in_shift=None, in_slope=LEAKY_SLOPE, in_res=None, in_sum_out=None, sigmoid=False, products=0,
+                bst_y=None, bst_k=None, bst_slope=LEAKY_SLOPE, stats=None, weight_mode=0):
+    """One launch of the 3x3x3 family with the operands the engine fuses into it (ru_conv3_l; layout flags as conv3d_layout).  in_scale / in_shift [N, Cin]: the
+    GroupNorm apply + LeakyReLU(in_slope) formed in the staging; in_res (voxel-major): added to the transformed input, the sum written to in_sum_out (a tensor
+    like x, or True to allocate one); add: joined in the store; stats: per-workgroup (sum, sumsq) of the stored value before the sigmoid -- or, with bst_y /
+    bst_k [N, 3, Cout], the GroupNorm-backward sums -- returned as partials [N, Cout, nblk, 2] (default: on with bst_y); weight_mode = 1: w is the FORWARD
+    convolution's [Cin, Cout, 3, 3, 3] and is packed as its data gradient.  route: decode with conv3_route."""
+    x, w, bias, add, in_scale, in_shift, in_res, bst_y, bst_k = (_prep(t) for t in (x, w, bias, add, in_scale, in_shift, in_res, bst_y, bst_k))
+    if in_c16:
+        n, cb, d, h, wd, _ = (int(v) for v in x.shape)
+        cin = cb * 16
+    else:
+        n, cin, d, h, wd = _dims5(x)
+    cout = int(w.shape[1 if weight_mode else 0])
+    dev = x.device
+    y = torch.empty((n, cout // 16, d, h, wd, 16) if out_c16 else (n, cout, d, h, wd), dtype=torch.float32, device=dev)
+    if in_sum_out is True:
+        in_sum_out = torch.full_like(x, float("nan"))
+    part, cap = None, 0
+    if stats is None:
+        stats = bst_y is not None
+    if stats:
+        cap = n * cout * max(((d + 1) // 2) * ((h + 1) // 2) * ((wd + 15) // 16), 1024) * 2      # nblk <= the (2,2,16) tiles of a sample, or one per workgroup
+        part = torch.full((cap,), float("nan"), dtype=torch.float32, device=dev)
+    flags = (int(in_c16) | (int(out_c16) << 1) | (int(few_channels) << 2) | (int(in_split) << 3) | (int(exact_f32) << 4) | (int(activations) << 5)
+             | (int(gradient) << 6))
+    lib = L.load()
+    ws = L.workspace(lib.ru_conv3_l_workspace_bytes(n, cin, cout, d, h, wd, flags), dev)
+    nblk, route = C.c_int(0), C.c_int(0)
+    L.check(lib.ru_conv3_l(L.f32(x), L.f32(w), L.ptr(bias, True), L.f32(y), n, cin, cout, d, h, wd, flags, int(weight_mode), L.ptr(add, True),
+                           L.ptr(in_scale, True), L.ptr(in_shift, True), float(in_slope), L.ptr(in_res, True), L.ptr(in_sum_out, True), int(bool(sigmoid)),
+                           int(products), L.ptr(bst_y, True), L.ptr(bst_k, True), float(bst_slope), L.ptr(part, True), cap, C.byref(nblk), C.byref(route),
+                           L.ptr(ws), ws.numel(), L.stream()), "ru_conv3_l")
+    if part is not None:
+        part = part[:n * cout * nblk.value * 2].view(n, cout, nblk.value, 2)
+    return Conv3Result(y, in_sum_out, part, nblk.value, route.value)

@@ -524,6 +524,24 @@ int ru_conv1_l(const float* x0, int C0, const float* x1, int C1, const float* w,
                const float* add, float out_slope, const float* mask, float mask_slope, int N, int Cout, size_t V,
                int s2d, int Dc, int Hc, int Wc, const float* bst_y, const float* bst_k, float bst_slope,
                float* stat_partials, size_t stat_floats, int* nblk, int* inst, void* ws, size_t ws_bytes, ru_stream_t stream);
+/* The 3x3x3 family, one launch at a time with the operands the engine fuses into it (flags as ru_conv3d_fwd_l; x / y / add / bst_y / in_res / in_sum_out in the layouts the
+ * flags name, in_res / in_sum_out always voxel-major like x):
+ *   y = act( conv3( pad0( lrelu(x*in_scale[n][c] + in_shift[n][c], in_slope) + in_res ), w ) + bias + add ),  act = sigmoid or none; in_scale null: no transform.
+ *   in_sum_out (with in_res): the staged sum before the padding, every voxel written once.
+ *   stat_partials [N][Cout][*nblk][2] (capacity stat_floats): per-workgroup (sum, sumsq) of the value after `add` and before the sigmoid; with bst_y / bst_k[N][3][Cout] /
+ *   bst_slope instead the GroupNorm-backward sums of that value d: u = bst_y*k1 + k2, dh = u > thr ? d : d*bst_slope, S1 = sum dh, S2' = sum dh*u.
+ *   products: 0 / 3 = three split-bf16 products, 1 = one bf16 product (gradient precision), 2 = x is an activation tensor (same as flag bit 5).
+ *   weight_mode 0: w = [Cout][Cin][3][3][3]; 1: w = [Cin][Cout][3][3][3] is the weight of the FORWARD convolution whose data gradient this launch computes
+ *   (channels swapped, taps mirrored in the packing).
+ *   *route (optional): the kernel taken -- family (1 one-stage sb, 2 persistent sb2, 3 sb2c4, 4 wz32, 5 wz32mx, 6 mx, 7 f32c; 8 wz16, the
+ *   16x16 Winograd-z kernel, which only a build with the developer switch RU_SB2_DBG can route to) | TZ << 4 | TY << 8 | IN16 << 12 |
+ *   OUT16 << 13 | MULTI << 14 | BST << 15 | ADD << 16 | HEAD << 17 | GRAD << 18 | products per operand pair << 20.
+ * The tail finalize of the statistics (the engine's ticket) and split-K are not reachable from here. */
+size_t ru_conv3_l_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W, int flags);
+int ru_conv3_l(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Cout, int D, int H, int W, int flags, int weight_mode,
+               const float* add, const float* in_scale, const float* in_shift, float in_slope, const float* in_res, float* in_sum_out,
+               int sigmoid, int products, const float* bst_y, const float* bst_k, float bst_slope, float* stat_partials, size_t stat_floats,
+               int* nblk, int* route, void* ws, size_t ws_bytes, ru_stream_t stream);
 size_t ru_wgrad1_l_workspace_bytes(int N, int Cin, int Cout, size_t V);
 int ru_wgrad1_l(const float* x, const float* x1, int C0, const float* dy, float* dw, int ldw, int N, int Cin, int Cout, size_t V,
                 int c16, int s2d, int Dc, int Hc, int Wc, int tap_split, const float* dg_w, int dg_ldw, float* dg_y0, float* dg_y1,
