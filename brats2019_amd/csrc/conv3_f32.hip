@@ -231,8 +231,7 @@ int conv3_f32_ksplit(int N, int Cin, int Cout, int D, int H, int W) {
     return ks;
 }
 
-int conv3_tiles_per_sample(int N, int Cin, int Cout, int D, int H, int W, int mode) {
-    if (conv3_effective_mode(mode, W) == RU_PREC_BF16X3) return conv3_sb_tiles_per_sample(N, Cin, Cout, D, H, W);
+int conv3_f32_tiles_per_sample(int N, int Cin, int Cout, int D, int H, int W) {
     if (conv3_f32_ksplit(N, Cin, Cout, D, H, W) > 1) return gn_stats_tiles((size_t)D * H * W);      // (the engine's split path: gn_stats_launch takes them)
     const C3Choice c = conv3_choose(N, Cin, Cout, D, H, W);
     return cdiv(D, c.tz) * cdiv(H, c.ty) * cdiv(W, 16);
@@ -263,7 +262,7 @@ static int launch_cfg(const Conv3Args& a, hipStream_t s) {
     return RU_OK;
 }
 
-int conv3_launch(const Conv3Args& a_in, hipStream_t s) {
+int conv3_launch(const Conv3Args& a_in, const Switches& sw, hipStream_t s) {
     Conv3Args a = a_in;
     a.CinP = conv3_cin_pad(a.Cin);
     a.CoutP = conv3_cout_pad(a.Cout);
@@ -273,7 +272,7 @@ int conv3_launch(const Conv3Args& a_in, hipStream_t s) {
     if (a.in_c16 || a.out_c16 || a.in_c4) RU_REQUIRE(a.mode == RU_PREC_BF16X3, "conv3: voxel-major tensors need the split-bf16 kernel");
     if (a.in_c16 || a.out_c16 || a.in_c4 || conv3_effective_mode(a.mode, a.W) == RU_PREC_BF16X3) {
         RU_REQUIRE(a.wfrag != nullptr, "conv3: bf16x3 mode needs packed weight fragments");
-        return conv3_sb_launch(a, s);
+        return conv3_sb_launch(a, sw, s);
     }
     RU_REQUIRE(a.wp != nullptr, "conv3: f32 mode needs packed weights");
     const C3Choice c = conv3_choose(a.N, a.Cin, a.Cout, a.D, a.H, a.W);

@@ -440,10 +440,9 @@ int conv3_f32c_tiles_per_sample(int N, int Cin, int Cout, int D, int H, int W) {
     return (int)f32c_grid_x(N, Cout, D, H, W, c.tz, c.ty);
 }
 
-// the 16 -> <= 4 voxel-major-in / NCDHW-out conv takes the head form, whose staging forms Conv3Args::in_res (RU_HEAD_RES=0: never; conv3_sb_head_takes_residual)
-bool conv3_f32c_head_takes_residual(int Cin, int Cout, int W) {
-    const char* e = getenv("RU_HEAD_RES");
-    return !(e && *e == '0') && f32c_head_form(Cin, Cout) && Cin % 16 == 0 && (W & 3) == 0;
+// the 16 -> <= 4 voxel-major-in / NCDHW-out conv takes the head form, whose staging forms Conv3Args::in_res (Switches::head_res off: never; conv3_sb_head_takes_residual)
+bool conv3_f32c_head_takes_residual(const Switches& sw, int Cin, int Cout, int W) {
+    return sw.head_res && f32c_head_form(Cin, Cout) && Cin % 16 == 0 && (W & 3) == 0;
 }
 
 // the kernel conv3_f32c_launch takes for `a` (ru_common.h: c3r_*): tile, IN16 / OUT16, HEAD.  Pure; the tile is f32c_choose's whether or not a kernel exists for it.  (An NCDHW input always writes

@@ -5,27 +5,12 @@
 
 namespace ru {
 
-bool conv3_mx_enabled() {
-    const char* e = getenv("RU_MX");                    // read per call: tests and tools switch it inside one process
-    return !(e && *e == '0');
-}
-
-bool conv3_mx_wz_enabled() {                          // RU_MX=1: the 16-channel kernel only (same-box A/B of the Winograd-z form); RU_MX=0: neither
-    const char* e = getenv("RU_MX");
-    return !(e && (*e == '0' || *e == '1'));
-}
-
 bool conv3_mx_shape_ok(int N, int Cin, int Cout, int D, int H, int W) {
     return mx_channels_ok(Cin, Cout) && sb_use_v2(sb_choose(N, Cout, D, H, W));
 }
 
-bool conv3_mxg_enabled() {                            // RU_MXG=0: the 16-channel data-gradient convolutions keep three bf16 products (same-box A/B, parity tests)
-    const char* e = getenv("RU_MXG");
-    return !(e && *e == '0');
-}
-
-bool conv3_mxg_usable(int N, int Cin, int Cout, int D, int H, int W) {
-    return conv3_mxg_enabled() && Cin == 16 && Cout == 16 && conv3_mx_shape_ok(N, Cin, Cout, D, H, W) && (size_t)D * H * W * 64 < ((size_t)1 << 31);
+bool conv3_mxg_usable(const Switches& sw, int N, int Cin, int Cout, int D, int H, int W) {
+    return sw.mxg && Cin == 16 && Cout == 16 && conv3_mx_shape_ok(N, Cin, Cout, D, H, W) && (size_t)D * H * W * 64 < ((size_t)1 << 31);
 }
 
 template <bool GRAD, bool BST, bool ADD>
@@ -47,7 +32,7 @@ static int mx_cfg(const Conv3Args& a, const void* mxfrag, hipStream_t s) {
     return RU_OK;
 }
 
-int conv3_mx_launch(const Conv3Args& a, const void* mxfrag, int r, hipStream_t s) {       // r = conv3_sb_route(a): <GRAD, BST, ADD>
+int conv3_mx_launch(const Conv3Args& a, const void* mxfrag, int r, hipStream_t s) {       // r = conv3_sb_route(a, sw): <GRAD, BST, ADD>
     RU_REQUIRE(a.in_c16 && a.out_c16 && !a.in_c4 && !a.bias && !a.sigmoid && !a.in_res && conv3_mx_shape_ok(a.N, a.Cin, a.Cout, a.D, a.H, a.W),
                "conv3_mx: voxel-major tensors, 16 input channels, whole 16-channel output blocks, no bias / input residual");
     RU_REQUIRE(a.N <= 32 || !a.stat_partials, "conv3_mx: at most 32 samples per call when statistics are requested");

@@ -153,10 +153,8 @@ __device__ __forceinline__ void mx_pack_one(const float* __restrict__ w, u32x4* 
     mxfrag[((size_t)cog * MX_UNITS + unit) * 64 + lane] = out;
 }
 
-// launch rule and entry (conv3_mx.hip)
-bool conv3_mx_enabled();                                 // RU_MX=0: every forward convolution keeps the three-product kernels (same-box A/B, parity tests)
-bool conv3_mx_wz_enabled();                              // ... and the Winograd-z form of the scheme at 32..128 channels (conv3_wz32mx.hpp); RU_MX=1: the 16-channel kernel only
+// launch rule and entry (conv3_mx.hip; Switches::mx / mx_wz, switches.hpp, say whether the scheme is taken at all)
 bool conv3_mx_shape_ok(int N, int Cin, int Cout, int D, int H, int W);
 int conv3_mx_launch(const Conv3Args& a, const void* mxfrag, int r, hipStream_t s);
-// (conv3_mxg_enabled / conv3_mxg_usable / conv3_mxg_split_launch: ru_common.h -- the engine and the weight gradient use them)
+// (conv3_mxg_usable / conv3_mxg_split_launch: ru_common.h -- the engine and the weight gradient use them)
 }  // namespace ru

@@ -646,15 +646,12 @@ static inline int sb_pack_threads(int cin_conv, int cout_conv, int forms) {
     return ncog * nchunk * SB_KSTEPS * 64 + (wz_channels_ok(cin_conv, cout_conv) ? (cout_conv / 32) * nchunk * (((WZ16_FORM && (forms & 1)) ? 4 * 2 * WZ_KSTEPS : 0) + ((forms & 2) ? 4 * 9 : 0) + ((forms & 8) ? WZ32MX_UNITS_XI : 0)) * 64 : 0)
          + (sb_head_shape(cin_conv, cout_conv) ? SB_HEAD_KSTEPS * 64 : 0) + (((forms & 4) && mx_channels_ok(cin_conv, cout_conv)) ? ncog * MX_UNITS * 64 : 0);
 }
-// what the launches of a TRAINING forward + backward read of a weight packed in `mode` (0: forward, 1: data gradient) under the RU_WZ / RU_WZ32 / RU_MX switches
-// (read per call, as the launches read them; a toggle BETWEEN a forward's pack and a launch that reads it is not supported -- tools and tests toggle between steps)
-static int sb_pack_forms(int mode) {
-    if (mode == 1) return conv3_mxg_enabled() ? (4 | 32) : 0;   // data-gradient launches (split-form inputs) take the direct kernels; 16 -> 16: the gradient-operand MX form beside them
-    const bool mxon = conv3_mx_enabled();                   // forward convolutions only: gradients never take the fp16 + MX-fp8 scheme
-    const char* e = getenv("RU_WZ");
-    if (e && *e == '0') return mxon ? 4 : 0;
-    if (mxon && conv3_mx_wz_enabled()) return 4 | 8;        // forward launches take the MX kernel of their shape: direct (16 channels) or Winograd-z (32..)
-    return (mxon ? 4 : 0) | (conv3_wz32_enabled() ? 2 : 1); // ... or ONE three-product Winograd-z form
+// what the launches of a TRAINING forward + backward under `sw` read of a weight packed in `mode` (0: forward, 1: data gradient)
+static int sb_pack_forms(const Switches& sw, int mode) {
+    if (mode == 1) return sw.mxg ? (4 | 32) : 0;            // data-gradient launches (split-form inputs) take the direct kernels; 16 -> 16: the gradient-operand MX form beside them
+    if (!sw.wz) return sw.mx ? 4 : 0;                       // forward convolutions only: gradients never take the fp16 + MX-fp8 scheme
+    if (sw.mx && sw.mx_wz) return 4 | 8;                    // forward launches take the MX kernel of their shape: direct (16 channels) or Winograd-z (32..)
+    return (sw.mx ? 4 : 0) | (sw.wz32 ? 2 : 1);             // ... or ONE three-product Winograd-z form
 }
 __global__ void conv3_sb_pack_kernel(const float* __restrict__ w, u32x4* __restrict__ wfrag, int Cin_f, int Cout_f, int mode, int nchunk, int ncog, int forms) {
     sb_pack_both(w, wfrag, Cin_f, Cout_f, mode, nchunk, ncog, forms, blockIdx.x * blockDim.x + threadIdx.x);
@@ -678,20 +675,16 @@ int conv3_sb_pack_batch(SbPackBatch& b, hipStream_t s) {
     b.n = 0;
     return RU_OK;
 }
-int conv3_sb_switch_signature() {
-    const char* e = getenv("RU_WZ");
-    return ((e && *e == '0') ? 0 : 1) | (conv3_wz32_enabled() ? 2 : 0) | (conv3_mx_enabled() ? 4 : 0) | (conv3_mx_wz_enabled() ? 8 : 0) | (conv3_mxg_enabled() ? 16 : 0);
+bool conv3_sb_forward_skips_direct(const Switches& sw, int N, int Cin, int Cout, int D, int H, int W) {
+    if (sw.wz && conv3_wz_shape_ok(N, Cin, Cout, D, H, W)) return true;             // conv3_wz32mx_kernel or conv3_wz32_kernel
+    return sw.mx && conv3_mx_shape_ok(N, Cin, Cout, D, H, W);                       // conv3_mx_kernel
 }
-bool conv3_sb_forward_skips_direct(int N, int Cin, int Cout, int D, int H, int W) {
-    if (conv3_sb_uses_wz(N, Cin, Cout, D, H, W, 2)) return true;                    // conv3_wz32mx_kernel or conv3_wz32_kernel
-    return conv3_mx_enabled() && conv3_mx_shape_ok(N, Cin, Cout, D, H, W);          // conv3_mx_kernel
-}
-int conv3_sb_pack_add(SbPackBatch& b, const float* w, void* wfrag, int Cin_f, int Cout_f, int mode, bool all_forms, hipStream_t s, bool skip_direct) {
+int conv3_sb_pack_add(SbPackBatch& b, const Switches& sw, const float* w, void* wfrag, int Cin_f, int Cout_f, int mode, bool all_forms, hipStream_t s, bool skip_direct) {
     if (b.n == RU_PACK_BATCH) { const int rc = conv3_sb_pack_batch(b, s); if (rc) return rc; }
     const int cin_conv = mode == 0 ? Cin_f : Cout_f, cout_conv = mode == 0 ? Cout_f : Cin_f;
     SbPackEntry& e = b.e[b.n++];
     e.w = w; e.wfrag = wfrag; e.Cin_f = Cin_f; e.Cout_f = Cout_f; e.mode = mode; e.nchunk = cdiv(cin_conv, 16); e.ncog = cdiv(cout_conv, 16);
-    e.forms = all_forms ? SB_FORMS_ALL : (sb_pack_forms(mode) | ((skip_direct && mode == 0) ? 16 : 0));
+    e.forms = all_forms ? SB_FORMS_ALL : (sb_pack_forms(sw, mode) | ((skip_direct && mode == 0) ? 16 : 0));
     return RU_OK;
 }
 
@@ -703,19 +696,12 @@ size_t conv3_sb_frag_bytes(int Cin_conv, int Cout_conv) {          // direct fra
          + (sb_head_shape(Cin_conv, Cout_conv) ? (size_t)SB_HEAD_KSTEPS * 2 * 64 * 16 : 0) + mx_frag_bytes(Cin_conv, Cout_conv);
 }
 // The inference head: the last Residual block's output x + lrelu(norm2(conv2)) (model.py:112-116) is formed in the head conv's staging instead of a pass of its
-// own (Conv3Args::in_res).  Exists in the head-form variant of the persistent kernel only: the same tests as conv3_sb_launch's way there.  RU_HEAD_RES=0: off (A/B).
-bool conv3_sb_head_takes_residual(int N, int Cin, int Cout, int D, int H, int W) {
-    const char* e = getenv("RU_HEAD_RES");
-    if (e && *e == '0') return false;
-    if (!conv3_sb_head_form_enabled() || !sb_head_shape(Cin, Cout) || Cin % 16 != 0 || (W & 3) != 0) return false;
+// own (Conv3Args::in_res).  Exists in the head-form variant of the persistent kernel only: the same tests as conv3_sb_launch's way there.  Switches::head_res off: never (A/B).
+bool conv3_sb_head_takes_residual(const Switches& sw, int N, int Cin, int Cout, int D, int H, int W) {
+    if (!sw.head_res || !sw.head_form || !sb_head_shape(Cin, Cout) || Cin % 16 != 0 || (W & 3) != 0) return false;
     if ((size_t)D * H * W * 64 >= ((size_t)1 << 31)) return false;
     return sb_use_v2(sb_choose(N, Cout, D, H, W));
 }
-bool conv3_sb_head_form_enabled() {
-    const char* e = getenv("RU_HEAD_FORM");
-    return !(e && e[0] == '0');
-}
-
 int conv3_sb_pack_weights(const float* w, void* wfrag, int Cin_f, int Cout_f, int mode, hipStream_t s, bool grad_operand) {
     const int cin_conv = mode == 0 ? Cin_f : Cout_f, cout_conv = mode == 0 ? Cout_f : Cin_f;
     const int nchunk = cdiv(cin_conv, 16), ncog = cdiv(cout_conv, 16);
@@ -724,23 +710,6 @@ int conv3_sb_pack_weights(const float* w, void* wfrag, int Cin_f, int Cout_f, in
     hipLaunchKernelGGL(conv3_sb_pack_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, w, (u32x4*)wfrag, Cin_f, Cout_f, mode, nchunk, ncog, forms);
     RU_CHECK_LAUNCH("conv3_sb_pack_kernel");
     return RU_OK;
-}
-
-// number of statistics partials per (sample, channel) the kernel chosen for this shape writes
-// The Winograd-z kernels (conv3_wz32.hpp, conv3_wz32mx.hpp) take the voxel-major FORWARD convolutions of 32 and more channels whose shape fills the chip;
-// RU_WZ=0 keeps every shape on the direct kernels (same-box A/B).  ONE rule for the launch and for the partial count the engine sizes.  Split-form inputs
-// (the data-gradient convolutions: gn_bwd_apply16's hi / lo packets) stay on the direct kernel: there the staging is a global -> LDS DMA copy with no VALU
-// work at all, while the z transform has to re-join, transform and re-split every value -- measured 120 / 143 / 104 us against 93 / 107 / 79 in round 5.
-bool conv3_sb_uses_wz(int N, int Cin, int Cout, int D, int H, int W, int products) {
-    const char* e = getenv("RU_WZ");                    // read per call: tests and tools switch it inside one process
-    const bool off = e && *e == '0';
-    return !off && products != 1 && conv3_wz_shape_ok(N, Cin, Cout, D, H, W);
-}
-int conv3_sb_tiles_per_sample(int N, int Cin, int Cout, int D, int H, int W, int products) {
-    if (conv3_sb_uses_wz(N, Cin, Cout, D, H, W, products)) return (int)wz_grid_x(N, Cout, D, H, W);
-    const SBChoice c = sb_choose(N, Cout, D, H, W);
-    if (sb_use_v2(c)) return (int)sb2_grid_x(N, Cout, D, H, W);        // persistent kernel: one per workgroup
-    return cdiv(D, c.tz) * cdiv(H, c.ty) * cdiv(W, 16);                 // one-stage kernel: one per tile
 }
 
 bool conv3_sb_bst_usable(int N, int Cout, int D, int H, int W) { return sb_use_v2(sb_choose(N, Cout, D, H, W)); }
@@ -786,9 +755,9 @@ static int sb2c4_cfg(const Conv3Args& a, hipStream_t s) {
     return RU_OK;
 }
 
-// The kernel conv3_sb_launch takes for `a` (ru_common.h: Conv3Family, c3r_*): the ONE place that decides.  Pure: it reads the arguments and the RU_* switches and
+// The kernel conv3_sb_launch takes for `a` (ru_common.h: Conv3Family, c3r_*): the ONE place that decides.  Pure: it reads the arguments and the switches and
 // judges nothing -- an argument set the launcher refuses still gets the value of the branch it would have reached.
-int conv3_sb_route(const Conv3Args& a) {
+int conv3_sb_route(const Conv3Args& a, const Switches& sw) {
     if (a.in_c4) return c3r_make(C3F_SB2C4, 4, 8, false, a.bst_y || a.out_c16, false, a.bst_y != nullptr);
     SBChoice c = sb_choose(a.N, a.Cout, a.D, a.H, a.W);
     if (sb_use_v2(c) && a.bias && a.out_c16) c = SBChoice{2, 8};
@@ -796,17 +765,20 @@ int conv3_sb_route(const Conv3Args& a) {
     if ((RU_SB2_DBG & 2048) && !a.stat_partials) c = SBChoice{2, 8};      // tools: time the one-stage kernel on a shape the persistent kernel would take
     if ((RU_SB2_DBG & 4096) && !a.stat_partials) c = SBChoice{2, 4};
 #endif      // (no engine path: the persistent kernel has the bias for NCDHW output only)
-    if (a.in_c16 && a.out_c16 && !a.in_s16 && !a.bias && !a.sigmoid && !a.bst_y && !a.add && conv3_sb_uses_wz(a.N, a.Cin, a.Cout, a.D, a.H, a.W, a.products)) {
-        if (a.products == 2 && conv3_mx_wz_enabled()) return c3r_make(C3F_WZ32MX, 2, 8, true, true, true);      // an activation tensor: fp16 + MX-fp8 products (conv3_wz32mx.hpp)
+    // The Winograd-z kernels (conv3_wz32.hpp, conv3_wz32mx.hpp) take the voxel-major FORWARD convolutions of 32 and more channels whose shape fills the chip.  Split-form
+    // inputs (the data-gradient convolutions: gn_bwd_apply16's hi / lo packets) stay on the direct kernel: there the staging is a global -> LDS DMA copy with no VALU
+    // work at all, while the z transform has to re-join, transform and re-split every value -- measured 120 / 143 / 104 us against 93 / 107 / 79 in round 5.
+    if (a.in_c16 && a.out_c16 && !a.in_s16 && !a.bias && !a.sigmoid && !a.bst_y && !a.add && sw.wz && a.products != 1 && conv3_wz_shape_ok(a.N, a.Cin, a.Cout, a.D, a.H, a.W)) {
+        if (a.products == 2 && sw.mx_wz) return c3r_make(C3F_WZ32MX, 2, 8, true, true, true);      // an activation tensor: fp16 + MX-fp8 products (conv3_wz32mx.hpp)
 #ifdef RU_SB2_DBG
-        if (!conv3_wz32_enabled()) return c3r_make(C3F_WZ16, 2, 8, true, true, true);
+        if (!sw.wz32) return c3r_make(C3F_WZ16, 2, 8, true, true, true);
 #endif
         return c3r_make(C3F_WZ32, 2, 8, true, true, true);                                                      // matrix waves on 32x32x16 MFMAs (conv3_wz32.hpp)
     }
     if (a.in_g16) return c3r_make(C3F_MX, 4, 8, true, true, false, a.bst_y != nullptr, a.add != nullptr, false, true);
     // Conv3Args::products == 2: the caller's input is an ACTIVATION tensor and it asks for the fp16 + MX-fp8 product scheme where a kernel for the shape exists
     // (conv3_mx.hpp: the 16-channel level); everywhere else the request means three products
-    if (a.products == 2 && a.in_c16 && a.out_c16 && !a.in_s16 && !a.bias && !a.sigmoid && !a.add && !a.bst_y && !a.in_res && conv3_mx_enabled() &&
+    if (a.products == 2 && a.in_c16 && a.out_c16 && !a.in_s16 && !a.bias && !a.sigmoid && !a.add && !a.bst_y && !a.in_res && sw.mx &&
         conv3_mx_shape_ok(a.N, a.Cin, a.Cout, a.D, a.H, a.W))
         return c3r_make(C3F_MX, 4, 8, true, true);
     const bool i16 = a.in_c16 != 0, o16 = a.out_c16 != 0;
@@ -815,11 +787,11 @@ int conv3_sb_route(const Conv3Args& a) {
     const bool multi = a.Cin > 16;
     if (i16 && o16 && a.bst_y) return c3r_make(C3F_SB2, 4, 8, i16, o16, multi, true, a.add != nullptr, false, false, np);
     if (a.add) return c3r_make(C3F_SB2, 4, 8, i16, o16, multi, false, true, false, false, np);
-    if (i16 && !o16 && sb_head_shape(a.Cin, a.Cout) && conv3_sb_head_form_enabled()) return c3r_make(C3F_SB2, 4, 8, i16, o16, false, false, false, true, false, np);
+    if (i16 && !o16 && sb_head_shape(a.Cin, a.Cout) && sw.head_form) return c3r_make(C3F_SB2, 4, 8, i16, o16, false, false, false, true, false, np);
     return c3r_make(C3F_SB2, 4, 8, i16, o16, multi, false, false, false, false, np);
 }
 
-// partials per (sample, channel) the kernel of route r writes (== the x extent of its grid): the count follows the route, so a launch that conv3_sb_uses_wz would
+// partials per (sample, channel) the kernel of route r writes (== the x extent of its grid): the count follows the route, so a launch whose shape the Winograd-z kernels would
 // accept but whose operands (residual, GroupNorm-backward sums, split-form input) keep it on a direct kernel counts as that kernel does
 int conv3_sb_route_nblk(int r, int N, int Cout, int D, int H, int W) {
     switch (c3r_family(r)) {
@@ -829,19 +801,19 @@ int conv3_sb_route_nblk(int r, int N, int Cout, int D, int H, int W) {
     }
 }
 
-int conv3_sb_launch(const Conv3Args& a, hipStream_t s) {
+int conv3_sb_launch(const Conv3Args& a, const Switches& sw, hipStream_t s) {
     RU_REQUIRE(!(a.sigmoid && a.out_c16), "conv3_sb: the fused sigmoid exists for NCDHW output only");
     RU_REQUIRE(!a.bst_y || (a.bst_k && a.stat_partials && (a.in_c16 || a.in_c4) && a.out_c16 && !a.bias && !a.sigmoid && (!a.add || !a.in_c4) &&
                             conv3_sb_bst_usable(a.N, a.Cout, a.D, a.H, a.W)),
                "conv3_sb: fused GroupNorm-backward statistics need the persistent voxel-major kernel, a partial buffer and no bias / activation");
-    RU_REQUIRE(!a.in_res || (a.in_c16 && !a.out_c16 && !a.in_c4 && !a.add && a.in_scale && conv3_sb_head_takes_residual(a.N, a.Cin, a.Cout, a.D, a.H, a.W)),
+    RU_REQUIRE(!a.in_res || (a.in_c16 && !a.out_c16 && !a.in_c4 && !a.add && a.in_scale && conv3_sb_head_takes_residual(sw, a.N, a.Cin, a.Cout, a.D, a.H, a.W)),
                "conv3_sb: a residual of the input is staged by the head-form kernel only (conv3_sb_head_takes_residual)");
     if (a.in_c4) {
         RU_REQUIRE(a.Cin <= 4 && !a.in_scale, "conv3_sb: the 4-channel kernel takes Cin <= 4 and no fused input transform");
         RU_REQUIRE(!a.out_c16 || a.Cout % 16 == 0, "conv3_sb: C16 output needs Cout %% 16 == 0");
         const SBChoice c4 = sb_choose(a.N, a.Cout, a.D, a.H, a.W);
         RU_REQUIRE(sb_use_v2(c4), "conv3_sb: the 4-channel kernel needs at least 256 (4,8,16) tiles x cout groups");
-        const int r4 = conv3_sb_route(a);
+        const int r4 = conv3_sb_route(a, sw);
         if (c3r_bst(r4)) return sb2c4_cfg<true, true>(a, s);
         return c3r_out16(r4) ? sb2c4_cfg<true>(a, s) : sb2c4_cfg<false>(a, s);
     }
@@ -850,7 +822,7 @@ int conv3_sb_launch(const Conv3Args& a, hipStream_t s) {
     RU_REQUIRE(!a.in_s16 || (a.in_c16 && !a.in_scale), "conv3_sb: a split-form input is voxel-major and has no fused transform");
     RU_REQUIRE(!a.out_c16 || a.Cout % 16 == 0, "conv3_sb: C16 output needs Cout %% 16 == 0");
     RU_REQUIRE(!(a.bias && a.out_c16 && a.stat_partials), "conv3_sb: bias + voxel-major output + statistics is not a path of the network");
-    const int r = conv3_sb_route(a);
+    const int r = conv3_sb_route(a, sw);
     const void* behind = static_cast<const char*>(a.wfrag) + conv3_sb_frag_bytes_direct(a.Cin, a.Cout);     // the non-direct fragments of the same weight
     switch (c3r_family(r)) {
     case C3F_WZ32: case C3F_WZ32MX: case C3F_WZ16:
@@ -858,7 +830,7 @@ int conv3_sb_launch(const Conv3Args& a, hipStream_t s) {
     case C3F_MX:
         // Conv3Args::in_g16: the input is a gradient in the operand form of the MX scheme (the caller asked conv3_mxg_usable before it wrote the tensor that way)
         if (c3r_grad(r))
-            RU_REQUIRE(a.in_s16 && a.out_c16 && !a.bias && !a.sigmoid && !a.in_res && conv3_mxg_usable(a.N, a.Cin, a.Cout, a.D, a.H, a.W),
+            RU_REQUIRE(a.in_s16 && a.out_c16 && !a.bias && !a.sigmoid && !a.in_res && conv3_mxg_usable(sw, a.N, a.Cin, a.Cout, a.D, a.H, a.W),
                        "conv3_sb: a gradient-operand input is taken by conv3_mx_kernel<GRAD> only (16 -> 16 channels, persistent-kernel shapes)");
         return conv3_mx_launch(a, behind, r, s);
     case C3F_SB2:

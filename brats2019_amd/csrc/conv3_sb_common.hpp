@@ -245,8 +245,7 @@ static inline SBChoice sb_choose(int N, int Cout, int D, int H, int W) {
     if (blocks(2, 8) >= 1024) return {2, 8};
     // fewer (2,4,16) tiles x cout groups than TWO per CU (the 128-channel level of a batch-1 forward: 256): the one-stage kernel walks its
     // input-channel chunks with every chunk's weight-fragment latency exposed and only a second resident workgroup can hide it -- half-size tiles
-    static const bool no22 = [] { const char* e = getenv("RU_SB1_NO22"); return e && *e == '1'; }();      // (tools: A/B of the half-size tile)
-    if (!no22 && blocks(2, 4) < 2 * sb_ncu() && blocks(2, 2) >= sb_ncu()) return {2, 2};
+    if (!env_sb1_no22() && blocks(2, 4) < 2 * sb_ncu() && blocks(2, 2) >= sb_ncu()) return {2, 2};
     return {2, 4};
 }
 

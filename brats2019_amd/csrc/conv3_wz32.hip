@@ -1,17 +1,10 @@
 // conv3_wz32.hip -- the Winograd-z convolution with its matrix waves on v_mfma_f32_32x32x16_bf16 (conv3_wz32.hpp): the kernel's own translation
-// unit and its launch.  conv3_wz_launch (conv3_wz.hip) routes the forward form here (RU_WZ32=0: the 16x16x32 matrix form, same-box A/B).
+// unit and its launch.  conv3_wz_launch (conv3_wz.hip) routes the forward form here (Switches::wz32 off, devtools builds: the 16x16x32 matrix form, same-box A/B).
 #include "conv3_wz32.hpp"
 
 namespace ru {
 
-bool conv3_wz32_enabled() {
-#ifdef RU_SB2_DBG
-    const char* e = getenv("RU_WZ32");                  // devtools builds: RU_WZ32=0 selects the 16x16x32 matrix form (read per call)
-    return !(e && *e == '0');
-#else
-    return true;                                        // the product library has this matrix form only
-#endif
-}
+bool conv3_wz16_form_built() { return WZ16_FORM; }
 
 int conv3_wz32_launch(const Conv3Args& a, const void* wz32frag, hipStream_t s) {
     RU_REQUIRE(a.in_c16 && a.out_c16 && !a.bias && !a.sigmoid && !a.in_c4 && a.products != 1 && !a.bst_y && !a.add && conv3_wz_shape_ok(a.N, a.Cin, a.Cout, a.D, a.H, a.W),

@@ -199,7 +199,6 @@ static inline long wz_grid_x(int N, int Cout, int D, int H, int W) {
 
 int conv3_wz_launch(const Conv3Args& a, const void* wzfrag, int r, hipStream_t s);
 int conv3_wz32_launch(const Conv3Args& a, const void* wz32frag, hipStream_t s);      // conv3_wz32.hip: forward form only (no residual, no GroupNorm-backward sums)
-bool conv3_wz32_enabled();                               // devtools builds: RU_WZ32=0 selects the 16x16x32 matrix form (same-box A/B); always true in the product library
-int conv3_wz32mx_launch(const Conv3Args& a, const void* wz32mxfrag, hipStream_t s);  // conv3_wz32mx.hip: the forward form with fp16 + MX-fp8 products (Conv3Args::products == 2, RU_MX)
+int conv3_wz32mx_launch(const Conv3Args& a, const void* wz32mxfrag, hipStream_t s);  // conv3_wz32mx.hip: the forward form with fp16 + MX-fp8 products (Conv3Args::products == 2, Switches::mx_wz)
 
 }  // namespace ru

@@ -67,12 +67,33 @@ struct Arena {
     size_t need() const { return peak + keep; }
 };
 
-// RU_TRACE=1 in the environment: every launch of the executor is named on stderr and followed by a stream synchronisation, so a
-// faulting kernel is the last line printed (debugging aid; one getenv per process, nothing on the normal path)
-static bool trace_on() {
-    static const bool on = [] { const char* e = getenv("RU_TRACE"); return e && *e && *e != '0'; }();
-    return on;
+// ---------------------------------------------------------------------- the environment (switches.hpp: the table of every variable)
+static bool env_is(const char* name, char c) { const char* e = getenv(name); return e && *e == c; }
+Switches switches_from_env() {
+    Switches sw;
+    sw.wz = !env_is("RU_WZ", '0');
+    sw.wz32 = !(conv3_wz16_form_built() && env_is("RU_WZ32", '0'));
+    sw.mx = !env_is("RU_MX", '0');
+    sw.mx_wz = sw.mx && !env_is("RU_MX", '1');
+    sw.mxg = !env_is("RU_MXG", '0');
+    sw.head_form = !env_is("RU_HEAD_FORM", '0');
+    sw.head_res = !env_is("RU_HEAD_RES", '0');
+    return sw;
 }
+bool env_trace() { static const bool on = [] { const char* e = getenv("RU_TRACE"); return e && *e && *e != '0'; }(); return on; }
+bool env_f32c_off() { static const bool off = env_is("RU_F32C", '0'); return off; }
+bool env_sb1_no22() { static const bool on = env_is("RU_SB1_NO22", '1'); return on; }
+int env_c1_scatter_cob() { static const int forced = [] { const char* e = getenv("RU_C1_SCATTER_COB"); return e ? atoi(e) : 0; }(); return forced; }
+bool env_c1_pair_off() { static const bool off = env_is("RU_C1_PAIR", '0'); return off; }
+unsigned env_fusion(unsigned fusion) {
+    if (env_is("RU_SIDE_STREAM", '0')) fusion &= ~(unsigned)RU_FUSE_SIDE_STREAM;                     // same-box A/B of the side stream
+    if (const char* e = getenv("RU_FUSION_OFF")) fusion &= ~(unsigned)strtoul(e, nullptr, 0);       // same-box A/B of any fusion bit (RU_FUSE_*)
+    if (const char* e = getenv("RU_FUSION_ON")) fusion |= (unsigned)strtoul(e, nullptr, 0) & 63u;
+    return fusion;
+}
+
+// RU_TRACE: every launch of the executor is named on stderr and followed by a stream synchronisation, so a faulting kernel is the last line printed
+// (debugging aid; nothing on the normal path)
 static int trace_sync(const char* what, hipStream_t s) {
     fprintf(stderr, "[ru] %s\n", what);
     const hipError_t e = hipStreamSynchronize(s);
@@ -139,7 +160,7 @@ static void sink_end(hipStream_t s) {
             const int rc__ = (call);      \
             if (t_sink) sink_end(s);      \
             if (rc__ != RU_OK) return rc__; \
-            if (trace_on()) { const int rt__ = trace_sync(#call, s); if (rt__ != RU_OK) return rt__; } \
+            if (env_trace()) { const int rt__ = trace_sync(#call, s); if (rt__ != RU_OK) return rt__; } \
         }                                 \
     } while (0)
 
@@ -234,7 +255,8 @@ struct ru_unet {
     const void* packed_base = nullptr;
     int packed_prec = -1;
     bool packed_c16 = false;
-    int pack_sig = -1;                   // conv3_sb_switch_signature() when the packs of the last forward were written
+    ru::Switches sw;                     // the switches of the public call that is executing (taken on its entry)
+    ru::Switches pack_sw;                // ... and those under which the packs of the last forward were written
     float *y0 = nullptr, *t0 = nullptr, *probs = nullptr;
     GNSave g0;
     const float* head_in = nullptr;
@@ -337,9 +359,7 @@ extern "C" ru_unet_t ru_unet_create(int depth, const int* encoder_layers, const 
         }
     }
     ru_unet* h = new ru_unet();
-    if (const char* e = getenv("RU_SIDE_STREAM")) { if (*e == '0') h->fusion &= ~(unsigned)RU_FUSE_SIDE_STREAM; }    // same-box A/B of the side stream
-    if (const char* e = getenv("RU_FUSION_OFF")) h->fusion &= ~(unsigned)strtoul(e, nullptr, 0);                   // same-box A/B of any fusion bit (RU_FUSE_*)
-    if (const char* e = getenv("RU_FUSION_ON")) h->fusion |= (unsigned)strtoul(e, nullptr, 0) & 63u;
+    h->fusion = env_fusion(h->fusion);
     h->depth = depth;
     h->nout = number_of_outputs;
     h->enc.assign(encoder_layers, encoder_layers + depth);
@@ -480,8 +500,8 @@ static int pack_all(ru_unet* h, const float* params, Arena& A, hipStream_t s) {
     // of its shape, the direct fragments are not written
     auto pack3 = [&](int pidx, size_t pk_off, size_t fk_off, int cin_f, int cout_f, int mode, int lvl = -1) -> int {
         const bool skipd = h->training && h->c16 && mode == 0 && lvl >= 0 &&
-                           conv3_sb_forward_skips_direct(h->N, cin_f, cout_f, h->D >> lvl, h->H >> lvl, h->W >> lvl);
-        if (h->precision == RU_PREC_BF16X3) RU_RUN(conv3_sb_pack_add(batch, P(h, params, pidx), h->fpack + fk_off, cin_f, cout_f, mode, !h->training, s, skipd));
+                           conv3_sb_forward_skips_direct(h->sw, h->N, cin_f, cout_f, h->D >> lvl, h->H >> lvl, h->W >> lvl);
+        if (h->precision == RU_PREC_BF16X3) RU_RUN(conv3_sb_pack_add(batch, h->sw, P(h, params, pidx), h->fpack + fk_off, cin_f, cout_f, mode, !h->training, s, skipd));
         // exact-f32 voxel-major inference: per-lane f32 fragments in the same slot (never larger than the split-bf16 ones)
         if (h->precision == RU_PREC_F32 && h->c16) RU_RUN(conv3_f32c_pack_weights(P(h, params, pidx), h->fpack + fk_off, cin_f, cout_f, mode, s));
         // outside the voxel-major flow the f32 layout is always kept: ragged W falls back to the f32 kernel
@@ -516,27 +536,35 @@ static int pack_all(ru_unet* h, const float* params, Arena& A, hipStream_t s) {
     return RU_OK;
 }
 
+// partials per (sample, channel) the split-bf16 launch of `a` writes: the count follows the route of the very arguments, taken as those of a launch WITH
+// statistics (the buffer is sized before it exists, and the dry walk has null pointers)
+static int sb_nblk(const ru_unet* h, Conv3Args a) {
+    static float with_statistics;
+    a.stat_partials = &with_statistics;
+    return conv3_sb_route_nblk(conv3_sb_route(a, h->sw), a.N, a.Cout, a.D, a.H, a.W);
+}
+
 // y = conv3(x) with optional fused input transform, tile statistics -> GNSave (mean/rstd/scale/shift)
 static int conv3_gn(ru_unet* h, Arena& A, hipStream_t s, const float* x, const float* wp, const char* wf, float* y, const GNSave* in_gn,
                     const float* gamma, const float* beta, GNSave& out_gn, int N, int Cin, int Cout, int D, int H, int W, bool x_c16 = true,
                     bool x_c4 = false) {
-    const int nblk = !h->c16 ? conv3_tiles_per_sample(N, Cin, Cout, D, H, W, h->precision)
-                     : (h->precision == RU_PREC_F32 ? conv3_f32c_tiles_per_sample(N, Cin, Cout, D, H, W) : conv3_sb_tiles_per_sample(N, Cin, Cout, D, H, W));
+    Conv3Args a{};
+    a.x = x; a.wp = wp; a.y = y; a.mode = h->precision; a.wfrag = wf;
+    a.in_scale = in_gn ? in_gn->scale : nullptr;
+    a.in_shift = in_gn ? in_gn->shift : nullptr;
+    a.in_slope = in_gn ? in_gn->act_slope : kSlope;
+    a.N = N; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W;
+    a.in_c16 = h->c16 && x_c16; a.out_c16 = h->c16; a.in_c4 = x_c4;
+    a.products = 2;          // a FORWARD convolution: its input is an activation tensor, so the shapes that have the kernel take the fp16 + MX-fp8 scheme (conv3_mx.hpp; Switches::mx)
+    const bool sb = h->c16 ? h->precision == RU_PREC_BF16X3 : conv3_effective_mode(h->precision, W) == RU_PREC_BF16X3;       // conv3_launch hands the launch to conv3_sb_launch
+    const int nblk = sb ? sb_nblk(h, a) : (h->c16 ? conv3_f32c_tiles_per_sample(N, Cin, Cout, D, H, W) : conv3_f32_tiles_per_sample(N, Cin, Cout, D, H, W));
     t_hint_c = Cout;
     float* partials = A.alloc((size_t)N * Cout * nblk * 2);
     out_gn.mean = A.alloc_keep((size_t)N * kGroups);
     out_gn.rstd = A.alloc_keep((size_t)N * kGroups);
     out_gn.scale = A.alloc_keep((size_t)N * Cout);
     out_gn.shift = A.alloc_keep((size_t)N * Cout);
-    Conv3Args a{};
-    a.x = x; a.wp = wp; a.y = y; a.mode = h->precision; a.wfrag = wf;
-    a.in_scale = in_gn ? in_gn->scale : nullptr;
-    a.in_shift = in_gn ? in_gn->shift : nullptr;
-    a.in_slope = in_gn ? in_gn->act_slope : kSlope;
     a.stat_partials = partials;
-    a.N = N; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W;
-    a.in_c16 = h->c16 && x_c16; a.out_c16 = h->c16; a.in_c4 = x_c4;
-    a.products = 2;          // a FORWARD convolution: its input is an activation tensor, so the shapes that have the kernel take the fp16 + MX-fp8 scheme (conv3_mx.hpp; RU_MX=0: never)
     const bool probed = h->probe_on && !A.dry && h->c16 && x_c16 && !x_c4 && Cin == 16 && Cout == 16 && D == h->D && H == h->H && W == h->W;
     if (probed) {
         while (h->probe_ev.size() < h->probe_used + 2) {
@@ -562,12 +590,12 @@ static int conv3_gn(ru_unet* h, Arena& A, hipStream_t s, const float* x, const f
         const size_t nel = (size_t)N * Cout * D * H * W;
         float* part = A.alloc((size_t)ksplit * nel);
         a.y = part; a.stat_partials = nullptr; a.ksplit = ksplit;
-        RU_RUN(conv3_launch(a, s));
+        RU_RUN(conv3_launch(a, h->sw, s));
         RU_RUN(sum_partials_launch(part, ksplit, nel, y, s));
         RU_RUN(gn_stats_launch(y, partials, N, Cout, (size_t)D * H * W, s));
     } else {
         t_hint_inst = (a.in_c16 && a.out_c16) ? (Cin == 16 && Cout == 16 ? INST_CONV16_FWD : (Cin >= 32 ? INST_CONV_DEEP_FWD : -1)) : -1;
-        RU_RUN(conv3_launch(a, s));
+        RU_RUN(conv3_launch(a, h->sw, s));
     }
     if (probed) {
         (void)hipEventRecord(h->probe_ev[h->probe_used + 1], s);
@@ -652,7 +680,7 @@ static int unet_forward_impl(ru_unet* h, const float* params, const float* x, fl
     // voxel-major flow: the split-bf16 engine, and (round 5) the exact-f32 INFERENCE forward -- conv3_f32c_kernel on voxel-major tensors with the same
     // fused statistics / staging-side GroupNorm + LeakyReLU / coarse-grid 1x1 / no concat as the split-bf16 flow (BASELINE configs[1]; the exact-f32
     // training path keeps the NCDHW kernels: its weight gradients exist there only).  RU_F32C=0: the NCDHW flow for the f32 forward too (A/B).
-    static const bool f32c_off = [] { const char* e = getenv("RU_F32C"); return e && *e == '0'; }();
+    const bool f32c_off = env_f32c_off();
     // (conv3_f32c_kernel addresses a 16-channel block of its input through 32-bit byte offsets and has no other kernel to fall back to: whole-volume
     // exact-f32 inference at 2^25 voxels and more, ~322^3, keeps the NCDHW flow; the split-bf16 kernels choose the one-stage kernel there themselves)
     const bool f32c_fits = (size_t)h->D * h->H * h->W * 64 < ((size_t)1 << 31);
@@ -768,8 +796,8 @@ static int unet_forward_impl(ru_unet* h, const float* params, const float* x, fl
             // the block in front of the head conv leaves its residual pass to that conv's staging (inference: one read of y2 and x instead of read y2 +
             // read x + write out + read out, 0.54 GB less per 128^3 volume; training: the staging also writes out, 0.27 GB less)
             const bool defer = i == 0 && j + 1 == h->dec_blocks[i].size() && h->c16 &&
-                               (h->precision == RU_PREC_BF16X3 ? conv3_sb_head_takes_residual(N, C0, h->nout, Dl[0], Hl[0], Wl[0])
-                                                               : (!h->training && conv3_f32c_head_takes_residual(C0, h->nout, Wl[0])));       // (exact f32: the voxel-major flow is inference only)
+                               (h->precision == RU_PREC_BF16X3 ? conv3_sb_head_takes_residual(h->sw, N, C0, h->nout, Dl[0], Hl[0], Wl[0])
+                                                               : (!h->training && conv3_f32c_head_takes_residual(h->sw, C0, h->nout, Wl[0])));       // (exact f32: the voxel-major flow is inference only)
             rc = block_fwd(h, params, A, s, h->dec_blocks[i][j], cur, N, Dl[i], Hl[i], Wl[i], h->dec_s[i][j], &cur, nullptr, defer);
             if (rc) return rc;
             if (defer) head_block = &h->dec_s[i][j];
@@ -789,8 +817,8 @@ static int unet_forward_impl(ru_unet* h, const float* params, const float* x, fl
         a.x = head_block->y2; a.in_scale = head_block->g2.scale; a.in_shift = head_block->g2.shift; a.in_slope = kSlope; a.in_res = head_block->x;
         a.in_sum_out = head_block->out;                  // (training: the block output, written on the way; null in inference)
     }
-    RU_RUN(conv3_launch(a, s));
-    if (!A.dry) { h->packed_params = h->training ? nullptr : params; h->packed_base = h->pack; h->packed_prec = h->precision; h->packed_c16 = h->c16; h->pack_sig = conv3_sb_switch_signature(); }   // a training forward is followed by an optimizer step
+    RU_RUN(conv3_launch(a, h->sw, s));
+    if (!A.dry) { h->packed_params = h->training ? nullptr : params; h->packed_base = h->pack; h->packed_prec = h->precision; h->packed_c16 = h->c16; h->pack_sw = h->sw; }   // a training forward is followed by an optimizer step
     return RU_OK;
 }
 
@@ -968,19 +996,18 @@ static int block_bwd(ru_unet* h, const float* params, float* grads, Arena& A, hi
     // form of the gradients dy2 / dy1 that enter the two data-gradient convs (and the two weight gradients): split hi / lo packets -- the direct conv kernel
     // copies them global -> LDS (the Winograd-z routes for them, RU_WZ=2 / 3 of round 5, were measured slower twice and are retired: profiles/r05_notes.txt)
     const bool ds16 = c16;
-    const int dgrad_products = c16 ? 1 : h->grad_products();      // (for the kernel choice / partial count only: a split-form input never takes the Winograd-z kernel)
     float *coef2 = nullptr, *coef1 = nullptr;
     int rc = gn_bwd(h, A, s, sv.y2, dout, sv.g2, P(h, params, bp.n2w), kSlope, dy2, G(h, grads, bp.n2w), G(h, grads, bp.n2b), N, C, V, sums2,
                     fa ? &coef2 : nullptr, ds16);
     if (rc) return rc;
     // the published gradients of the 16-channel level have ONE reader each, the data-gradient conv that follows: where conv3_mx_kernel<GRAD> takes the shape they are
     // written in the gradient-operand form of the MX scheme (bf16 main + e4m3 cross terms, a per-voxel exponent; RU_MXG=0 or one-product gradients: the split form)
-    const bool g16 = fa && h->grad_products() == 3 && conv3_mxg_usable(N, C, C, D, H, W);
+    const bool g16 = fa && h->grad_products() == 3 && conv3_mxg_usable(h->sw, N, C, C, D, H, W);
     const GbApply gb2{sv.y2, dout, &sv.g2, coef2, g16};
     // weight gradients whose dy has no other producer role (no fused apply: dy2 / dy1 are complete when gn_bwd returns) leave the chain:
     // on the side stream they run beside the data-gradient convs and the GroupNorm passes of the chain (a 188-register weight-gradient
     // workgroup leaves a third wave's registers free on its CU: the memory-bound passes fit beside it)
-    const bool aside = !A.dry && (h->fusion & RU_FUSE_SIDE_STREAM) && c16 && h->precision == RU_PREC_BF16X3 && !fa && !trace_on();
+    const bool aside = !A.dry && (h->fusion & RU_FUSE_SIDE_STREAM) && c16 && h->precision == RU_PREC_BF16X3 && !fa && !env_trace();
     hipStream_t sw = s;
     if (aside) { rc = side_fork(h, s); if (rc) return rc; sw = h->side; }
     rc = wgrad3_run(A, sw, h->wgrad_mode(), sv.y1, &sv.g1, dy2, G(h, grads, bp.conv2), N, C, C, D, H, W, c16, c16, nullptr, ds16, fa ? &gb2 : nullptr);
@@ -993,17 +1020,18 @@ static int block_bwd(ru_unet* h, const float* params, float* grads, Arena& A, hi
     const bool fuse1 = c16 && h->precision == RU_PREC_BF16X3 && conv3_sb_bst_usable(N, C, D, H, W) && (h->fusion & RU_FUSE_GN_BWD_STATS);
     FusedSums sums1;
     if (fuse1) {
-        sums1.nblk = conv3_sb_tiles_per_sample(N, C, C, D, H, W, dgrad_products);
+        d2.bst_y = sv.y1; d2.bst_k = sv.g1.k; d2.bst_slope = kSlope;                                 // constants written by the forward finalize
+        sums1.nblk = sb_nblk(h, d2);
         sums1.part = A.alloc((size_t)N * C * sums1.nblk * 2);
         sums1.coef = A.alloc((size_t)N * C * 3);
-        d2.bst_y = sv.y1; d2.bst_k = sv.g1.k; d2.bst_slope = kSlope; d2.stat_partials = sums1.part;  // constants written by the forward finalize
+        d2.stat_partials = sums1.part;
         if (!A.dry && h->tails()) {                      // ... and the conv's last workgroup finalizes them (coefficients, dgamma, dbeta of norm1)
             fill_bwd_tail(h, d2.fin, sums1, sv.g1, P(h, params, bp.n1w), G(h, grads, bp.n1w), G(h, grads, bp.n1b), N, C, V, 1);
             sums1.done = true;
         }
     }
     t_hint_inst = c16 ? (C == 16 ? INST_CONV16_DGRAD : INST_CONV_DEEP_DGRAD) : -1;
-    RU_RUN(conv3_launch(d2, s));
+    RU_RUN(conv3_launch(d2, h->sw, s));
     float* dy1 = A.alloc((size_t)N * C * V);
     rc = gn_bwd(h, A, s, sv.y1, da1, sv.g1, P(h, params, bp.n1w), kSlope, dy1, G(h, grads, bp.n1w), G(h, grads, bp.n1b), N, C, V, fuse1 ? &sums1 : nullptr,
                 fa ? &coef1 : nullptr, ds16);
@@ -1019,17 +1047,18 @@ static int block_bwd(ru_unet* h, const float* params, float* grads, Arena& A, hi
     d1.N = N; d1.Cin = C; d1.Cout = C; d1.D = D; d1.H = H; d1.W = W;
     if (nx) nx->out = FusedSums();
     if (nx && fuse1 && bp.down < 0) {                   // same shape and kernel choice as d2: dx = dout + dgrad(conv1) IS the gradient entering nx
-        nx->out.nblk = conv3_sb_tiles_per_sample(N, C, C, D, H, W, dgrad_products);
+        d1.bst_y = nx->y; d1.bst_k = nx->k; d1.bst_slope = nx->slope;
+        nx->out.nblk = sb_nblk(h, d1);
         nx->out.part = A.alloc((size_t)N * C * nx->out.nblk * 2);
         nx->out.coef = A.alloc((size_t)N * C * 3);
-        d1.bst_y = nx->y; d1.bst_k = nx->k; d1.bst_slope = nx->slope; d1.stat_partials = nx->out.part;
+        d1.stat_partials = nx->out.part;
         if (!A.dry && h->tails() && nx->g) {
             fill_bwd_tail(h, d1.fin, nx->out, *nx->g, nx->gamma, nx->dgamma, nx->dbeta, N, C, V, 1);
             nx->out.done = true;
         }
     }
     t_hint_inst = c16 ? (C == 16 ? INST_CONV16_DGRAD : INST_CONV_DEEP_DGRAD) : -1;
-    RU_RUN(conv3_launch(d1, s));
+    RU_RUN(conv3_launch(d1, h->sw, s));
     if (bp.down < 0) { *dxprev_out = dx; return RU_OK; }
     // down-sampling conv backward (Appendix A2): 1x1 over the space-to-depth view
     const int Cp = bp.cin_down;
@@ -1121,17 +1150,18 @@ static int unet_backward_impl(ru_unet* h, const float* params, const float* dpro
     const BlockSave* hb = (depth >= 2 && !h->dec_s[0].empty()) ? &h->dec_s[0].back() : nullptr;
     FusedSums hsums;
     if (head4 && hb && !no_bst && conv3_sb_bst_usable(N, C0, Dl[0], Hl[0], Wl[0])) {
-        hsums.nblk = conv3_sb_tiles_per_sample(N, h->nout, C0, Dl[0], Hl[0], Wl[0]);
+        dh.bst_y = hb->y2; dh.bst_k = hb->g2.k; dh.bst_slope = kSlope;
+        hsums.nblk = sb_nblk(h, dh);
         hsums.part = A.alloc((size_t)N * C0 * hsums.nblk * 2);
         hsums.coef = A.alloc((size_t)N * C0 * 3);
-        dh.bst_y = hb->y2; dh.bst_k = hb->g2.k; dh.bst_slope = kSlope; dh.stat_partials = hsums.part;
+        dh.stat_partials = hsums.part;
         if (!A.dry && h->tails()) {
             const BlockP& lb = *hb->bp;
             fill_bwd_tail(h, dh.fin, hsums, hb->g2, P(h, params, lb.n2w), G(h, grads, lb.n2w), G(h, grads, lb.n2b), N, C0, Vl(0), 1);
             hsums.done = true;
         }
     }
-    RU_RUN(conv3_launch(dh, s));
+    RU_RUN(conv3_launch(dh, h->sw, s));
     const float* dcur = dcur_buf;
     std::vector<const float*> dskip(depth - 1, nullptr);
     FusedSums carry = hsums;                                     // sums of the norm2 the current gradient enters, taken by the kernel that produced it
@@ -1307,7 +1337,7 @@ static int unet_backward_impl(ru_unet* h, const float* params, const float* dpro
             RU_RUN(conv3_pack_weights(P(h, params, h->conv_in), wpd, kInCh, C0, 1, s));
         }
         di.x = dy0; di.wp = wpd; di.y = dx_in; di.N = N; di.Cin = C0; di.Cout = kInCh; di.D = Dl[0]; di.H = Hl[0]; di.W = Wl[0];
-        RU_RUN(conv3_launch(di, s));
+        RU_RUN(conv3_launch(di, h->sw, s));
     }
     if (t_red && !t_red->side.e.empty()) RU_RUN(wgrad_reduce_flush(t_red->side, h->side));   // (stream order on the side stream: behind its weight-gradient kernels)
     if (!A.dry) { rc = side_join(h, s); if (rc) return rc; }     // the caller's stream sees every gradient
@@ -1332,6 +1362,7 @@ extern "C" size_t ru_unet_workspace_bytes(ru_unet_t h, int N, int D, int H, int 
     tmp.tickets = nullptr;
     tmp.fork_ev.clear();
     tmp.N = N; tmp.D = D; tmp.H = H; tmp.W = W; tmp.training = training != 0;
+    tmp.sw = switches_from_env();
     Arena A;
     A.dry = true;
     if (unet_forward_impl(&tmp, nullptr, nullptr, nullptr, A, nullptr) != RU_OK) return 0;
@@ -1347,6 +1378,7 @@ extern "C" int ru_unet_forward(ru_unet_t h, const float* params, const float* x,
     int rc = check_dims(h, N, D, H, W);
     if (rc) return rc;
     h->have_fwd = false;
+    h->sw = switches_from_env();
     h->N = N; h->D = D; h->H = H; h->W = W; h->training = training != 0;
     h->ws = (char*)ws; h->ws_bytes = ws_bytes;
     Arena A;
@@ -1380,11 +1412,12 @@ static int backward_entry(ru_unet_t h, const float* params, const float* dprobs,
     ru::t_sink = h->probe_families ? h->sink : nullptr;
     h->red.main.e.clear();
     h->red.side.e.clear();
-    ru::t_red = (h->fusion & RU_FUSE_BATCH_WREDUCE) && !trace_on() ? &h->red : nullptr;
+    ru::t_red = (h->fusion & RU_FUSE_BATCH_WREDUCE) && !env_trace() ? &h->red : nullptr;
     // a training forward packs only the fragment forms its switches launch (sb_pack_forms): a switch flipped between that forward and this backward would make
-    // a launch read fragments that were never packed -- refused instead (round-5 advisor finding; tools and tests toggle between steps, which is fine)
-    RU_REQUIRE(h->precision != RU_PREC_BF16X3 || h->pack_sig == conv3_sb_switch_signature(),
-               "ru_unet_backward: RU_WZ / RU_MX / RU_MXG changed since the forward whose packs this backward reads (signature %d then, %d now)", h->pack_sig, conv3_sb_switch_signature());
+    // a launch read fragments that were never packed -- refused instead
+    h->sw = switches_from_env();
+    RU_REQUIRE(h->precision != RU_PREC_BF16X3 || h->pack_sw.pack_bits() == h->sw.pack_bits(),
+               "ru_unet_backward: RU_WZ / RU_MX / RU_MXG changed since the forward whose packs this backward reads (signature %d then, %d now)", h->pack_sw.pack_bits(), h->sw.pack_bits());
     int rc = unet_backward_impl(h, params, dprobs, grads, dx, A, (hipStream_t)stream, crit);
     ru::t_red = nullptr;
     ru::t_sink = nullptr;
@@ -1487,7 +1520,7 @@ extern "C" int ru_conv3d_fwd_p(const float* x, const float* w, const float* bias
         int rc = prep_conv3_weights(a, w, Cin, Cout, 0, precision, W, C, s);
         if (rc) return rc;
         a.x = x; a.bias = bias; a.y = y; a.N = N; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W;
-        return conv3_launch(a, s);
+        return conv3_launch(a, switches_from_env(), s);
     }
     RU_REQUIRE(!bias, "ru_conv3d_fwd: bias only supported for k=3 (model.py:348)");
     if (k == 1) {
@@ -1533,7 +1566,7 @@ extern "C" int ru_conv3d_bwd_data_p(const float* dy, const float* w, float* dx, 
         int rc = prep_conv3_weights(a, w, Cin, Cout, 1, precision, W, C, s);
         if (rc) return rc;
         a.x = dy; a.y = dx; a.N = N; a.Cin = Cout; a.Cout = Cin; a.D = D; a.H = H; a.W = W;
-        return conv3_launch(a, s);
+        return conv3_launch(a, switches_from_env(), s);
     }
     if (k == 1) {
         Conv1Args a{};
@@ -1730,6 +1763,7 @@ extern "C" int ru_upsample2x_trilinear_bwd_l(const float* dy, float* dx, int N, 
 extern "C" int ru_conv3d_fwd_l(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Cout, int D, int H, int W,
                                int flags, void* ws, size_t ws_bytes, ru_stream_t stream) {
     RU_REQUIRE(x && w && y, "ru_conv3d_fwd_l: null argument");
+    const Switches sw = switches_from_env();
     hipStream_t s = (hipStream_t)stream;
     WsCarver C(ws, ws_bytes);
     Conv3Args a{};
@@ -1740,7 +1774,7 @@ extern "C" int ru_conv3d_fwd_l(const float* x, const float* w, const float* bias
     RU_REQUIRE(!f32 || ((flags & 3) != 0 && !(flags & (4 | 8))), "ru_conv3d_fwd_l: the exact-f32 form needs a voxel-major side and takes neither the 4-channel copy nor a split-form input");
     // flag bit 6: x (float32, voxel-major) is a GRADIENT -- where conv3_mx_kernel<GRAD> takes the shape it is converted to the gradient-operand form of the MX scheme
     // (conv3_mxg_split_launch; in a training step wgrad3_tz<1,0,3,3> writes that form) and convolved with bf16 main + MX cross products; elsewhere the bit is ignored
-    const bool gop = (flags & 64) && !f32 && (flags & 3) == 3 && !(flags & (4 | 8)) && !bias && conv3_mxg_usable(N, Cin, Cout, D, H, W);
+    const bool gop = (flags & 64) && !f32 && (flags & 3) == 3 && !(flags & (4 | 8)) && !bias && conv3_mxg_usable(sw, N, Cin, Cout, D, H, W);
     int rc = f32 ? conv3_f32c_pack_weights(w, wf, Cin, Cout, 0, s) : conv3_sb_pack_weights(w, wf, Cin, Cout, 0, s, gop);
     if (rc) return rc;
     a.mode = f32 ? RU_PREC_F32 : RU_PREC_BF16X3; a.wfrag = wf;
@@ -1768,7 +1802,7 @@ extern "C" int ru_conv3d_fwd_l(const float* x, const float* w, const float* bias
         if (rc) return rc;
         a.x = x4; a.wfrag = wf4; a.in_c4 = 1;
     }
-    return f32 ? conv3_launch(a, s) : conv3_sb_launch(a, s);
+    return f32 ? conv3_launch(a, sw, s) : conv3_sb_launch(a, sw, s);
 }
 
 extern "C" int ru_conv3d_bwd_weight_l(const float* x, const float* dy, float* dw, int N, int Cin, int Cout, int D, int H, int W,
@@ -1838,6 +1872,7 @@ extern "C" int ru_conv3_l(const float* x, const float* w, const float* bias, flo
     RU_REQUIRE(x && w && y, "ru_conv3_l: null argument");
     RU_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, "ru_conv3_l: bad shape");
     RU_REQUIRE(weight_mode == 0 || weight_mode == 1, "ru_conv3_l: weight_mode is 0 (forward packing) or 1 (data-gradient packing)");
+    const Switches sw = switches_from_env();
     hipStream_t s = (hipStream_t)stream;
     WsCarver C(ws, ws_bytes);
     Conv3Args a{};
@@ -1846,7 +1881,7 @@ extern "C" int ru_conv3_l(const float* x, const float* w, const float* bias, flo
     const bool f32 = (flags & 16) != 0;
     a.products = (flags & 32) ? 2 : products;
     RU_REQUIRE(!f32 || ((flags & 3) != 0 && !(flags & (4 | 8))), "ru_conv3_l: the exact-f32 form needs a voxel-major side and takes neither the 4-channel copy nor a split-form input");
-    const bool gop = (flags & 64) && !f32 && (flags & 3) == 3 && !(flags & (4 | 8)) && !bias && conv3_mxg_usable(N, Cin, Cout, D, H, W);
+    const bool gop = (flags & 64) && !f32 && (flags & 3) == 3 && !(flags & (4 | 8)) && !bias && conv3_mxg_usable(sw, N, Cin, Cout, D, H, W);
     const int Cin_f = weight_mode ? Cout : Cin, Cout_f = weight_mode ? Cin : Cout;       // w's own extents [Cout_f][Cin_f][27]
     int rc = f32 ? conv3_f32c_pack_weights(w, wf, Cin_f, Cout_f, weight_mode, s) : conv3_sb_pack_weights(w, wf, Cin_f, Cout_f, weight_mode, s, gop);
     if (rc) return rc;
@@ -1876,12 +1911,12 @@ extern "C" int ru_conv3_l(const float* x, const float* w, const float* bias, flo
         if (rc) return rc;
         a.x = x4; a.wfrag = wf4; a.in_c4 = 1;
     }
-    const int r = f32 ? conv3_f32c_route(a) : conv3_sb_route(a);
+    const int r = f32 ? conv3_f32c_route(a) : conv3_sb_route(a, sw);
     if (route) *route = r;
     const int nb = f32 ? conv3_f32c_tiles_per_sample(N, Cin, Cout, D, H, W) : conv3_sb_route_nblk(r, N, Cout, D, H, W);     // partials per (sample, channel)
     if (nblk) *nblk = nb;
     RU_REQUIRE(!stat_partials || stat_floats >= (size_t)N * Cout * nb * 2, "ru_conv3_l: statistics buffer too small");
-    return f32 ? conv3_launch(a, s) : conv3_sb_launch(a, s);
+    return f32 ? conv3_launch(a, sw, s) : conv3_sb_launch(a, sw, s);
 }
 
 extern "C" size_t ru_wgrad1_l_workspace_bytes(int N, int Cin, int Cout, size_t V) { return 4096 + align_up(wgrad1_workspace_bytes(N, Cin, Cout, V), 256); }

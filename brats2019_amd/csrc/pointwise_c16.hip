@@ -731,12 +731,11 @@ Conv1Inst conv1_16_choose(const Conv1Args& a) {
     const int CBo = a.Cout / 16;
     Conv1Inst c{CBo >= 4 ? 4 : (CBo >= 2 ? 2 : 1), a.s2d, 0, 0};
     if (a.s2d == 2) {
-        static const int forced = [] { const char* e = getenv("RU_C1_SCATTER_COB"); return e ? atoi(e) : 0; }();
+        const int forced = env_c1_scatter_cob();
         if ((forced == 2 || forced == 4 || forced == 1) && forced <= CBo) c.cob = forced;
     }
     if (a.bst_y) c.nslot = a.s2d == 2 ? (CBo >> 3) : c.cob;
-    static const bool pair_off = [] { const char* e = getenv("RU_C1_PAIR"); return e && *e == '0'; }();
-    c.pair = a.s2d == 2 && a.bst_y && !pair_off && a.Wc % 8 == 0 && c.cob == 4 && !a.mask && (c.nslot == 1 || c.nslot == 2);
+    c.pair = a.s2d == 2 && a.bst_y && !env_c1_pair_off() && a.Wc % 8 == 0 && c.cob == 4 && !a.mask && (c.nslot == 1 || c.nslot == 2);
     return c;
 }
 int conv1_16_bst_nblk(const Conv1Args& a) {

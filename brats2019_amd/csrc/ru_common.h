@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/resunet_hip.h"
+#include "switches.hpp"
 
 namespace ru {
 
@@ -209,18 +210,18 @@ int conv3_cin_pad(int Cin);                       // CinP for a given Cin
 static inline int conv3_cout_pad(int Cout) { return round_up(Cout, 16); }
 // effective mode for a shape (the split-bf16 kernel needs W % 4 == 0; otherwise the f32 kernel runs)
 static inline int conv3_effective_mode(int mode, int W) { return (mode == RU_PREC_BF16X3 && (W & 3) == 0) ? RU_PREC_BF16X3 : RU_PREC_F32; }
-// number of spatial tiles per sample the kernel will use (== nblk of stat_partials)
-int conv3_tiles_per_sample(int N, int Cin, int Cout, int D, int H, int W, int mode);
-int conv3_launch(const Conv3Args& a, hipStream_t s);
+// number of spatial tiles per sample the exact-f32 NCDHW kernel will use (== nblk of stat_partials; the split-bf16 kernels: conv3_sb_route_nblk)
+int conv3_f32_tiles_per_sample(int N, int Cin, int Cout, int D, int H, int W);
+int conv3_launch(const Conv3Args& a, const Switches& sw, hipStream_t s);
 // exact-f32 convolution on voxel-major tensors (conv3_f32c.hip): forward only; `wfr` = fragments from conv3_f32c_pack_weights (Conv3Args::wfrag when
 // mode == RU_PREC_F32 and a voxel-major side is set -- conv3_launch routes there)
 size_t conv3_f32c_frag_bytes(int Cin_conv, int Cout_conv);
 int conv3_f32c_pack_weights(const float* w, void* wfr, int Cin_f, int Cout_f, int mode, hipStream_t s);
 int conv3_f32c_tiles_per_sample(int N, int Cin, int Cout, int D, int H, int W);
 int conv3_f32c_launch(const Conv3Args& a, const void* wfr, hipStream_t s);
-bool conv3_f32c_head_takes_residual(int Cin, int Cout, int W);
+bool conv3_f32c_head_takes_residual(const Switches& sw, int Cin, int Cout, int W);
 // The kernel a launch of the 3x3x3 family takes, as ONE packed value: conv3_sb_route / conv3_f32c_route are the only places that decide (pure host functions of the
-// arguments and the RU_* switches; no RU_REQUIRE -- those stay with the launchers, which dispatch on the value), and ru_conv3_l reports it.
+// arguments and the Switches value the caller took on entry; no RU_REQUIRE -- those stay with the launchers, which dispatch on the value), and ru_conv3_l reports it.
 //   bits 0-3 family | 4-7 TZ | 8-11 TY | 12 IN16 | 13 OUT16 | 14 MULTI | 15 BST | 16 ADD | 17 HEAD | 18 GRAD | 20-21 NP (MFMA products per operand pair: 1 / 3)
 // IN16 / OUT16: voxel-major input / output; MULTI: more than one 16-channel input chunk; BST: GroupNorm-backward sums instead of (sum, sumsq); ADD: residual operand;
 // HEAD: the <= 4-output-channel head form; GRAD (conv3_mx_kernel only): gradient-operand input.  Flags a family has no template parameter for are 0.
@@ -239,15 +240,13 @@ static inline bool c3r_add(int r) { return (r >> 16) & 1; }
 static inline bool c3r_head(int r) { return (r >> 17) & 1; }
 static inline bool c3r_grad(int r) { return (r >> 18) & 1; }
 static inline int c3r_np(int r) { return (r >> 20) & 3; }
-int conv3_sb_route(const Conv3Args& a);
+int conv3_sb_route(const Conv3Args& a, const Switches& sw);
 int conv3_f32c_route(const Conv3Args& a);         // always carries f32c_choose's tile: the launcher reports one no kernel exists for
 int conv3_sb_route_nblk(int r, int N, int Cout, int D, int H, int W);     // partials per (sample, channel) the kernel of route r = conv3_sb_route(a) writes
 // split-bf16 path (conv3_sb.hip)
-int conv3_sb_tiles_per_sample(int N, int Cin, int Cout, int D, int H, int W, int products = 3);    // products: Conv3Args::products of the launch
-bool conv3_sb_head_form_enabled();                // RU_HEAD_FORM=0 keeps the <= 4-output-channel convolutions on the 16-column kernel (A/B runs, parity tests)
-bool conv3_sb_uses_wz(int N, int Cin, int Cout, int D, int H, int W, int products);
-bool conv3_sb_head_takes_residual(int N, int Cin, int Cout, int D, int H, int W);   // the 16 -> <=4 voxel-major-in / NCDHW-out conv of this shape takes the head-form kernel, which stages Conv3Args::in_res (RU_HEAD_RES=0: never)
-int conv3_sb_launch(const Conv3Args& a, hipStream_t s);
+bool conv3_wz16_form_built();                     // devtools builds only: the 16x16x32 Winograd-z matrix form is instantiated, so Switches::wz32 can be off
+bool conv3_sb_head_takes_residual(const Switches& sw, int N, int Cin, int Cout, int D, int H, int W);   // the 16 -> <=4 voxel-major-in / NCDHW-out conv of this shape takes the head-form kernel, which stages Conv3Args::in_res
+int conv3_sb_launch(const Conv3Args& a, const Switches& sw, hipStream_t s);
 size_t conv3_sb_frag_bytes(int Cin_conv, int Cout_conv);          // direct fragments + the Winograd-z fragments behind them (where the channel counts allow)
 size_t conv3_sb_frag_bytes_direct(int Cin_conv, int Cout_conv);
 size_t conv3_sb4_frag_bytes(int Cout_conv);
@@ -260,16 +259,13 @@ struct SbPackEntry { const float* w; void* wfrag; int Cin_f, Cout_f, mode, nchun
 struct SbPackBatch { SbPackEntry e[RU_PACK_BATCH]; int n; };
 // all_forms false: only the forms a training step launches (sb_pack_forms); skip_direct (training, forward weights): every launch that reads this pack takes the
 // Winograd-z / fp16 + MX-fp8 kernel of its shape, so the direct three-product fragments -- a third of a deep-level weight's bytes -- are not written
-int conv3_sb_pack_add(SbPackBatch& b, const float* w, void* wfrag, int Cin_f, int Cout_f, int mode, bool all_forms, hipStream_t s, bool skip_direct = false);
-int conv3_sb_switch_signature();                   // the kernel-choice switches as the launches read them now (RU_WZ, RU_MX, devtools RU_WZ32): the engine records it with a
-                                                  // training forward's packs and refuses a backward under another signature (packs hold only the forms that signature launches)
+int conv3_sb_pack_add(SbPackBatch& b, const Switches& sw, const float* w, void* wfrag, int Cin_f, int Cout_f, int mode, bool all_forms, hipStream_t s, bool skip_direct = false);
 // the gradient-operand form of the MX product scheme (conv3_mx.hip; conv3_mx_pack.hpp MXG_*)
-bool conv3_mxg_enabled();                                // RU_MXG=0: the data-gradient convolutions of the 16-channel level keep three bf16 products
-bool conv3_mxg_usable(int N, int Cin, int Cout, int D, int H, int W);      // ... and the shape is one conv3_mx_kernel<GRAD> takes: the producer of the gradient asks before it writes the operand form
+bool conv3_mxg_usable(const Switches& sw, int N, int Cin, int Cout, int D, int H, int W);      // Switches::mxg and the shape is one conv3_mx_kernel<GRAD> takes: the producer of the gradient asks before it writes the operand form
 // fp32 voxel-major [N][1][D][H][W][16] -> the gradient operand form: per voxel 64 bytes [bf16 hi ch 0-7 | hi ch 8-15 | e4m3(lo * 2^(8-e)), e4m3(g * 2^-e) ch 0-7 | the same ch 8-15],
 // e from the voxel's largest |hi| (what wgrad3_tz<1,0,3,3> publishes in the step; this launch serves the op-level entry and the tests)
 int conv3_mxg_split_launch(const float* x, void* g16, size_t nvox, hipStream_t s);
-bool conv3_sb_forward_skips_direct(int N, int Cin, int Cout, int D, int H, int W);     // a forward launch of this shape on activations (products == 2) takes a non-direct kernel under the current switches
+bool conv3_sb_forward_skips_direct(const Switches& sw, int N, int Cin, int Cout, int D, int H, int W);     // a forward launch of this shape on activations (products == 2) takes a non-direct kernel
 int conv3_sb_pack_batch(SbPackBatch& b, hipStream_t s);
 // pack [Cout][Cin][27] -> wp.  mode 0: forward; mode 1: data-gradient (taps flipped, in/out swapped:
 // the packed conv maps Cout_f input channels to Cin_f output channels).

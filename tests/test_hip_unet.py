@@ -1052,7 +1052,7 @@ def _backward_in_context(L, loss):
         loss.backward()
 
 
-@pytest.mark.parametrize("switch", ["RU_MX", "RU_MXG"])
+@pytest.mark.parametrize("switch", ["RU_WZ", "RU_MX", "RU_MXG"])
 def test_backward_refuses_switches_flipped_since_its_forward(switch):
     """round-5 advisor finding: a training forward packs only the fragment forms its kernel switches launch; a switch flipped between that forward and the
     backward would make a launch read fragments that were never packed.  The engine records the switches' signature with the packs and refuses such a backward
@@ -1073,6 +1073,23 @@ def test_backward_refuses_switches_flipped_since_its_forward(switch):
     finally:
         os.environ.pop(switch, None)
     assert all(p.grad is None or bool(torch.isfinite(p.grad).all()) for p in net.parameters())
+
+
+def test_ncdhw_split_bf16_forward_sizes_its_partials_by_the_kernel_it_launches():
+    """Channels that are not all multiples of 16 keep the split-bf16 engine on NCDHW tensors, where no launch takes a Winograd-z kernel.  A 32-channel level
+    whose SHAPE those kernels would accept (2 x 32^3: 256 (2,8,16) tiles x one 32-channel block, the smallest that fills 256 compute units) must still size
+    and finalize its GroupNorm partials by the direct kernel's grid -- the count follows the route of the launch's own arguments.  Checked against the exact-f32
+    engine on the same parameters at the split-bf16 forward's bar (1e-3 on probabilities, BASELINE.json north_star)."""
+    cfg = dict(depth=2, encoder_layers=[1, 1], decoder_layers=[1, 1], number_of_channels=[8, 32], number_of_outputs=3)
+    x = T(O.make_input(2, 64, 64, 64, seed=3)).cuda()
+    probs = {}
+    for precision in ("f32", "bf16x3"):
+        net, _ = build_model(cfg, 3, precision)
+        net.eval()
+        with torch.no_grad():
+            probs[precision] = net([x])[0].clone()
+    assert bool(torch.isfinite(probs["bf16x3"]).all())
+    assert float((probs["bf16x3"] - probs["f32"]).abs().max()) <= 1e-3
 
 
 def test_gradient_operand_convolutions_agree_through_the_network():

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Whole-network A/B of the Winograd-z kernel inside one process (RU_WZ is read per launch): probabilities, loss and every parameter
+"""Whole-network A/B of the Winograd-z kernel inside one process (RU_WZ is read per public call): probabilities, loss and every parameter
 gradient with RU_WZ=1 against RU_WZ=0 on the same inputs.  usage: wz_engine_diff.py [N] [D] [H] [W] [fusion bits as 0/1 0/1]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
