@@ -133,6 +133,8 @@ SIGNATURES = {
     "ru_elastic_noise": (_i, [C.c_ulonglong, _i, _i, _i, _vp, _vp]),
     "ru_elastic_field": (_i, [_vp, _d, _d, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ru_elastic_warp": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ru_intensity_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ru_intensity_augment": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ru_layout_convert": (_i, [_vp, _vp, _i, _i, _sz, _i, _vp]),
     "ru_upsample2x_trilinear_fwd_l": (_i, [_vp, _vp] + [_i] * 5 + [_f, _vp]),
     "ru_upsample2x_trilinear_bwd_l": (_i, [_vp, _vp] + [_i] * 5 + [_vp]),
@@ -173,6 +175,16 @@ LESION_COLUMNS = {"dice": 0, "hd95": 1}
 
 # ru_postprocess_regions (include/resunet_hip.h)
 POSTPROCESS_MASKS, POSTPROCESS_LABELS, POSTPROCESS_REGIONS, POSTPROCESS_STATS = 0, 1, 3, 6
+
+
+# ru_intensity_augment (include/resunet_hip.h): stage bits and the per-channel parameter block
+INT_BLUR, INT_LOWRES, INT_NOISE, INT_BRIGHTNESS, INT_CONTRAST, INT_GAMMA, INT_GAMMA_INVERT, INT_GAMMA_RETAIN = 1, 2, 4, 8, 16, 32, 64, 128
+INT_MAXC, INT_MAX_RADIUS = 8, 8
+
+
+class IntensityParams(C.Structure):
+    _fields_ = [("mask", _i * 8), ("blur_sigma", _d * 8), ("lowres_zoom", _d * 8), ("noise_variance", _d * 8), ("noise_seed", C.c_ulonglong * 8),
+                ("brightness", _d * 8), ("contrast", _d * 8), ("gamma", _d * 8)]
 
 
 class CritTerm(C.Structure):

@@ -12,6 +12,11 @@ Opt-in: elastic deformation (dataloader.py:24-48 `elastic_transform`, which the 
 commented out at :177 / :180 -- about 14 s of scipy per patch).  `SimpleReader(..., elastic=True)` or an `elastic` entry in the parameters
 of `augment_patch` adds three more kernels after the zoom pass (csrc/elastic.hip: noise, float64 displacement field, warp); the default path
 is the one above, unchanged.  `elastic_*_host` are the numpy restatements (tests/test_elastic_host.py holds them to the reference's outputs).
+
+Opt-in: intensity augmentation (csrc/intensity.hip), the transforms nnU-Net made standard and the reference does not have: Gaussian blur, simulated
+low resolution, additive Gaussian noise, brightness, contrast and gamma, per channel, on the data tensor `augment_patch` returns.
+`SimpleReader(..., intensity=True)` draws them from a private generator; `intensity_augment` takes explicit parameters and
+`intensity_augment_host` is the float64 restatement.
 """
 from __future__ import annotations
 
@@ -346,14 +351,268 @@ def elastic_warp_host(data, target, disp, flips=(False, False, False), transpose
     return data_out, target_out
 
 
+# ---------------------------------------------------------------------------------------------------------------- intensity augmentation
+# csrc/intensity.hip (`ru_intensity_augment`) and its float64 numpy restatement.  Per channel, in this order: blur, low resolution, noise,
+# brightness, contrast, gamma.  nnU-Net runs its noise before its blur; here the two spatial stages come first.
+INTENSITY_KEYS = ("blur_sigma", "lowres_zoom", "noise_variance", "noise_seed", "brightness", "contrast", "gamma", "gamma_invert", "gamma_retain_stats")
+
+
+def _check_intensity_params(params, channels):
+    """argument checks of `intensity_augment` / `intensity_augment_host`: ValueError before any launch; returns the list of dicts"""
+    params = list(params)
+    if not 1 <= channels <= L.INT_MAXC:
+        raise ValueError("intensity: 1..%d channels, got %d" % (L.INT_MAXC, channels))
+    if len(params) != channels:
+        raise ValueError("intensity: one parameter dict per channel (%d), got %d" % (channels, len(params)))
+    for c, q in enumerate(params):
+        unknown = set(q) - set(INTENSITY_KEYS)
+        if unknown:
+            raise ValueError("intensity: channel %d: unknown keys %s" % (c, sorted(unknown)))
+        if "blur_sigma" in q:
+            sigma = float(q["blur_sigma"])
+            if not (sigma > 0.0 and np.isfinite(sigma)):
+                raise ValueError("intensity: channel %d: blur sigma must be positive and finite, got %r" % (c, sigma))
+            if elastic_radius(sigma) > L.INT_MAX_RADIUS:
+                raise ValueError("intensity: channel %d: blur radius int(4 sigma + 0.5) = %d exceeds %d" % (c, elastic_radius(sigma), L.INT_MAX_RADIUS))
+        if "lowres_zoom" in q and not 0.0 < float(q["lowres_zoom"]) <= 1.0:
+            raise ValueError("intensity: channel %d: low-res zoom must lie in (0, 1], got %r" % (c, q["lowres_zoom"]))
+        if "noise_variance" in q:
+            var = float(q["noise_variance"])
+            if not (var >= 0.0 and np.isfinite(var)):
+                raise ValueError("intensity: channel %d: noise variance must be non-negative and finite, got %r" % (c, var))
+            if "noise_seed" not in q:
+                raise ValueError("intensity: channel %d: noise_variance needs a noise_seed" % c)
+        elif "noise_seed" in q:
+            raise ValueError("intensity: channel %d: noise_seed without noise_variance" % c)
+        for key in ("brightness", "contrast"):
+            if key in q and not np.isfinite(float(q[key])):
+                raise ValueError("intensity: channel %d: %s must be finite, got %r" % (c, key, q[key]))
+        if "gamma" in q:
+            g = float(q["gamma"])
+            if not (g > 0.0 and np.isfinite(g)):
+                raise ValueError("intensity: channel %d: gamma must be positive and finite, got %r" % (c, g))
+        elif "gamma_invert" in q or "gamma_retain_stats" in q:
+            raise ValueError("intensity: channel %d: gamma_invert / gamma_retain_stats without gamma" % c)
+    return params
+
+
+def intensity_param_block(params):
+    """the `ru_intensity_params` block (ctypes) of a checked list of per-channel dicts"""
+    blk = L.IntensityParams()
+    for c, q in enumerate(params):
+        m = 0
+        if "blur_sigma" in q:
+            m |= L.INT_BLUR
+            blk.blur_sigma[c] = float(q["blur_sigma"])
+        if "lowres_zoom" in q:
+            m |= L.INT_LOWRES
+            blk.lowres_zoom[c] = float(q["lowres_zoom"])
+        if "noise_variance" in q:
+            m |= L.INT_NOISE
+            blk.noise_variance[c] = float(q["noise_variance"])
+            blk.noise_seed[c] = int(q["noise_seed"]) & _M64
+        if "brightness" in q:
+            m |= L.INT_BRIGHTNESS
+            blk.brightness[c] = float(q["brightness"])
+        if "contrast" in q:
+            m |= L.INT_CONTRAST
+            blk.contrast[c] = float(q["contrast"])
+        if "gamma" in q:
+            m |= L.INT_GAMMA | (L.INT_GAMMA_INVERT if q.get("gamma_invert") else 0) | (L.INT_GAMMA_RETAIN if q.get("gamma_retain_stats") else 0)
+            blk.gamma[c] = float(q["gamma"])
+        blk.mask[c] = m
+    return blk
+
+
+def intensity_augment(data, params):
+    """A new float32 device tensor of `data`'s shape [C,P0,P1,P2]: `ru_intensity_augment`.  `params` holds one dict per channel with any of
+    `blur_sigma`, `lowres_zoom`, `noise_variance` + `noise_seed`, `brightness`, `contrast`, `gamma` (+ `gamma_invert`, `gamma_retain_stats`); a
+    missing key switches that stage off, an empty dict copies the channel bit for bit.  The stages and their order: include/resunet_hip.h,
+    restated by `intensity_augment_host`.  Arguments are checked before any launch."""
+    L.require_gpu()
+    if not isinstance(data, torch.Tensor) or not data.is_cuda or data.dim() != 4:
+        raise ValueError("intensity: data must be a [C,P0,P1,P2] device tensor")
+    c, p0, p1, p2 = (int(v) for v in data.shape)
+    params = _check_intensity_params(params, c)
+    if min(p0, p1, p2) < 1:
+        raise ValueError("intensity: the patch extents must be positive, got %s" % (tuple(data.shape),))
+    data = data.contiguous().float()
+    out = torch.empty_like(data)
+    lib = L.load()
+    ws = L.workspace(lib.ru_intensity_workspace_bytes(c, p0, p1, p2), data.device)
+    blk = intensity_param_block(params)
+    L.check(lib.ru_intensity_augment(L.f32(data), L.f32(out), c, p0, p1, p2, C.byref(blk), L.ptr(ws), ws.numel(), L.stream()), "ru_intensity_augment")
+    return out
+
+
+def intensity_noise_host(seed, channel, count):
+    """The first `count` values n(seed, channel, v), v = 0 .. count-1, of `ru_intensity_augment`'s noise in float64 (the device rounds ln, sqrt and
+    cos to float32): key = mix64(seed + (channel + 1) G); z1 = mix64(key + (2 v + 1) G), z2 = mix64(key + (2 v + 2) G); u1 = ((z1 >> 11) + 1) / 2^53
+    in (0, 1], u2 = (z2 >> 11) / 2^53 in [0, 1); n = sqrt(-2 ln u1) cos(2 pi u2).  mix64 and G are `elastic_noise_host`'s."""
+    v = np.arange(int(count), dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        key = _mix64(np.array([(int(seed) + (int(channel) + 1) * _GOLDEN) & _M64], dtype=np.uint64))
+        z1 = _mix64(key + (np.uint64(2) * v + np.uint64(1)) * np.uint64(_GOLDEN))
+        z2 = _mix64(key + (np.uint64(2) * v + np.uint64(2)) * np.uint64(_GOLDEN))
+    u1 = ((z1 >> np.uint64(11)).astype(np.float64) + 1.0) / 9007199254740992.0
+    u2 = (z2 >> np.uint64(11)).astype(np.float64) / 9007199254740992.0
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+
+
+def intensity_blur_host(x, sigma):
+    """scipy.ndimage.gaussian_filter(x, sigma, mode='reflect') of one channel restated: radius int(4 sigma + 0.5), weights exp(-0.5 d^2 / sigma^2) / sum,
+    axes 0, 1, 2 in turn on the half-sample-symmetric extension, periodic beyond one reflection (`_reflect`)"""
+    x = np.asarray(x, np.float64)
+    r = elastic_radius(sigma)
+    d = np.arange(-r, r + 1)
+    w = np.exp(-0.5 / (float(sigma) * float(sigma)) * d ** 2)
+    w = w / w.sum()
+    for ax in range(x.ndim):
+        n = x.shape[ax]
+        xp = np.take(x, _reflect(np.arange(-r, n + r), n), axis=ax)
+        x = sum(w[k] * np.take(xp, np.arange(k, k + n), axis=ax) for k in range(2 * r + 1))
+    return x
+
+
+def lowres_axis_host(n, zoom):
+    """(s0, s1, t) of one axis of the low-res stage: output voxel i = (1 - t[i]) x[s0[i]] + t[i] x[s1[i]].  n_c = max(1, floor(n zoom + 0.5)); coarse
+    sample j is the source voxel min(floor((j + 0.5) n / n_c), n - 1); i sits at c = clamp((i + 0.5) n_c / n - 0.5, 0, n_c - 1) between coarse
+    samples floor(c) and min(floor(c) + 1, n_c - 1).  The indices are formed in integers, as the kernel forms them."""
+    n = int(n)
+    nc = max(1, int(np.floor(n * float(zoom) + 0.5)))
+    i = np.arange(n, dtype=np.int64)
+    num = np.maximum((2 * i + 1) * nc - n, 0)
+    j0 = num // (2 * n)
+    t = (num % (2 * n)) / (2.0 * n)
+    t = np.where(j0 >= nc - 1, 0.0, t)
+    j0 = np.minimum(j0, nc - 1)
+    j1 = np.minimum(j0 + 1, nc - 1)
+    src = lambda j: np.minimum(((2 * j + 1) * n) // (2 * nc), n - 1)
+    return src(j0), src(j1), t
+
+
+def intensity_lowres_host(x, zoom):
+    """the low-res stage of one channel: nearest-neighbour down to the coarse grid and linear interpolation back, axis by axis (`lowres_axis_host`)"""
+    x = np.asarray(x, np.float64)
+    for ax in range(x.ndim):
+        s0, s1, t = lowres_axis_host(x.shape[ax], zoom)
+        shape = [1] * x.ndim
+        shape[ax] = -1
+        t = t.reshape(shape)
+        x = (1.0 - t) * np.take(x, s0, axis=ax) + t * np.take(x, s1, axis=ax)
+    return x
+
+
+def intensity_contrast_host(x, factor):
+    x = np.asarray(x, np.float64)
+    mean = x.mean()
+    return np.clip((x - mean) * float(factor) + mean, x.min(), x.max())
+
+
+def intensity_gamma_host(x, gamma, invert=False, retain_stats=False):
+    x = np.asarray(x, np.float64)
+    if invert:
+        x = -x
+    mean, std, mn = x.mean(), x.std(), x.min()
+    rng = x.max() - mn
+    y = np.power((x - mn) / (rng + 1e-7), float(gamma)) * rng + mn
+    if retain_stats:
+        sy = y.std()
+        y = (y - y.mean()) * (std / (sy if sy >= 1e-8 else 1e-8)) + mean
+    return -y if invert else y
+
+
+def intensity_augment_host(data, params):
+    """float64 numpy restatement of `ru_intensity_augment` on data [C,P0,P1,P2] (returned float64): the oracle of the device path.  Per channel, in
+    order: blur (`intensity_blur_host`), low resolution (`intensity_lowres_host`), x + sqrt(noise_variance) n(noise_seed, channel, v)
+    (`intensity_noise_host`, v the linear voxel index), x * brightness, clip((x - mean) contrast + mean, min, max), gamma
+    (`intensity_gamma_host`); mean, std (population), min, max are the channel's as it enters the stage."""
+    data = np.asarray(data.detach().cpu().numpy() if isinstance(data, torch.Tensor) else data, np.float64)
+    if data.ndim != 4:
+        raise ValueError("intensity: data must be [C,P0,P1,P2], got %s" % (data.shape,))
+    params = _check_intensity_params(params, data.shape[0])
+    out = np.empty_like(data)
+    for c, q in enumerate(params):
+        x = data[c]
+        if "blur_sigma" in q:
+            x = intensity_blur_host(x, q["blur_sigma"])
+        if "lowres_zoom" in q:
+            x = intensity_lowres_host(x, q["lowres_zoom"])
+        if "noise_variance" in q:
+            x = x + np.sqrt(float(q["noise_variance"])) * intensity_noise_host(q["noise_seed"], c, x.size).reshape(x.shape)
+        if "brightness" in q:
+            x = x * float(q["brightness"])
+        if "contrast" in q:
+            x = intensity_contrast_host(x, q["contrast"])
+        if "gamma" in q:
+            x = intensity_gamma_host(x, q["gamma"], bool(q.get("gamma_invert")), bool(q.get("gamma_retain_stats")))
+        out[c] = x
+    return out
+
+
+class IntensityConfig(object):
+    """Probabilities and ranges of `draw_intensity_params`; the defaults are nnU-Net's.  `p_*` is the chance per patch; blur and low-res then pick
+    each channel with `p_*_channel`, the other transforms take every channel of a patch they fire on, each with a value of its own.  Ranges are
+    (low, high) of a uniform draw.  One gamma stage exists per channel: the inverted draw (`p_gamma_invert`) and the plain one (`p_gamma`) are made
+    independently, and where both fire the inverted one wins.  Both run with `gamma_retain_stats`."""
+
+    def __init__(self, p_blur=0.2, p_blur_channel=0.5, blur_sigma=(0.5, 1.0), p_lowres=0.25, p_lowres_channel=0.5, lowres_zoom=(0.5, 1.0),
+                 p_noise=0.1, noise_variance=(0.0, 0.1), p_brightness=0.15, brightness=(0.75, 1.25), p_contrast=0.15, contrast=(0.75, 1.25),
+                 p_gamma_invert=0.1, p_gamma=0.3, gamma=(0.7, 1.5), gamma_retain_stats=True):
+        self.p_blur, self.p_blur_channel, self.blur_sigma = float(p_blur), float(p_blur_channel), tuple(blur_sigma)
+        self.p_lowres, self.p_lowres_channel, self.lowres_zoom = float(p_lowres), float(p_lowres_channel), tuple(lowres_zoom)
+        self.p_noise, self.noise_variance = float(p_noise), tuple(noise_variance)
+        self.p_brightness, self.brightness = float(p_brightness), tuple(brightness)
+        self.p_contrast, self.contrast = float(p_contrast), tuple(contrast)
+        self.p_gamma_invert, self.p_gamma, self.gamma = float(p_gamma_invert), float(p_gamma), tuple(gamma)
+        self.gamma_retain_stats = bool(gamma_retain_stats)
+
+
+def draw_intensity_params(channels, rng, config=None):
+    """One dict per channel for `intensity_augment`, drawn from `rng` (a private `random.Random`) ONLY: the global `random` / `numpy.random` streams
+    are not touched.  Order of the draws: blur, low-res, noise, brightness, contrast, inverted gamma, plain gamma; per transform the per-patch
+    draw first, then (only if it fired) the channels in order.  See `IntensityConfig` for the probabilities and for the gamma rule."""
+    cfg = config or IntensityConfig()
+    params = [dict() for _ in range(int(channels))]
+    if rng.random() < cfg.p_blur:
+        for q in params:
+            if rng.random() < cfg.p_blur_channel:
+                q["blur_sigma"] = rng.uniform(*cfg.blur_sigma)
+    if rng.random() < cfg.p_lowres:
+        for q in params:
+            if rng.random() < cfg.p_lowres_channel:
+                q["lowres_zoom"] = rng.uniform(*cfg.lowres_zoom)
+    if rng.random() < cfg.p_noise:
+        for q in params:
+            q["noise_variance"] = rng.uniform(*cfg.noise_variance)
+            q["noise_seed"] = rng.getrandbits(63)
+    if rng.random() < cfg.p_brightness:
+        for q in params:
+            q["brightness"] = rng.uniform(*cfg.brightness)
+    if rng.random() < cfg.p_contrast:
+        for q in params:
+            q["contrast"] = rng.uniform(*cfg.contrast)
+    inverted = rng.random() < cfg.p_gamma_invert
+    inverted_values = [rng.uniform(*cfg.gamma) for _ in params] if inverted else None
+    plain = rng.random() < cfg.p_gamma
+    plain_values = [rng.uniform(*cfg.gamma) for _ in params] if plain else None
+    if inverted or plain:
+        for q, g in zip(params, inverted_values if inverted else plain_values):
+            q["gamma"], q["gamma_invert"], q["gamma_retain_stats"] = g, inverted, cfg.gamma_retain_stats
+    return params
+
+
 class SimpleReader(torch.utils.data.Dataset):
     """dataloader.py:67-216 over in-memory cases: `cases` is a list of (image [C,D,H,W], label [D,H,W]) arrays (or of callables
     returning such a pair -- the place for a NIfTI reader).  Items are ([data], [target]) like the reference's, on the device.
     A case may be (image, label, soft) with soft [3,D,H,W] float32 teacher probabilities: its targets are distilled from `soft`
     (see DeviceCase); the draws are the same.  `elastic=True` deforms every patch (see augment_patch) with the sigma and alpha the reference
-    draws; the field seeds come from a private generator seeded with `elastic_seed`, so the global streams are those of `elastic=False`."""
+    draws; the field seeds come from a private generator seeded with `elastic_seed`, so the global streams are those of `elastic=False`.
+    `intensity=True` (nnU-Net's defaults) or an `IntensityConfig` runs `intensity_augment` on the data tensor of every patch, elastic or not, with
+    parameters drawn from a private `random.Random(intensity_seed)`; targets and the global streams are those of `intensity=False`."""
 
-    def __init__(self, cases, patch_size, images_in_epoch=4000, patches_from_single_image=1, device="cuda", elastic=False, elastic_seed=None):
+    def __init__(self, cases, patch_size, images_in_epoch=4000, patches_from_single_image=1, device="cuda", elastic=False, elastic_seed=None,
+                 intensity=False, intensity_seed=None):
         super(SimpleReader, self).__init__()
         self.cases = list(cases)
         self.patch_size = tuple(patch_size)
@@ -362,6 +621,8 @@ class SimpleReader(torch.utils.data.Dataset):
         self.device = device
         self.elastic = bool(elastic)
         self.elastic_rng = random.Random(elastic_seed)
+        self.intensity = intensity if isinstance(intensity, IntensityConfig) else (IntensityConfig() if intensity else None)
+        self.intensity_rng = random.Random(intensity_seed)
         self.real_length = len(self.cases)
         self.patches_from_current_image = self.patches_from_single_image + 1     # first item loads (the reference's constructor + first item do)
         self.current_image_index = 0
@@ -382,6 +643,8 @@ class SimpleReader(torch.utils.data.Dataset):
         self._load(index)
         p = draw_augment_params(self.case.bbox, self.patch_size, int(self.case.image.shape[0]), elastic=self.elastic, elastic_rng=self.elastic_rng)
         data, target = augment_patch(self.case, p)
+        if self.intensity is not None:
+            data = intensity_augment(data, draw_intensity_params(int(data.shape[0]), self.intensity_rng, self.intensity))
         return [data], [target]
 
     def __len__(self):

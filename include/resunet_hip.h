@@ -723,6 +723,54 @@ int ru_elastic_field(const double* noise, double sigma, double alpha, int P0, in
 int ru_elastic_warp(const float* data_in, int C, const float* target_in, int T, const double* disp, int P0, int P1, int P2, int flags,
                     const float* gain, const float* bias, float* data_out, float* target_out, ru_stream_t stream);
 
+/* ---------------------------------------------------------------- intensity augmentation of a training patch (csrc/intensity.hip).  Opt-in, a stage of
+ * its own behind ru_augment_patch / ru_elastic_warp; the call only enqueues.  in, out [C][P0][P1][P2] float32, C in 1..8, out may not overlap in.
+ * `p` is a HOST pointer read at launch: per channel a mask of RU_INT_* bits and the parameters of the stages whose bit is set.  A channel with no
+ * bit set is copied bit for bit.  Per channel the stages run in this order (dataloader.intensity_augment_host restates them in float64):
+ *   RU_INT_BLUR        scipy.ndimage.gaussian_filter(x, blur_sigma, mode='reflect'): radius r = int(4 sigma + 0.5), weights exp(-0.5 d^2 / sigma^2) / sum,
+ *                      three separable passes along axis 0, 1, 2 on the half-sample-symmetric extension (d c b a | a b c d | d c b a), periodic beyond
+ *                      one reflection, so r may exceed an extent.  float32 weights, data and sums.
+ *   RU_INT_LOWRES      per axis (extent P, z = lowres_zoom): n_c = max(1, floor(P z + 0.5)); coarse sample j = the source voxel
+ *                      min(floor((j + 0.5) P / n_c), P - 1); output voxel i = linear interpolation of the coarse samples at
+ *                      c = clamp((i + 0.5) n_c / P - 0.5, 0, n_c - 1).  Trilinear over 8 source voxels; indices in exact integer arithmetic.
+ *                      (= zoom(zoom(x, n_c / P, order=0, mode='nearest', grid_mode=True), P / n_c, order=1, mode='nearest', grid_mode=True))
+ *   RU_INT_NOISE       x + sqrt(noise_variance) * n(noise_seed, channel, v), v = the linear voxel index inside the channel.  With mix64 = splitmix64's
+ *                      finalizer (ru_elastic_noise's) and G = 0x9E3779B97F4A7C15, all in 64-bit wrapping arithmetic:
+ *                        key = mix64(noise_seed + (channel + 1) G),  z1 = mix64(key + (2 v + 1) G),  z2 = mix64(key + (2 v + 2) G),
+ *                        u1 = ((z1 >> 11) + 1) / 2^53 in (0, 1],  u2 = (z2 >> 11) / 2^53 in [0, 1),  n = sqrt(-2 ln u1) cos(2 pi u2)   (Box-Muller)
+ *                      The device evaluates ln, sqrt and cos in float32.  A pure function of (seed, channel, v): no state, any launch shape.
+ *   RU_INT_BRIGHTNESS  x * brightness
+ *   RU_INT_CONTRAST    clip((x - mean) * contrast + mean, min, max) with mean, min, max of the channel as it enters this stage
+ *   RU_INT_GAMMA       with min, range = max - min, mean, std (population) of the channel as it enters this stage, after the negation if
+ *                      RU_INT_GAMMA_INVERT is set: y = ((x - min) / (range + 1e-7))^gamma * range + min; with RU_INT_GAMMA_RETAIN
+ *                      y = (y - mean_y) * (std / (std_y >= 1e-8 ? std_y : 1e-8)) + mean; with RU_INT_GAMMA_INVERT the result is negated back.
+ *                      t^gamma is formed as exp2(gamma log2 t).  The two modifier bits mean nothing without RU_INT_GAMMA.
+ * Channel statistics: per-workgroup partials summed in float64 in a fixed order (as ru_zscore_stats): no float atomics, two calls give the same bytes,
+ * min and max are exact.  Refused (RU_EINVAL, before any launch): C outside 1..8, overlapping in / out, unknown mask bits, blur_sigma <= 0 or not
+ * finite or radius > 8 (sigma up to 2.0), lowres_zoom outside (0, 1], noise_variance < 0 or not finite, gamma <= 0 or not finite, brightness or
+ * contrast not finite, ws smaller than ru_intensity_workspace_bytes(C, P0, P1, P2), P0 > 65535. */
+#define RU_INT_BLUR 1
+#define RU_INT_LOWRES 2
+#define RU_INT_NOISE 4
+#define RU_INT_BRIGHTNESS 8
+#define RU_INT_CONTRAST 16
+#define RU_INT_GAMMA 32
+#define RU_INT_GAMMA_INVERT 64
+#define RU_INT_GAMMA_RETAIN 128
+typedef struct ru_intensity_params {      /* every array is indexed by channel; 8 = the pipeline's channel limit (ru_augment_patch) */
+    int mask[8];
+    double blur_sigma[8];
+    double lowres_zoom[8];
+    double noise_variance[8];
+    unsigned long long noise_seed[8];
+    double brightness[8];
+    double contrast[8];
+    double gamma[8];
+} ru_intensity_params;
+size_t ru_intensity_workspace_bytes(int C, int P0, int P1, int P2);
+int ru_intensity_augment(const float* in, float* out, int C, int P0, int P1, int P2, const ru_intensity_params* p, void* ws, size_t ws_bytes,
+                         ru_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
