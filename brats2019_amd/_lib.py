@@ -146,6 +146,8 @@ SIGNATURES = {
     "ru_conv3_l_workspace_bytes": (_sz, [_i] * 7),
     "ru_conv3_l": (_i, [_vp, _vp, _vp, _vp] + [_i] * 8 + [_vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _vp, _f, _vp, _sz, C.POINTER(_i), C.POINTER(_i), _vp, _sz, _vp]),
     "ru_wgrad1_l_workspace_bytes": (_sz, [_i, _i, _i, _sz]),
+    "ru_wgrad3_l_workspace_bytes": (_sz, [_i] * 7),
+    "ru_wgrad3_l": (_i, [_vp, _vp, _vp] + [_i] * 8 + [_vp, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, C.POINTER(_i), _vp, _sz, _vp]),
     "ru_wgrad1_l": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _sz] + [_i] * 6 + [_vp, _i, _vp, _vp, _f, C.POINTER(_i), _vp, _sz, _vp]),
 }
 

@@ -1937,6 +1937,48 @@ extern "C" int ru_wgrad1_l(const float* x, const float* x1, int C0, const float*
     return wgrad1_launch(a, (hipStream_t)stream);
 }
 
+// The transpose-read 3x3x3 weight gradient, one launch at a time with every operand of Wgrad3Args the engine sets: a thin filler like ru_conv3_l (no kernels,
+// no arithmetic of its own).  flags: 1 dy is in split form, 2 x is NCDHW with dw_cin <= 4 channels (4-channel copy made here), 4 dy is NCDHW with dw_cout <= 4
+// channels (likewise), 8 swapped, 16 gb_g16, 32 the reduction of the partials is deferred to a list of this call's own and flushed behind the kernel.
+extern "C" size_t ru_wgrad3_l_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W, int flags) {
+    return 4096 + align_up(wgrad3_tr_workspace_bytes(N, Cin, Cout, D, H, W), 256) + ((flags & 2) ? align_up((size_t)N * D * H * W * 16, 256) : 0) + ((flags & 4) ? align_up((size_t)N * D * H * W * 16, 256) : 0);
+}
+extern "C" int ru_wgrad3_l(const float* x, const float* dy, float* dw, int N, int Cin, int Cout, int D, int H, int W, int flags, int products,
+                           const float* in_scale, const float* in_shift, float in_slope, int dw_cin, int dw_cout,
+                           const float* gb_y, const float* gb_d, const float* gb_scale, const float* gb_shift, const float* gb_coef, float gb_slope, float* gb_out,
+                           int* inst, void* ws, size_t ws_bytes, ru_stream_t stream) {
+    RU_REQUIRE(x && (dy || gb_y) && dw, "ru_wgrad3_l: null argument");
+    RU_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, "ru_wgrad3_l: bad shape");
+    hipStream_t s = (hipStream_t)stream;
+    WsCarver C(ws, ws_bytes);
+    Wgrad3Args a{};
+    a.x = x; a.dy = dy ? dy : gb_y; a.dw = dw; a.mode = RU_PREC_BF16X3; a.x_c16 = 1; a.dy_c16 = 1;
+    a.N = N; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W;
+    a.in_scale = in_scale; a.in_shift = in_shift; a.in_slope = in_slope; a.dw_cin = dw_cin; a.dw_cout = dw_cout;
+    a.dy_s16 = flags & 1; a.x_c4 = (flags >> 1) & 1; a.dy_c4 = (flags >> 2) & 1; a.swapped = (flags >> 3) & 1; a.gb_g16 = (flags >> 4) & 1; a.products = products;
+    a.gb_y = gb_y; a.gb_d = gb_d; a.gb_scale = gb_scale; a.gb_shift = gb_shift; a.gb_coef = gb_coef; a.gb_slope = gb_slope; a.gb_out = gb_out;
+    a.ws_bytes = wgrad3_tr_workspace_bytes(N, Cin, Cout, D, H, W);
+    a.ws = C.take(a.ws_bytes / 4);
+    RU_WS_OK(C);
+    for (int side = 0; side < 2; ++side) {                       // a few-channel side arrives NCDHW and is copied as the engine's stem and head copy it
+        if (!(side == 0 ? a.x_c4 : a.dy_c4)) continue;
+        const int cfew = side == 0 ? dw_cin : dw_cout;
+        const size_t V = (size_t)D * H * W;
+        RU_REQUIRE(cfew > 0 && cfew <= 4 && (side == 0 || dy), "ru_wgrad3_l: a 4-channel copy holds 1..4 channels (dw_cin / dw_cout)");
+        float* c4 = C.take((size_t)N * 4 * V);
+        RU_WS_OK(C);
+        const int rc = pad_to_c4_launch(side == 0 ? x : dy, c4, N, cfew, V, s);
+        if (rc) return rc;
+        if (side == 0) a.x = c4; else a.dy = c4;
+    }
+    if (inst) *inst = wgrad3_tr_inst(a);
+    WgradRedList own;
+    if (flags & 32) a.defer = &own;
+    const int rc = wgrad3_tr_launch(a, s);
+    if (rc) return rc;
+    return (flags & 32) ? wgrad_reduce_flush(own, s) : RU_OK;
+}
+
 // ====================================================================== training input pipeline (dataloader.py)
 extern "C" size_t ru_zscore_workspace_bytes(int C, size_t V) { return zscore_workspace_bytes(C, V) + 256; }
 extern "C" int ru_zscore_stats(const float* image, double* stats, int C, size_t V, void* ws, size_t ws_bytes, ru_stream_t stream) {

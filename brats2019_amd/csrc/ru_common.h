@@ -326,6 +326,9 @@ int wgrad3_sb_launch(const Wgrad3Args& a, hipStream_t s);
 // both tensors voxel-major: transpose-read kernel (wgrad_tr.hip); workspace 0 if the channel counts do not fit
 size_t wgrad3_tr_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W);
 int wgrad3_tr_launch(const Wgrad3Args& a, hipStream_t s);
+// the instantiation wgrad3_tz_kernel<OT, XS, DS, NP> wgrad3_tr_launch takes for `a`: OT | XS << 4 | DS << 8 | NP << 12, negative where the launch is refused
+// (the one place that decides; the launcher switches on it and ru_wgrad3_l reports it)
+int wgrad3_tr_inst(const Wgrad3Args& a);
 
 // 1x1x1: dw[o][c] = sum_{n,v} dy[n][o][v] * x[n][c][v]; result written to dw[o*ldw + c] (ldw >= Cin)
 struct Wgrad1Args {

@@ -499,7 +499,9 @@ __global__ __launch_bounds__(512, 2) void wgrad3_tz_kernel(const Wgrad3Args a, f
 struct WTRChoice { int ot, nbx, ngroups, ncg; };
 static WTRChoice wtr_choose(int N, int Cin, int Cout, int D, int H, int W) {
     WTRChoice c;
-    c.ot = Cout >= 32 ? 2 : 1;
+    // two output blocks per workgroup need an even number of them: an odd count (Cout = 48, 80, ...) takes OT = 1, whose grid has one
+    // group per block (with OT = 2 the last block had no workgroup, and the reduction summed partials nobody wrote)
+    c.ot = (Cout >= 32 && (Cout / 16) % 2 == 0) ? 2 : 1;
     c.ncg = Cin / 16;
     c.ngroups = (Cout / 16 / c.ot) * c.ncg;
     const long ntile = (long)N * cdiv(D, 4) * cdiv(H, 4) * cdiv(W, 16);
@@ -514,6 +516,44 @@ size_t wgrad3_tr_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W) 
     if (Cin % 16 || Cout % 16) return 0;
     const WTRChoice c = wtr_choose(N, Cin, Cout, D, H, W);
     return (size_t)c.nbx * 27 * Cout * Cin * sizeof(float);       // one partial per workgroup
+}
+
+// The one place that decides which wgrad3_tz_kernel<OT, XS, DS, NP> a launch takes (the launcher switches on the value, ru_wgrad3_l reports it):
+// OT | XS << 4 | DS << 8 | NP << 12, or -(k) for the k-th refusal of wgrad3_tr_launch, in the order the launcher states them.
+enum { WTR_NO_LAYOUT = -1, WTR_NO_GB_OPERANDS = -2, WTR_NO_G16 = -3, WTR_NO_C4_GB = -4, WTR_NO_C4_OT2 = -5, WTR_NO_C4_BLOCK = -6, WTR_NO_TWO_C4 = -7, WTR_NO_C4_XFORM = -8 };
+static constexpr int wtr_pack(int ot, int xs, int ds, int np = 3) { return ot | (xs << 4) | (ds << 8) | (np << 12); }
+int wgrad3_tr_inst(const Wgrad3Args& a) {
+    if (!(a.x_c16 && a.dy_c16 && a.Cin > 0 && a.Cout > 0 && a.Cin % 16 == 0 && a.Cout % 16 == 0)) return WTR_NO_LAYOUT;
+    const int ot = wtr_choose(a.N, a.Cin, a.Cout, a.D, a.H, a.W).ot;
+    const bool p1 = a.products == 1;                     // one-product forms exist for the variants the engine's backward runs
+    // the packed-tap staging (XS == 2) holds (tap, channel) pairs where the transform indexes channels: it would scale with the wrong channel's constants
+    if (a.x_c4 && a.in_scale) return WTR_NO_C4_XFORM;
+    if (a.gb_y) {
+        if (!(!a.dy_c4 && a.gb_d && a.gb_scale && a.gb_shift && a.gb_coef && (a.gb_out || a.x_c4))) return WTR_NO_GB_OPERANDS;
+        const bool g16 = a.gb_g16 != 0;                  // the form gb_out is published in: this predicate, and nothing else, picks DS == 4
+        if (g16 && !(ot == 1 && !p1 && !a.x_c4)) return WTR_NO_G16;
+        if (a.x_c4) {                                    // stem: x = network input
+            if (!(ot == 1 && a.Cin == 16)) return WTR_NO_C4_GB;
+            return wtr_pack(1, 2, 3, p1 ? 1 : 3);        // (taps packed into the 16 columns: XS == 2)
+        }
+        if (ot == 2) return wtr_pack(2, 0, 3);           // two output blocks per workgroup: the constants of a block are fetched when it is converted
+        if (p1) return wtr_pack(1, 0, 3, 1);
+        return wtr_pack(1, 0, g16 ? 4 : 3);
+    }
+    const int xs = a.x_c4 ? 1 : 0, ds = a.dy_c4 ? 2 : (a.dy_s16 ? 1 : 0);
+    if (ot == 2) {
+        if (!(xs == 0 && ds != 2)) return WTR_NO_C4_OT2;
+        return wtr_pack(2, 0, ds, (p1 && ds == 1) ? 1 : 3);
+    }
+    // (an odd number of output blocks arrives here with Cout > 16: a 4-channel copy still stands for the only block of its side)
+    if (!((xs == 0 || a.Cin == 16) && (ds != 2 || a.Cout == 16))) return WTR_NO_C4_BLOCK;
+    if (xs == 1) {
+        if (ds == 2) return WTR_NO_TWO_C4;
+        if (ds == 1) return wtr_pack(1, 2, 1);
+        return wtr_pack(1, 2, 0, p1 ? 1 : 3);
+    }
+    if (ds == 2) return wtr_pack(1, 0, 2, p1 ? 1 : 3);
+    return wtr_pack(1, 0, ds);
 }
 
 template <int OT, int XS, int DS, int NP = 3>
@@ -537,37 +577,39 @@ static int wtz_cfg(const Wgrad3Args& a, const WTRChoice& c, hipStream_t s) {
 }
 
 int wgrad3_tr_launch(const Wgrad3Args& a, hipStream_t s) {
-    RU_REQUIRE(a.x_c16 && a.dy_c16 && a.Cin % 16 == 0 && a.Cout % 16 == 0, "wgrad3_tr: needs voxel-major x and dy with channel counts %% 16 == 0");
+    const int inst = wgrad3_tr_inst(a);
+    RU_REQUIRE(inst != WTR_NO_LAYOUT, "wgrad3_tr: needs voxel-major x and dy with channel counts %% 16 == 0");
     const WTRChoice c = wtr_choose(a.N, a.Cin, a.Cout, a.D, a.H, a.W);
     if (!a.ws || a.ws_bytes < wgrad3_tr_workspace_bytes(a.N, a.Cin, a.Cout, a.D, a.H, a.W)) {
         set_error("wgrad3_tr: workspace too small");
         return RU_ENOMEM;
     }
-    const bool p1 = a.products == 1;                     // one-product forms exist for the variants the engine's backward runs
-    if (a.gb_y) {
-        RU_REQUIRE(!a.dy_c4 && a.gb_d && a.gb_scale && a.gb_shift && a.gb_coef && (a.gb_out || a.x_c4),
-                   "wgrad3_tr: the fused GroupNorm-backward apply needs all of its operands");
-        if (a.x_c4) {                                    // stem: x = network input
-            RU_REQUIRE(c.ot == 1, "wgrad3_tr: a 4-channel copy stands for ONE 16-channel block");
-            return p1 ? wtz_cfg<1, 2, 3, 1>(a, c, s) : wtz_cfg<1, 2, 3>(a, c, s);      // (taps packed into the 16 columns: XS == 2)
-        }
-        if (p1 && c.ot == 1) return wtz_cfg<1, 0, 3, 1>(a, c, s);
-        if (c.ot == 2) return wtz_cfg<2, 0, 3>(a, c, s);   // two output blocks per workgroup: the constants of a block are fetched when it is converted
-        return a.gb_g16 ? wtz_cfg<1, 0, 4>(a, c, s) : wtz_cfg<1, 0, 3>(a, c, s);
+    RU_REQUIRE(inst != WTR_NO_C4_XFORM, "wgrad3_tr: a 4-channel copy of x takes no fused transform");
+    RU_REQUIRE(inst != WTR_NO_GB_OPERANDS, "wgrad3_tr: the fused GroupNorm-backward apply needs all of its operands");
+    RU_REQUIRE(inst != WTR_NO_G16, "wgrad3_tr: the gradient-operand form is published by the one-block, three-product kernel on a voxel-major x only");
+    RU_REQUIRE(inst != WTR_NO_C4_GB, "wgrad3_tr: a 4-channel copy stands for ONE 16-channel block");
+    RU_REQUIRE(inst != WTR_NO_C4_OT2 && inst != WTR_NO_C4_BLOCK, "wgrad3_tr: 4-channel copies stand for ONE 16-channel block");
+    RU_REQUIRE(inst != WTR_NO_TWO_C4, "wgrad3_tr: only one operand can be a 4-channel copy");
+    switch (inst) {
+        case wtr_pack(1, 2, 3, 1): return wtz_cfg<1, 2, 3, 1>(a, c, s);
+        case wtr_pack(1, 2, 3): return wtz_cfg<1, 2, 3>(a, c, s);
+        case wtr_pack(1, 0, 3, 1): return wtz_cfg<1, 0, 3, 1>(a, c, s);
+        case wtr_pack(2, 0, 3): return wtz_cfg<2, 0, 3>(a, c, s);
+        case wtr_pack(1, 0, 4): return wtz_cfg<1, 0, 4>(a, c, s);
+        case wtr_pack(1, 0, 3): return wtz_cfg<1, 0, 3>(a, c, s);
+        case wtr_pack(2, 0, 1, 1): return wtz_cfg<2, 0, 1, 1>(a, c, s);
+        case wtr_pack(2, 0, 1): return wtz_cfg<2, 0, 1>(a, c, s);
+        case wtr_pack(2, 0, 0): return wtz_cfg<2, 0, 0>(a, c, s);
+        case wtr_pack(1, 2, 1): return wtz_cfg<1, 2, 1>(a, c, s);
+        case wtr_pack(1, 2, 0, 1): return wtz_cfg<1, 2, 0, 1>(a, c, s);
+        case wtr_pack(1, 2, 0): return wtz_cfg<1, 2, 0>(a, c, s);
+        case wtr_pack(1, 0, 2, 1): return wtz_cfg<1, 0, 2, 1>(a, c, s);
+        case wtr_pack(1, 0, 2): return wtz_cfg<1, 0, 2>(a, c, s);
+        case wtr_pack(1, 0, 1): return wtz_cfg<1, 0, 1>(a, c, s);
+        case wtr_pack(1, 0, 0): return wtz_cfg<1, 0, 0>(a, c, s);
     }
-    const int xs = a.x_c4 ? 1 : 0, ds = a.dy_c4 ? 2 : (a.dy_s16 ? 1 : 0);
-    if (c.ot == 2) {
-        RU_REQUIRE(xs == 0 && ds != 2, "wgrad3_tr: 4-channel copies stand for ONE 16-channel block");
-        if (p1 && ds == 1) return wtz_cfg<2, 0, 1, 1>(a, c, s);
-        return ds == 1 ? wtz_cfg<2, 0, 1>(a, c, s) : wtz_cfg<2, 0, 0>(a, c, s);
-    }
-    if (xs == 1) {
-        RU_REQUIRE(ds != 2, "wgrad3_tr: only one operand can be a 4-channel copy");
-        if (ds == 1) return wtz_cfg<1, 2, 1>(a, c, s);
-        return p1 ? wtz_cfg<1, 2, 0, 1>(a, c, s) : wtz_cfg<1, 2, 0>(a, c, s);
-    }
-    if (ds == 2) return p1 ? wtz_cfg<1, 0, 2, 1>(a, c, s) : wtz_cfg<1, 0, 2>(a, c, s);
-    return ds == 1 ? wtz_cfg<1, 0, 1>(a, c, s) : wtz_cfg<1, 0, 0>(a, c, s);
+    set_error("wgrad3_tr: no kernel for instantiation %d", inst);
+    return RU_EINVAL;
 }
 
 }  // namespace ru

@@ -1099,3 +1099,46 @@ def conv3_fused(x, w, bias=None, in_c16=False, out_c16=False, few_channels=False
     if part is not None:
         part = part[:n * cout * nblk.value * 2].view(n, cout, nblk.value, 2)
     return Conv3Result(y, in_sum_out, part, nblk.value, route.value)
+
+
+Wgrad3Result = collections.namedtuple("Wgrad3Result", "dw gb_out inst")
+
+
+def wgrad3_inst(packed):
+    """ru_wgrad3_l's kernel report (wgrad3_tr_inst) -> (OT, XS, DS, NP) of wgrad3_tz_kernel; None where the launch is refused."""
+    return None if packed < 0 else (packed & 15, (packed >> 4) & 15, (packed >> 8) & 15, (packed >> 12) & 15)
+
+
+def wgrad3_fused(x, dy, in_scale=None, in_shift=None, in_slope=LEAKY_SLOPE, dy_split=False, x_c4=False, dy_c4=False, swapped=False, products=0, gb_g16=False,
+                 dw_cin=0, dw_cout=0, gb_y=None, gb_d=None, gb_scale=None, gb_shift=None, gb_coef=None, gb_slope=LEAKY_SLOPE, gb_out=False, deferred=False,
+                 cin=None, cout=None):
+    """One launch of the transpose-read 3x3x3 weight gradient with the operands the engine fuses into it (ru_wgrad3_l).  x, dy, gb_y, gb_d: voxel-major
+    [N, C/16, D, H, W, 16]; with x_c4 / dy_c4 that side is NCDHW with <= 4 channels (dw_cin / dw_cout of them) and is copied to the 4-channel form.  dy_split: dy is
+    in split form (to_split_c16).  gb_*: the GroupNorm-backward apply forms dy in the staging (dy may be None); gb_out = True allocates the published tensor
+    prefilled with NaN (split form, or the gradient-operand form with gb_g16).  dw: [dw_cout, dw_cin, 3, 3, 3], swapped: [dw_cin, dw_cout, 3, 3, 3] (the
+    convolution's own [Cout, Cin]).  cin / cout: the channel counts the launch is told when a 4-channel side should stand beside more than one block (16
+    otherwise; such a launch is refused).  inst: decode with wgrad3_inst."""
+    x, dy, in_scale, in_shift, gb_y, gb_d, gb_scale, gb_shift, gb_coef = (_prep(t) for t in (x, dy, in_scale, in_shift, gb_y, gb_d, gb_scale, gb_shift, gb_coef))
+    side = gb_y if gb_y is not None else dy
+    if x_c4:
+        n, _, d, h, wd = _dims5(x)
+        cin = int(cin or 16)
+    else:
+        n, cb, d, h, wd, _ = (int(v) for v in x.shape)
+        cin = cb * 16
+    cout = int(cout or 16) if (dy_c4 and gb_y is None) else int(side.shape[1]) * 16
+    dev = x.device
+    ci, co = (dw_cin or cin), (dw_cout or cout)
+    dw = torch.full((ci, co, 3, 3, 3) if swapped else (co, ci, 3, 3, 3), float("nan"), dtype=torch.float32, device=dev)
+    if gb_out is True:
+        gb_out = torch.full((n, cout // 16, d, h, wd, 16), float("nan"), dtype=torch.float32, device=dev)
+    elif gb_out is False:
+        gb_out = None
+    flags = int(dy_split) | (int(x_c4) << 1) | (int(dy_c4) << 2) | (int(swapped) << 3) | (int(gb_g16) << 4) | (int(deferred) << 5)
+    lib = L.load()
+    ws = L.workspace(lib.ru_wgrad3_l_workspace_bytes(n, cin, cout, d, h, wd, flags), dev)
+    inst = C.c_int(0)
+    L.check(lib.ru_wgrad3_l(L.f32(x), L.ptr(dy, True), L.f32(dw), n, cin, cout, d, h, wd, flags, int(products), L.ptr(in_scale, True), L.ptr(in_shift, True),
+                            float(in_slope), int(dw_cin), int(dw_cout), L.ptr(gb_y, True), L.ptr(gb_d, True), L.ptr(gb_scale, True), L.ptr(gb_shift, True),
+                            L.ptr(gb_coef, True), float(gb_slope), L.ptr(gb_out, True), C.byref(inst), L.ptr(ws), ws.numel(), L.stream()), "ru_wgrad3_l")
+    return Wgrad3Result(dw, gb_out, inst.value)

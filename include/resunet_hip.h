@@ -546,6 +546,27 @@ size_t ru_wgrad1_l_workspace_bytes(int N, int Cin, int Cout, size_t V);
 int ru_wgrad1_l(const float* x, const float* x1, int C0, const float* dy, float* dw, int ldw, int N, int Cin, int Cout, size_t V,
                 int c16, int s2d, int Dc, int Hc, int Wc, int tap_split, const float* dg_w, int dg_ldw, float* dg_y0, float* dg_y1,
                 float dg_mask_slope, int* inst, void* ws, size_t ws_bytes, ru_stream_t stream);
+/* The transpose-read 3x3x3 weight gradient (both operands voxel-major, Cin and Cout multiples of 16), one launch at a time with the operands the engine fuses into it:
+ *   dw[o][c][tap] = sum_{n,v} dy[n][v][o] * pad0( lrelu(x*in_scale[n][c] + in_shift[n][c], in_slope) )[n][v + tap][c];  in_scale null: no transform.
+ *   flags: 1 = dy is in split form (64 bytes per voxel and block: bf16 hi ch 0-7 | hi ch 8-15 | lo ch 0-7 | lo ch 8-15);
+ *          2 = x is NCDHW with dw_cin <= 4 channels and stands for one 16-channel block (Cin = 16): the 4-channel copy is made in the workspace and its three
+ *              dx taps are packed into the block's columns;  4 = dy is NCDHW with dw_cout <= 4 channels (Cout = 16), likewise copied;
+ *          8 = swapped: x (with its halo) is the convolution's OUTPUT gradient and dy its input; dw is then [dw_cin][dw_cout][27] = the convolution's
+ *              [Cout_conv][Cin_conv][27], taps mirrored by the reduction;
+ *          16 = gb_out is published in the gradient-operand form (bf16 hi ch 0-7 | hi ch 8-15 | e4m3 lo / 2^(e-8), e4m3 value / 2^e ch 0-7 | the same ch 8-15)
+ *              instead of the split form;  32 = the reduction of the partials runs deferred (queued, then flushed as one batch launch): same result.
+ *   products: 0 / 3 = three split-bf16 products, 1 = one bf16 product where such a kernel exists.
+ *   dw_cin / dw_cout (0 = Cin / Cout): the real channel counts dw is truncated to; dw is [dw_cout][dw_cin][27].
+ *   gb_y (optional; dy may then be null): the dy operand is the GroupNorm-backward apply formed in the staging from the forward tensor gb_y and the gradient
+ *   gb_d (voxel-major), gb_scale / gb_shift [N][Cout], gb_coef [N][Cout][3] and gb_slope,
+ *       dy = cA * ((y*scale + shift) > 0 ? d : d*slope) + (cB*y + cC),
+ *   and is written to gb_out (voxel-major, 64 bytes per voxel and block; may be null with flag 2 only) in the form flag 16 names.
+ *   *inst (optional): the instantiation taken, OT | XS << 4 | DS << 8 | NP << 12 of wgrad3_tz_kernel<OT, XS, DS, NP>; negative: the launch is refused. */
+size_t ru_wgrad3_l_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W, int flags);
+int ru_wgrad3_l(const float* x, const float* dy, float* dw, int N, int Cin, int Cout, int D, int H, int W, int flags, int products,
+                const float* in_scale, const float* in_shift, float in_slope, int dw_cin, int dw_cout,
+                const float* gb_y, const float* gb_d, const float* gb_scale, const float* gb_shift, const float* gb_coef, float gb_slope, float* gb_out,
+                int* inst, void* ws, size_t ws_bytes, ru_stream_t stream);
 
 /* trilinear x2 and its transpose on C16 tensors (C % 16 == 0; D,H,W = extents of the COARSE side, as in
  * ru_upsample2x_trilinear_*).  out_slope: LeakyReLU slope applied to the interpolated value (the decoder fuses model.py:401-402
