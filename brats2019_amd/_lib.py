@@ -129,6 +129,7 @@ SIGNATURES = {
     "ru_zscore_stats": (_i, [_vp, _vp, _i, _sz, _vp, _sz, _vp]),
     "ru_augment_patch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "ru_augment_patch_soft": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ru_augment_patch_affine": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "ru_elastic_workspace_bytes": (_sz, [_i, _i, _i]),
     "ru_elastic_noise": (_i, [C.c_ulonglong, _i, _i, _i, _vp, _vp]),
     "ru_elastic_field": (_i, [_vp, _d, _d, _i, _i, _i, _vp, _vp, _sz, _vp]),
@@ -182,6 +183,10 @@ POSTPROCESS_MASKS, POSTPROCESS_LABELS, POSTPROCESS_REGIONS, POSTPROCESS_STATS = 
 # ru_intensity_augment (include/resunet_hip.h): stage bits and the per-channel parameter block
 INT_BLUR, INT_LOWRES, INT_NOISE, INT_BRIGHTNESS, INT_CONTRAST, INT_GAMMA, INT_GAMMA_INVERT, INT_GAMMA_RETAIN = 1, 2, 4, 8, 16, 32, 64, 128
 INT_MAXC, INT_MAX_RADIUS = 8, 8
+
+
+# ru_augment_patch_affine (include/resunet_hip.h): thread mappings
+AFFINE_MAPPINGS = {"default": 0, "row": 1, "brick": 2}
 
 
 class IntensityParams(C.Structure):

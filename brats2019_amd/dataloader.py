@@ -17,6 +17,11 @@ Opt-in: intensity augmentation (csrc/intensity.hip), the transforms nnU-Net made
 low resolution, additive Gaussian noise, brightness, contrast and gamma, per channel, on the data tensor `augment_patch` returns.
 `SimpleReader(..., intensity=True)` draws them from a private generator; `intensity_augment` takes explicit parameters and
 `intensity_augment_host` is the float64 restatement.
+
+Opt-in: rotation (csrc/rotate.hip), the spatial transform nnU-Net's recipes rely on most and the reference cannot afford.  A `rotation` entry in the
+parameters of `augment_patch` replaces the zoom pass by `ru_augment_patch_affine`: the patch is gathered from the WHOLE resident volume through a
+3 x 3 matrix and an offset (scipy's affine_transform convention, order 1, zero fill outside the volume), so a rotated patch shows real tissue in its
+corners.  `SimpleReader(..., rotation=True)` draws the angles from a private generator; `affine_patch_host` is the float64 restatement.
 """
 from __future__ import annotations
 
@@ -140,10 +145,19 @@ def augment_patch(case, p, patch_size=None):
 
     With an `elastic` entry in `p` (dict(sigma, alpha, seed), or `noise` [3,P0,P1,P2] float64 in place of `seed`) the patch is deformed as
     the reference's commented lines :177 / :180 would: the zoom pass runs without flips, gain or bias, then `elastic_noise` ->
-    `elastic_field` -> `elastic_warp` (order 1 on the image, order 0 on the targets) and the warp applies flips, transpose, gain and bias."""
+    `elastic_field` -> `elastic_warp` (order 1 on the image, order 0 on the targets) and the warp applies flips, transpose, gain and bias.
+
+    With a `rotation` entry in `p` the affine pass (`ru_augment_patch_affine`, see `affine_patch_host`) takes the place of the zoom pass, in the same
+    slot: directly, or in front of the elastic warp with flags 0, gain 1 and bias 0.  The entry is dict(angles=(a0, a1, a2)) in radians -- the patch
+    is rotated by `rotation_matrix(angles)` and zoomed by p["scale"] about its own centre: matrix = R diag(scale), offset = centre - matrix (P - 1) / 2
+    with centre = crop_lo + (P - 1) / 2 -- or dict(matrix=3x3[, offset=3]) for an explicit transform (p["scale"] is not applied then; without
+    `offset` the matrix acts about the patch centre as above).  The crop need not lie inside the volume: outside it the image is raw 0, the targets 0.
+    An optional `mapping` ("row" / "brick") picks the kernel's thread mapping; the result does not depend on it."""
     patch = tuple(int(v) for v in (patch_size or case.patch_size))
     c, d, h, w = (int(v) for v in case.image.shape)
     el = p.get("elastic")
+    rot = p.get("rotation")
+    affine = None if rot is None else _rotation_transform(rot, p["crop_lo"], p["scale"], patch)      # argument checks before any launch
     noise = None
     if el is not None:                                   # argument checks before any launch
         sigma, alpha = float(el["sigma"]), float(el["alpha"])
@@ -160,6 +174,18 @@ def augment_patch(case, p, patch_size=None):
     soft = getattr(case, "soft", None)
     gain = [float(v) for v in p["gain"]] if direct else [1.0] * c
     bias = [float(v) for v in p["bias"]] if direct else [0.0] * c
+    if affine is not None:
+        matrix, offset, mapping = affine
+        L.check(lib.ru_augment_patch_affine(L.f32(case.image), L.ptr(case.label), None if soft is None else L.f32(soft),
+                                            _arr(C.c_float, [float(v) for v in case.mean]), _arr(C.c_float, [float(1.0 / v) for v in case.std]),
+                                            c, d, h, w, _arr(C.c_int, list(patch)), _arr(C.c_double, [float(v) for v in matrix.reshape(-1)]),
+                                            _arr(C.c_double, [float(v) for v in offset]), flags, _arr(C.c_float, gain), _arr(C.c_float, bias),
+                                            mapping, L.f32(data), L.f32(target), L.stream()), "ru_augment_patch_affine")
+        if direct:
+            return data, target
+        if noise is None:
+            noise = elastic_noise(int(el["seed"]), patch, case.image.device)
+        return elastic_warp(data, target, elastic_field(noise, sigma, alpha), p["flips"], p["transpose"], p["gain"], p["bias"])
     tail = (_arr(C.c_float, [float(v) for v in case.mean]), _arr(C.c_float, [float(1.0 / v) for v in case.std]),
             c, d, h, w, _arr(C.c_int, [int(v) for v in p["crop_lo"]]), _arr(C.c_int, list(patch)),
             _arr(C.c_double, [float(v) for v in p["scale"]]), flags,
@@ -175,6 +201,166 @@ def augment_patch(case, p, patch_size=None):
         noise = elastic_noise(int(el["seed"]), patch, case.image.device)
     disp = elastic_field(noise, sigma, alpha)
     return elastic_warp(data, target, disp, p["flips"], p["transpose"], p["gain"], p["bias"])
+
+
+# ---------------------------------------------------------------------------------------------------------------- rotation
+# csrc/rotate.hip (`ru_augment_patch_affine`) and its float64 numpy restatement.  Array axes: 0 = D, 1 = H, 2 = W.
+AFFINE_MIN_DET = 1e-6
+
+
+def rotation_matrix(angles):
+    """3 x 3 float64 R = R0(a0) @ R1(a1) @ R2(a2) for angles in radians about the array axes 0 = D, 1 = H, 2 = W.  With c = cos a, s = sin a:
+    R0 = [[1,0,0],[0,c,-s],[0,s,c]], R1 = [[c,0,s],[0,1,0],[-s,0,c]], R2 = [[c,-s,0],[s,c,0],[0,0,1]]."""
+    a = np.asarray(angles, np.float64)
+    if a.shape != (3,):
+        raise ValueError("rotation: angles must be three values (radians about D, H, W), got shape %s" % (a.shape,))
+    if not np.isfinite(a).all():
+        raise ValueError("rotation: angles must be finite, got %r" % (a,))
+    (c0, c1, c2), (s0, s1, s2) = np.cos(a), np.sin(a)
+    r0 = np.array([[1.0, 0.0, 0.0], [0.0, c0, -s0], [0.0, s0, c0]])
+    r1 = np.array([[c1, 0.0, s1], [0.0, 1.0, 0.0], [-s1, 0.0, c1]])
+    r2 = np.array([[c2, -s2, 0.0], [s2, c2, 0.0], [0.0, 0.0, 1.0]])
+    return r0 @ r1 @ r2 + 0.0                            # + 0.0: no negative zeros
+
+
+def _check_affine(matrix, offset):
+    """argument checks of the affine pass: ValueError before any launch; returns (matrix [3,3], offset [3]) float64"""
+    try:
+        m, o = np.asarray(matrix, np.float64), np.asarray(offset, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("rotation: matrix and offset must be numeric arrays")
+    if m.shape != (3, 3):
+        raise ValueError("rotation: matrix must be 3 x 3, got shape %s" % (m.shape,))
+    if o.shape != (3,):
+        raise ValueError("rotation: offset must hold three values, got shape %s" % (o.shape,))
+    if not (np.isfinite(m).all() and np.isfinite(o).all()):
+        raise ValueError("rotation: matrix and offset must be finite")
+    det = float(np.linalg.det(m))
+    if not abs(det) >= AFFINE_MIN_DET:
+        raise ValueError("rotation: the matrix is singular: |det| = %g is below %g (a collapsed patch)" % (abs(det), AFFINE_MIN_DET))
+    return np.ascontiguousarray(m), np.ascontiguousarray(o)
+
+
+def _rotation_transform(rot, crop_lo, scale, patch):
+    """(matrix, offset, mapping code) of a `rotation` entry of `augment_patch` (see there); every argument error is a ValueError"""
+    if not isinstance(rot, dict):
+        raise ValueError("rotation: the entry must be dict(angles=...) or dict(matrix=...[, offset=...]), got %r" % (rot,))
+    unknown = set(rot) - {"angles", "matrix", "offset", "mapping"}
+    if unknown:
+        raise ValueError("rotation: unknown keys %s" % sorted(unknown))
+    mapping = rot.get("mapping") or "default"
+    if mapping not in L.AFFINE_MAPPINGS:
+        raise ValueError("rotation: mapping must be one of %s, got %r" % (sorted(L.AFFINE_MAPPINGS), mapping))
+    if min(patch) < 1 or int(np.prod([int(v) for v in patch], dtype=object)) >= 2 ** 31 - 1:
+        raise ValueError("rotation: the patch extents must be positive and hold fewer than 2^31 - 1 voxels, got %s" % (tuple(patch),))
+    half = (np.array(patch, np.float64) - 1.0) / 2.0
+    lo = np.asarray(crop_lo, np.float64)
+    if lo.shape != (3,) or not np.isfinite(lo).all():
+        raise ValueError("rotation: crop_lo must hold three finite values, got %r" % (crop_lo,))
+    if "angles" in rot:
+        if "matrix" in rot or "offset" in rot:
+            raise ValueError("rotation: give either angles or a matrix (with an optional offset), not both")
+        sc = np.asarray(scale, np.float64)
+        if sc.shape != (3,) or not np.isfinite(sc).all():
+            raise ValueError("rotation: scale must hold three finite values, got %r" % (scale,))
+        matrix = rotation_matrix(rot["angles"]) * sc[None, :]             # R diag(scale)
+        offset = None
+    elif "matrix" in rot:
+        matrix, offset = rot["matrix"], rot.get("offset")
+    else:
+        raise ValueError("rotation: the entry needs angles or a matrix")
+    matrix, _ = _check_affine(matrix, np.zeros(3))
+    if offset is None:
+        offset = (lo + half) - matrix @ half
+    matrix, offset = _check_affine(matrix, offset)
+    return matrix, offset, L.AFFINE_MAPPINGS[mapping]
+
+
+def affine_patch_host(image, label_or_soft, mean, std, patch, matrix, offset, flips=(False, False, False), transpose=False, gain=None, bias=None):
+    """float64 numpy restatement of `ru_augment_patch_affine`, the oracle of the device path: (data [C,Q0,Q1,P2], target [3,Q0,Q1,P2]) float64 from
+    plain arrays -- image [C,D,H,W] raw, label [D,H,W] in {0,1,2,3} or soft [3,D,H,W], mean / std per channel.
+
+    For output index q = (i, j, k) of the patch, before flips and transpose, s = matrix q + offset (per axis ((m0 i + m1 j) + m2 k) + offset) in
+    whole-volume voxel coordinates; f = floor(s), t = s - f; the eight corners f + {0,1}^3 are weighted by products of 1 - t and t and a corner
+    outside the volume contributes 0: scipy.ndimage.affine_transform(volume, matrix, offset, output_shape=patch, order=1, mode='grid-constant',
+    cval=0) of every image channel and of every one-hot class (or soft channel).  A coordinate that is not a number, below -2 or above the extent
+    counts as -2 / the extent (all fill).  Then ((acc - mean) / std) gain + bias, WT = 1 + 2 + 3, TC = 1 + 3, ET = 3, flips, D <-> H transpose."""
+    image = np.asarray(image, np.float64)
+    if image.ndim != 4:
+        raise ValueError("rotation: image must be [C,D,H,W], got shape %s" % (image.shape,))
+    c, dims = image.shape[0], image.shape[1:]
+    other = np.asarray(label_or_soft)
+    if other.shape != tuple(dims) and other.shape != (3,) + tuple(dims):
+        raise ValueError("rotation: label must be [D,H,W] or soft [3,D,H,W] of the image's extents %s, got %s" % (tuple(dims), other.shape))
+    patch = tuple(int(v) for v in patch)
+    if len(patch) != 3 or min(patch) < 1:
+        raise ValueError("rotation: patch must hold three positive extents, got %s" % (patch,))
+    m, o = _check_affine(matrix, offset)
+    mean, std = np.asarray(mean, np.float64).reshape(-1), np.asarray(std, np.float64).reshape(-1)
+    gain = np.ones(c) if gain is None else np.asarray(gain, np.float64).reshape(-1)
+    bias = np.zeros(c) if bias is None else np.asarray(bias, np.float64).reshape(-1)
+    if not (mean.size == std.size == gain.size == bias.size == c):
+        raise ValueError("rotation: mean, std, gain and bias need one value per image channel (%d)" % c)
+    q = np.meshgrid(*[np.arange(n, dtype=np.float64) for n in patch], indexing="ij")
+    idx, wt, inside = [], [], []
+    with np.errstate(over="ignore", invalid="ignore"):
+        for ax in range(3):
+            s = ((m[ax, 0] * q[0] + m[ax, 1] * q[1]) + m[ax, 2] * q[2]) + o[ax]
+            s = np.where(s >= -2.0, s, -2.0)                                   # NaN too
+            s = np.minimum(s, float(dims[ax]))
+            f = np.floor(s)
+            i0 = f.astype(np.int64)
+            idx.append((i0, i0 + 1))
+            wt.append((1.0 - (s - f), s - f))
+            inside.append(((i0 >= 0) & (i0 < dims[ax]), (i0 + 1 >= 0) & (i0 + 1 < dims[ax])))
+    if other.ndim == 3:
+        lab = other.astype(np.int64)
+        chans = np.stack([lab == 1, lab == 2, lab == 3]).astype(np.float64)
+    else:
+        chans = other.astype(np.float64)
+    src = np.concatenate([image, chans])
+    acc = np.zeros((c + 3,) + patch)
+    for qa in range(2):
+        for qb in range(2):
+            for qc in range(2):
+                w = wt[0][qa] * wt[1][qb] * wt[2][qc]
+                ok = inside[0][qa] & inside[1][qb] & inside[2][qc]
+                v = src[:, np.clip(idx[0][qa], 0, dims[0] - 1), np.clip(idx[1][qb], 0, dims[1] - 1), np.clip(idx[2][qc], 0, dims[2] - 1)]
+                acc += w[None] * np.where(ok[None], v, 0.0)
+    sh = (-1, 1, 1, 1)
+    data = ((acc[:c] - mean.reshape(sh)) * (1.0 / std).reshape(sh)) * gain.reshape(sh) + bias.reshape(sh)
+    cw = acc[c:]
+    target = cw if other.ndim == 4 else np.stack([(cw[0] + cw[1]) + cw[2], cw[0] + cw[2], cw[2]])
+
+    def finish(t):
+        for ax, f in enumerate(flips):
+            if f:
+                t = np.flip(t, axis=ax + 1)
+        return np.ascontiguousarray(t.transpose((0, 2, 1, 3)) if transpose else t)
+
+    return finish(data), finish(target)
+
+
+class RotationConfig(object):
+    """Probability and range of `draw_rotation_params`; the defaults are nnU-Net's for 3-D patches: a patch is rotated with probability `p_rotation`,
+    by angles uniform in +-max_angle[axis] (radians) about each of the axes D, H, W."""
+
+    def __init__(self, p_rotation=0.2, max_angle=(np.pi / 6.0, np.pi / 6.0, np.pi / 6.0)):
+        self.p_rotation = float(p_rotation)
+        self.max_angle = tuple(float(v) for v in np.asarray(max_angle, np.float64).reshape(-1))
+        if not 0.0 <= self.p_rotation <= 1.0:
+            raise ValueError("rotation: p_rotation must lie in [0, 1], got %r" % (p_rotation,))
+        if len(self.max_angle) != 3 or not all(np.isfinite(v) and v >= 0.0 for v in self.max_angle):
+            raise ValueError("rotation: max_angle must hold three finite non-negative angles (radians), got %r" % (max_angle,))
+
+
+def draw_rotation_params(rng, config=None):
+    """None, or the `rotation` entry dict(angles=(a0, a1, a2)) of `augment_patch`, drawn from `rng` (a private `random.Random`) ONLY: the global
+    `random` / `numpy.random` streams are not touched.  One draw decides (`p_rotation`); only if it fires, three angles follow in axis order."""
+    cfg = config or RotationConfig()
+    if not rng.random() < cfg.p_rotation:
+        return None
+    return dict(angles=tuple(rng.uniform(-m, m) for m in cfg.max_angle))
 
 
 # ---------------------------------------------------------------------------------------------------------------- elastic deformation
@@ -609,10 +795,13 @@ class SimpleReader(torch.utils.data.Dataset):
     (see DeviceCase); the draws are the same.  `elastic=True` deforms every patch (see augment_patch) with the sigma and alpha the reference
     draws; the field seeds come from a private generator seeded with `elastic_seed`, so the global streams are those of `elastic=False`.
     `intensity=True` (nnU-Net's defaults) or an `IntensityConfig` runs `intensity_augment` on the data tensor of every patch, elastic or not, with
-    parameters drawn from a private `random.Random(intensity_seed)`; targets and the global streams are those of `intensity=False`."""
+    parameters drawn from a private `random.Random(intensity_seed)`; targets and the global streams are those of `intensity=False`.
+    `rotation=True` (nnU-Net's defaults) or a `RotationConfig` rotates a patch with probability `p_rotation` about its own centre (see augment_patch),
+    the angles drawn from a private `random.Random(rotation_seed)`: a patch that draws no rotation takes the path above bit for bit, one that does
+    keeps its crop, scale, flip, transpose, gain and bias draws, and the global streams are those of `rotation=False`."""
 
     def __init__(self, cases, patch_size, images_in_epoch=4000, patches_from_single_image=1, device="cuda", elastic=False, elastic_seed=None,
-                 intensity=False, intensity_seed=None):
+                 intensity=False, intensity_seed=None, rotation=False, rotation_seed=None):
         super(SimpleReader, self).__init__()
         self.cases = list(cases)
         self.patch_size = tuple(patch_size)
@@ -623,6 +812,8 @@ class SimpleReader(torch.utils.data.Dataset):
         self.elastic_rng = random.Random(elastic_seed)
         self.intensity = intensity if isinstance(intensity, IntensityConfig) else (IntensityConfig() if intensity else None)
         self.intensity_rng = random.Random(intensity_seed)
+        self.rotation = rotation if isinstance(rotation, RotationConfig) else (RotationConfig() if rotation else None)
+        self.rotation_rng = random.Random(rotation_seed)
         self.real_length = len(self.cases)
         self.patches_from_current_image = self.patches_from_single_image + 1     # first item loads (the reference's constructor + first item do)
         self.current_image_index = 0
@@ -642,6 +833,10 @@ class SimpleReader(torch.utils.data.Dataset):
         index = index % self.real_length
         self._load(index)
         p = draw_augment_params(self.case.bbox, self.patch_size, int(self.case.image.shape[0]), elastic=self.elastic, elastic_rng=self.elastic_rng)
+        if self.rotation is not None:
+            rot = draw_rotation_params(self.rotation_rng, self.rotation)
+            if rot is not None:
+                p["rotation"] = rot
         data, target = augment_patch(self.case, p)
         if self.intensity is not None:
             data = intensity_augment(data, draw_intensity_params(int(data.shape[0]), self.intensity_rng, self.intensity))

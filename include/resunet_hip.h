@@ -722,6 +722,30 @@ int ru_augment_patch_soft(const float* image, const unsigned char* label, const 
                           int C, int D, int H, int W, const int* crop_lo, const int* patch, const double* scale, int flags,
                           const float* gain, const float* bias, float* data_out, float* target_out, ru_stream_t stream);
 
+/* ---------------------------------------------------------------- rotation augmentation (csrc/rotate.hip).  Opt-in; ru_augment_patch is not touched.
+ * ru_augment_patch_affine: ONE pass from the resident raw case to a rotated / zoomed / sheared training patch, in ru_augment_patch's slot.  Per image
+ *   channel, per one-hot label class (soft = NULL) or per channel of soft [3][D][H][W] (label may then be NULL):
+ *     scipy.ndimage.affine_transform(volume, matrix, offset, output_shape=patch, order=1, mode='grid-constant', cval=0)
+ *   on the WHOLE volume: for output index q = (i, j, k) of the patch, before flips and transpose, the source coordinate is s = matrix q + offset in
+ *   float64 (matrix row-major 3 x 3, whole-volume voxel coordinates; per axis ((m0 i + m1 j) + m2 k) + offset, every operation rounded on its own);
+ *   f = floor(s), t = (float)(s - f); the eight corners f + {0,1}^3 are weighted by products of 1 - t and t.  A corner outside [0,D) x [0,H) x [0,W)
+ *   contributes the fill: raw intensity 0 for the image (it z-scores to what real background gets), label 0, soft 0.  A coordinate that is not a
+ *   number, below -2 or above the axis extent counts as -2 / the extent (both corners outside).  The crop need not lie inside the volume.
+ *   Then ru_augment_patch's tail, expression for expression: ((acc - mean) * inv_std) * gain + bias, the class weights summed to WT / TC / ET, flips
+ *   (flags bit 0/1/2), the D <-> H transpose (bit 3).  data_out [C][Q0][Q1][P2], target_out [3][Q0][Q1][P2], (Q0, Q1) = (P1, P0) when transposed.
+ *   With matrix = diag(1) and an integer offset inside the volume the result is ru_augment_patch's at scale 1, bit for bit.
+ *   mapping: RU_AFFINE_MAP_ROW (256 consecutive output voxels along W per workgroup), RU_AFFINE_MAP_BRICK (a 4 x 2 x 8 brick of output voxels per
+ *   wavefront) or RU_AFFINE_MAP_DEFAULT; the bytes written do not depend on it.  The small parameter arrays are HOST pointers, read at launch.  No
+ *   workspace, no atomics; the call only enqueues (graph-capturable).  Refused (RU_EINVAL, before any launch): a null pointer, C outside 1..8, a
+ *   volume or patch extent <= 0, P0 P1 P2 >= 2^31 - 1, flags outside bits 0..3, an unknown mapping, a matrix or offset entry that is not finite,
+ *   |det(matrix)| < 1e-6 (a collapsed patch). */
+#define RU_AFFINE_MAP_DEFAULT 0
+#define RU_AFFINE_MAP_ROW 1
+#define RU_AFFINE_MAP_BRICK 2
+int ru_augment_patch_affine(const float* image, const unsigned char* label, const float* soft, const float* mean, const float* inv_std,
+                            int C, int D, int H, int W, const int* patch, const double* matrix, const double* offset, int flags,
+                            const float* gain, const float* bias, int mapping, float* data_out, float* target_out, ru_stream_t stream);
+
 /* ---------------------------------------------------------------- elastic deformation of a training patch (dataloader.py:24-48 elastic_transform,
  * the commented-out call sites :177 / :180 and the draws :166-168).  Opt-in; ru_augment_patch is not touched.  All three calls only enqueue.
  * ru_elastic_noise: noise_out [3][P0][P1][P2] float64, uniform in [-1, 1): a counter-based generator (two rounds of splitmix64's finalizer), a pure
