@@ -52,6 +52,15 @@ SIGNATURES = {
     "ru_crit_grad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _sz, _i, _vp, _vp]),
     "ru_adam_amsgrad_step": (_i, [_vp] * 5 + [_sz] + [_f] * 5 + [_i, _vp]),
     "ru_adam_step": (_i, [_vp] * 5 + [_sz] + [_f] * 5 + [_i, _vp]),
+    "ru_gradnorm_slots": (_sz, [_sz]),
+    "ru_gradnorm_workspace_bytes": (_sz, [_sz, _sz]),
+    "ru_gradnorm_partial": (_i, [_vp, _sz, _sz, _vp, _sz, _vp]),
+    "ru_gradnorm_finalize": (_i, [_vp, _sz, _d, _vp, _vp, _vp]),
+    "ru_scale_by": (_i, [_vp, _sz, _vp, _vp]),
+    "ru_sgd_step": (_i, [_vp, _vp, _vp, _sz, _f, _f, _f, _f, _i, _i, _vp, _vp]),
+    "ru_adamw_step": (_i, [_vp] * 5 + [_sz] + [_f] * 5 + [_i, _i, _vp, _vp]),
+    "ru_ema_update": (_i, [_vp, _vp, _sz, _f, _vp]),
+    "ru_swap_f32": (_i, [_vp, _vp, _sz, _vp]),
     "ru_unet_create": (_vp, [_i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i]),
     "ru_unet_destroy": (None, [_vp]),
     "ru_unet_set_precision": (_i, [_vp, _i]),

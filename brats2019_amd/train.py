@@ -80,6 +80,9 @@ class Trainer(object):
         self.fuse_criteria = True          # criterion=[Dice_loss_joint, BCE_Loss] -> one sums pass + one gradient pass (loss.fuse_criterion_list)
         self.log_every = 50                # loss scalars are queued on the device and written every `log_every` steps: no per-step host sync
         self._pending_scalars = []
+        self.clip_grad_norm = None         # a number: clip the global gradient norm to it every step (optim.clip_grad_norm_, no host sync); the norm is logged as misc/grad-norm
+        self.ema_decay = None              # a number in [0, 1]: keep an exponential moving average of the weights (optim.EMA); evaluation and best_model use it
+        self._ema = None
         rank, world = world_info()
         if rank == 0:
             if os.path.exists(self.model_path):
@@ -136,6 +139,14 @@ class Trainer(object):
         if self.state.optimizer_state is not None and not continue_form_pretraining:
             optimizer.load_state_dict(self.state.optimizer_state)
             print("Loaded optimizer state")
+            if hasattr(scheduler, "resume_at"):        # a schedule that is a closed form of the step count (optim.PolyLR) continues where the checkpoint stopped
+                scheduler.resume_at(self.state.global_step)
+        self._ema = None
+        if self.ema_decay is not None:
+            from . import optim as hip_optim
+            self._ema = hip_optim.EMA(self.model, self.ema_decay)
+            if getattr(self.state, "ema_state", None) is not None and not continue_form_pretraining:
+                self._ema.load_state_dict(self.state.ema_state)
         if not self.state.train_metric:
             for m in train_metrics:
                 self.state.train_metric[m.name] = []
@@ -158,11 +169,12 @@ class Trainer(object):
             # main.py:134 passes the CLASS torch.optim.Adam: on the HIP path it is instantiated as brats2019_amd.optim.Adam -- the same
             # torch.optim.Optimizer surface and state_dict() layout (a checkpoint of either resumes under the other, train.py:92-94),
             # with the update as one ru_adam_step launch per contiguous run of the flat parameter buffer.  `hip_optimizer = False` keeps torch's.
+            # torch.optim.AdamW maps to brats2019_amd.optim.AdamW in the same way; brats2019_amd.optim.SGD is handed over as itself.
             made = None
-            if optimizer is torch.optim.Adam and self.hip_optimizer and self.state.cuda:
+            if optimizer in (torch.optim.Adam, torch.optim.AdamW) and self.hip_optimizer and self.state.cuda:
                 from . import optim as hip_optim
                 try:
-                    made = hip_optim.Adam(params=self.model.parameters(), **optimizer_params)
+                    made = (hip_optim.AdamW if optimizer is torch.optim.AdamW else hip_optim.Adam)(params=self.model.parameters(), **optimizer_params)
                 except NotImplementedError:              # options only torch's own Adam takes (fused=, foreach=, ...): keep the caller's class
                     made = None
             optimizer = made if made is not None else optimizer(params=self.model.parameters(), **optimizer_params)
@@ -226,7 +238,15 @@ class Trainer(object):
             with hip_loss.hand_over_to_network():                            # this loop never looks at d(loss)/d(probs): the network's node forms it
                 loss.backward()                                              # train.py:210
             all_reduce_gradients(self.model)                                 # nn.DataParallel's reduce_add (main.py:61); no-op on one rank
+            grad_norm = None
+            if self.clip_grad_norm is not None:
+                # on the reduced bucket, the same bytes on every rank: no further collective.  One of this package's optimizers folds the
+                # device coefficient into its step; any other has its gradients scaled in place.  Neither waits for the host.
+                from . import optim as hip_optim
+                grad_norm = hip_optim.clip_grad_norm_(self.model.parameters(), self.clip_grad_norm, optimizer=optimizer)
             optimizer.step()
+            if self._ema is not None:
+                self._ema.update()
             optimizer.zero_grad()
             if scheduler is not None:
                 scheduler.step()                                             # per iteration (train.py:222-223)
@@ -236,9 +256,11 @@ class Trainer(object):
                 # train.py:226-227 logs lv.item() per step -- a host sync per step; here the values wait on the device and go out in batches
                 for i, lv in enumerate(loss_val):
                     self._pending_scalars.append(("loss/loss-%d" % i, lv.detach(), global_step))
+                if grad_norm is not None:
+                    self._pending_scalars.append(("misc/grad-norm", grad_norm, global_step))
                 for i, group in enumerate(optimizer.param_groups):
                     self.tb_writer.add_scalar("misc/lr-%d" % i, group["lr"], global_step)
-                if len(self._pending_scalars) >= self.log_every * max(1, len(loss_val)):
+                if len(self._pending_scalars) >= self.log_every * max(1, len(loss_val) + int(grad_norm is not None)):
                     self._flush_scalars()
             global_step += 1
         self._flush_scalars()
@@ -247,6 +269,8 @@ class Trainer(object):
             results[m.name].append(m.get())
             _log_metric(self.tb_writer, m, "train/", epoch)
         self.state.optimizer_state = optimizer.state_dict()
+        if self._ema is not None:
+            self.state.ema_state = self._ema.state_dict()                    # (an attribute only then: without the option the pickle is the reference's)
         return global_step
 
     def _flush_scalars(self):
@@ -321,6 +345,15 @@ class Trainer(object):
         return [output.cpu()]
 
     def _evaluate_and_save(self, loader, split_into_tiles, val_metrics, track_metric, results, epoch, comparator):
+        if self._ema is None:
+            return self._evaluate_and_save_current(loader, split_into_tiles, val_metrics, track_metric, results, epoch, comparator)
+        self._ema.swap()                       # evaluate, and save best_model, under the averaged weights
+        try:
+            return self._evaluate_and_save_current(loader, split_into_tiles, val_metrics, track_metric, results, epoch, comparator)
+        finally:
+            self._ema.swap()
+
+    def _evaluate_and_save_current(self, loader, split_into_tiles, val_metrics, track_metric, results, epoch, comparator):
         for m in val_metrics:
             m.reset()
         self.model.eval()

@@ -188,6 +188,42 @@ int ru_adam_step(float* w, const float* g, float* m, float* v, float* vmax_or_nu
                  float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                  ru_stream_t stream);
 
+/* ---------------------------------------------------------------- the rest of the recipe (optim.hip; brats2019_amd.optim)
+ * Streaming kernels over runs of the flat parameter / gradient bucket.  A run may start at any ELEMENT offset: a lane owns 4 consecutive
+ * floats and moves them as 16 bytes, the elements before the first 16-byte boundary and after the last whole quad go one by one (all
+ * of a call's pointers must sit at the same offset from a 16-byte boundary for that, as runs of buffers laid out alike do; otherwise the
+ * whole run goes one float per lane).  Grids are capped and stride.  Nothing waits for the host, and there are no float atomics.
+ *
+ * Global L2 norm of any number of runs, in float64 (squares and sums: 1e20 does not overflow, 1e-30 does not vanish).  A partial call
+ * on n elements writes ru_gradnorm_slots(n) float64 partial sums into ws[first_slot ...], one per workgroup; give every run its own
+ * slots.  ru_gradnorm_workspace_bytes(n_total, n_runs) covers any split of n_total elements into n_runs runs.  The finalize is ONE
+ * workgroup that adds slots [0, n_slots) in a fixed order (a lane adds its contiguous share in index order, lane 0 the 256 shares in
+ * lane order): the same bytes in give the same bytes out.  It writes norm_out[0] = sqrt(sum) (float64, device) and
+ * coef_out[0] = (float) min(1, max_norm / (norm + 1e-6)) (device), torch.nn.utils.clip_grad_norm_'s coefficient with its clamp, formed
+ * in float64.  A non-finite norm gives a non-finite coefficient (error_if_nonfinite=False); there is no skip policy.  */
+size_t ru_gradnorm_slots(size_t n);
+size_t ru_gradnorm_workspace_bytes(size_t n_total, size_t n_runs);
+int ru_gradnorm_partial(const float* g, size_t n, size_t first_slot, double* ws, size_t ws_bytes, ru_stream_t stream);
+int ru_gradnorm_finalize(const double* ws, size_t n_slots, double max_norm, double* norm_out, float* coef_out, ru_stream_t stream);
+/* g[i] = coef[0] * g[i] in place, coef on the device: clipping for optimizers that are not this library's.  */
+int ru_scale_by(float* g, size_t n, const float* coef, ru_stream_t stream);
+/* torch.optim.SGD's update with the device coefficient folded in (coef_or_null == NULL: gc = g):
+ *   gc = coef[0] * g;  d = gc + weight_decay * w;  buf = first ? d : momentum * buf + (1 - dampening) * d;
+ *   u = nesterov ? d + momentum * buf : buf;  w -= lr * u.
+ * momentum == 0 takes no buffer (buf_or_null == NULL, u = d); `first` is torch's "momentum_buffer is None" (buf is written, not read).
+ * coef * g is rounded on its own, so a coefficient of exactly 1 gives the bytes of the call without one.  */
+int ru_sgd_step(float* w, const float* g, float* buf_or_null, size_t n, float lr, float momentum, float dampening, float weight_decay,
+                int nesterov, int first, const float* coef_or_null, ru_stream_t stream);
+/* decoupled != 0: torch.optim.AdamW (w *= 1 - lr * weight_decay first, the gradient is not decayed).  decoupled == 0: the arithmetic of
+ * ru_adam_step, line for line, on coef[0] * g (equal bytes when coef_or_null == NULL).  `step` is 1-based.  */
+int ru_adamw_step(float* w, const float* g, float* m, float* v, float* vmax_or_null, size_t n,
+                  float lr, float beta1, float beta2, float eps, float weight_decay, int decoupled, int step,
+                  const float* coef_or_null, ru_stream_t stream);
+/* ema[i] = fmaf(decay, ema[i], (1 - decay) * w[i]), decay in [0, 1].  */
+int ru_ema_update(float* ema, const float* w, size_t n, float decay, ru_stream_t stream);
+/* exchanges a[0..n) and b[0..n) in place (they must not overlap).  */
+int ru_swap_f32(float* a, float* b, size_t n, ru_stream_t stream);
+
 /* ---------------------------------------------------------------- whole-network engine
  * model.UNet(depth, encoder_layers, decoder_layers, number_of_channels, number_of_outputs) (model.py:309)
  * with block=Residual and 4 input channels (model.py:336).  Parameters live in ONE flat float buffer in

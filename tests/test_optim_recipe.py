@@ -1,0 +1,582 @@
+"""GPU checks of the optimisation recipe (csrc/optim.hip, brats2019_amd/optim.py, Trainer.clip_grad_norm / ema_decay): every kernel at every
+length and alignment with guards, the float64 norm, the update kernels against their float64 restatements, the exact cases, and the whole
+network under SGD-Nesterov + PolyLR + clipping (+ EMA, checkpoint and resume) against torch's own optimizer and clip_grad_norm_."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import resunet_oracle as O
+from brats2019_amd import optim
+
+pytestmark = pytest.mark.gpu
+T = torch.from_numpy
+
+NS = [1, 3, 4, 5, 255, 1027, 4099, (1 << 21) + 4099]         # the last is past one sweep of the 2048-workgroup grid (2048 * 256 lanes * 4 floats = 2^21)
+OFFSETS = [0, 1, 2, 3]
+GUARD = -12345.0
+PAD = 4                                                      # guard elements on either side of a run
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from brats2019_amd import _lib as L
+    L.require_gpu()
+    return L.load()
+
+
+def _stream():
+    from brats2019_amd import _lib as L
+    return L.stream()
+
+
+class Slab:
+    """a run of n floats at element offset `off` from a 16-byte boundary, PAD guard elements before it and PAD + (4 - off) after"""
+
+    def __init__(self, values, off):
+        self.n, self.lo = len(values), PAD + off
+        host = np.full(self.lo + self.n + PAD + 4, GUARD, dtype=np.float32)
+        host[self.lo:self.lo + self.n] = values
+        self.t = T(host).cuda()
+        assert self.t.data_ptr() % 16 == 0
+        self.ptr = C.c_void_p(self.t.data_ptr() + 4 * self.lo)
+
+    def get(self):
+        h = self.t.cpu().numpy()
+        assert np.all(h[:self.lo] == GUARD) and np.all(h[self.lo + self.n:] == GUARD), "a kernel wrote outside its run"
+        return h[self.lo:self.lo + self.n].copy()
+
+
+def _rand(rng, n, scale=1.0, positive=False):
+    v = rng.standard_normal(n).astype(np.float32) * np.float32(scale)
+    return np.abs(v) if positive else v
+
+
+def _gradnorm(lib, slabs, max_norm):
+    """(norm float64, coef float32 as numpy scalars, the device tensors) over the runs of `slabs`"""
+    slots = [int(lib.ru_gradnorm_slots(s.n)) for s in slabs]
+    total = sum(slots)
+    ws = torch.full((total + 2,), -7.0, dtype=torch.float64, device="cuda")
+    out = torch.full((3,), -7.0, dtype=torch.float64, device="cuda")
+    coef = torch.full((3,), -7.0, dtype=torch.float32, device="cuda")
+    first = 0
+    for s, k in zip(slabs, slots):
+        assert lib.ru_gradnorm_partial(s.ptr, s.n, first, C.c_void_p(ws.data_ptr() + 8), total * 8, _stream()) == 0, lib.ru_last_error()
+        first += k
+    assert lib.ru_gradnorm_finalize(C.c_void_p(ws.data_ptr() + 8), total, max_norm, C.c_void_p(out.data_ptr() + 8), C.c_void_p(coef.data_ptr() + 4), _stream()) == 0
+    wsh, oh, ch = ws.cpu().numpy(), out.cpu().numpy(), coef.cpu().numpy()
+    assert wsh[0] == -7.0 and wsh[-1] == -7.0 and oh[0] == oh[2] == -7.0 and ch[0] == ch[2] == -7.0
+    return oh[1], ch[1], (ws, out, coef)
+
+
+def _coef_tensor(value):
+    return torch.tensor([value], dtype=torch.float32, device="cuda")
+
+
+def _rel(got, want, scale):
+    return float(np.max(np.abs(got.astype(np.float64) - want) / scale))
+
+
+def _within(got, want, terms, tol=1e-5):
+    """|got - want| <= tol * (sum of the magnitudes of the terms that were added up): the running bound of a float32 evaluation, which unlike a
+    bound relative to the RESULT holds where the terms cancel.  A step has about ten roundings of 6e-8 each (a third of a per cent of 1e-5 over
+    three steps); an element taken twice, skipped or fed a wrong operand is off by a tenth of the terms or more."""
+    s = sum(np.abs(np.asarray(t, dtype=np.float64)) for t in terms)
+    return bool(np.all(np.abs(got.astype(np.float64) - want) <= tol * s))
+
+
+# ---------------------------------------------------------------------- lengths and alignment, every kernel
+@pytest.mark.parametrize("off", OFFSETS)
+@pytest.mark.parametrize("n", NS)
+def test_every_kernel_at_every_length_and_alignment(lib, n, off):
+    """each kernel on a run of n floats that starts `off` elements past a 16-byte boundary: every element of the run equals the float64
+    restatement to float32 rounding (`_within`), and nothing outside [off, off + n) is written"""
+    rng = np.random.default_rng(1000 * n + off)
+    w0, g0, b0, e0 = _rand(rng, n), _rand(rng, n), _rand(rng, n), _rand(rng, n)
+    v0 = _rand(rng, n, 1.0, positive=True)
+    # norm
+    norm, coef, _ = _gradnorm(lib, [Slab(g0, off)], 0.5)
+    want = np.sqrt(np.sum(g0.astype(np.float64) ** 2))
+    assert abs(norm - want) <= 1e-9 * want
+    assert coef == np.float32(min(1.0, 0.5 / (norm + 1e-6)))
+    c = 0.37
+    cdev = _coef_tensor(c)
+    c = float(np.float32(c))
+    # scale
+    g = Slab(g0, off)
+    assert lib.ru_scale_by(g.ptr, n, C.c_void_p(cdev.data_ptr()), _stream()) == 0
+    assert np.array_equal(g.get(), np.float32(c) * g0)
+    # SGD, Nesterov momentum, later step, with coefficient
+    w, g, b = Slab(w0, off), Slab(g0, off), Slab(b0, off)
+    assert lib.ru_sgd_step(w.ptr, g.ptr, b.ptr, n, 0.1, 0.99, 0.0, 0.01, 1, 0, C.c_void_p(cdev.data_ptr()), _stream()) == 0, lib.ru_last_error()
+    rw, rb = optim.sgd_step_host(w0, g0, b0, np.float32(0.1), np.float32(0.99), 0.0, np.float32(0.01), True, coef=c)
+    assert _within(w.get(), rw, (w0, 0.2 * g0, 0.2 * b0), 1e-6) and _within(b.get(), rb, (b0, g0, w0), 1e-6)
+    assert np.array_equal(g.get(), g0)
+    # AdamW, amsgrad
+    w, g, m, v, vm = Slab(w0, off), Slab(g0, off), Slab(b0, off), Slab(v0, off), Slab(0.5 * v0, off)
+    assert lib.ru_adamw_step(w.ptr, g.ptr, m.ptr, v.ptr, vm.ptr, n, 1e-2, 0.9, 0.99, 1e-8, 0.1, 1, 3, C.c_void_p(cdev.data_ptr()), _stream()) == 0, lib.ru_last_error()
+    f = np.float32
+    rw, rm, rv, rvm = optim.adamw_step_host(w0, g0, b0, v0, 0.5 * v0, f(1e-2), f(0.9), f(0.99), f(1e-8), f(0.1), True, 3, coef=c)
+    per_m = np.abs(rw - w0 * (1.0 - 1e-2 * 0.1)) / np.maximum(np.abs(rm), 1e-300)        # step_size / denom, element by element
+    assert _within(w.get(), rw, (w0, per_m * b0, per_m * g0), 2e-6)
+    assert _within(m.get(), rm, (b0, g0), 1e-6) and _rel(v.get(), rv, rv) < 1e-6 and _rel(vm.get(), rvm, rvm) < 1e-6
+    assert np.array_equal(g.get(), g0)
+    # EMA
+    e, w = Slab(e0, off), Slab(w0, off)
+    assert lib.ru_ema_update(e.ptr, w.ptr, n, 0.9, _stream()) == 0
+    assert _rel(e.get(), optim.ema_host(e0, w0, f(0.9)), np.maximum(np.abs(e0), np.abs(w0))) < 1e-6
+    assert np.array_equal(w.get(), w0)
+    # swap
+    a, b = Slab(w0, off), Slab(g0, off)
+    assert lib.ru_swap_f32(a.ptr, b.ptr, n, _stream()) == 0
+    assert np.array_equal(a.get(), g0) and np.array_equal(b.get(), w0)
+
+
+def test_runs_laid_out_differently_take_the_scalar_path(lib):
+    """pointers at DIFFERENT offsets from a 16-byte boundary cannot share 16-byte lanes: the whole run goes one float per lane, same result"""
+    rng = np.random.default_rng(5)
+    n = 4099
+    w0, g0, b0 = _rand(rng, n), _rand(rng, n), _rand(rng, n)
+    w, g, b = Slab(w0, 1), Slab(g0, 2), Slab(b0, 0)
+    assert lib.ru_sgd_step(w.ptr, g.ptr, b.ptr, n, 0.1, 0.9, 0.0, 0.0, 0, 0, None, _stream()) == 0
+    w2, g2, b2 = Slab(w0, 3), Slab(g0, 3), Slab(b0, 3)
+    assert lib.ru_sgd_step(w2.ptr, g2.ptr, b2.ptr, n, 0.1, 0.9, 0.0, 0.0, 0, 0, None, _stream()) == 0
+    assert np.array_equal(w.get(), w2.get()) and np.array_equal(b.get(), b2.get())
+
+
+# ---------------------------------------------------------------------- the norm
+@pytest.mark.parametrize("scale", [1.0, 1e20, 1e-30])
+def test_norm_is_float64_and_neither_overflows_nor_vanishes(lib, scale):
+    """against numpy float64 at 1e-9 relative: any order of float64 additions of n non-negative terms is within (n - 1) * 2^-53 (5e-10 at the
+    network's 4.5 M floats, 1.1e-11 here), float32 squares would overflow at 1e20 and vanish at 1e-30"""
+    rng = np.random.default_rng(11)
+    g0 = _rand(rng, 100003, scale)
+    norm, coef, _ = _gradnorm(lib, [Slab(g0, 1)], 12.0)
+    want = np.sqrt(np.sum(g0.astype(np.float64) ** 2))
+    assert np.isfinite(norm) and norm > 0 and abs(norm - want) <= 1e-9 * want
+    assert coef == np.float32(min(1.0, 12.0 / (norm + 1e-6)))
+
+
+def test_norm_over_three_unequal_runs_is_reproducible(lib):
+    rng = np.random.default_rng(12)
+    parts = [_rand(rng, n) for n in (4099, 1027, 255)]
+    slabs = [Slab(p, o) for p, o in zip(parts, (3, 0, 2))]
+    norm, coef, dev = _gradnorm(lib, slabs, 1.0)
+    want = np.sqrt(sum(np.sum(p.astype(np.float64) ** 2) for p in parts))
+    assert abs(norm - want) <= 1e-9 * want
+    want_c, got_c = optim.clip_coef_host(parts, 1.0)[1], float(coef)
+    assert want_c < 1.0 and abs(got_c - want_c) <= 1e-7 * want_c
+    norm2, coef2, dev2 = _gradnorm(lib, slabs, 1.0)
+    assert all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in zip(dev, dev2))          # slots, norm and coefficient: identical bytes
+    # max_norm above the norm: the clamp gives exactly 1
+    assert _gradnorm(lib, slabs, 1e6)[1] == np.float32(1.0)
+
+
+def test_nan_gradient_gives_nan_norm_and_coefficient(lib):
+    g0 = _rand(np.random.default_rng(13), 1027)
+    g0[700] = np.nan
+    norm, coef, _ = _gradnorm(lib, [Slab(g0, 2)], 12.0)
+    assert np.isnan(norm) and np.isnan(coef)
+    g0[700] = np.inf
+    norm, coef, _ = _gradnorm(lib, [Slab(g0, 2)], 12.0)
+    assert np.isinf(norm) and coef == 0.0                      # torch: max_norm / (inf + 1e-6) = 0
+
+
+# ---------------------------------------------------------------------- update kernels against the float64 restatements, 3 steps
+# max over elements and steps of |w - restatement| / max(|w before|, |lr u|), measured on the MI355X; the bar is 4 x that (and at most 1e-5)
+MEASURED = {
+    "sgd-plain": 1.232e-06, "sgd-momentum": 4.763e-06, "sgd-dampening": 2.313e-06, "sgd-nesterov": 9.350e-06, "sgd-weight_decay": 4.647e-06,
+    "adamw": 2.453e-06, "adamw-amsgrad": 3.201e-06, "adam-coef": 1.531e-06, "adam-coef-amsgrad": 1.548e-06, "ema": 1.383e-06,
+}
+# (these maxima sit on the few elements of the 70,001 whose terms cancel -- a small weight meeting a small step: relative to the terms that were
+# added up, `_within`, the same runs are inside 1e-6.  With momentum 0.99 the maximum is close to the 1e-5 cap, which then is the bar.)
+SGD_VARIANTS = {"sgd-plain": dict(), "sgd-momentum": dict(momentum=0.9), "sgd-dampening": dict(momentum=0.9, dampening=0.3),
+                "sgd-nesterov": dict(momentum=0.99, nesterov=True), "sgd-weight_decay": dict(momentum=0.9, weight_decay=0.05)}
+N_UPD, OFF_UPD = 70001, 1
+
+
+def _bar(name, err):
+    print("%s: max error against the float64 restatement %.3e" % (name, err))
+    assert err < 1e-5, "a wrong formula, not rounding"
+    assert MEASURED[name] is not None and err <= 4.0 * MEASURED[name], (name, err)
+
+
+@pytest.mark.parametrize("name", sorted(SGD_VARIANTS))
+def test_sgd_kernel_follows_the_float64_restatement(lib, name):
+    """3 consecutive steps from the same float32 inputs; the restatement runs in float64 throughout.  Measured on the MI355X (MEASURED): plain
+    1.23e-6, momentum 4.76e-6, dampening 2.31e-6, nesterov 9.35e-6, weight decay 4.65e-6 of max(|w|, |lr u|); the bar is 4 x that, at most 1e-5."""
+    kw = SGD_VARIANTS[name]
+    f = np.float32
+    mom, damp, wd, nest = kw.get("momentum", 0.0), kw.get("dampening", 0.0), kw.get("weight_decay", 0.0), kw.get("nesterov", False)
+    rng = np.random.default_rng(21)
+    w0 = _rand(rng, N_UPD)
+    w, b = Slab(w0, OFF_UPD), Slab(np.zeros(N_UPD, np.float32), OFF_UPD)
+    rw, rb, err = w0.astype(np.float64), None, 0.0
+    for step in range(3):
+        g0 = _rand(rng, N_UPD)
+        g = Slab(g0, OFF_UPD)
+        assert lib.ru_sgd_step(w.ptr, g.ptr, b.ptr if mom else None, N_UPD, 0.1, mom, damp, wd, int(nest), int(step == 0), None, _stream()) == 0, lib.ru_last_error()
+        before = rw
+        rw, rb = optim.sgd_step_host(rw, g0, rb, f(0.1), f(mom), f(damp), f(wd), nest)
+        err = max(err, _rel(w.get(), rw, np.maximum(np.abs(before), np.abs(rw - before))))
+        if mom:
+            assert _within(b.get(), rb, (rb, g0, before))
+    _bar(name, err)
+
+
+@pytest.mark.parametrize("name", ["adamw", "adamw-amsgrad", "adam-coef", "adam-coef-amsgrad"])
+def test_adamw_kernel_follows_the_float64_restatement(lib, name):
+    """torch.optim.AdamW's arithmetic (decoupled) and ru_adam_step's on coef * g (not decoupled), with and without amsgrad, 3 steps.
+    Measured on the MI355X (MEASURED): AdamW 2.45e-6, with amsgrad 3.20e-6; not decoupled with a coefficient 1.53e-6, with amsgrad 1.55e-6 of
+    max(|w|, |lr u|); the bar is 4 x that, at most 1e-5."""
+    ams, dec = name.endswith("amsgrad"), name.startswith("adamw")
+    f = np.float32
+    rng = np.random.default_rng(22)
+    w0 = _rand(rng, N_UPD)
+    zeros = np.zeros(N_UPD, np.float32)
+    w, m, v, vm = Slab(w0, OFF_UPD), Slab(zeros, OFF_UPD), Slab(zeros, OFF_UPD), Slab(zeros, OFF_UPD)
+    cdev = None if dec else _coef_tensor(0.61)
+    c = None if dec else float(f(0.61))
+    rw, rm, rv, rvm, err = w0.astype(np.float64), zeros.astype(np.float64), zeros.astype(np.float64), (zeros.astype(np.float64) if ams else None), 0.0
+    for step in range(1, 4):
+        g0 = _rand(rng, N_UPD)
+        g = Slab(g0, OFF_UPD)
+        assert lib.ru_adamw_step(w.ptr, g.ptr, m.ptr, v.ptr, vm.ptr if ams else None, N_UPD, 1e-2, 0.9, 0.99, 1e-8, 0.1, int(dec), step,
+                                 None if dec else C.c_void_p(cdev.data_ptr()), _stream()) == 0, lib.ru_last_error()
+        before = rw
+        rw, rm, rv, rvm = optim.adamw_step_host(rw, g0, rm, rv, rvm, f(1e-2), f(0.9), f(0.99), f(1e-8), f(0.1), dec, step, coef=c)
+        err = max(err, _rel(w.get(), rw, np.maximum(np.abs(before), np.abs(rw - before))))
+        g2 = 0.01 * (np.abs(g0.astype(np.float64)) + 0.1 * np.abs(before)) ** 2         # (1 - b2) * (|coef g| + wd |w|)^2: the decayed gradient may cancel
+        assert _within(m.get(), rm, (rm, g0, before)) and _within(v.get(), rv, (rv, g2))
+        if ams:
+            assert _within(vm.get(), rvm, (rvm, g2))
+    _bar(name, err)
+
+
+def test_ema_kernel_follows_the_float64_restatement(lib):
+    """3 consecutive updates towards moving weights.  Measured on the MI355X (MEASURED): 1.38e-6 of max(|ema|, |w|); the bar is 4 x that."""
+    rng = np.random.default_rng(23)
+    e0 = _rand(rng, N_UPD)
+    e, re_, err = Slab(e0, OFF_UPD), e0.astype(np.float64), 0.0
+    for _ in range(3):
+        w0 = _rand(rng, N_UPD)
+        assert lib.ru_ema_update(e.ptr, Slab(w0, OFF_UPD).ptr, N_UPD, 0.9, _stream()) == 0
+        before = re_
+        re_ = optim.ema_host(re_, w0, np.float32(0.9))
+        err = max(err, _rel(e.get(), re_, np.maximum(np.abs(before), np.abs(w0))))
+    _bar("ema", err)
+
+
+@pytest.mark.parametrize("amsgrad", [True, False])
+def test_adamw_not_decoupled_without_coefficient_equals_ru_adam_step_bytes(lib, amsgrad):
+    rng = np.random.default_rng(24)
+    n, off = 4099, 1
+    w0, zeros = _rand(rng, n), np.zeros(n, np.float32)
+    a = [Slab(w0, off), Slab(zeros, off), Slab(zeros, off), Slab(zeros, off)]
+    b = [Slab(w0, off), Slab(zeros, off), Slab(zeros, off), Slab(zeros, off)]
+    for step in range(1, 4):
+        g = Slab(_rand(rng, n, 1e-2 if step == 2 else 1.0), off)
+        assert lib.ru_adam_step(a[0].ptr, g.ptr, a[1].ptr, a[2].ptr, a[3].ptr if amsgrad else None, n, 1e-3, 0.9, 0.999, 1e-8, 1e-6, step, _stream()) == 0
+        assert lib.ru_adamw_step(b[0].ptr, g.ptr, b[1].ptr, b[2].ptr, b[3].ptr if amsgrad else None, n, 1e-3, 0.9, 0.999, 1e-8, 1e-6, 0, step, None, _stream()) == 0
+        for x, y in zip(a, b):
+            assert np.array_equal(x.get().view(np.uint32), y.get().view(np.uint32)), step
+
+
+# ---------------------------------------------------------------------- exact cases
+def test_a_coefficient_of_one_changes_no_byte(lib):
+    """max_norm above the norm: the finalize's coefficient is exactly 1 and a step with it equals the step without it, byte for byte"""
+    rng = np.random.default_rng(31)
+    n, off = 4099, 3
+    w0, g0, b0, v0 = _rand(rng, n), _rand(rng, n), _rand(rng, n), _rand(rng, n, positive=True)
+    _, coef, (_, _, cdev) = _gradnorm(lib, [Slab(g0, off)], 1e9)
+    assert coef == np.float32(1.0)
+    cptr = C.c_void_p(cdev.data_ptr() + 4)
+    outs = []
+    for cp in (None, cptr):
+        w, g, b = Slab(w0, off), Slab(g0, off), Slab(b0, off)
+        assert lib.ru_sgd_step(w.ptr, g.ptr, b.ptr, n, 0.1, 0.99, 0.0, 0.01, 1, 0, cp, _stream()) == 0
+        res = [w.get(), b.get()]
+        for dec in (0, 1):
+            w, g, m, v, vm = Slab(w0, off), Slab(g0, off), Slab(b0, off), Slab(v0, off), Slab(v0, off)
+            assert lib.ru_adamw_step(w.ptr, g.ptr, m.ptr, v.ptr, vm.ptr, n, 1e-2, 0.9, 0.99, 1e-8, 0.1, dec, 2, cp, _stream()) == 0
+            res += [w.get(), m.get(), v.get(), vm.get()]
+        outs.append(res)
+    for x, y in zip(*outs):
+        assert np.array_equal(x.view(np.uint32), y.view(np.uint32))
+
+
+def test_ema_decay_zero_and_one_and_swap_twice(lib):
+    rng = np.random.default_rng(32)
+    n, off = 4099, 2
+    e0, w0 = _rand(rng, n), _rand(rng, n)
+    e, w = Slab(e0, off), Slab(w0, off)
+    assert lib.ru_ema_update(e.ptr, w.ptr, n, 1.0, _stream()) == 0
+    assert np.array_equal(e.get(), e0)
+    assert lib.ru_ema_update(e.ptr, w.ptr, n, 0.0, _stream()) == 0
+    assert np.array_equal(e.get(), w0)
+    a, b = Slab(e0, off), Slab(w0, off)
+    assert lib.ru_swap_f32(a.ptr, b.ptr, n, _stream()) == 0 and lib.ru_swap_f32(a.ptr, b.ptr, n, _stream()) == 0
+    assert np.array_equal(a.get(), e0) and np.array_equal(b.get(), w0)
+
+
+def _net(seed):
+    from brats2019_amd import model as M
+    net = M.UNet(**O.DEFAULT_CFG)
+    net.load_state_dict({k: T(v) for k, v in O.make_params(seed, **O.DEFAULT_CFG).items()})
+    return net.cuda()
+
+
+def test_ema_swap_serves_the_averaged_weights_to_a_frozen_forward():
+    """EMA.swap() must drop the executor's packed weight copies: a forward after it gives the probabilities of a model loaded with the averaged
+    weights, byte for byte, and the swap back restores the first ones"""
+    net = _net(51).eval()
+    x = T(O.make_input(1, 16, 16, 16, seed=52)).cuda()
+    ema = optim.EMA(net, 0.5)
+    w_before = {k: v.detach().clone() for k, v in net.state_dict().items()}
+    gen = torch.Generator(device="cuda").manual_seed(3)
+    with torch.no_grad():
+        for p in net.parameters():
+            p.add_(0.05 * torch.randn(p.shape, generator=gen, device="cuda"))
+    w_after = {k: v.detach().clone() for k, v in net.state_dict().items()}
+    ema.update()
+    assert ema.last_launches == 3                                   # the network's three live runs
+    shadow = ema.state_dict()["shadow"]
+    dead = {k for k, v in net._get_engine().layout.entries.items() if v[2]}
+    for k in shadow:                                                # the never-executed stage is its own average: left out of the update
+        want = w_before[k].cpu().numpy() if k in dead else optim.ema_host(w_before[k].cpu().numpy(), w_after[k].cpu().numpy(), 0.5)
+        np.testing.assert_allclose(shadow[k].cpu().numpy(), want, rtol=1e-6, atol=1e-7)
+    with torch.no_grad():
+        net.freeze_params(True)
+        p_live = net([x])[0].clone()
+        ema.swap()
+        assert not net._get_engine()._frozen                        # the packs of the weights that just left are gone
+        p_avg = net([x])[0].clone()
+        net.freeze_params(True)
+        p_avg_frozen = [net([x])[0].clone() for _ in range(2)]
+        from brats2019_amd import model as M
+        ref = M.UNet(**O.DEFAULT_CFG)
+        ref.load_state_dict({k: (w_after[k] if k in dead else shadow[k]).cpu() for k in shadow})
+        ref = ref.cuda().eval().freeze_params(True)
+        p_ref = ref([x])[0]
+        assert torch.equal(p_avg, p_ref) and all(torch.equal(p, p_ref) for p in p_avg_frozen) and not torch.equal(p_live, p_ref)
+        with pytest.raises(RuntimeError):
+            ema.update()                                            # not while the averaged weights are swapped in
+        ema.swap()
+        assert torch.equal(net([x])[0], p_live)
+    for k, v in net.state_dict().items():
+        assert torch.equal(v, w_after[k])
+    # state_dict round trip into a second EMA
+    other = optim.EMA(net, 0.9)
+    other.load_state_dict(ema.state_dict())
+    assert other.decay == 0.5 and other.num_updates == 1 and all(torch.equal(other.state_dict()["shadow"][k], shadow[k]) for k in shadow)
+
+
+# ---------------------------------------------------------------------- clip_grad_norm_
+def test_clip_grad_norm_without_an_optimizer_of_ours_scales_like_torch():
+    """scattered tensors (one launch each) and two adjacent views (one run): the gradients after ru_scale_by against torch.nn.utils.clip_grad_norm_
+    on copies.  Bar 1e-6 relative: torch forms the norm and the coefficient in float32 (a few 1e-7 over these 1.3e4 terms), then one product."""
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    shapes = [(33, 7), (4099,), (5,), (2, 3, 4)]
+    ps = [torch.nn.Parameter(torch.zeros(s, device="cuda")) for s in shapes]
+    flat = torch.zeros(1027 + 255, device="cuda")
+    ps += [torch.nn.Parameter(flat[:1027]), torch.nn.Parameter(flat[1027:])]
+    gflat = torch.randn(1027 + 255, generator=gen, device="cuda")
+    for p in ps[:4]:
+        p.grad = torch.randn(p.shape, generator=gen, device="cuda")
+    ps[4].grad, ps[5].grad = gflat[:1027], gflat[1027:]
+    ps.append(torch.nn.Parameter(torch.zeros(9, device="cuda")))                        # no gradient: skipped
+    mine = [p.grad.clone() for p in ps[:6]]
+    qs = [torch.nn.Parameter(p.detach().clone()) for p in ps[:6]]
+    for q, g in zip(qs, mine):
+        q.grad = g.clone()
+    g64 = [g.cpu().numpy().astype(np.float64) for g in mine]
+    want = float(torch.nn.utils.clip_grad_norm_(qs, 12.0))
+    norm = optim.clip_grad_norm_(ps, 12.0)
+    assert norm.dtype == torch.float64 and norm.dim() == 0 and norm.is_cuda
+    assert optim.clip_grad_norm_.last_launches == 5 + 1 + 5                             # five runs: norm passes, finalize, scale passes
+    ref_norm, ref_coef = optim.clip_coef_host(g64, 12.0)
+    assert abs(float(norm) - ref_norm) <= 1e-9 * ref_norm and abs(float(norm) - want) <= 1e-6 * want and ref_coef < 1.0
+    for p, q, g in zip(ps[:6], qs, g64):
+        np.testing.assert_allclose(p.grad.cpu().numpy(), q.grad.cpu().numpy(), rtol=1e-6, atol=0)
+        np.testing.assert_allclose(p.grad.cpu().numpy(), ref_coef * g, rtol=2e-7, atol=0)
+
+
+@pytest.mark.parametrize("cls", ["SGD", "Adam", "AdamW"])
+def test_clip_grad_norm_hands_the_coefficient_to_our_optimizer(cls):
+    """the gradients are not rewritten; the next step() folds the coefficient in (Adam through ru_adamw_step(decoupled=0) only then) and clears it;
+    the step equals the float64 restatement on coef * g, and a state_dict written here continues under the torch class"""
+    gen = torch.Generator(device="cuda").manual_seed(8)
+    flat = torch.randn(4099 + 1027, generator=gen, device="cuda")
+    ps = [torch.nn.Parameter(flat[:4099]), torch.nn.Parameter(flat[4099:])]
+    kw = dict(lr=0.05, momentum=0.99, nesterov=True) if cls == "SGD" else dict(lr=1e-2, weight_decay=0.1, amsgrad=True)
+    opt = getattr(optim, cls)(ps, **kw)
+    gflat = torch.randn(4099 + 1027, generator=gen, device="cuda")
+    ps[0].grad, ps[1].grad = gflat[:4099], gflat[4099:]
+    w0, g0 = flat.cpu().numpy(), gflat.cpu().numpy()
+    norm = optim.clip_grad_norm_(ps, 3.0, optimizer=opt)
+    assert optim.clip_grad_norm_.last_launches == 2 and opt._pending_coef is not None
+    assert torch.equal(gflat.cpu(), T(g0))                                               # untouched
+    coef = float(opt._pending_coef.cpu()[0])
+    assert abs(coef - optim.clip_coef_host([g0], 3.0)[1]) <= 1e-7 * coef and coef < 1.0
+    opt.step()
+    assert opt._pending_coef is None and opt.last_launches == 1
+    f = np.float32
+    if cls == "SGD":
+        want, _ = optim.sgd_step_host(w0, g0, None, 0.05, f(0.99), 0.0, 0.0, True, coef=coef)
+        assert set(opt.state[ps[0]]) == {"momentum_buffer"} and opt.state[ps[1]]["momentum_buffer"].data_ptr() == opt.state[ps[0]]["momentum_buffer"].data_ptr() + 4 * 4099
+    else:
+        z = np.zeros_like(w0)
+        want = optim.adamw_step_host(w0, g0, z, z, z, f(1e-2), f(0.9), f(0.999), f(1e-8), f(0.1), cls == "AdamW", 1, coef=coef)[0]
+    got = flat.cpu().numpy()
+    assert _rel(got, want, np.maximum(np.abs(w0), np.abs(want - w0))) < 1e-5
+    # a second step has no coefficient pending: plain update; then the state continues under torch's class
+    opt.step()
+    tcls = dict(SGD=torch.optim.SGD, Adam=torch.optim.Adam, AdamW=torch.optim.AdamW)[cls]
+    qs = [torch.nn.Parameter(p.detach().clone()) for p in ps]
+    topt = tcls(qs, **kw)
+    import copy
+    topt.load_state_dict(copy.deepcopy(opt.state_dict()))
+    for q, p in zip(qs, ps):
+        q.grad = p.grad.clone()
+    opt.step()
+    topt.step()
+    for q, p in zip(qs, ps):
+        np.testing.assert_allclose(p.detach().cpu().numpy(), q.detach().cpu().numpy(), rtol=2e-5, atol=2e-6)
+
+
+# ---------------------------------------------------------------------- the whole network: SGD-Nesterov + PolyLR + clipping (+ EMA)
+SEED, DHW = 61, (32, 32, 32)
+# relative L2 distance of the weights after 3 steps between optim.SGD + optim.clip_grad_norm_ and torch.optim.SGD + torch.nn.utils.clip_grad_norm_,
+# measured on the MI355X; the bar is 4 x that
+MEASURED_NETWORK_REL_L2 = 3.824e-08
+
+
+def _loader(steps):
+    return [([T(O.make_input(1, *DHW, seed=SEED + i))], [T(O.make_target(1, *DHW, seed=SEED + i))]) for i in range(steps)]
+
+
+def _criterion():
+    from brats2019_amd import loss as L
+    return [L.Dice_loss_joint(index=0, priority=1), L.BCE_Loss(index=0, bg_weight=1e-2)]
+
+
+SGD_KW = dict(lr=1e-2, momentum=0.99, nesterov=True)
+POLY_KW = dict(max_steps=6, exponent=0.9)
+
+
+def _weights(net):
+    return torch.cat([p.detach().reshape(-1) for p in net.parameters()]).cpu().numpy()
+
+
+@pytest.fixture(scope="module")
+def first_norm():
+    """the global gradient norm of the first step (float64, optim.clip_grad_norm_ with a bound far above it)"""
+    from brats2019_amd import loss as L
+    net = _net(SEED).train()
+    (data, target), = _loader(1)
+    out = net([data[0].cuda()])
+    loss, _ = L.fuse_criterion_list(_criterion())(out, [target[0].cuda()])
+    with L.hand_over_to_network():
+        loss.backward()
+    norm = optim.clip_grad_norm_(net.parameters(), 1e30)
+    assert optim.clip_grad_norm_.last_launches == 3 + 1 + 3          # the aliased bucket: three live runs
+    ref = np.sqrt(sum(float((p.grad.double() ** 2).sum()) for p in net.parameters() if p.grad is not None))
+    assert abs(float(norm) - ref) <= 1e-9 * ref
+    return float(norm)
+
+
+def _train(tmp_path, name, clip, epochs, steps_per_epoch, ema_decay=None, model="fresh", rewrite=True):
+    from brats2019_amd import train as TR, metrics as MT
+    net = _net(SEED) if model == "fresh" else None
+    tr = TR.Trainer(name=name, models_root=str(tmp_path), model=net, rewrite=rewrite, connect_tb=False)
+    tr.clip_grad_norm, tr.ema_decay = clip, ema_decay
+    scalars = []
+
+    class Rec:
+        def add_scalar(self, tag, val, step):
+            scalars.append((tag, float(val), step))
+    tr.tb_writer = Rec()
+    loader = _loader(steps_per_epoch)
+    tr.train(criterion=_criterion(), optimizer=optim.SGD, optimizer_params=dict(SGD_KW), scheduler=optim.PolyLR, scheduler_params=dict(POLY_KW),
+             training_data_loader=loader, evaluation_data_loader=[loader[0]], split_into_tiles=False, pretrained_weights=None,
+             train_metrics=[MT.Dice(name="Dice")], val_metrics=[MT.Dice(name="Dice")], track_metric="Dice", epoches=epochs,
+             default_val=np.zeros(3), comparator=lambda a, b: True, eval_cpu=False, continue_form_pretraining=False)
+    return tr, scalars
+
+
+def test_network_sgd_nesterov_polylr_clipping_against_torch(tmp_path, first_norm):
+    """Shipped configuration, 32^3, batch 1, 3 steps through Trainer.train with optim.SGD(momentum 0.99, nesterov) + PolyLR + clip_grad_norm at
+    half the first step's norm (so clipping engages), against the same loop with torch.optim.SGD + torch.nn.utils.clip_grad_norm_ on the same HIP
+    network.  Relative L2 of the weights measured on the MI355X: 3.82e-8 (the three steps move the weights by 1.87e-3); the bar is 4 x that."""
+    from brats2019_amd import loss as L
+    clip = 0.5 * first_norm
+    tr, scalars = _train(tmp_path, "ours", clip, 1, 3)
+    w_ours = _weights(tr.model)
+    norms = [v for tag, v, _ in scalars if tag == "misc/grad-norm"]
+    assert len(norms) == 3 and abs(norms[0] - first_norm) <= 1e-6 * first_norm and norms[0] > clip and all(np.isfinite(norms))
+    lrs = [v for tag, v, _ in scalars if tag == "misc/lr-0"]
+    assert lrs == pytest.approx([1e-2 * (1 - s / 6) ** 0.9 for s in (1, 2, 3)], rel=1e-12)             # logged after scheduler.step(), as the loop always did
+    assert isinstance(tr.state.optimizer_state["state"][0]["momentum_buffer"], torch.Tensor) and not hasattr(tr.state, "ema_state")
+    # the loop as written, torch's optimizer and torch's clipping
+    net = _net(SEED).train()
+    w_start = _weights(net)
+    opt = torch.optim.SGD(net.parameters(), **SGD_KW)
+    sch = optim.PolyLR(opt, **POLY_KW)
+    fused = L.fuse_criterion_list(_criterion())
+    opt.zero_grad()
+    ref_norms = []
+    for data, target in _loader(3):
+        out = net([data[0].cuda()])
+        loss, _ = fused(out, [target[0].cuda()])
+        with L.hand_over_to_network():
+            loss.backward()
+        ref_norms.append(float(torch.nn.utils.clip_grad_norm_(net.parameters(), clip)))
+        opt.step()
+        opt.zero_grad()
+        sch.step()
+    w_ref = _weights(net)
+    np.testing.assert_allclose(norms, ref_norms, rtol=1e-3)            # the two runs see the same gradients, up to what their weights differ by
+    rel = float(np.linalg.norm(w_ours.astype(np.float64) - w_ref) / np.linalg.norm(w_ref.astype(np.float64)))
+    moved = float(np.linalg.norm(w_ref.astype(np.float64) - w_start) / np.linalg.norm(w_start.astype(np.float64)))
+    print("whole network, 3 steps: relative L2 ours vs torch %.3e (the steps moved the weights by %.3e)" % (rel, moved))
+    assert moved > 1e-4 and rel < 1e-2 * moved
+    assert MEASURED_NETWORK_REL_L2 is not None and rel <= 4.0 * MEASURED_NETWORK_REL_L2, rel
+
+
+def test_network_with_ema_saves_averaged_best_model_and_resumes_bit_identically(tmp_path, first_norm):
+    """the same recipe with ema_decay = 0.9 over 3 epochs of one step: best_model holds the averaged weights, TrainingState carries ema_state, and
+    a new Trainer resuming from last_model after the first epoch reaches the weights, momentum buffers and averages of the uninterrupted run bit for bit"""
+    clip = 0.5 * first_norm
+    full, _ = _train(tmp_path, "full", clip, 3, 1, ema_decay=0.9)
+    w_full = _weights(full.model)
+    half, _ = _train(tmp_path, "half", clip, 1, 1, ema_decay=0.9)
+    w_half = _weights(half.model)
+    res, _ = _train(tmp_path, "half", clip, 2, 1, ema_decay=0.9, model=None, rewrite=False)
+    assert res.resume_training and res.state.global_step == 3
+    w_res = _weights(res.model)
+    assert np.abs(w_half - w_full).max() > 1e-6
+    assert np.array_equal(w_res.view(np.uint32), w_full.view(np.uint32))
+    sf, sr = full.state.ema_state, res.state.ema_state
+    assert sf["num_updates"] == 3 and sf["decay"] == 0.9
+    assert all(torch.equal(sf["shadow"][k], sr["shadow"][k]) for k in sf["shadow"])
+    bf, br = full.state.optimizer_state["state"], res.state.optimizer_state["state"]
+    assert all(torch.equal(bf[k]["momentum_buffer"], br[k]["momentum_buffer"]) for k in bf)
+    # best_model (the comparator accepts every epoch, so it is the last epoch's) holds the averaged weights; last_model the live ones
+    best = torch.load(full._ckpt("best_model"), map_location="cpu", weights_only=False)
+    last = torch.load(full._ckpt("last_model"), map_location="cpu", weights_only=False)
+    sd_best, sd_last = best["model"].state_dict(), last["model"].state_dict()
+    live = dict(full.model.state_dict())
+    dead = {k for k, v in full.model._get_engine().layout.entries.items() if v[2]}
+    differ = 0
+    for k in sd_best:
+        assert torch.equal(sd_best[k], sf["shadow"][k].cpu()) and torch.equal(sd_last[k], live[k].cpu()), k
+        differ += int(not torch.equal(sd_best[k], sd_last[k]))
+        assert k not in dead or torch.equal(sd_best[k], sd_last[k])
+    assert differ >= len(sd_best) - len(dead) - 2 and hasattr(last["state"], "ema_state")
+    # the averages are what the float64 restatement gives from the three live weight sets: w1, w2 are not kept, so check the closed form on one
+    # parameter through the recorded checkpoints instead: ema_3 = 0.9 * ema_2 + 0.1 * w_3 with ema_2 from the epoch-1 checkpoint's state
+    e2 = torch.load(full._ckpt("_epoch_1"), map_location="cpu", weights_only=False)["state"].ema_state["shadow"]
+    k = "conv_output.weight"
+    want = optim.ema_host(e2[k].cpu().numpy(), live[k].cpu().numpy(), np.float32(0.9))
+    np.testing.assert_allclose(sf["shadow"][k].cpu().numpy(), want, rtol=1e-6, atol=1e-8)
