@@ -50,6 +50,13 @@ SIGNATURES = {
     "ru_crit_reduce": (_i, [_vp, _i, _i, _vp, _vp]),
     "ru_crit_eval": (_i, [_vp, _vp, _i, _i, _d, _d, _vp, _i, _vp, _vp, _vp]),
     "ru_crit_grad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _sz, _i, _vp, _vp]),
+    "ru_focal_workspace_bytes": (_sz, [_sz]),
+    "ru_focal_sum": (_i, [_vp, _vp, _sz, _f, _f, _f, _vp, _vp, _sz, _vp]),
+    "ru_focal_grad": (_i, [_vp, _vp, _sz, _f, _f, _f, _d, _vp, _vp, _vp]),
+    "ru_tversky_eval": (_i, [_vp, _i, _i, _d, _d, _d, _d, _d, _vp, _vp, _vp]),
+    "ru_topk_workspace_bytes": (_sz, [_sz]),
+    "ru_topk_select": (_i, [_vp, _vp, _sz, C.c_ulonglong, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ru_topk_grad": (_i, [_vp, _vp, _vp, _vp, _sz, C.c_ulonglong, _f, _d, _vp, _vp, _vp]),
     "ru_adam_amsgrad_step": (_i, [_vp] * 5 + [_sz] + [_f] * 5 + [_i, _vp]),
     "ru_adam_step": (_i, [_vp] * 5 + [_sz] + [_f] * 5 + [_i, _vp]),
     "ru_gradnorm_slots": (_sz, [_sz]),

@@ -13,6 +13,9 @@ each phase; the separate modules stay available so `criterion=[Dice_loss_joint()
 The reference's other criteria on the same output -- MSE_Loss, CE_Loss, Dice1D, GDL_joint, sens_loss_joint, Dice_loss_separate
 (loss.py:15-195) -- and lists of any of them go through the criterion-list kernels (csrc/criteria.hip): one moments pass, one
 all-reduce of [7C+1] float64 totals, one evaluate launch, one gradient pass.
+
+Beyond the reference: FocalLoss, TverskyLoss (focal-Tversky with gamma = 4/3) and TopKLoss (csrc/hardcrit.hip; definitions in
+INTEGRATION.md), each its own autograd function, with float64 host restatements focal_host, tversky_host and topk_host.
 """
 from __future__ import annotations
 
@@ -332,3 +335,217 @@ class Dice_loss_separate(_TermLoss):
 
 
 _TERM_CLASSES = (Dice_loss_joint, BCE_Loss, MSE_Loss, CE_Loss, Dice1D, GDL_joint, sens_loss_joint, Dice_loss_separate)
+
+
+# ------------------------------------------------------------------ focal, Tversky, top-k (csrc/hardcrit.hip)
+# Not in the reference's loss.py: the criteria people train with against lesion-wise scoring.  Each is its own autograd function that
+# always writes d(loss)/d(pred), as _TermLoss does; none is in _TERM_CLASSES, so a list that contains one is evaluated as written.
+class _FocalFn(torch.autograd.Function):
+    """One sum pass, one all-reduce of the float64 sum, and in backward one gradient pass."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, gamma, a1, a0w, group):
+        total = ops.focal_sum(pred, gt, gamma, a1, a0w)
+        world = _all_reduce_sums(total, group)
+        count = float(pred.numel()) * world
+        ctx.save_for_backward(pred, gt)
+        ctx.cfg = (gamma, a1, a0w, count)
+        return (total[0] / count).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, gout):
+        pred, gt = ctx.saved_tensors
+        gamma, a1, a0w, count = ctx.cfg
+        return ops.focal_grad(pred, gt, gamma, a1, a0w, count, gout).to(pred.dtype), None, None, None, None, None
+
+
+class _TverskyFn(torch.autograd.Function):
+    """The moments pass of the criterion lists (no log moments), its reduce and all-reduce, one evaluate launch, and in backward one
+    ru_crit_grad launch with the coefficients the evaluate wrote."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, alpha, beta, gamma, smooth, priority, group):
+        moments = ops.crit_moments(pred, gt, _lib.CRIT_MASK_ALL & ~_lib.CRIT_MASK_LOGS)
+        totals = ops.crit_reduce(moments)
+        _all_reduce_sums(totals, group)
+        value, coef = ops.tversky_eval(totals, int(pred.shape[0]), int(pred.shape[1]), alpha, beta, gamma, smooth, priority)
+        ctx.save_for_backward(pred, gt, coef)
+        return value[0].to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, gout):
+        pred, gt, coef = ctx.saved_tensors
+        return ops.crit_grad(pred, gt, coef, gout, False).to(pred.dtype), None, None, None, None, None, None, None
+
+
+def _topk_count(numel, k):
+    """nnU-Net's rule: int(numel * k / 100), at least 1"""
+    return max(1, int(numel * k / 100))
+
+
+class _TopKFn(torch.autograd.Function):
+    """An exact selection within this rank's shard (ru_topk_select), one all-reduce of the float64 value, and in backward one gradient
+    pass over the stored keys."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, k, bg_weight, group):
+        K = _topk_count(pred.numel(), k)
+        out, state, keys = ops.topk_select(pred, gt, K, bg_weight)
+        value = out[:1].clone()
+        world = _all_reduce_sums(value, group)
+        ctx.save_for_backward(pred, gt, keys, state)
+        ctx.cfg = (K, bg_weight, world)
+        return (value[0] / world).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, gout):
+        pred, gt, keys, state = ctx.saved_tensors
+        K, bg_weight, world = ctx.cfg
+        return ops.topk_grad(pred, gt, keys, state, K, bg_weight, world, gout).to(pred.dtype), None, None, None, None
+
+
+class FocalLoss(_LossBase):
+    """mean of -(a1 g (1-p)^gamma log(p+1e-6) + a0 bg_weight (1-g) p^gamma log((1+1e-6)-p)); a1 = alpha, a0 = 1 - alpha when alpha is given,
+    else both 1.  gamma = 0, alpha = None is BCE_Loss.  0 < gamma < 1 is refused: its gradient is infinite at p = 0 or 1, which a
+    saturated sigmoid reaches.  Under data parallelism the mean runs over the global batch."""
+
+    def __init__(self, index=0, gamma=2.0, alpha=None, bg_weight=1):
+        super().__init__()
+        _check_focal(gamma, alpha, bg_weight)
+        self.index, self.gamma, self.alpha, self.bg_weight = index, gamma, alpha, bg_weight
+
+    def forward(self, x, y):
+        assert x[self.index].shape == y[self.index].shape
+        a1, a0 = (1.0, 1.0) if self.alpha is None else (float(self.alpha), 1.0 - float(self.alpha))
+        return _FocalFn.apply(x[self.index], y[self.index], float(self.gamma), a1, a0 * float(self.bg_weight), self.data_parallel)
+
+
+class TverskyLoss(_LossBase):
+    """priority * mean_c (1 - TI_c)^(1/gamma), TI_c = (TP + s) / (TP + alpha FP + beta FN + s) with TP = sum pg, FP = sum p - TP,
+    FN = sum g - TP over batch and space jointly, as Dice_loss_joint sums.  gamma = 4/3 is the focal-Tversky loss.  Under data
+    parallelism the sums run over the global batch."""
+
+    def __init__(self, index=0, alpha=0.3, beta=0.7, gamma=1.0, smooth=1.0, priority=1):
+        super().__init__()
+        _check_tversky(alpha, beta, gamma, smooth)
+        self.index, self.alpha, self.beta, self.gamma, self.smooth, self.priority = index, alpha, beta, gamma, smooth, priority
+
+    def forward(self, x, y):
+        assert x[self.index].shape == y[self.index].shape
+        return _TverskyFn.apply(x[self.index], y[self.index], float(self.alpha), float(self.beta), float(self.gamma), float(self.smooth),
+                                float(self.priority), self.data_parallel)
+
+
+class TopKLoss(_LossBase):
+    """The mean of the K = max(1, int(numel * k / 100)) largest per-element BCE values -(g log(p+1e-6) + bg_weight (1-g) log((1+1e-6)-p)):
+    nnU-Net's top-k rule on the region BCE.  The selection is exact and stays on the device; elements that tie at the threshold share
+    the remaining weight equally.  Under data parallelism each rank selects within its own shard and the value is the mean over ranks."""
+
+    def __init__(self, index=0, k=10.0, bg_weight=1):
+        super().__init__()
+        _check_topk(k, bg_weight)
+        self.index, self.k, self.bg_weight = index, k, bg_weight
+
+    def forward(self, x, y):
+        assert x[self.index].shape == y[self.index].shape
+        return _TopKFn.apply(x[self.index], y[self.index], float(self.k), float(self.bg_weight), self.data_parallel)
+
+
+def _check_focal(gamma, alpha, bg_weight):
+    if not (gamma == 0 or gamma >= 1):
+        raise ValueError("FocalLoss: gamma must be 0 or at least 1 (0 < gamma < 1 has an infinite gradient at p = 0 or 1), got %r" % (gamma,))
+    if alpha is not None and not 0 <= alpha <= 1:
+        raise ValueError("FocalLoss: alpha must lie in [0, 1], got %r" % (alpha,))
+    if not bg_weight >= 0:
+        raise ValueError("FocalLoss: bg_weight must not be negative, got %r" % (bg_weight,))
+
+
+def _check_tversky(alpha, beta, gamma, smooth):
+    if not (alpha >= 0 and beta >= 0):
+        raise ValueError("TverskyLoss: alpha and beta must not be negative, got %r, %r" % (alpha, beta))
+    if not gamma >= 1:
+        raise ValueError("TverskyLoss: gamma must be at least 1, got %r" % (gamma,))
+    if not smooth > 0:
+        raise ValueError("TverskyLoss: smooth must be positive, got %r" % (smooth,))
+
+
+def _check_topk(k, bg_weight):
+    if not 0 < k <= 100:
+        raise ValueError("TopKLoss: k is a percentage in (0, 100], got %r" % (k,))
+    if not bg_weight >= 0:
+        raise ValueError("TopKLoss: bg_weight must not be negative, got %r" % (bg_weight,))
+
+
+# ------------------------------------------------------------------ float64 host restatements (numpy only; nothing shared with the device path)
+def _host_operands(p, g):
+    """p, g as float64 and the two log arguments as BCE_Loss forms them: p + 1e-6 and (1 + 1e-6) - p in float32"""
+    import numpy as np
+    p32 = np.ascontiguousarray(np.asarray(p, dtype=np.float32))
+    pe = (p32 + np.float32(1e-6)).astype(np.float64)
+    qe = (np.float32(1.0 + 1e-6) - p32).astype(np.float64)
+    return p32.astype(np.float64), np.asarray(g, dtype=np.float64), pe, qe
+
+
+def focal_host(p, g, gamma=2.0, alpha=None, bg_weight=1):
+    """FocalLoss in float64 -> (value, d value / d p)."""
+    import numpy as np
+    _check_focal(gamma, alpha, bg_weight)
+    pd, gd, pe, qe = _host_operands(p, g)
+    a1, a0 = (1.0, 1.0) if alpha is None else (float(alpha), 1.0 - float(alpha))
+    a0 *= float(bg_weight)
+    lp, lq, om = np.log(pe), np.log(qe), 1.0 - pd
+    if gamma == 0:
+        f = -(a1 * gd * lp + a0 * (1.0 - gd) * lq)
+        df = -a1 * gd / pe + a0 * (1.0 - gd) / qe
+    else:
+        f = -(a1 * gd * om ** gamma * lp + a0 * (1.0 - gd) * pd ** gamma * lq)
+        df = (-a1 * gd * (om ** gamma / pe - gamma * om ** (gamma - 1.0) * lp)
+              - a0 * (1.0 - gd) * (gamma * pd ** (gamma - 1.0) * lq - pd ** gamma / qe))
+    return float(f.mean()), df / f.size
+
+
+def tversky_host(p, g, alpha=0.3, beta=0.7, gamma=1.0, smooth=1.0, priority=1):
+    """TverskyLoss in float64 on [N, C, ...] arrays -> (value, d value / d p)."""
+    import numpy as np
+    _check_tversky(alpha, beta, gamma, smooth)
+    pd, gd = np.asarray(p, dtype=np.float32).astype(np.float64), np.asarray(g, dtype=np.float64)
+    C = pd.shape[1]
+    axes = (0,) + tuple(range(2, pd.ndim))
+    shape = (1, C) + (1,) * (pd.ndim - 2)
+    tp = (pd * gd).sum(axis=axes)
+    fp, fn = pd.sum(axis=axes) - tp, gd.sum(axis=axes) - tp
+    den = tp + alpha * fp + beta * fn + smooth
+    u = 1.0 - (tp + smooth) / den
+    value = priority * np.mean(u ** (1.0 / gamma))
+    o = -priority / C * (1.0 / gamma) * u ** (1.0 / gamma - 1.0)
+    a = o * (den - (tp + smooth) * (1.0 - alpha - beta)) / den ** 2
+    c = -o * alpha * (tp + smooth) / den ** 2
+    return float(value), a.reshape(shape) * gd + c.reshape(shape)
+
+
+def topk_host_threshold(p, g, k=10.0, bg_weight=1):
+    """(l, K, t, n_gt, n_eq) of TopKLoss in float64: the per-element values, the count, the K-th largest value (NaN ranks above all, as in
+    torch.topk), how many lie above it and how many equal it."""
+    import numpy as np
+    _check_topk(k, bg_weight)
+    pd, gd, pe, qe = _host_operands(p, g)
+    l = -(gd * np.log(pe) + float(bg_weight) * (1.0 - gd) * np.log(qe)) + 0.0
+    K = _topk_count(l.size, k)
+    flat = l.reshape(-1)
+    t = float(np.partition(flat, flat.size - K)[flat.size - K])          # numpy orders NaN last, that is highest
+    nans = int(np.isnan(flat).sum())
+    if np.isnan(t):
+        return l, K, t, 0, nans
+    return l, K, t, int((flat > t).sum()) + nans, int((flat == t).sum())
+
+
+def topk_host(p, g, k=10.0, bg_weight=1):
+    """TopKLoss in float64 -> (value, d value / d p); ties at the threshold share the remaining weight equally."""
+    import numpy as np
+    l, K, t, n_gt, n_eq = topk_host_threshold(p, g, k, bg_weight)
+    pd, gd, pe, qe = _host_operands(p, g)
+    dl = float(bg_weight) * (1.0 - gd) / qe - gd / pe
+    above = (l > t) | np.isnan(l)
+    value = (l[above].sum() + (K - n_gt) * t) / K
+    w = np.where(above, 1.0 / K, np.where(l == t, (K - n_gt) / (max(n_eq, 1) * K), 0.0))
+    return float(value), dl * w

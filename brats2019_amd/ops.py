@@ -237,6 +237,70 @@ def crit_grad(p, g, coef, scale=None, with_logs=True):
     return dp
 
 
+def _pair(p, g):
+    p, g = _prep(p), _prep(g)
+    if p.shape != g.shape:
+        raise AssertionError("prediction/target shape mismatch")
+    return p, g
+
+
+def focal_sum(p, g, gamma, a1, a0w):
+    """Focal loss, pass 1 (csrc/hardcrit.hip): float64 device tensor [1] = the sum over THIS shard of
+    -(a1 g (1-p)^gamma log(p+1e-6) + a0w (1-g) p^gamma log((1+1e-6)-p)); the loss is the (all-reduced) sum over the global count."""
+    p, g = _pair(p, g)
+    lib = L.load()
+    out = torch.empty(1, dtype=torch.float64, device=p.device)
+    ws = L.workspace(lib.ru_focal_workspace_bytes(p.numel()), p.device)
+    L.check(lib.ru_focal_sum(L.f32(p), L.f32(g), p.numel(), float(gamma), float(a1), float(a0w), L.ptr(out), L.ptr(ws), ws.numel(), L.stream()),
+            "ru_focal_sum")
+    return out
+
+
+def focal_grad(p, g, gamma, a1, a0w, count, scale=None):
+    """Focal loss, pass 2: dp = df/dp / count, times `scale` (a float32 device scalar, autograd's incoming gradient) when given."""
+    p, g = _pair(p, g)
+    dp = torch.empty_like(p)
+    sc = None if scale is None else scale.detach().to(torch.float32).contiguous()
+    L.check(L.load().ru_focal_grad(L.f32(p), L.f32(g), p.numel(), float(gamma), float(a1), float(a0w), float(count), L.ptr(sc, True), L.f32(dp),
+                                   L.stream()), "ru_focal_grad")
+    return dp
+
+
+def tversky_eval(totals, n, c, alpha, beta, gamma, smooth, priority):
+    """From crit_reduce's (all-reduced) totals -> (value float64 [1], coef float32 [n, c, 5] for crit_grad(..., with_logs=False))."""
+    value = torch.empty(1, dtype=torch.float64, device=totals.device)
+    coef = torch.empty((n, c, 5), dtype=torch.float32, device=totals.device)
+    L.check(L.load().ru_tversky_eval(L.ptr(totals), int(n), int(c), float(alpha), float(beta), float(gamma), float(smooth), float(priority),
+                                     L.ptr(value), L.ptr(coef), L.stream()), "ru_tversky_eval")
+    return value, coef
+
+
+def topk_select(p, g, K, bg_weight=1.0):
+    """The K largest per-element BCE values l of THIS shard, exactly (radix select on the device, no host sync) ->
+    (out float64 [2] = (their mean, the threshold t), state int64 [4] = (key of t, K - n_gt, n_gt, n_eq), keys int32 [numel]: l stored
+    once as order-preserving keys, which topk_grad reads back)."""
+    p, g = _pair(p, g)
+    lib = L.load()
+    n = p.numel()
+    keys = torch.empty(n, dtype=torch.int32, device=p.device)
+    state = torch.empty(4, dtype=torch.int64, device=p.device)
+    out = torch.empty(2, dtype=torch.float64, device=p.device)
+    ws = L.workspace(lib.ru_topk_workspace_bytes(n), p.device)
+    L.check(lib.ru_topk_select(L.f32(p), L.f32(g), n, int(K), float(bg_weight), L.ptr(keys), L.ptr(state), L.ptr(out), L.ptr(ws), ws.numel(),
+                               L.stream()), "ru_topk_select")
+    return out, state, keys
+
+
+def topk_grad(p, g, keys, state, K, bg_weight=1.0, world=1, scale=None):
+    """d(mean of the K largest l)/dp / world: dl/dp / K above the threshold, dl/dp (K - n_gt) / (n_eq K) at it, 0 below; times `scale`."""
+    p, g = _pair(p, g)
+    dp = torch.empty_like(p)
+    sc = None if scale is None else scale.detach().to(torch.float32).contiguous()
+    L.check(L.load().ru_topk_grad(L.f32(p), L.f32(g), L.ptr(keys), L.ptr(state), p.numel(), int(K), float(bg_weight), float(world),
+                                  L.ptr(sc, True), L.f32(dp), L.stream()), "ru_topk_grad")
+    return dp
+
+
 def adam_amsgrad_step(w, g, m, v, vmax, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
     """torch.optim.Adam(amsgrad=True) update on flat float32 buffers (main.py:133-137)."""
     L.check(L.load().ru_adam_amsgrad_step(L.f32(w), L.f32(g), L.f32(m), L.f32(v), L.f32(vmax), w.numel(), lr, betas[0], betas[1],

@@ -176,6 +176,36 @@ int ru_crit_eval(const double* totals, const double* moments, int N, int C, doub
 int ru_crit_grad(const float* p, const float* g, const float* coef, const float* scale, int N, int C, size_t V, int with_logs,
                  float* dp, ru_stream_t stream);
 
+/* ---------------------------------------------------------------- criteria for hard voxels and small regions (csrc/hardcrit.hip)
+ * Beside the reference's list: focal loss, Tversky / focal-Tversky and top-k cross entropy on the same float32 probabilities p and targets
+ * g in [0, 1] (soft labels allowed), n = N*C*V elements taken flat.  p + 1e-6 and (1 + 1e-6) - p are float32 expressions, as in BCE_Loss.
+ * No float atomics, no host synchronisation; two calls give identical bytes.
+ *   ru_focal_sum    : *sum_out (float64) = sum over this shard of f = -(a1 g (1-p)^gamma log(p+1e-6) + a0w (1-g) p^gamma log((1+1e-6)-p)),
+ *                     a0w = a0 * bg_weight.  gamma == 0 or gamma >= 1.  One streaming pass, one float64 partial per workgroup, added in a
+ *                     fixed order.  The loss is the (all-reduced) sum / count.  ws: ru_focal_workspace_bytes(n).
+ *   ru_focal_grad   : dp = df/dp / count * (*scale when scale != NULL; a float32 DEVICE scalar); count = n * world.
+ *   ru_tversky_eval : from ru_crit_reduce's (all-reduced) totals: *value = priority * mean_c (1 - TI_c)^(1/gamma), TI_c = (TP + s) /
+ *                     (TP + alpha FP + beta FN + s), TP = sum pg, FP = sum p - TP, FN = sum g - TP over batch and space; coef[N*C*5] in
+ *                     ru_crit_grad's layout (a and c non-zero): the backward is ru_crit_grad(..., with_logs = 0).
+ *   ru_topk_select  : the K largest l = -(g log(p+1e-6) + bg_weight (1-g) log((1+1e-6)-p)) of this shard, exactly.  l is formed once and
+ *                     stored in keys[n] as a 32-bit key in l's order (-0 as +0, NaN above all); the K-th largest key is found by a radix
+ *                     select of 11 / 11 / 10 bits (integer histograms).  out2[0] = (sum of l > t + (K - n_gt) t) / K, out2[1] = t;
+ *                     state[4] = {the key of t, K - n_gt, n_gt, n_eq}.  n < 2^32.  ws: ru_topk_workspace_bytes(n).
+ *   ru_topk_grad    : dp = dl/dp / (K * world) where l > t, dl/dp (K - n_gt) / (n_eq K world) where l == t, else 0, times *scale; reads
+ *                     the keys and the state ru_topk_select left, so both see the same bits of l. */
+size_t ru_focal_workspace_bytes(size_t n);
+int ru_focal_sum(const float* p, const float* g, size_t n, float gamma, float a1, float a0w, double* sum_out, void* ws, size_t ws_bytes,
+                 ru_stream_t stream);
+int ru_focal_grad(const float* p, const float* g, size_t n, float gamma, float a1, float a0w, double count, const float* scale, float* dp,
+                  ru_stream_t stream);
+int ru_tversky_eval(const double* totals, int N, int C, double alpha, double beta, double gamma, double smooth, double priority,
+                    double* value, float* coef, ru_stream_t stream);
+size_t ru_topk_workspace_bytes(size_t n);
+int ru_topk_select(const float* p, const float* g, size_t n, unsigned long long K, float bg_weight, unsigned* keys, unsigned long long* state,
+                   double* out2, void* ws, size_t ws_bytes, ru_stream_t stream);
+int ru_topk_grad(const float* p, const float* g, const unsigned* keys, const unsigned long long* state, size_t n, unsigned long long K,
+                 float bg_weight, double world, const float* scale, float* dp, ru_stream_t stream);
+
 /* ---------------------------------------------------------------- optimizer (main.py:133-142)
  * torch.optim.Adam(amsgrad=True) with L2 weight decay added to the gradient; `step` is 1-based.  */
 int ru_adam_amsgrad_step(float* w, const float* g, float* m, float* v, float* vmax, size_t n,
