@@ -57,6 +57,13 @@ SIGNATURES = {
     "ru_topk_workspace_bytes": (_sz, [_sz]),
     "ru_topk_select": (_i, [_vp, _vp, _sz, C.c_ulonglong, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ru_topk_grad": (_i, [_vp, _vp, _vp, _vp, _sz, C.c_ulonglong, _f, _d, _vp, _vp, _vp]),
+    "ru_signed_sqdist_workspace_bytes": (_sz, [_i] * 4),
+    "ru_signed_sqdist": (_i, [_vp] + [_i] * 4 + [_vp, _vp, _sz, _vp]),
+    "ru_boundary_workspace_bytes": (_sz, [_sz]),
+    "ru_boundary_sum": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "ru_boundary_grad": (_i, [_vp, _sz, _f, _vp, _vp, _vp]),
+    "ru_hddt_sum": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _vp, _vp, _sz, _vp]),
+    "ru_hddt_grad": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _vp, _vp, _vp]),
     "ru_adam_amsgrad_step": (_i, [_vp] * 5 + [_sz] + [_f] * 5 + [_i, _vp]),
     "ru_adam_step": (_i, [_vp] * 5 + [_sz] + [_f] * 5 + [_i, _vp]),
     "ru_gradnorm_slots": (_sz, [_sz]),

@@ -12,11 +12,12 @@
 //            into float64 slots, topk_final_kernel adds them in index order; topk_grad_kernel reads the same stored keys, so every pass
 //            sees the same bits of l.
 //
-// All passes are flat streaming work over n = N*C*V elements in optim.hip's lane layout: a lane owns 4 consecutive floats moved as 16 bytes,
+// All passes are flat streaming work over n = N*C*V elements in optim.hip's lane layout (flat_lanes.hpp): a lane owns 4 consecutive floats moved as 16 bytes,
 // the elements before the first 16-byte boundary and after the last whole quad are taken one by one, the grid is capped and strides.  No
 // float atomics: sums are float64 slots added in a fixed order; the histograms are integers.  Nothing waits for the host.
 #include "ru_common.h"
 #include "pw_helpers.hpp"
+#include "flat_lanes.hpp"
 
 #include <math.h>
 #include <stdint.h>
@@ -24,33 +25,10 @@
 namespace ru {
 namespace {
 
-constexpr int HC_BLOCK = 256;
-constexpr unsigned HC_GRID_CAP = 2048;           // 256 CUs x 8 workgroups; the rest by grid stride
+constexpr int HC_BLOCK = FL_BLOCK;             // the lane layout, the grid cap and the slot sums: flat_lanes.hpp
 constexpr int HC_BINS = 2048;                    // 11 bits per radix level (the last level uses 10 of them)
 constexpr int HC_WAVES = HC_BLOCK / 64;
 constexpr int HC_STATE = 4;                      // state[0] key found so far (low bits 0), [1] rank that remains, [2] n_gt, [3] n_eq
-
-// [0, head) one by one | nq quads from `head` | the remaining (< 4) elements one by one.  Quads only when every pointer of the call sits at
-// the same offset from a 16-byte boundary; otherwise everything goes one by one.
-struct Lanes { size_t head, nq; };
-template <int N>
-inline Lanes lanes_for(size_t n, const void* const (&ptrs)[N]) {
-    const uintptr_t a0 = (uintptr_t)ptrs[0] & 15u;
-    bool alike = (a0 & 3u) == 0;
-    for (int i = 1; i < N; ++i)
-        if (ptrs[i] && ((uintptr_t)ptrs[i] & 15u) != a0) alike = false;
-    if (!alike) return Lanes{n, 0};
-    size_t head = ((16u - a0) & 15u) / 4u;
-    if (head > n) head = n;
-    return Lanes{head, (n - head) / 4};
-}
-// an upper bound of the grid for every alignment: the slot count of a sum is a function of n alone
-inline unsigned hc_slots(size_t n) { return grid1d((n + 3) / 4 + 3, HC_BLOCK, HC_GRID_CAP); }
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ uint4 ld4u(const unsigned* p) { return *reinterpret_cast<const uint4*>(p); }
-__device__ __forceinline__ void st4u(unsigned* p, const uint4& v) { *reinterpret_cast<uint4*>(p) = v; }
 
 // the float32 constants of the reference's BCE expressions (loss.py:77): pred + 1e-6, (1. + 1e-6) - pred
 __device__ __forceinline__ float hc_pe(float p) { return p + 1e-6f; }
@@ -103,25 +81,6 @@ __global__ __launch_bounds__(HC_BLOCK) void focal_sum_kernel(const float* __rest
     }
     const double tot = block_sum_d(acc, buf);
     if (threadIdx.x == 0) slots[blockIdx.x] = tot;                   // every workgroup writes its slot, zeros included
-}
-
-// one workgroup: lane t adds its contiguous share of the slots in index order, lane 0 then adds the 256 shares in lane order
-__device__ __forceinline__ double sum_slots(const double* __restrict__ slots, size_t n_slots, double* part) {
-    const size_t per = (n_slots + HC_BLOCK - 1) / HC_BLOCK;
-    const size_t lo = per * threadIdx.x, hi = lo + per < n_slots ? lo + per : n_slots;
-    double acc = 0.0;
-    for (size_t i = lo; i < hi; ++i) acc += slots[i];
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    double tot = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < HC_BLOCK; ++i) tot += part[i];
-    return tot;                                                      // valid in lane 0
-}
-__global__ __launch_bounds__(HC_BLOCK) void sum_slots_kernel(const double* __restrict__ slots, size_t n_slots, double* __restrict__ out) {
-    __shared__ double part[HC_BLOCK];
-    const double tot = sum_slots(slots, n_slots, part);
-    if (threadIdx.x == 0) *out = tot;
 }
 
 // dp = df/dp * mult * (*scale if given)
@@ -354,15 +313,6 @@ __global__ __launch_bounds__(HC_BLOCK) void topk_grad_kernel(const float* __rest
     }
 }
 
-inline unsigned hc_grid(const Lanes& l, size_t n) {
-    const size_t edge = n - 4 * l.nq;
-    return grid1d(l.nq > edge ? l.nq : edge, HC_BLOCK, HC_GRID_CAP);
-}
-inline bool aligned4(const void* a) { return ((uintptr_t)a & 3u) == 0; }
-inline bool overlap(const void* a, const void* b, size_t n) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + 4 * n && y < x + 4 * n;
-}
 inline bool focal_params_ok(float gamma, float a1, float a0w) { return (gamma == 0.f || gamma >= 1.f) && a1 >= 0.f && a0w >= 0.f; }
 
 // workspace of ru_topk_select: [HC_STATE u64 state | 3 histograms of HC_BINS u32 | slots]
@@ -374,7 +324,7 @@ constexpr size_t TOPK_SLOT_OFF = TOPK_HIST_OFF + 3 * HC_BINS * sizeof(unsigned);
 
 using namespace ru;
 
-extern "C" size_t ru_focal_workspace_bytes(size_t n) { return n ? hc_slots(n) * sizeof(double) : 0; }
+extern "C" size_t ru_focal_workspace_bytes(size_t n) { return n ? fl_slots(n) * sizeof(double) : 0; }
 
 extern "C" int ru_focal_sum(const float* p, const float* g, size_t n, float gamma, float a1, float a0w, double* sum_out, void* ws, size_t ws_bytes,
                             ru_stream_t stream) {
@@ -385,7 +335,7 @@ extern "C" int ru_focal_sum(const float* p, const float* g, size_t n, float gamm
     hipStream_t s = (hipStream_t)stream;
     const void* const ptrs[2] = {p, g};
     const Lanes l = lanes_for(n, ptrs);
-    const unsigned grid = hc_slots(n);                               // at least hc_grid(l, n): lanes past the work write 0
+    const unsigned grid = fl_slots(n);                               // at least fl_grid(l, n): lanes past the work write 0
     const FocalP k{gamma, a1, a0w};
     double* slots = (double*)ws;
     switch (focal_mode(gamma)) {
@@ -410,7 +360,7 @@ extern "C" int ru_focal_grad(const float* p, const float* g, size_t n, float gam
     hipStream_t s = (hipStream_t)stream;
     const void* const ptrs[3] = {p, g, dp};
     const Lanes l = lanes_for(n, ptrs);
-    const unsigned grid = hc_grid(l, n);
+    const unsigned grid = fl_grid(l, n);
     const FocalP k{gamma, a1, a0w};
     const float mult = (float)(1.0 / count);
     switch (focal_mode(gamma)) {
@@ -433,7 +383,7 @@ extern "C" int ru_tversky_eval(const double* totals, int N, int C, double alpha,
     return RU_OK;
 }
 
-extern "C" size_t ru_topk_workspace_bytes(size_t n) { return n ? TOPK_SLOT_OFF + hc_slots(n) * sizeof(double) : 0; }
+extern "C" size_t ru_topk_workspace_bytes(size_t n) { return n ? TOPK_SLOT_OFF + fl_slots(n) * sizeof(double) : 0; }
 
 extern "C" int ru_topk_select(const float* p, const float* g, size_t n, unsigned long long K, float bg_weight, unsigned* keys, unsigned long long* state,
                               double* out2, void* ws, size_t ws_bytes, ru_stream_t stream) {
@@ -454,21 +404,21 @@ extern "C" int ru_topk_select(const float* p, const float* g, size_t n, unsigned
     const Lanes l1 = lanes_for(n, kp);
     const void* const ko[1] = {keys};
     const Lanes l2 = lanes_for(n, ko);
-    hipLaunchKernelGGL(topk_key_kernel, dim3(hc_grid(l1, n)), dim3(HC_BLOCK), 0, s, p, g, n, l1.head, l1.nq, bg_weight, keys, hist);
+    hipLaunchKernelGGL(topk_key_kernel, dim3(fl_grid(l1, n)), dim3(HC_BLOCK), 0, s, p, g, n, l1.head, l1.nq, bg_weight, keys, hist);
     RU_CHECK_LAUNCH("topk_key_kernel");
     hipLaunchKernelGGL(topk_scan_kernel, dim3(1), dim3(HC_BLOCK), 0, s, (const unsigned*)hist, 21, K, st);
     RU_CHECK_LAUNCH("topk_scan_kernel");
-    hipLaunchKernelGGL((topk_hist_kernel<10, 11>), dim3(hc_grid(l2, n)), dim3(HC_BLOCK), 0, s, (const unsigned*)keys, n, l2.head, l2.nq,
+    hipLaunchKernelGGL((topk_hist_kernel<10, 11>), dim3(fl_grid(l2, n)), dim3(HC_BLOCK), 0, s, (const unsigned*)keys, n, l2.head, l2.nq,
                        (const unsigned long long*)st, hist + HC_BINS);
     RU_CHECK_LAUNCH("topk_hist_kernel");
     hipLaunchKernelGGL(topk_scan_kernel, dim3(1), dim3(HC_BLOCK), 0, s, (const unsigned*)(hist + HC_BINS), 10, 0ull, st);
     RU_CHECK_LAUNCH("topk_scan_kernel");
-    hipLaunchKernelGGL((topk_hist_kernel<0, 10>), dim3(hc_grid(l2, n)), dim3(HC_BLOCK), 0, s, (const unsigned*)keys, n, l2.head, l2.nq,
+    hipLaunchKernelGGL((topk_hist_kernel<0, 10>), dim3(fl_grid(l2, n)), dim3(HC_BLOCK), 0, s, (const unsigned*)keys, n, l2.head, l2.nq,
                        (const unsigned long long*)st, hist + 2 * HC_BINS);
     RU_CHECK_LAUNCH("topk_hist_kernel");
     hipLaunchKernelGGL(topk_scan_kernel, dim3(1), dim3(HC_BLOCK), 0, s, (const unsigned*)(hist + 2 * HC_BINS), 0, 0ull, st);
     RU_CHECK_LAUNCH("topk_scan_kernel");
-    const unsigned grid = hc_slots(n);
+    const unsigned grid = fl_slots(n);
     hipLaunchKernelGGL(topk_value_kernel, dim3(grid), dim3(HC_BLOCK), 0, s, (const unsigned*)keys, n, l2.head, l2.nq, (const unsigned long long*)st, slots);
     RU_CHECK_LAUNCH("topk_value_kernel");
     hipLaunchKernelGGL(topk_final_kernel, dim3(1), dim3(HC_BLOCK), 0, s, (const double*)slots, (size_t)grid, (const unsigned long long*)st, K, out2);
@@ -486,7 +436,7 @@ extern "C" int ru_topk_grad(const float* p, const float* g, const unsigned* keys
     RU_REQUIRE(!overlap(p, dp, n) && !overlap(g, dp, n) && !overlap(keys, dp, n), "ru_topk_grad: dp overlaps an input");
     const void* const ptrs[4] = {p, g, keys, dp};
     const Lanes l = lanes_for(n, ptrs);
-    hipLaunchKernelGGL(topk_grad_kernel, dim3(hc_grid(l, n)), dim3(HC_BLOCK), 0, (hipStream_t)stream, p, g, keys, n, l.head, l.nq, bg_weight, state, K,
+    hipLaunchKernelGGL(topk_grad_kernel, dim3(fl_grid(l, n)), dim3(HC_BLOCK), 0, (hipStream_t)stream, p, g, keys, n, l.head, l.nq, bg_weight, state, K,
                        1.0 / ((double)K * world), scale, dp);
     RU_CHECK_LAUNCH("topk_grad_kernel");
     return RU_OK;

@@ -16,6 +16,10 @@ all-reduce of [7C+1] float64 totals, one evaluate launch, one gradient pass.
 
 Beyond the reference: FocalLoss, TverskyLoss (focal-Tversky with gamma = 4/3) and TopKLoss (csrc/hardcrit.hip; definitions in
 INTEGRATION.md), each its own autograd function, with float64 host restatements focal_host, tversky_host and topk_host.
+
+BoundaryLoss and HausdorffDTLoss (csrc/boundary.hip; definitions in INTEGRATION.md) weigh each voxel by its exact Euclidean distance to the
+boundary of the target (and, for the latter, of the thresholded prediction); the maps are made on the device in every step
+(ops.signed_sqdist).  Host restatements: signed_sqdist_host, boundary_host, hddt_host.
 """
 from __future__ import annotations
 
@@ -451,6 +455,115 @@ class TopKLoss(_LossBase):
         return _TopKFn.apply(x[self.index], y[self.index], float(self.k), float(self.bg_weight), self.data_parallel)
 
 
+# ------------------------------------------------------------------ boundary and Hausdorff-DT losses (csrc/boundary.hip)
+# Criteria on exact distance maps of the masks x > 0.5, made on the device in every step, so they follow zoom, rotation and elastic
+# augmentation.  Like the classes above each always writes d(loss)/d(pred), and neither is in _TERM_CLASSES.
+class _BoundaryFn(torch.autograd.Function):
+    """The target's map (three transform passes), one sum pass, one all-reduce of the float64 sum, and in backward one gradient pass
+    that reads the map alone."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, priority, group):
+        s_g = ops.signed_sqdist(gt)
+        total = ops.boundary_sum(pred, s_g)
+        world = _all_reduce_sums(total, group)
+        count = float(pred.numel()) * world
+        ctx.save_for_backward(s_g)
+        ctx.cfg = (priority, count, pred.dtype)
+        return (total[0] * (priority / count)).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, gout):
+        (s_g,) = ctx.saved_tensors
+        priority, count, dtype = ctx.cfg
+        return ops.boundary_grad(s_g, priority / count, gout).to(dtype), None, None, None
+
+
+class _HausdorffDTFn(torch.autograd.Function):
+    """The maps of the target and of the thresholded prediction, one sum pass, one all-reduce of the float64 sum, and in backward one
+    gradient pass; the maps are constants under differentiation."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, alpha, priority, group):
+        s_p, s_g = ops.signed_sqdist(pred), ops.signed_sqdist(gt)
+        total = ops.hddt_sum(pred, gt, s_p, s_g, alpha)
+        world = _all_reduce_sums(total, group)
+        count = float(pred.numel()) * world
+        ctx.save_for_backward(pred, gt, s_p, s_g)
+        ctx.cfg = (alpha, priority, count)
+        return (total[0] * (priority / count)).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, gout):
+        pred, gt, s_p, s_g = ctx.saved_tensors
+        alpha, priority, count = ctx.cfg
+        return ops.hddt_grad(pred, gt, s_p, s_g, alpha, priority / count, gout).to(pred.dtype), None, None, None, None
+
+
+class BoundaryLoss(_LossBase):
+    """priority * mean(p * phi_G): Kervadec et al.'s boundary loss.  phi_G is the level set of the target mask G = g > 0.5 of each
+    (sample, channel): the Euclidean distance F to G outside it, -(F - 1) inside, 0 for an empty or full channel.  The
+    value may be negative.  `priority` is read on every call, so an increasing schedule is an assignment between epochs.  Under data
+    parallelism the mean runs over the global batch."""
+
+    def __init__(self, index=0, priority=1):
+        super().__init__()
+        _check_boundary(priority)
+        self.index, self.priority = index, priority
+
+    def forward(self, x, y):
+        assert x[self.index].shape == y[self.index].shape
+        _check_boundary(self.priority)
+        _check_extents("BoundaryLoss", x[self.index].shape)
+        return _BoundaryFn.apply(x[self.index], y[self.index], float(self.priority), self.data_parallel)
+
+
+class HausdorffDTLoss(_LossBase):
+    """priority * mean((p - g)^2 (F_P^alpha + F_G^alpha)): Karimi & Salehi's distance-transform loss in the form of MONAI's
+    HausdorffDTLoss.  F_P, F_G are the unsigned Euclidean distances to the boundary of P = p > 0.5 and G = g > 0.5 of each (sample,
+    channel), 0 for an empty or full channel, and constants under differentiation.  `priority` is read on every call.  Under data
+    parallelism the mean runs over the global batch."""
+
+    def __init__(self, index=0, alpha=2.0, priority=1):
+        super().__init__()
+        _check_hddt(alpha, priority)
+        self.index, self.alpha, self.priority = index, alpha, priority
+
+    def forward(self, x, y):
+        assert x[self.index].shape == y[self.index].shape
+        _check_hddt(self.alpha, self.priority)
+        _check_extents("HausdorffDTLoss", x[self.index].shape)
+        return _HausdorffDTFn.apply(x[self.index], y[self.index], float(self.alpha), float(self.priority), self.data_parallel)
+
+
+def _finite(v):
+    import math
+    import numbers
+    return isinstance(v, numbers.Real) and math.isfinite(v)
+
+
+def _check_boundary(priority):
+    if not _finite(priority):
+        raise ValueError("BoundaryLoss: priority must be a finite number, got %r" % (priority,))
+
+
+def _check_hddt(alpha, priority):
+    if not (_finite(alpha) and alpha > 0):
+        raise ValueError("HausdorffDTLoss: alpha must be positive and finite, got %r" % (alpha,))
+    if not _finite(priority):
+        raise ValueError("HausdorffDTLoss: priority must be a finite number, got %r" % (priority,))
+
+
+MAX_EXTENT = 512          # csrc/mask_bits.hpp: every axis of a distance-transformed volume
+
+
+def _check_extents(who, shape):
+    if len(shape) != 5:
+        raise ValueError("%s: expected [N, C, D, H, W] tensors, got shape %s" % (who, tuple(shape)))
+    if not all(1 <= int(v) <= MAX_EXTENT for v in shape[2:]):
+        raise ValueError("%s: every axis of the volume must be in [1, %d], got %s" % (who, MAX_EXTENT, tuple(shape[2:])))
+
+
 def _check_focal(gamma, alpha, bg_weight):
     if not (gamma == 0 or gamma >= 1):
         raise ValueError("FocalLoss: gamma must be 0 or at least 1 (0 < gamma < 1 has an infinite gradient at p = 0 or 1), got %r" % (gamma,))
@@ -549,3 +662,59 @@ def topk_host(p, g, k=10.0, bg_weight=1):
     value = (l[above].sum() + (K - n_gt) * t) / K
     w = np.where(above, 1.0 / K, np.where(l == t, (K - n_gt) / (max(n_eq, 1) * K), 0.0))
     return float(value), dl * w
+
+
+def _sqdist_to_host(sites):
+    """exact squared Euclidean distance of every voxel of a [D, H, W] grid to the nearest True voxel of `sites`: the separable minimum
+    f(i) = min_j f(j) + (i - j)^2 over each axis in turn, by brute force in int64"""
+    import numpy as np
+    f = np.where(sites, 0, 1 << 40).astype(np.int64)
+    for axis in (2, 1, 0):
+        i = np.arange(f.shape[axis], dtype=np.int64)
+        cost = (i[:, None] - i[None, :]) ** 2
+        f = np.moveaxis((np.moveaxis(f, axis, -1)[..., None, :] + cost).min(axis=-1), -1, axis)
+    return f
+
+
+def signed_sqdist_host(x):
+    """ops.signed_sqdist in numpy (no scipy): x [..., D, H, W] -> int32 of x's shape, one mask x > 0.5 per leading index; + the squared
+    distance to the mask outside it, - the squared distance to its complement inside, 0 everywhere for an empty or full mask."""
+    import numpy as np
+    x = np.asarray(x, dtype=np.float32)
+    if x.ndim < 3:
+        raise ValueError("expected a [..., D, H, W] array, got shape %s" % (x.shape,))
+    if not all(1 <= v <= MAX_EXTENT for v in x.shape[-3:]):
+        raise ValueError("signed_sqdist_host: every axis of the volume must be in [1, %d], got %s" % (MAX_EXTENT, x.shape[-3:]))
+    masks = (x > np.float32(0.5)).reshape((-1,) + x.shape[-3:])
+    out = np.zeros(masks.shape, dtype=np.int32)
+    for k, m in enumerate(masks):
+        if m.any() and not m.all():
+            out[k] = np.where(m, -_sqdist_to_host(~m), _sqdist_to_host(m))
+    return out.reshape(x.shape)
+
+
+def _phi_host(s):
+    import numpy as np
+    F = np.sqrt(np.abs(s).astype(np.float64))
+    return np.where(s > 0, F, np.where(s < 0, -(F - 1.0), 0.0))
+
+
+def boundary_host(p, g, priority=1):
+    """BoundaryLoss in float64 -> (value, d value / d p)."""
+    import numpy as np
+    _check_boundary(priority)
+    pd = np.asarray(p, dtype=np.float32).astype(np.float64)
+    _check_extents("boundary_host", pd.shape)
+    phi = _phi_host(signed_sqdist_host(g))
+    return float(priority * (pd * phi).sum() / pd.size), priority * phi / pd.size
+
+
+def hddt_host(p, g, alpha=2.0, priority=1):
+    """HausdorffDTLoss in float64 -> (value, d value / d p); the distance maps are constants."""
+    import numpy as np
+    _check_hddt(alpha, priority)
+    pd, gd = np.asarray(p, dtype=np.float32).astype(np.float64), np.asarray(g, dtype=np.float32).astype(np.float64)
+    _check_extents("hddt_host", pd.shape)
+    w = (np.abs(signed_sqdist_host(p)).astype(np.float64) ** (alpha / 2.0) + np.abs(signed_sqdist_host(g)).astype(np.float64) ** (alpha / 2.0))
+    d = pd - gd
+    return float(priority * (d * d * w).sum() / pd.size), 2.0 * priority * d * w / pd.size

@@ -301,6 +301,76 @@ def topk_grad(p, g, keys, state, K, bg_weight=1.0, world=1, scale=None):
     return dp
 
 
+def signed_sqdist(x):
+    """Exact signed squared Euclidean distance maps (csrc/boundary.hip): x float32 [..., D, H, W], one mask x > 0.5 per leading index ->
+    int32 tensor of x's shape: + the squared distance to the nearest voxel of the mask outside it, - the squared distance to the nearest
+    voxel not in the mask inside it, 0 everywhere for an empty or full mask.  Unit spacing, every axis at most 512; no host sync."""
+    x = _prep(x)
+    if x.dim() < 3:
+        raise ValueError("expected a [..., D, H, W] tensor, got shape %s" % (tuple(x.shape),))
+    d, h, w = [int(v) for v in x.shape[-3:]]
+    if max(d, h, w) > 512 or min(d, h, w) < 1:
+        raise ValueError("signed_sqdist: every axis of the volume must be in [1, 512], got %s" % ((d, h, w),))
+    items = x.numel() // (d * h * w)
+    lib = L.load()
+    out = torch.empty(x.shape, dtype=torch.int32, device=x.device)
+    ws = L.workspace(lib.ru_signed_sqdist_workspace_bytes(items, d, h, w), x.device)
+    L.check(lib.ru_signed_sqdist(L.f32(x), items, d, h, w, L.ptr(out), L.ptr(ws), ws.numel(), L.stream()), "ru_signed_sqdist")
+    return out
+
+
+def _map_of(s, like):
+    if s.dtype != torch.int32 or s.shape != like.shape or not s.is_contiguous():
+        raise ValueError("a distance map must be a contiguous int32 tensor of the prediction's shape (ops.signed_sqdist)")
+    return s
+
+
+def boundary_sum(p, s_g):
+    """Boundary loss, pass 1: float64 device tensor [1] = the sum over THIS shard of p * phi_G, phi formed from the int32 map s_g =
+    signed_sqdist(g); the loss is priority * the (all-reduced) sum / the global count."""
+    p = _prep(p)
+    s_g = _map_of(s_g, p)
+    lib = L.load()
+    out = torch.empty(1, dtype=torch.float64, device=p.device)
+    ws = L.workspace(lib.ru_boundary_workspace_bytes(p.numel()), p.device)
+    L.check(lib.ru_boundary_sum(L.f32(p), L.ptr(s_g), p.numel(), L.ptr(out), L.ptr(ws), ws.numel(), L.stream()), "ru_boundary_sum")
+    return out
+
+
+def boundary_grad(s_g, coef, scale=None):
+    """Boundary loss, pass 2: dp = coef * phi_G (coef = priority / global count), times `scale` (a float32 device scalar) when given."""
+    if s_g.dtype != torch.int32 or not s_g.is_contiguous():
+        raise ValueError("a distance map must be a contiguous int32 tensor (ops.signed_sqdist)")
+    dp = torch.empty(s_g.shape, dtype=torch.float32, device=s_g.device)
+    sc = None if scale is None else scale.detach().to(torch.float32).contiguous()
+    L.check(L.load().ru_boundary_grad(L.ptr(s_g), s_g.numel(), float(coef), L.ptr(sc, True), L.f32(dp), L.stream()), "ru_boundary_grad")
+    return dp
+
+
+def hddt_sum(p, g, s_p, s_g, alpha):
+    """Hausdorff-DT loss, pass 1: float64 device tensor [1] = the sum over THIS shard of (p - g)^2 (F_P^alpha + F_G^alpha) with the
+    unsigned distances F = sqrt(|s|) of the int32 maps s_p = signed_sqdist(p), s_g = signed_sqdist(g)."""
+    p, g = _pair(p, g)
+    s_p, s_g = _map_of(s_p, p), _map_of(s_g, p)
+    lib = L.load()
+    out = torch.empty(1, dtype=torch.float64, device=p.device)
+    ws = L.workspace(lib.ru_boundary_workspace_bytes(p.numel()), p.device)
+    L.check(lib.ru_hddt_sum(L.f32(p), L.f32(g), L.ptr(s_p), L.ptr(s_g), p.numel(), float(alpha), L.ptr(out), L.ptr(ws), ws.numel(), L.stream()),
+            "ru_hddt_sum")
+    return out
+
+
+def hddt_grad(p, g, s_p, s_g, alpha, coef, scale=None):
+    """Hausdorff-DT loss, pass 2: dp = coef * 2 (p - g) (F_P^alpha + F_G^alpha) (coef = priority / global count), times `scale`."""
+    p, g = _pair(p, g)
+    s_p, s_g = _map_of(s_p, p), _map_of(s_g, p)
+    dp = torch.empty_like(p)
+    sc = None if scale is None else scale.detach().to(torch.float32).contiguous()
+    L.check(L.load().ru_hddt_grad(L.f32(p), L.f32(g), L.ptr(s_p), L.ptr(s_g), p.numel(), float(alpha), float(coef), L.ptr(sc, True), L.f32(dp),
+                                  L.stream()), "ru_hddt_grad")
+    return dp
+
+
 def adam_amsgrad_step(w, g, m, v, vmax, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
     """torch.optim.Adam(amsgrad=True) update on flat float32 buffers (main.py:133-137)."""
     L.check(L.load().ru_adam_amsgrad_step(L.f32(w), L.f32(g), L.f32(m), L.f32(v), L.f32(vmax), w.numel(), lr, betas[0], betas[1],

@@ -206,6 +206,32 @@ int ru_topk_select(const float* p, const float* g, size_t n, unsigned long long 
 int ru_topk_grad(const float* p, const float* g, const unsigned* keys, const unsigned long long* state, size_t n, unsigned long long K,
                  float bg_weight, double world, const float* scale, float* dp, ru_stream_t stream);
 
+/* ---------------------------------------------------------------- boundary and Hausdorff distance-transform losses (csrc/boundary.hip)
+ * Criteria on exact Euclidean distance maps made on the device (definitions: INTEGRATION.md).  Unit isotropic spacing, every axis in
+ * [1, 512] (larger: RU_EINVAL).  No float atomics, no host synchronisation; two calls give identical bytes.
+ *   ru_signed_sqdist : x: float32 [items][D][H][W], one mask M = x > 0.5f per item (an item is a (sample, channel) pair).  out: int32
+ *                      [items][D][H][W] = s_M: + the squared distance to the nearest voxel of M at a voxel outside M, - the squared
+ *                      distance to the nearest voxel not in M at a voxel inside it, both exact integers of at least 1; 0 everywhere when M
+ *                      is empty or the whole grid (decided on the device).  The W, H and D passes of csrc/edt_exact.hpp; every voxel is
+ *                      written once.  items <= 32767.  ws: ru_signed_sqdist_workspace_bytes(items, D, H, W) (8 bytes per voxel and item).
+ *   With F = sqrt(|s|) and phi = F where s > 0, -(F - 1) where s < 0, 0 where s == 0, both formed in float32 from the integer:
+ *   ru_boundary_sum  : *sum_out (float64) = sum over this shard of p * phi_G (each product exact in float64).  One streaming pass, one
+ *                      float64 partial per workgroup, added in a fixed order.  ws: ru_boundary_workspace_bytes(n).
+ *   ru_boundary_grad : dp = coef * phi_G * (*scale when scale != NULL; a float32 DEVICE scalar); coef = priority / (n * world).
+ *   ru_hddt_sum      : *sum_out = sum of (p - g)^2 (F_P^alpha + F_G^alpha); the weight in float32 (alpha == 2: the integers themselves,
+ *                      alpha == 1: sqrtf, else powf(|s|, alpha / 2)), the difference and the products in float64.  alpha > 0, finite.
+ *                      ws: ru_boundary_workspace_bytes(n).
+ *   ru_hddt_grad     : dp = coef * 2 (p - g) (F_P^alpha + F_G^alpha) * (*scale); the maps are constants under differentiation. */
+size_t ru_signed_sqdist_workspace_bytes(int items, int D, int H, int W);
+int ru_signed_sqdist(const float* x, int items, int D, int H, int W, int* out, void* ws, size_t ws_bytes, ru_stream_t stream);
+size_t ru_boundary_workspace_bytes(size_t n);
+int ru_boundary_sum(const float* p, const int* s_g, size_t n, double* sum_out, void* ws, size_t ws_bytes, ru_stream_t stream);
+int ru_boundary_grad(const int* s_g, size_t n, float coef, const float* scale, float* dp, ru_stream_t stream);
+int ru_hddt_sum(const float* p, const float* g, const int* s_p, const int* s_g, size_t n, float alpha, double* sum_out, void* ws,
+                size_t ws_bytes, ru_stream_t stream);
+int ru_hddt_grad(const float* p, const float* g, const int* s_p, const int* s_g, size_t n, float alpha, float coef, const float* scale,
+                 float* dp, ru_stream_t stream);
+
 /* ---------------------------------------------------------------- optimizer (main.py:133-142)
  * torch.optim.Adam(amsgrad=True) with L2 weight decay added to the gradient; `step` is 1-based.  */
 int ru_adam_amsgrad_step(float* w, const float* g, float* m, float* v, float* vmax, size_t n,
