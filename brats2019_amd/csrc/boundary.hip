@@ -12,9 +12,9 @@
 //                      empty or full channel is decided from the count the W pass left on the device: its t = 0 blocks write zeros.
 //   losses   phi = F outside, -(F - 1) inside, 0 where s = 0, with F = sqrt(|s|) (Kervadec's one_hot2dist); boundary = sum p phi_G;
 //            hddt = sum (p - g)^2 (F_P^alpha + F_G^alpha).  phi and F^alpha are formed from the int32 value where they are used: no float
-//            map is stored.  The passes are flat streaming work in hardcrit.hip's lane layout: a lane owns 4 consecutive elements moved as 16
-//            bytes, heads and tails one by one, the grid capped and striding, one float64 slot per workgroup added in a fixed order by one
-//            workgroup.  No float atomics, nothing waits for the host, the same bytes give the same bytes.
+//            map is stored.  The passes are flat streaming work in the lane layout of flat_lanes.hpp: the sums are ops of its sum_kernel (one
+//            float64 slot per workgroup, added in a fixed order by one workgroup), the gradients ops of its stream_kernel.  No float
+//            atomics, nothing waits for the host, the same bytes give the same bytes.
 #include "ru_common.h"
 #include "edt_exact.hpp"
 #include "flat_lanes.hpp"
@@ -129,86 +129,53 @@ __device__ __forceinline__ float hd_deriv(float p, float g, int sp, int sg, floa
     return 2.f * (p - g) * hd_weight<MODE>(sp, sg, half);
 }
 
-__global__ __launch_bounds__(FL_BLOCK) void boundary_sum_kernel(const float* __restrict__ p, const int* __restrict__ s, size_t n, size_t head, size_t nq,
-                                                                double* __restrict__ slots) {
-    __shared__ double buf[4];
-    const size_t t = (size_t)blockIdx.x * FL_BLOCK + threadIdx.x, T = (size_t)gridDim.x * FL_BLOCK;
-    double acc = 0.0;
-    for (size_t q = t; q < nq; q += T) {
-        const float4 pv = ld4(p + head + 4 * q);
-        const int4 sv = ld4i(s + head + 4 * q);
-        acc += ((double)pv.x * (double)bd_phi(sv.x) + (double)pv.y * (double)bd_phi(sv.y)) +
+struct BoundarySumOp {
+    const float* p; const int* s;
+    __device__ __forceinline__ double quad(size_t i) const {
+        const float4 pv = ld4(p + i);
+        const int4 sv = ld4i(s + i);
+        return ((double)pv.x * (double)bd_phi(sv.x) + (double)pv.y * (double)bd_phi(sv.y)) +
                ((double)pv.z * (double)bd_phi(sv.z) + (double)pv.w * (double)bd_phi(sv.w));
     }
-    const size_t edge = n - 4 * nq;
-    for (size_t e = t; e < edge; e += T) {
-        const size_t i = e < head ? e : e + 4 * nq;
-        acc += (double)p[i] * (double)bd_phi(s[i]);
-    }
-    const double tot = block_sum_d(acc, buf);
-    if (threadIdx.x == 0) slots[blockIdx.x] = tot;                   // every workgroup writes its slot, zeros included
-}
+    __device__ __forceinline__ double one(size_t i) const { return (double)p[i] * (double)bd_phi(s[i]); }
+};
 
 // dp = phi * mult * (*scale if given)
-__global__ __launch_bounds__(FL_BLOCK) void boundary_grad_kernel(const int* __restrict__ s, size_t n, size_t head, size_t nq, float mult,
-                                                                 const float* __restrict__ scale, float* __restrict__ dp) {
-    const size_t t = (size_t)blockIdx.x * FL_BLOCK + threadIdx.x, T = (size_t)gridDim.x * FL_BLOCK;
-    const float m = scale ? mult * *scale : mult;
-    for (size_t q = t; q < nq; q += T) {
-        const size_t i = head + 4 * q;
-        const int4 sv = ld4i(s + i);
+struct BoundaryGradOp {
+    const int* s; float m; const float* scale; float* dp;           // m = mult, from begin() on times *scale
+    __device__ __forceinline__ void begin() { if (scale) m *= *scale; }
+    __device__ __forceinline__ void one(size_t i) const { dp[i] = m * bd_phi(s[i]); }
+    __device__ __forceinline__ int4 load(size_t i) const { return ld4i(s + i); }
+    __device__ __forceinline__ void finish(size_t i, const int4& sv) const {
         st4(dp + i, make_float4(m * bd_phi(sv.x), m * bd_phi(sv.y), m * bd_phi(sv.z), m * bd_phi(sv.w)));
     }
-    const size_t edge = n - 4 * nq;
-    for (size_t e = t; e < edge; e += T) {
-        const size_t i = e < head ? e : e + 4 * nq;
-        dp[i] = m * bd_phi(s[i]);
-    }
-}
+};
 
 template <int MODE>
-__global__ __launch_bounds__(FL_BLOCK) void hddt_sum_kernel(const float* __restrict__ p, const float* __restrict__ g, const int* __restrict__ sp,
-                                                            const int* __restrict__ sg, size_t n, size_t head, size_t nq, float half,
-                                                            double* __restrict__ slots) {
-    __shared__ double buf[4];
-    const size_t t = (size_t)blockIdx.x * FL_BLOCK + threadIdx.x, T = (size_t)gridDim.x * FL_BLOCK;
-    double acc = 0.0;
-    for (size_t q = t; q < nq; q += T) {
-        const size_t i = head + 4 * q;
+struct HddtSumOp {
+    const float* p; const float* g; const int* sp; const int* sg; float half;
+    __device__ __forceinline__ double quad(size_t i) const {
         const float4 pv = ld4(p + i), gv = ld4(g + i);
         const int4 a = ld4i(sp + i), b = ld4i(sg + i);
-        acc += (hd_term<MODE>(pv.x, gv.x, a.x, b.x, half) + hd_term<MODE>(pv.y, gv.y, a.y, b.y, half)) +
+        return (hd_term<MODE>(pv.x, gv.x, a.x, b.x, half) + hd_term<MODE>(pv.y, gv.y, a.y, b.y, half)) +
                (hd_term<MODE>(pv.z, gv.z, a.z, b.z, half) + hd_term<MODE>(pv.w, gv.w, a.w, b.w, half));
     }
-    const size_t edge = n - 4 * nq;
-    for (size_t e = t; e < edge; e += T) {
-        const size_t i = e < head ? e : e + 4 * nq;
-        acc += hd_term<MODE>(p[i], g[i], sp[i], sg[i], half);
-    }
-    const double tot = block_sum_d(acc, buf);
-    if (threadIdx.x == 0) slots[blockIdx.x] = tot;
-}
+    __device__ __forceinline__ double one(size_t i) const { return hd_term<MODE>(p[i], g[i], sp[i], sg[i], half); }
+};
 
 // dp = 2 (p - g) (F_P^alpha + F_G^alpha) * mult * (*scale if given)
 template <int MODE>
-__global__ __launch_bounds__(FL_BLOCK) void hddt_grad_kernel(const float* __restrict__ p, const float* __restrict__ g, const int* __restrict__ sp,
-                                                             const int* __restrict__ sg, size_t n, size_t head, size_t nq, float half, float mult,
-                                                             const float* __restrict__ scale, float* __restrict__ dp) {
-    const size_t t = (size_t)blockIdx.x * FL_BLOCK + threadIdx.x, T = (size_t)gridDim.x * FL_BLOCK;
-    const float m = scale ? mult * *scale : mult;
-    for (size_t q = t; q < nq; q += T) {
-        const size_t i = head + 4 * q;
-        const float4 pv = ld4(p + i), gv = ld4(g + i);
-        const int4 a = ld4i(sp + i), b = ld4i(sg + i);
-        st4(dp + i, make_float4(m * hd_deriv<MODE>(pv.x, gv.x, a.x, b.x, half), m * hd_deriv<MODE>(pv.y, gv.y, a.y, b.y, half),
-                                m * hd_deriv<MODE>(pv.z, gv.z, a.z, b.z, half), m * hd_deriv<MODE>(pv.w, gv.w, a.w, b.w, half)));
+struct HddtGradOp {
+    const float* p; const float* g; const int* sp; const int* sg; float half, m; const float* scale; float* dp;     // m as BoundaryGradOp's
+    __device__ __forceinline__ void begin() { if (scale) m *= *scale; }
+    __device__ __forceinline__ void one(size_t i) const { dp[i] = m * hd_deriv<MODE>(p[i], g[i], sp[i], sg[i], half); }
+    struct Q { float4 p, g; int4 a, b; };
+    __device__ __forceinline__ Q load(size_t i) const { return Q{ld4(p + i), ld4(g + i), ld4i(sp + i), ld4i(sg + i)}; }
+    __device__ __forceinline__ void finish(size_t i, const Q& q) const {
+        st4(dp + i, make_float4(m * hd_deriv<MODE>(q.p.x, q.g.x, q.a.x, q.b.x, half), m * hd_deriv<MODE>(q.p.y, q.g.y, q.a.y, q.b.y, half),
+                                m * hd_deriv<MODE>(q.p.z, q.g.z, q.a.z, q.b.z, half), m * hd_deriv<MODE>(q.p.w, q.g.w, q.a.w, q.b.w, half)));
     }
-    const size_t edge = n - 4 * nq;
-    for (size_t e = t; e < edge; e += T) {
-        const size_t i = e < head ? e : e + 4 * nq;
-        dp[i] = m * hd_deriv<MODE>(p[i], g[i], sp[i], sg[i], half);
-    }
-}
+};
 
 inline bool alpha_ok(float alpha) { return alpha > 0.f && alpha <= 3.4e38f; }      // NaN fails the first comparison
 
@@ -248,16 +215,8 @@ extern "C" int ru_boundary_sum(const float* p, const int* s_g, size_t n, double*
     RU_REQUIRE(p && s_g && sum_out && ws && n > 0, "ru_boundary_sum: bad argument");
     RU_REQUIRE(aligned4(p) && aligned4(s_g) && ((uintptr_t)ws & 7u) == 0 && ((uintptr_t)sum_out & 7u) == 0, "ru_boundary_sum: misaligned pointer");
     RU_REQUIRE(ws_bytes >= ru_boundary_workspace_bytes(n), "ru_boundary_sum: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
     const void* const ptrs[2] = {p, s_g};
-    const Lanes l = lanes_for(n, ptrs);
-    const unsigned grid = fl_slots(n);                               // at least fl_grid(l, n): lanes past the work write 0
-    double* slots = (double*)ws;
-    hipLaunchKernelGGL(boundary_sum_kernel, dim3(grid), dim3(FL_BLOCK), 0, s, p, s_g, n, l.head, l.nq, slots);
-    RU_CHECK_LAUNCH("boundary_sum_kernel");
-    hipLaunchKernelGGL(sum_slots_kernel, dim3(1), dim3(FL_BLOCK), 0, s, (const double*)slots, (size_t)grid, sum_out);
-    RU_CHECK_LAUNCH("sum_slots_kernel");
-    return RU_OK;
+    return total_launch(BoundarySumOp{p, s_g}, n, lanes_for(n, ptrs), (double*)ws, sum_out, (hipStream_t)stream, "boundary_sum_kernel");
 }
 
 extern "C" int ru_boundary_grad(const int* s_g, size_t n, float coef, const float* scale, float* dp, ru_stream_t stream) {
@@ -266,10 +225,7 @@ extern "C" int ru_boundary_grad(const int* s_g, size_t n, float coef, const floa
     RU_REQUIRE(aligned4(s_g) && aligned4(dp), "ru_boundary_grad: misaligned pointer");
     RU_REQUIRE(!overlap(s_g, dp, n), "ru_boundary_grad: dp overlaps the map");
     const void* const ptrs[2] = {s_g, dp};
-    const Lanes l = lanes_for(n, ptrs);
-    hipLaunchKernelGGL(boundary_grad_kernel, dim3(fl_grid(l, n)), dim3(FL_BLOCK), 0, (hipStream_t)stream, s_g, n, l.head, l.nq, coef, scale, dp);
-    RU_CHECK_LAUNCH("boundary_grad_kernel");
-    return RU_OK;
+    return stream_launch(BoundaryGradOp{s_g, coef, scale, dp}, n, lanes_for(n, ptrs), (hipStream_t)stream, "boundary_grad_kernel");
 }
 
 extern "C" int ru_hddt_sum(const float* p, const float* g, const int* s_p, const int* s_g, size_t n, float alpha, double* sum_out, void* ws,
@@ -282,18 +238,10 @@ extern "C" int ru_hddt_sum(const float* p, const float* g, const int* s_p, const
     hipStream_t s = (hipStream_t)stream;
     const void* const ptrs[4] = {p, g, s_p, s_g};
     const Lanes l = lanes_for(n, ptrs);
-    const unsigned grid = fl_slots(n);
     const float half = 0.5f * alpha;
-    double* slots = (double*)ws;
-    switch (hd_mode(alpha)) {
-    case 1: hipLaunchKernelGGL(hddt_sum_kernel<1>, dim3(grid), dim3(FL_BLOCK), 0, s, p, g, s_p, s_g, n, l.head, l.nq, half, slots); break;
-    case 2: hipLaunchKernelGGL(hddt_sum_kernel<2>, dim3(grid), dim3(FL_BLOCK), 0, s, p, g, s_p, s_g, n, l.head, l.nq, half, slots); break;
-    default: hipLaunchKernelGGL(hddt_sum_kernel<3>, dim3(grid), dim3(FL_BLOCK), 0, s, p, g, s_p, s_g, n, l.head, l.nq, half, slots); break;
-    }
-    RU_CHECK_LAUNCH("hddt_sum_kernel");
-    hipLaunchKernelGGL(sum_slots_kernel, dim3(1), dim3(FL_BLOCK), 0, s, (const double*)slots, (size_t)grid, sum_out);
-    RU_CHECK_LAUNCH("sum_slots_kernel");
-    return RU_OK;
+    return with_mode<1, 3>(hd_mode(alpha), [&](auto mode) {
+        return total_launch(HddtSumOp<mode()>{p, g, s_p, s_g, half}, n, l, (double*)ws, sum_out, s, "hddt_sum_kernel");
+    });
 }
 
 extern "C" int ru_hddt_grad(const float* p, const float* g, const int* s_p, const int* s_g, size_t n, float alpha, float coef, const float* scale,
@@ -306,13 +254,8 @@ extern "C" int ru_hddt_grad(const float* p, const float* g, const int* s_p, cons
     hipStream_t s = (hipStream_t)stream;
     const void* const ptrs[5] = {p, g, s_p, s_g, dp};
     const Lanes l = lanes_for(n, ptrs);
-    const unsigned grid = fl_grid(l, n);
     const float half = 0.5f * alpha;
-    switch (hd_mode(alpha)) {
-    case 1: hipLaunchKernelGGL(hddt_grad_kernel<1>, dim3(grid), dim3(FL_BLOCK), 0, s, p, g, s_p, s_g, n, l.head, l.nq, half, coef, scale, dp); break;
-    case 2: hipLaunchKernelGGL(hddt_grad_kernel<2>, dim3(grid), dim3(FL_BLOCK), 0, s, p, g, s_p, s_g, n, l.head, l.nq, half, coef, scale, dp); break;
-    default: hipLaunchKernelGGL(hddt_grad_kernel<3>, dim3(grid), dim3(FL_BLOCK), 0, s, p, g, s_p, s_g, n, l.head, l.nq, half, coef, scale, dp); break;
-    }
-    RU_CHECK_LAUNCH("hddt_grad_kernel");
-    return RU_OK;
+    return with_mode<1, 3>(hd_mode(alpha), [&](auto mode) {
+        return stream_launch(HddtGradOp<mode()>{p, g, s_p, s_g, half, coef, scale, dp}, n, l, s, "hddt_grad_kernel");
+    });
 }

@@ -2,19 +2,19 @@
 // focal-Tversky and top-k cross entropy on the [N, C, V] probability / target pair.
 //
 //   focal    f = -(a1 g (1-p)^gamma log(p + 1e-6) + a0w (1-g) p^gamma log((1 + 1e-6) - p)), mean over all elements
-//            focal_sum_kernel -> one float64 slot per workgroup, sum_slots_kernel adds the slots in index order; focal_grad_kernel writes dp
+//            FocalSumOp -> one float64 slot per workgroup, sum_slots_kernel adds the slots in index order; FocalGradOp writes dp
 //   Tversky  a closed form in ru_crit_moments' sums (sum pg, sum p, sum g): tversky_eval_kernel writes the value and the per-row
 //            coefficients that ru_crit_grad applies
 //   top-k    the mean of the K largest l = -(g log(p + 1e-6) + w (1-g) log((1 + 1e-6) - p)).  topk_key_kernel forms l ONCE, stores it as an
 //            order-preserving 32-bit key and histograms the key's top 11 bits; two more passes over the stored keys histogram the next 11 and
 //            the last 10 bits of the keys that share the prefix found so far (topk_hist_kernel), a one-workgroup scan after each pass picks
-//            the bin of the K-th largest key and the rank that remains (topk_scan_kernel).  topk_value_kernel sums the l above the threshold
-//            into float64 slots, topk_final_kernel adds them in index order; topk_grad_kernel reads the same stored keys, so every pass
+//            the bin of the K-th largest key and the rank that remains (topk_scan_kernel).  TopkValueOp sums the l above the threshold
+//            into float64 slots, topk_final_kernel adds them in index order; TopkGradOp reads the same stored keys, so every pass
 //            sees the same bits of l.
 //
-// All passes are flat streaming work over n = N*C*V elements in optim.hip's lane layout (flat_lanes.hpp): a lane owns 4 consecutive floats moved as 16 bytes,
-// the elements before the first 16-byte boundary and after the last whole quad are taken one by one, the grid is capped and strides.  No
-// float atomics: sums are float64 slots added in a fixed order; the histograms are integers.  Nothing waits for the host.
+// All passes are flat streaming work over n = N*C*V elements in the lane layout of flat_lanes.hpp: the sums are ops of its sum_kernel, the
+// gradients ops of its stream_kernel, the two histogram kernels call its walk between their own prologue and epilogue.  No float atomics:
+// sums are float64 slots added in a fixed order; the histograms are integers.  Nothing waits for the host.
 #include "ru_common.h"
 #include "pw_helpers.hpp"
 #include "flat_lanes.hpp"
@@ -64,43 +64,29 @@ __device__ __forceinline__ float focal_deriv(float p, float g, const FocalP& k) 
 }
 
 template <int MODE>
-__global__ __launch_bounds__(HC_BLOCK) void focal_sum_kernel(const float* __restrict__ p, const float* __restrict__ g, size_t n, size_t head, size_t nq,
-                                                             FocalP k, double* __restrict__ slots) {
-    __shared__ double buf[4];
-    const size_t t = (size_t)blockIdx.x * HC_BLOCK + threadIdx.x, T = (size_t)gridDim.x * HC_BLOCK;
-    double acc = 0.0;
-    for (size_t q = t; q < nq; q += T) {
-        const float4 pv = ld4(p + head + 4 * q), gv = ld4(g + head + 4 * q);
-        acc += ((double)focal_value<MODE>(pv.x, gv.x, k) + (double)focal_value<MODE>(pv.y, gv.y, k)) +
+struct FocalSumOp {
+    const float* p; const float* g; FocalP k;
+    __device__ __forceinline__ double quad(size_t i) const {
+        const float4 pv = ld4(p + i), gv = ld4(g + i);
+        return ((double)focal_value<MODE>(pv.x, gv.x, k) + (double)focal_value<MODE>(pv.y, gv.y, k)) +
                ((double)focal_value<MODE>(pv.z, gv.z, k) + (double)focal_value<MODE>(pv.w, gv.w, k));
     }
-    const size_t edge = n - 4 * nq;
-    for (size_t e = t; e < edge; e += T) {
-        const size_t i = e < head ? e : e + 4 * nq;
-        acc += (double)focal_value<MODE>(p[i], g[i], k);
-    }
-    const double tot = block_sum_d(acc, buf);
-    if (threadIdx.x == 0) slots[blockIdx.x] = tot;                   // every workgroup writes its slot, zeros included
-}
+    __device__ __forceinline__ double one(size_t i) const { return (double)focal_value<MODE>(p[i], g[i], k); }
+};
 
 // dp = df/dp * mult * (*scale if given)
 template <int MODE>
-__global__ __launch_bounds__(HC_BLOCK) void focal_grad_kernel(const float* __restrict__ p, const float* __restrict__ g, size_t n, size_t head, size_t nq,
-                                                              FocalP k, float mult, const float* __restrict__ scale, float* __restrict__ dp) {
-    const size_t t = (size_t)blockIdx.x * HC_BLOCK + threadIdx.x, T = (size_t)gridDim.x * HC_BLOCK;
-    const float m = scale ? mult * *scale : mult;
-    for (size_t q = t; q < nq; q += T) {
-        const size_t i = head + 4 * q;
-        const float4 pv = ld4(p + i), gv = ld4(g + i);
-        st4(dp + i, make_float4(m * focal_deriv<MODE>(pv.x, gv.x, k), m * focal_deriv<MODE>(pv.y, gv.y, k), m * focal_deriv<MODE>(pv.z, gv.z, k),
-                                m * focal_deriv<MODE>(pv.w, gv.w, k)));
+struct FocalGradOp {
+    const float* p; const float* g; FocalP k; float m; const float* scale; float* dp;      // m = mult, from begin() on times *scale
+    __device__ __forceinline__ void begin() { if (scale) m *= *scale; }
+    __device__ __forceinline__ void one(size_t i) const { dp[i] = m * focal_deriv<MODE>(p[i], g[i], k); }
+    struct Q { float4 p, g; };
+    __device__ __forceinline__ Q load(size_t i) const { return Q{ld4(p + i), ld4(g + i)}; }
+    __device__ __forceinline__ void finish(size_t i, const Q& q) const {
+        st4(dp + i, make_float4(m * focal_deriv<MODE>(q.p.x, q.g.x, k), m * focal_deriv<MODE>(q.p.y, q.g.y, k), m * focal_deriv<MODE>(q.p.z, q.g.z, k),
+                                m * focal_deriv<MODE>(q.p.w, q.g.w, k)));
     }
-    const size_t edge = n - 4 * nq;
-    for (size_t e = t; e < edge; e += T) {
-        const size_t i = e < head ? e : e + 4 * nq;
-        dp[i] = m * focal_deriv<MODE>(p[i], g[i], k);
-    }
-}
+};
 
 inline int focal_mode(float gamma) { return gamma == 0.f ? 0 : gamma == 1.f ? 1 : gamma == 2.f ? 2 : 3; }
 
@@ -184,49 +170,45 @@ __device__ __forceinline__ void hist_flush(const unsigned* lds, unsigned* __rest
 }
 
 // level 1: l -> key, stored; histogram of key >> 21
-__global__ __launch_bounds__(HC_BLOCK) void topk_key_kernel(const float* __restrict__ p, const float* __restrict__ g, size_t n, size_t head, size_t nq,
-                                                            float w, unsigned* __restrict__ keys, unsigned* __restrict__ hist) {
+__global__ __launch_bounds__(HC_BLOCK) void topk_key_kernel(const float* __restrict__ p, const float* __restrict__ g, size_t n, Lanes l, float w,
+                                                            unsigned* __restrict__ keys, unsigned* __restrict__ hist) {
     __shared__ unsigned lds[HC_WAVES * HC_BINS];
     hist_clear(lds);
     Hist H{lds + (threadIdx.x >> 6) * HC_BINS};
-    const size_t t = (size_t)blockIdx.x * HC_BLOCK + threadIdx.x, T = (size_t)gridDim.x * HC_BLOCK;
-    for (size_t q = t; q < nq; q += T) {
-        const size_t i = head + 4 * q;
-        const float4 pv = ld4(p + i), gv = ld4(g + i);
-        const uint4 k = make_uint4(topk_key(pv.x, gv.x, w), topk_key(pv.y, gv.y, w), topk_key(pv.z, gv.z, w), topk_key(pv.w, gv.w, w));
-        st4u(keys + i, k);
-        H.add4(true, true, true, true, k.x >> 21, k.y >> 21, k.z >> 21, k.w >> 21);
-    }
-    const size_t edge = n - 4 * nq;
-    for (size_t e = t; e < edge; e += T) {
-        const size_t i = e < head ? e : e + 4 * nq;
-        const unsigned k = topk_key(p[i], g[i], w);
-        keys[i] = k;
-        H.add(k >> 21, 1u);
-    }
+    fl_walk(l, n,
+            [&](size_t i) {
+                const float4 pv = ld4(p + i), gv = ld4(g + i);
+                const uint4 k = make_uint4(topk_key(pv.x, gv.x, w), topk_key(pv.y, gv.y, w), topk_key(pv.z, gv.z, w), topk_key(pv.w, gv.w, w));
+                st4u(keys + i, k);
+                H.add4(true, true, true, true, k.x >> 21, k.y >> 21, k.z >> 21, k.w >> 21);
+            },
+            [&](size_t i) {
+                const unsigned k = topk_key(p[i], g[i], w);
+                keys[i] = k;
+                H.add(k >> 21, 1u);
+            });
     hist_flush(lds, hist);
 }
 
 // levels 2 and 3: of the keys whose top `SHIFT + BITS`.. bits equal the prefix found so far, histogram the next BITS bits
 template <int SHIFT, int BITS>
-__global__ __launch_bounds__(HC_BLOCK) void topk_hist_kernel(const unsigned* __restrict__ keys, size_t n, size_t head, size_t nq,
+__global__ __launch_bounds__(HC_BLOCK) void topk_hist_kernel(const unsigned* __restrict__ keys, size_t n, Lanes l,
                                                              const unsigned long long* __restrict__ state, unsigned* __restrict__ hist) {
     __shared__ unsigned lds[HC_WAVES * HC_BINS];
     hist_clear(lds);
     Hist H{lds + (threadIdx.x >> 6) * HC_BINS};
     const unsigned pre = (unsigned)state[0] >> (SHIFT + BITS);
     constexpr unsigned MASK = (1u << BITS) - 1u;
-    const size_t t = (size_t)blockIdx.x * HC_BLOCK + threadIdx.x, T = (size_t)gridDim.x * HC_BLOCK;
-    for (size_t q = t; q < nq; q += T) {
-        const uint4 k = ld4u(keys + head + 4 * q);
-        H.add4((k.x >> (SHIFT + BITS)) == pre, (k.y >> (SHIFT + BITS)) == pre, (k.z >> (SHIFT + BITS)) == pre, (k.w >> (SHIFT + BITS)) == pre,
-               (k.x >> SHIFT) & MASK, (k.y >> SHIFT) & MASK, (k.z >> SHIFT) & MASK, (k.w >> SHIFT) & MASK);
-    }
-    const size_t edge = n - 4 * nq;
-    for (size_t e = t; e < edge; e += T) {
-        const unsigned k = keys[e < head ? e : e + 4 * nq];
-        if ((k >> (SHIFT + BITS)) == pre) H.add((k >> SHIFT) & MASK, 1u);
-    }
+    fl_walk(l, n,
+            [&](size_t i) {
+                const uint4 k = ld4u(keys + i);
+                H.add4((k.x >> (SHIFT + BITS)) == pre, (k.y >> (SHIFT + BITS)) == pre, (k.z >> (SHIFT + BITS)) == pre, (k.w >> (SHIFT + BITS)) == pre,
+                       (k.x >> SHIFT) & MASK, (k.y >> SHIFT) & MASK, (k.z >> SHIFT) & MASK, (k.w >> SHIFT) & MASK);
+            },
+            [&](size_t i) {
+                const unsigned k = keys[i];
+                if ((k >> (SHIFT + BITS)) == pre) H.add((k >> SHIFT) & MASK, 1u);
+            });
     hist_flush(lds, hist);
 }
 
@@ -258,26 +240,17 @@ __global__ __launch_bounds__(HC_BLOCK) void topk_scan_kernel(const unsigned* __r
     }
 }
 
-// slots[block] = sum of l over the keys above the threshold, float64
-__global__ __launch_bounds__(HC_BLOCK) void topk_value_kernel(const unsigned* __restrict__ keys, size_t n, size_t head, size_t nq,
-                                                              const unsigned long long* __restrict__ state, double* __restrict__ slots) {
-    __shared__ double buf[4];
-    const unsigned tk = (unsigned)state[0];
-    const size_t t = (size_t)blockIdx.x * HC_BLOCK + threadIdx.x, T = (size_t)gridDim.x * HC_BLOCK;
-    double acc = 0.0;
-    for (size_t q = t; q < nq; q += T) {
-        const uint4 k = ld4u(keys + head + 4 * q);
-        acc += ((k.x > tk ? (double)topk_unkey(k.x) : 0.0) + (k.y > tk ? (double)topk_unkey(k.y) : 0.0)) +
-               ((k.z > tk ? (double)topk_unkey(k.z) : 0.0) + (k.w > tk ? (double)topk_unkey(k.w) : 0.0));
+// the sum of l over the keys above the threshold, float64
+struct TopkValueOp {
+    const unsigned* keys; const unsigned long long* state;
+    __device__ __forceinline__ double above(unsigned k, unsigned tk) const { return k > tk ? (double)topk_unkey(k) : 0.0; }
+    __device__ __forceinline__ double quad(size_t i) const {
+        const unsigned tk = (unsigned)state[0];
+        const uint4 k = ld4u(keys + i);
+        return (above(k.x, tk) + above(k.y, tk)) + (above(k.z, tk) + above(k.w, tk));
     }
-    const size_t edge = n - 4 * nq;
-    for (size_t e = t; e < edge; e += T) {
-        const unsigned k = keys[e < head ? e : e + 4 * nq];
-        if (k > tk) acc += (double)topk_unkey(k);
-    }
-    const double tot = block_sum_d(acc, buf);
-    if (threadIdx.x == 0) slots[blockIdx.x] = tot;
-}
+    __device__ __forceinline__ double one(size_t i) const { return above(keys[i], (unsigned)state[0]); }
+};
 
 // out[0] = (sum of the slots + (K - n_gt) * t) / K, out[1] = t
 __global__ __launch_bounds__(HC_BLOCK) void topk_final_kernel(const double* __restrict__ slots, size_t n_slots, const unsigned long long* __restrict__ state,
@@ -292,26 +265,26 @@ __global__ __launch_bounds__(HC_BLOCK) void topk_final_kernel(const double* __re
 }
 
 // dp = dl/dp * mult * (*scale) above the threshold, times (K - n_gt) / n_eq at it, 0 below
-__global__ __launch_bounds__(HC_BLOCK) void topk_grad_kernel(const float* __restrict__ p, const float* __restrict__ g, const unsigned* __restrict__ keys,
-                                                             size_t n, size_t head, size_t nq, float w, const unsigned long long* __restrict__ state,
-                                                             unsigned long long K, double mult, const float* __restrict__ scale, float* __restrict__ dp) {
-    const unsigned tk = (unsigned)state[0];
-    const double m = scale ? mult * (double)*scale : mult;
-    const float m_gt = (float)m, m_eq = (float)(m * (double)(K - state[2]) / (double)state[3]);
-    auto one = [&](float pi, float gi, unsigned k) { return k > tk ? m_gt * topk_dl(pi, gi, w) : k == tk ? m_eq * topk_dl(pi, gi, w) : 0.f; };
-    const size_t t = (size_t)blockIdx.x * HC_BLOCK + threadIdx.x, T = (size_t)gridDim.x * HC_BLOCK;
-    for (size_t q = t; q < nq; q += T) {
-        const size_t i = head + 4 * q;
-        const float4 pv = ld4(p + i), gv = ld4(g + i);
-        const uint4 k = ld4u(keys + i);
-        st4(dp + i, make_float4(one(pv.x, gv.x, k.x), one(pv.y, gv.y, k.y), one(pv.z, gv.z, k.z), one(pv.w, gv.w, k.w)));
+struct TopkGradOp {
+    const float* p; const float* g; const unsigned* keys; float w; const unsigned long long* state; unsigned long long K; double mult;
+    const float* scale; float* dp;
+    unsigned tk; float m_gt, m_eq;                                   // begin()
+    __device__ __forceinline__ void begin() {
+        const double m = scale ? mult * (double)*scale : mult;
+        tk = (unsigned)state[0];
+        m_gt = (float)m;
+        m_eq = (float)(m * (double)(K - state[2]) / (double)state[3]);
     }
-    const size_t edge = n - 4 * nq;
-    for (size_t e = t; e < edge; e += T) {
-        const size_t i = e < head ? e : e + 4 * nq;
-        dp[i] = one(p[i], g[i], keys[i]);
+    __device__ __forceinline__ float dl(float pi, float gi, unsigned k) const {
+        return k > tk ? m_gt * topk_dl(pi, gi, w) : k == tk ? m_eq * topk_dl(pi, gi, w) : 0.f;
     }
-}
+    __device__ __forceinline__ void one(size_t i) const { dp[i] = dl(p[i], g[i], keys[i]); }
+    struct Q { float4 p, g; uint4 k; };
+    __device__ __forceinline__ Q load(size_t i) const { return Q{ld4(p + i), ld4(g + i), ld4u(keys + i)}; }
+    __device__ __forceinline__ void finish(size_t i, const Q& q) const {
+        st4(dp + i, make_float4(dl(q.p.x, q.g.x, q.k.x), dl(q.p.y, q.g.y, q.k.y), dl(q.p.z, q.g.z, q.k.z), dl(q.p.w, q.g.w, q.k.w)));
+    }
+};
 
 inline bool focal_params_ok(float gamma, float a1, float a0w) { return (gamma == 0.f || gamma >= 1.f) && a1 >= 0.f && a0w >= 0.f; }
 
@@ -335,19 +308,10 @@ extern "C" int ru_focal_sum(const float* p, const float* g, size_t n, float gamm
     hipStream_t s = (hipStream_t)stream;
     const void* const ptrs[2] = {p, g};
     const Lanes l = lanes_for(n, ptrs);
-    const unsigned grid = fl_slots(n);                               // at least fl_grid(l, n): lanes past the work write 0
     const FocalP k{gamma, a1, a0w};
-    double* slots = (double*)ws;
-    switch (focal_mode(gamma)) {
-    case 0: hipLaunchKernelGGL(focal_sum_kernel<0>, dim3(grid), dim3(HC_BLOCK), 0, s, p, g, n, l.head, l.nq, k, slots); break;
-    case 1: hipLaunchKernelGGL(focal_sum_kernel<1>, dim3(grid), dim3(HC_BLOCK), 0, s, p, g, n, l.head, l.nq, k, slots); break;
-    case 2: hipLaunchKernelGGL(focal_sum_kernel<2>, dim3(grid), dim3(HC_BLOCK), 0, s, p, g, n, l.head, l.nq, k, slots); break;
-    default: hipLaunchKernelGGL(focal_sum_kernel<3>, dim3(grid), dim3(HC_BLOCK), 0, s, p, g, n, l.head, l.nq, k, slots); break;
-    }
-    RU_CHECK_LAUNCH("focal_sum_kernel");
-    hipLaunchKernelGGL(sum_slots_kernel, dim3(1), dim3(HC_BLOCK), 0, s, (const double*)slots, (size_t)grid, sum_out);
-    RU_CHECK_LAUNCH("sum_slots_kernel");
-    return RU_OK;
+    return with_mode<0, 3>(focal_mode(gamma), [&](auto mode) {
+        return total_launch(FocalSumOp<mode()>{p, g, k}, n, l, (double*)ws, sum_out, s, "focal_sum_kernel");
+    });
 }
 
 extern "C" int ru_focal_grad(const float* p, const float* g, size_t n, float gamma, float a1, float a0w, double count, const float* scale, float* dp,
@@ -360,17 +324,11 @@ extern "C" int ru_focal_grad(const float* p, const float* g, size_t n, float gam
     hipStream_t s = (hipStream_t)stream;
     const void* const ptrs[3] = {p, g, dp};
     const Lanes l = lanes_for(n, ptrs);
-    const unsigned grid = fl_grid(l, n);
     const FocalP k{gamma, a1, a0w};
     const float mult = (float)(1.0 / count);
-    switch (focal_mode(gamma)) {
-    case 0: hipLaunchKernelGGL(focal_grad_kernel<0>, dim3(grid), dim3(HC_BLOCK), 0, s, p, g, n, l.head, l.nq, k, mult, scale, dp); break;
-    case 1: hipLaunchKernelGGL(focal_grad_kernel<1>, dim3(grid), dim3(HC_BLOCK), 0, s, p, g, n, l.head, l.nq, k, mult, scale, dp); break;
-    case 2: hipLaunchKernelGGL(focal_grad_kernel<2>, dim3(grid), dim3(HC_BLOCK), 0, s, p, g, n, l.head, l.nq, k, mult, scale, dp); break;
-    default: hipLaunchKernelGGL(focal_grad_kernel<3>, dim3(grid), dim3(HC_BLOCK), 0, s, p, g, n, l.head, l.nq, k, mult, scale, dp); break;
-    }
-    RU_CHECK_LAUNCH("focal_grad_kernel");
-    return RU_OK;
+    return with_mode<0, 3>(focal_mode(gamma), [&](auto mode) {
+        return stream_launch(FocalGradOp<mode()>{p, g, k, mult, scale, dp}, n, l, s, "focal_grad_kernel");
+    });
 }
 
 extern "C" int ru_tversky_eval(const double* totals, int N, int C, double alpha, double beta, double gamma, double smooth, double priority,
@@ -404,24 +362,22 @@ extern "C" int ru_topk_select(const float* p, const float* g, size_t n, unsigned
     const Lanes l1 = lanes_for(n, kp);
     const void* const ko[1] = {keys};
     const Lanes l2 = lanes_for(n, ko);
-    hipLaunchKernelGGL(topk_key_kernel, dim3(fl_grid(l1, n)), dim3(HC_BLOCK), 0, s, p, g, n, l1.head, l1.nq, bg_weight, keys, hist);
+    hipLaunchKernelGGL(topk_key_kernel, dim3(fl_grid(l1, n)), dim3(HC_BLOCK), 0, s, p, g, n, l1, bg_weight, keys, hist);
     RU_CHECK_LAUNCH("topk_key_kernel");
     hipLaunchKernelGGL(topk_scan_kernel, dim3(1), dim3(HC_BLOCK), 0, s, (const unsigned*)hist, 21, K, st);
     RU_CHECK_LAUNCH("topk_scan_kernel");
-    hipLaunchKernelGGL((topk_hist_kernel<10, 11>), dim3(fl_grid(l2, n)), dim3(HC_BLOCK), 0, s, (const unsigned*)keys, n, l2.head, l2.nq,
+    hipLaunchKernelGGL((topk_hist_kernel<10, 11>), dim3(fl_grid(l2, n)), dim3(HC_BLOCK), 0, s, (const unsigned*)keys, n, l2,
                        (const unsigned long long*)st, hist + HC_BINS);
     RU_CHECK_LAUNCH("topk_hist_kernel");
     hipLaunchKernelGGL(topk_scan_kernel, dim3(1), dim3(HC_BLOCK), 0, s, (const unsigned*)(hist + HC_BINS), 10, 0ull, st);
     RU_CHECK_LAUNCH("topk_scan_kernel");
-    hipLaunchKernelGGL((topk_hist_kernel<0, 10>), dim3(fl_grid(l2, n)), dim3(HC_BLOCK), 0, s, (const unsigned*)keys, n, l2.head, l2.nq,
+    hipLaunchKernelGGL((topk_hist_kernel<0, 10>), dim3(fl_grid(l2, n)), dim3(HC_BLOCK), 0, s, (const unsigned*)keys, n, l2,
                        (const unsigned long long*)st, hist + 2 * HC_BINS);
     RU_CHECK_LAUNCH("topk_hist_kernel");
     hipLaunchKernelGGL(topk_scan_kernel, dim3(1), dim3(HC_BLOCK), 0, s, (const unsigned*)(hist + 2 * HC_BINS), 0, 0ull, st);
     RU_CHECK_LAUNCH("topk_scan_kernel");
-    const unsigned grid = fl_slots(n);
-    hipLaunchKernelGGL(topk_value_kernel, dim3(grid), dim3(HC_BLOCK), 0, s, (const unsigned*)keys, n, l2.head, l2.nq, (const unsigned long long*)st, slots);
-    RU_CHECK_LAUNCH("topk_value_kernel");
-    hipLaunchKernelGGL(topk_final_kernel, dim3(1), dim3(HC_BLOCK), 0, s, (const double*)slots, (size_t)grid, (const unsigned long long*)st, K, out2);
+    if (int rc = sum_launch(TopkValueOp{keys, st}, n, l2, slots, s, "topk_value_kernel")) return rc;
+    hipLaunchKernelGGL(topk_final_kernel, dim3(1), dim3(HC_BLOCK), 0, s, (const double*)slots, (size_t)fl_slots(n), (const unsigned long long*)st, K, out2);
     RU_CHECK_LAUNCH("topk_final_kernel");
     if (hipMemcpyAsync(state, st, HC_STATE * sizeof(unsigned long long), hipMemcpyDeviceToDevice, s) != hipSuccess)
         return hip_fail(hipGetLastError(), "ru_topk_select: copy");
@@ -435,9 +391,6 @@ extern "C" int ru_topk_grad(const float* p, const float* g, const unsigned* keys
     RU_REQUIRE(aligned4(p) && aligned4(g) && aligned4(keys) && aligned4(dp) && ((uintptr_t)state & 7u) == 0, "ru_topk_grad: misaligned pointer");
     RU_REQUIRE(!overlap(p, dp, n) && !overlap(g, dp, n) && !overlap(keys, dp, n), "ru_topk_grad: dp overlaps an input");
     const void* const ptrs[4] = {p, g, keys, dp};
-    const Lanes l = lanes_for(n, ptrs);
-    hipLaunchKernelGGL(topk_grad_kernel, dim3(fl_grid(l, n)), dim3(HC_BLOCK), 0, (hipStream_t)stream, p, g, keys, n, l.head, l.nq, bg_weight, state, K,
-                       1.0 / ((double)K * world), scale, dp);
-    RU_CHECK_LAUNCH("topk_grad_kernel");
-    return RU_OK;
+    return stream_launch(TopkGradOp{p, g, keys, bg_weight, state, K, 1.0 / ((double)K * world), scale, dp, 0u, 0.f, 0.f}, n, lanes_for(n, ptrs), (hipStream_t)stream,
+                         "topk_grad_kernel");
 }

@@ -1,106 +1,45 @@
 // optim.hip -- the rest of the optimisation recipe beside ru_adam_step (pointwise.hip): the global gradient norm and its clipping
 // coefficient, SGD with (Nesterov) momentum, AdamW, an exponential moving average of the weights and an in-place exchange of two buffers.
 //
-//   torch.nn.utils.clip_grad_norm_   norm over any number of runs, coef = min(1, max_norm / (norm + 1e-6))  -> gradnorm_partial_kernel,
-//                                                                                                             gradnorm_finalize_kernel
+//   torch.nn.utils.clip_grad_norm_   norm over any number of runs, coef = min(1, max_norm / (norm + 1e-6))  -> SquareOp, gradnorm_finalize_kernel
 //   torch.optim.SGD                  d = coef*g + wd*w; buf = first ? d : mom*buf + (1-damp)*d; u = nesterov ? d + mom*buf : buf; w -= lr*u
 //   torch.optim.AdamW / Adam         decoupled: w *= 1 - lr*wd first; else adam_kernel's arithmetic on coef*g
 //
-// All of it is streaming work over runs of the flat parameter / gradient bucket, which start at arbitrary ELEMENT offsets.  One lane
-// layout serves every kernel (stream_kernel): a lane owns 4 consecutive floats and moves them as 16 bytes; the elements before the run's
-// first 16-byte boundary and those after its last whole quad are taken one float at a time by the first lanes of the grid.  The grid is
-// capped at OPT_GRID_CAP workgroups and strides.  The coefficient stays on the device (a float the finalize wrote): nothing here waits
-// for the host.  No float atomics: the norm's partial sums are float64, one slot per workgroup, added in slot order by one workgroup.
+// All of it is streaming work over runs of the flat parameter / gradient bucket, which start at arbitrary ELEMENT offsets, in the lane
+// layout of flat_lanes.hpp: the update kernels are ops of its stream_kernel, the norm's partial sums an op of its sum_kernel.  The coefficient
+// stays on the device (a float the finalize wrote): nothing here waits for the host.  No float atomics: the norm's partial sums are float64,
+// one slot per workgroup, added in slot order by one workgroup.
 #include "ru_common.h"
 #include "pw_helpers.hpp"
+#include "flat_lanes.hpp"
 
 #include <math.h>
 #include <stdint.h>
 
 namespace ru {
-
-constexpr int OPT_BLOCK = 256;
-constexpr unsigned OPT_GRID_CAP = 2048;          // 256 CUs x 8 workgroups: one resident wave of workgroups, the rest by grid stride
-
-// [0, head) scalar | nq quads from `head` | the remaining (< 4) elements scalar.  The quads are 16-byte aligned for EVERY pointer of the
-// call only if all of them sit at the same offset from a 16-byte boundary (runs of buffers laid out alike do); otherwise all is scalar.
-struct Lanes { size_t head, nq; };
-template <int N>
-static inline Lanes lanes_for(size_t n, const void* const (&ptrs)[N]) {
-    const uintptr_t a0 = (uintptr_t)ptrs[0] & 15u;
-    bool alike = (a0 & 3u) == 0;
-    for (int i = 1; i < N; ++i)
-        if (ptrs[i] && ((uintptr_t)ptrs[i] & 15u) != a0) alike = false;
-    if (!alike) return Lanes{n, 0};
-    size_t head = ((16u - a0) & 15u) / 4u;
-    if (head > n) head = n;
-    return Lanes{head, (n - head) / 4};
-}
-static inline unsigned opt_grid(const Lanes& l, size_t n) {
-    const size_t edge = n - 4 * l.nq;
-    return grid1d(l.nq > edge ? l.nq : edge, OPT_BLOCK, OPT_GRID_CAP);
-}
+namespace {
 
 __device__ __forceinline__ float mul_rn(float a, float b) {        // a product that is rounded on its own, never folded into an fma
 #pragma clang fp contract(off)
     return a * b;
 }
 
-// Op: `load(i)` fetches elements [i, i + 4) of every operand through 16-byte accesses, `finish(i, q)` updates and stores them; `one(i)` does
-// element i; both run the same scalar arithmetic.  (Keeping the loads of two quads in flight per lane measured no faster: every pass on the
-// network's runs sits within a few microseconds of its three launches' floor, tools/optim_time.py.)
-template <class Op>
-__global__ __launch_bounds__(OPT_BLOCK) void stream_kernel(Op op, size_t n, size_t head, size_t nq) {
-    const size_t t = (size_t)blockIdx.x * OPT_BLOCK + threadIdx.x, T = (size_t)gridDim.x * OPT_BLOCK;
-    for (size_t q = t; q < nq; q += T) {
-        auto a = op.load(head + 4 * q);
-        op.finish(head + 4 * q, a);
-    }
-    const size_t edge = n - 4 * nq;                                  // head + tail: at most 6 elements when the quads exist
-    for (size_t e = t; e < edge; e += T) op.one(e < head ? e : e + 4 * nq);
-}
-template <class Op>
-static int stream_launch(const Op& op, size_t n, const Lanes& l, hipStream_t s, const char* what) {
-    hipLaunchKernelGGL(stream_kernel<Op>, dim3(opt_grid(l, n)), dim3(OPT_BLOCK), 0, s, op, n, l.head, l.nq);
-    RU_CHECK_LAUNCH(what);
-    return RU_OK;
-}
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
-
 // ------------------------------------------------------------------ global L2 norm, float64
-__global__ __launch_bounds__(OPT_BLOCK) void gradnorm_partial_kernel(const float* __restrict__ g, size_t n, size_t head, size_t nq, double* __restrict__ slots) {
-    __shared__ double buf[4];
-    const size_t t = (size_t)blockIdx.x * OPT_BLOCK + threadIdx.x, T = (size_t)gridDim.x * OPT_BLOCK;
-    double acc = 0.0;
-    auto sq = [](const float4& v) {
+struct SquareOp {
+    const float* g;
+    __device__ __forceinline__ double quad(size_t i) const {
+        const float4 v = ld4(g + i);
         const double x = v.x, y = v.y, z = v.z, w = v.w;
         return (x * x + y * y) + (z * z + w * w);
-    };
-    for (size_t q = t; q < nq; q += T) acc += sq(ld4(g + head + 4 * q));
-    const size_t edge = n - 4 * nq;
-    for (size_t e = t; e < edge; e += T) {
-        const double x = g[e < head ? e : e + 4 * nq];
-        acc += x * x;
     }
-    const double tot = block_sum_d(acc, buf);
-    if (threadIdx.x == 0) slots[blockIdx.x] = tot;                   // every workgroup of the grid writes its own slot, zeros included
-}
+    __device__ __forceinline__ double one(size_t i) const { const double x = g[i]; return x * x; }
+};
 
-// one workgroup: lane t adds its contiguous share of the slots in index order, lane 0 then adds the 256 shares in lane order
-__global__ __launch_bounds__(OPT_BLOCK) void gradnorm_finalize_kernel(const double* __restrict__ slots, size_t n_slots, double max_norm,
-                                                                      double* __restrict__ norm_out, float* __restrict__ coef_out) {
-    __shared__ double part[OPT_BLOCK];
-    const size_t per = (n_slots + OPT_BLOCK - 1) / OPT_BLOCK;
-    const size_t lo = per * threadIdx.x, hi = lo + per < n_slots ? lo + per : n_slots;
-    double acc = 0.0;
-    for (size_t i = lo; i < hi; ++i) acc += slots[i];
-    part[threadIdx.x] = acc;
-    __syncthreads();
+__global__ __launch_bounds__(FL_BLOCK) void gradnorm_finalize_kernel(const double* __restrict__ slots, size_t n_slots, double max_norm,
+                                                                     double* __restrict__ norm_out, float* __restrict__ coef_out) {
+    __shared__ double part[FL_BLOCK];
+    const double tot = sum_slots(slots, n_slots, part);
     if (threadIdx.x == 0) {
-        double tot = 0.0;
-        for (int i = 0; i < OPT_BLOCK; ++i) tot += part[i];
         const double norm = sqrt(tot);
         const double c = max_norm / (norm + 1e-6);                   // clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max=1.0); NaN stays NaN
         *norm_out = norm;
@@ -219,31 +158,26 @@ struct SwapOp {
 };
 
 template <bool AMS, bool DEC>
-static int adamw_launch(float* w, const float* g, float* m, float* v, float* vmax, const float* coef, size_t n, float lr, float b1, float b2, float eps,
+int adamw_launch(float* w, const float* g, float* m, float* v, float* vmax, const float* coef, size_t n, float lr, float b1, float b2, float eps,
                         float wd, int step, const Lanes& l, hipStream_t s) {
     const double bc1 = 1.0 - pow((double)b1, (double)step), bc2 = 1.0 - pow((double)b2, (double)step);       // as adam_launch
     AdamWOp<AMS, DEC> op{w, g, m, v, vmax, coef, (float)((double)lr / bc1), b1, b2, eps, wd, (float)sqrt(bc2), (float)(1.0 - (double)lr * (double)wd)};
     return stream_launch(op, n, l, s, "adamw_kernel");
 }
 
-static inline bool overlap(const void* a, const void* b, size_t n) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + 4 * n && y < x + 4 * n;
-}
-
+}  // namespace
 }  // namespace ru
 
 using namespace ru;
 
 extern "C" size_t ru_gradnorm_slots(size_t n) {
-    if (n == 0) return 0;
-    return grid1d((n + 3) / 4 + 3, OPT_BLOCK, OPT_GRID_CAP);         // an upper bound of the grid for every alignment of the run
+    return n ? fl_slots(n) : 0;
 }
 
 extern "C" size_t ru_gradnorm_workspace_bytes(size_t n_total, size_t n_runs) {
     // at least the sum of ru_gradnorm_slots over any split of n_total elements into n_runs runs: a run of n elements takes
     // ceil((ceil(n / 4) + 3) / 256) <= (n / 4 + 1) / 256 + 2 slots
-    return sizeof(double) * ((n_total / 4 + n_runs) / OPT_BLOCK + 2 * n_runs + 1);
+    return sizeof(double) * ((n_total / 4 + n_runs) / FL_BLOCK + 2 * n_runs + 1);
 }
 
 extern "C" int ru_gradnorm_partial(const float* g, size_t n, size_t first_slot, double* ws, size_t ws_bytes, ru_stream_t stream) {
@@ -251,18 +185,15 @@ extern "C" int ru_gradnorm_partial(const float* g, size_t n, size_t first_slot, 
     RU_REQUIRE(((uintptr_t)g & 3u) == 0 && ((uintptr_t)ws & 7u) == 0, "ru_gradnorm_partial: misaligned pointer");
     if (n == 0) return RU_OK;
     const void* const ptrs[1] = {g};
-    const Lanes l = lanes_for(n, ptrs);
-    const unsigned grid = (unsigned)ru_gradnorm_slots(n);             // the slot count is a function of n alone: lanes past the work write 0
+    const size_t grid = fl_slots(n);                                 // the slot count is a function of n alone: lanes past the work write 0
     RU_REQUIRE((first_slot + grid) * sizeof(double) <= ws_bytes, "ru_gradnorm_partial: workspace too small for slots [%zu, %zu)", first_slot, first_slot + grid);
-    hipLaunchKernelGGL(gradnorm_partial_kernel, dim3(grid), dim3(OPT_BLOCK), 0, (hipStream_t)stream, g, n, l.head, l.nq, ws + first_slot);
-    RU_CHECK_LAUNCH("gradnorm_partial_kernel");
-    return RU_OK;
+    return sum_launch(SquareOp{g}, n, lanes_for(n, ptrs), ws + first_slot, (hipStream_t)stream, "gradnorm_partial_kernel");
 }
 
 extern "C" int ru_gradnorm_finalize(const double* ws, size_t n_slots, double max_norm, double* norm_out, float* coef_out, ru_stream_t stream) {
     RU_REQUIRE(ws && norm_out && coef_out, "ru_gradnorm_finalize: null argument");
     RU_REQUIRE(!(max_norm < 0.0), "ru_gradnorm_finalize: max_norm must not be negative");
-    hipLaunchKernelGGL(gradnorm_finalize_kernel, dim3(1), dim3(OPT_BLOCK), 0, (hipStream_t)stream, ws, n_slots, max_norm, norm_out, coef_out);
+    hipLaunchKernelGGL(gradnorm_finalize_kernel, dim3(1), dim3(FL_BLOCK), 0, (hipStream_t)stream, ws, n_slots, max_norm, norm_out, coef_out);
     RU_CHECK_LAUNCH("gradnorm_finalize_kernel");
     return RU_OK;
 }

@@ -1,6 +1,6 @@
 """The float64 host restatements of the focal, Tversky and top-k losses (loss.focal_host, tversky_host, topk_host) against straightforward
 float64 torch expressions and their autograd, the parameter checks, the declarations of the device entries, and the property of the
-committed top-k inputs that tests/test_hardcrit.py relies on.  No GPU."""
+committed top-k inputs that tests/test_hardcrit.py and tests/test_flat_passes.py rely on.  No GPU."""
 import os
 import re
 
@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import flat_sweep as F
 import hardcrit_inputs as I
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -173,3 +174,16 @@ def test_committed_topk_inputs_leave_few_elements_near_the_threshold():
             assert n_eq == 1 and n_gt == K - 1                        # no float64 tie at the threshold
             near = int((np.abs(l - t) <= I.BAND * abs(t)).sum())
             assert 1 <= near <= I.BAND_CAP, (bg_weight, k, near)
+
+
+def test_sweep_topk_inputs_leave_few_elements_near_the_threshold():
+    """the same property for the inputs of tests/test_flat_passes.py's top-k sweep up to 4099 elements (and its case with pointers at
+    different offsets), where the gradient is compared element by element outside the band; K is max(1, n // 10) there"""
+    from brats2019_amd import loss as L
+    for n, off in [c for c in F.SWEEP if c[0] <= 4099] + [(F.MIXED_N, 4)]:
+        p, g = F.probabilities(n, off)
+        K, k, bg_weight = F.topk_case(n, off)
+        l, K_h, t, n_gt, n_eq = L.topk_host_threshold(p, g, k=k, bg_weight=bg_weight)
+        assert K_h == K and n_eq == 1 and n_gt == K - 1               # no float64 tie at the threshold
+        near = int((np.abs(l - t) <= I.BAND * abs(t)).sum())
+        assert 1 <= near <= I.BAND_CAP, (n, off, near)

@@ -7,16 +7,12 @@ import numpy as np
 import pytest
 import torch
 
+from flat_sweep import NS, OFFSETS, Slab
 from oracle import resunet_oracle as O
 from brats2019_amd import optim
 
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
-
-NS = [1, 3, 4, 5, 255, 1027, 4099, (1 << 21) + 4099]         # the last is past one sweep of the 2048-workgroup grid (2048 * 256 lanes * 4 floats = 2^21)
-OFFSETS = [0, 1, 2, 3]
-GUARD = -12345.0
-PAD = 4                                                      # guard elements on either side of a run
 
 
 @pytest.fixture(scope="module")
@@ -29,23 +25,6 @@ def lib():
 def _stream():
     from brats2019_amd import _lib as L
     return L.stream()
-
-
-class Slab:
-    """a run of n floats at element offset `off` from a 16-byte boundary, PAD guard elements before it and PAD + (4 - off) after"""
-
-    def __init__(self, values, off):
-        self.n, self.lo = len(values), PAD + off
-        host = np.full(self.lo + self.n + PAD + 4, GUARD, dtype=np.float32)
-        host[self.lo:self.lo + self.n] = values
-        self.t = T(host).cuda()
-        assert self.t.data_ptr() % 16 == 0
-        self.ptr = C.c_void_p(self.t.data_ptr() + 4 * self.lo)
-
-    def get(self):
-        h = self.t.cpu().numpy()
-        assert np.all(h[:self.lo] == GUARD) and np.all(h[self.lo + self.n:] == GUARD), "a kernel wrote outside its run"
-        return h[self.lo:self.lo + self.n].copy()
 
 
 def _rand(rng, n, scale=1.0, positive=False):
