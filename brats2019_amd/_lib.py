@@ -153,6 +153,10 @@ SIGNATURES = {
     "ru_augment_patch": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "ru_augment_patch_soft": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "ru_augment_patch_affine": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "ru_case_probe": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "ru_case_pack": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "ru_case_unpack": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ru_augment_batch_packed": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "ru_elastic_workspace_bytes": (_sz, [_i, _i, _i]),
     "ru_elastic_noise": (_i, [C.c_ulonglong, _i, _i, _i, _vp, _vp]),
     "ru_elastic_field": (_i, [_vp, _d, _d, _i, _i, _i, _vp, _vp, _sz, _vp]),
@@ -210,6 +214,23 @@ INT_MAXC, INT_MAX_RADIUS = 8, 8
 
 # ru_augment_patch_affine (include/resunet_hip.h): thread mappings
 AFFINE_MAPPINGS = {"default": 0, "row": 1, "brick": 2}
+
+
+# packed cases and the batched gather (include/resunet_hip.h): RU_PACK_*, RU_AUG_*, ru_case_desc, ru_patch_desc
+PACK_F32, PACK_U16 = 0, 1
+PACK_KINDS = {"float32": PACK_F32, "uint16": PACK_U16}
+AUG_ZOOM, AUG_AFFINE = 0, 1
+AUG_BATCH_MAX = 8
+
+
+class CaseDesc(C.Structure):
+    _fields_ = [("image", _vp), ("label", _vp), ("soft", _vp), ("kind", _i), ("C", _i), ("dims", _i * 3), ("box_lo", _i * 3), ("box_size", _i * 3),
+                ("mean", _f * 8), ("inv_std", _f * 8)]
+
+
+class PatchDesc(C.Structure):
+    _fields_ = [("mode", _i), ("flags", _i), ("mapping", _i), ("crop_lo", _i * 3), ("scale", _d * 3), ("matrix", _d * 9), ("offset", _d * 3),
+                ("gain", _f * 8), ("bias", _f * 8)]
 
 
 class IntensityParams(C.Structure):

@@ -3,6 +3,7 @@
 // and its transpose, the Dice+BCE criterion, and Adam(amsgrad).  All are streaming kernels: 16-byte coalesced
 // accesses along W (NCDHW), one pass per tensor, two-stage deterministic reductions (no float atomics).
 #include "pw_helpers.hpp"
+#include "augment_voxel.hpp"
 
 namespace ru {
 
@@ -1249,75 +1250,20 @@ int zscore_stats_launch(const float* x, double* stats, int C, size_t V, void* ws
 // 'reflect' = linear interpolation on the half-sample-symmetric extension of the CROP, source coordinate = scale * output index)
 // of the z-scored modalities and of the one-hot label -> flips of D, H, W -> optional D<->H transpose -> per-channel gain / bias
 // -> WT / TC / ET soft targets.  One thread per output voxel: the 8 corner offsets and weights are shared by all channels.
-__device__ __forceinline__ int reflect_idx(int i, int n) {
-    int m = i % (2 * n);
-    if (m < 0) m += 2 * n;
-    return m < n ? m : 2 * n - 1 - m;
-}
 // SOFT: the three target channels are the SAME interpolation (corner offsets, weights, flips, transpose) of a.soft's float channels instead of
 // the one-hot label -- affine_transform(soft, (1, sx, sy, sz), order=1, mode='reflect'), dataloader.py:179 applied to a teacher's region maps.
+// The per-voxel function is zoom_voxel (augment_voxel.hpp), shared with the packed gather of resident.hip.
 template <bool SOFT>
 __global__ __launch_bounds__(256) void augment_patch_kernel(const AugmentArgs a) {
     const int P0 = a.P[0], P1 = a.P[1], P2 = a.P[2];
     const bool tr = (a.flags & 8) != 0;
     const int Q0 = tr ? P1 : P0, Q1 = tr ? P0 : P1;                // output extents
     const size_t total = (size_t)Q0 * Q1 * P2;
-    const size_t HW = (size_t)a.H * a.W, DHW = (size_t)a.D * HW;
+    const SrcVolume S(a.image, a.label, a.soft, a.D, a.H, a.W);
     for (size_t o = (size_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (size_t)gridDim.x * 256) {
         const int k = (int)(o % P2);
         const size_t r = o / P2;
-        const int j = (int)(r % Q1), i = (int)(r / Q1);
-        const int pa = tr ? j : i, pb = tr ? i : j;                // indices before the transpose
-        const int p[3] = {(a.flags & 1) ? P0 - 1 - pa : pa, (a.flags & 2) ? P1 - 1 - pb : pb, (a.flags & 4) ? P2 - 1 - k : k};
-        size_t off[3][2];
-        float wgt[3][2];
-#pragma unroll
-        for (int ax = 0; ax < 3; ++ax) {
-            const double x = (double)p[ax] * a.scale[ax];
-            const double f = floor(x);
-            const int i0 = (int)f;
-            const float t = (float)(x - f);
-            const size_t stride = ax == 0 ? HW : (ax == 1 ? (size_t)a.W : 1);
-            off[ax][0] = (size_t)(reflect_idx(i0, a.P[ax]) + a.lo[ax]) * stride;
-            off[ax][1] = (size_t)(reflect_idx(i0 + 1, a.P[ax]) + a.lo[ax]) * stride;
-            wgt[ax][0] = 1.f - t;
-            wgt[ax][1] = t;
-        }
-        float acc[RU_AUG_MAXC];
-#pragma unroll
-        for (int c = 0; c < RU_AUG_MAXC; ++c) acc[c] = 0.f;
-        float cw1 = 0.f, cw2 = 0.f, cw3 = 0.f;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int qa = q >> 2, qb = (q >> 1) & 1, qc = q & 1;
-            const float w = wgt[0][qa] * wgt[1][qb] * wgt[2][qc];
-            const size_t v = off[0][qa] + off[1][qb] + off[2][qc];
-#pragma unroll
-            for (int c = 0; c < RU_AUG_MAXC; ++c)
-                if (c < a.C) acc[c] += w * a.image[(size_t)c * DHW + v];
-            if (SOFT) {                                            // cw1..3 hold WT, TC, ET
-                cw1 += w * a.soft[v];
-                cw2 += w * a.soft[DHW + v];
-                cw3 += w * a.soft[2 * DHW + v];
-            } else {
-                const int l = a.label[v];
-                cw1 += l == 1 ? w : 0.f;
-                cw2 += l == 2 ? w : 0.f;
-                cw3 += l == 3 ? w : 0.f;
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < RU_AUG_MAXC; ++c)
-            if (c < a.C) a.data[(size_t)c * total + o] = ((acc[c] - a.mean[c]) * a.istd[c]) * a.gain[c] + a.bias[c];
-        if (SOFT) {
-            a.target[o] = cw1;
-            a.target[total + o] = cw2;
-            a.target[2 * total + o] = cw3;
-        } else {
-            a.target[o] = (cw1 + cw2) + cw3;                       // WT = 1 + 2 + 3
-            a.target[total + o] = cw1 + cw3;                       // TC = 1 + 3
-            a.target[2 * total + o] = cw3;                         // ET = 3
-        }
+        zoom_voxel<SOFT>(a, S, a.data, a.target, (int)(r / Q1), (int)(r % Q1), k, o, total);
     }
 }
 int augment_patch_launch(const AugmentArgs& a, hipStream_t s) {

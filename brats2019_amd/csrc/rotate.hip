@@ -28,6 +28,7 @@
 // Both mappings run the same per-voxel function, so they give the same bytes.  No atomics, no workspace, no synchronisation: the call only enqueues.
 #include "ru_common.h"
 #include "pw_helpers.hpp"
+#include "augment_voxel.hpp"
 
 #include <limits.h>
 #include <math.h>
@@ -47,108 +48,29 @@ struct AffineArgs {
     float mean[RU_AUG_MAXC], istd[RU_AUG_MAXC], gain[RU_AUG_MAXC], bias[RU_AUG_MAXC];
 };
 
-// source coordinate of one axis; the roundings are the host restatement's (no fused multiply-add)
-__device__ __forceinline__ double affine_coord(const double* m, double off, double q0, double q1, double q2, int n) {
-#pragma clang fp contract(off)
-    double s = ((m[0] * q0 + m[1] * q1) + m[2] * q2) + off;
-    if (!(s >= -2.0)) s = -2.0;                                    // NaN too
-    if (s > (double)n) s = (double)n;
-    return s;
-}
-
-// one output voxel (i, j, k) of the final layout [Q0][Q1][P2], linear index o
-template <bool SOFT>
-__device__ __forceinline__ void affine_voxel(const AffineArgs& a, int i, int j, int k, size_t o, size_t total) {
-    const bool tr = (a.flags & 8) != 0;
-    const size_t HW = (size_t)a.H * a.W, DHW = (size_t)a.D * HW;
-    const int pa = tr ? j : i, pb = tr ? i : j;                    // indices before the transpose
-    const int p[3] = {(a.flags & 1) ? a.P[0] - 1 - pa : pa, (a.flags & 2) ? a.P[1] - 1 - pb : pb, (a.flags & 4) ? a.P[2] - 1 - k : k};
-    const int dims[3] = {a.D, a.H, a.W};
-    size_t off[3][2];
-    float wgt[3][2];
-    bool in[3][2];
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-        const double x = affine_coord(a.m + 3 * ax, a.off[ax], (double)p[0], (double)p[1], (double)p[2], dims[ax]);
-        const double f = floor(x);
-        const int i0 = (int)f;                                     // -2 .. dims[ax]
-        const float t = (float)(x - f);
-        const size_t stride = ax == 0 ? HW : (ax == 1 ? (size_t)a.W : 1);
-        in[ax][0] = i0 >= 0 && i0 < dims[ax];
-        in[ax][1] = i0 + 1 >= 0 && i0 + 1 < dims[ax];
-        off[ax][0] = in[ax][0] ? (size_t)i0 * stride : 0;          // an outside corner is never loaded; its offset only has to be harmless
-        off[ax][1] = in[ax][1] ? (size_t)(i0 + 1) * stride : 0;
-        wgt[ax][0] = 1.f - t;
-        wgt[ax][1] = t;
-    }
-    float acc[RU_AUG_MAXC];
-#pragma unroll
-    for (int c = 0; c < RU_AUG_MAXC; ++c) acc[c] = 0.f;
-    float cw1 = 0.f, cw2 = 0.f, cw3 = 0.f;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const int qa = q >> 2, qb = (q >> 1) & 1, qc = q & 1;
-        const float w = wgt[0][qa] * wgt[1][qb] * wgt[2][qc];
-        const size_t v = off[0][qa] + off[1][qb] + off[2][qc];
-        const bool inside = in[0][qa] && in[1][qb] && in[2][qc];
-#pragma unroll
-        for (int c = 0; c < RU_AUG_MAXC; ++c)
-            if (c < a.C) acc[c] += w * (inside ? a.image[(size_t)c * DHW + v] : 0.f);
-        if (SOFT) {                                                // cw1..3 hold WT, TC, ET
-            cw1 += w * (inside ? a.soft[v] : 0.f);
-            cw2 += w * (inside ? a.soft[DHW + v] : 0.f);
-            cw3 += w * (inside ? a.soft[2 * DHW + v] : 0.f);
-        } else {
-            const int l = inside ? a.label[v] : 0;
-            cw1 += l == 1 ? w : 0.f;
-            cw2 += l == 2 ? w : 0.f;
-            cw3 += l == 3 ? w : 0.f;
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < RU_AUG_MAXC; ++c)
-        if (c < a.C) a.data[(size_t)c * total + o] = ((acc[c] - a.mean[c]) * a.istd[c]) * a.gain[c] + a.bias[c];
-    if (SOFT) {
-        a.target[o] = cw1;
-        a.target[total + o] = cw2;
-        a.target[2 * total + o] = cw3;
-    } else {
-        a.target[o] = (cw1 + cw2) + cw3;                           // WT = 1 + 2 + 3
-        a.target[total + o] = cw1 + cw3;                           // TC = 1 + 3
-        a.target[2 * total + o] = cw3;                             // ET = 3
-    }
-}
-
+// The per-voxel function is affine_voxel (augment_voxel.hpp), shared with the packed gather of resident.hip; so are the brick constants.
 template <bool SOFT>
 __global__ __launch_bounds__(256) void affine_row_kernel(const AffineArgs a) {
     const bool tr = (a.flags & 8) != 0;
     const int Q0 = tr ? a.P[1] : a.P[0], Q1 = tr ? a.P[0] : a.P[1], P2 = a.P[2];
     const size_t total = (size_t)Q0 * Q1 * P2;
+    const SrcVolume S(a.image, a.label, a.soft, a.D, a.H, a.W);
     for (size_t o = (size_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (size_t)gridDim.x * 256) {
         const int k = (int)(o % P2);
         const size_t r = o / P2;
-        affine_voxel<SOFT>(a, (int)(r / Q1), (int)(r % Q1), k, o, total);
+        affine_voxel<SOFT>(a, S, S.dims, a.data, a.target, (int)(r / Q1), (int)(r % Q1), k, o, total);
     }
 }
 
-// a wave's brick is AF_BI x AF_BJ x AF_BK = 64 output voxels (D x H x W of the output layout); a workgroup's 4 waves sit 2 x 2 along H and W
-constexpr unsigned AF_BI = 4, AF_BJ = 2, AF_BK = 8, AF_WJ = 2, AF_WK = 2;
-constexpr unsigned AF_TILE_I = AF_BI, AF_TILE_J = AF_BJ * AF_WJ, AF_TILE_K = AF_BK * AF_WK;       // 4 x 4 x 16 per workgroup
-static_assert(AF_BI * AF_BJ * AF_BK == 64 && AF_WJ * AF_WK == 4, "one brick per wavefront, four wavefronts per workgroup");
-struct AffineTiles { unsigned n0, n1, n2; };                       // tiles per output axis; n0 * n1 * n2 workgroups
 template <bool SOFT>
 __global__ __launch_bounds__(256) void affine_brick_kernel(const AffineArgs a, const AffineTiles tiles) {
     const bool tr = (a.flags & 8) != 0;
     const int Q0 = tr ? a.P[1] : a.P[0], Q1 = tr ? a.P[0] : a.P[1], P2 = a.P[2];
     const size_t total = (size_t)Q0 * Q1 * P2;
-    const unsigned t2 = blockIdx.x % tiles.n2, r = blockIdx.x / tiles.n2;
-    const unsigned t1 = r % tiles.n1, t0 = r / tiles.n1;
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const int i = (int)(t0 * AF_TILE_I + lane / (AF_BK * AF_BJ));
-    const int j = (int)(t1 * AF_TILE_J + (wave / AF_WK) * AF_BJ + (lane / AF_BK) % AF_BJ);
-    const int k = (int)(t2 * AF_TILE_K + (wave % AF_WK) * AF_BK + lane % AF_BK);
-    if (i < Q0 && j < Q1 && k < P2)                                // bricks are clipped at the far faces
-        affine_voxel<SOFT>(a, i, j, k, ((size_t)i * Q1 + j) * P2 + k, total);
+    const SrcVolume S(a.image, a.label, a.soft, a.D, a.H, a.W);
+    int i, j, k;
+    if (brick_voxel(tiles, blockIdx.x, threadIdx.x, Q0, Q1, P2, i, j, k))      // bricks are clipped at the far faces
+        affine_voxel<SOFT>(a, S, S.dims, a.data, a.target, i, j, k, ((size_t)i * Q1 + j) * P2 + k, total);
 }
 
 }  // namespace ru

@@ -22,6 +22,13 @@ Opt-in: rotation (csrc/rotate.hip), the spatial transform nnU-Net's recipes rely
 parameters of `augment_patch` replaces the zoom pass by `ru_augment_patch_affine`: the patch is gathered from the WHOLE resident volume through a
 3 x 3 matrix and an offset (scipy's affine_transform convention, order 1, zero fill outside the volume), so a rotated patch shows real tissue in its
 corners.  `SimpleReader(..., rotation=True)` draws the angles from a private generator; `affine_patch_host` is the float64 restatement.
+
+Opt-in: the whole training set resident in HBM (csrc/resident.hip).  A list reader uploads a case (143 MB of float32 at BraTS size), runs numpy over its
+label and waits for the device every time it changes case -- once per patch with the reference's settings.  `ResidentCases(cases, patch_size)` does that
+work ONCE per case and keeps each case cropped to its non-zero box, as uint16 where that is exact (see `pack_case_host`); `SimpleReader(store, ...)`
+then only selects a view, `augment_patch` takes the view (`ResidentCase`) in place of a `DeviceCase`, `augment_batch` cuts a whole batch in one launch
+and `ResidentLoader` stands in for the `DataLoader`.  The per-voxel arithmetic is the one function of csrc/augment_voxel.hpp, so every patch equals the
+list reader's bit for bit.
 """
 from __future__ import annotations
 
@@ -154,7 +161,8 @@ def augment_patch(case, p, patch_size=None):
     `offset` the matrix acts about the patch centre as above).  The crop need not lie inside the volume: outside it the image is raw 0, the targets 0.
     An optional `mapping` ("row" / "brick") picks the kernel's thread mapping; the result does not depend on it."""
     patch = tuple(int(v) for v in (patch_size or case.patch_size))
-    c, d, h, w = (int(v) for v in case.image.shape)
+    resident = isinstance(case, ResidentCase)            # a view of a ResidentCases store: the packed gather runs in the slot of the two passes
+    c, d, h, w = ((case.channels,) + case.shape) if resident else (int(v) for v in case.image.shape)
     el = p.get("elastic")
     rot = p.get("rotation")
     affine = None if rot is None else _rotation_transform(rot, p["crop_lo"], p["scale"], patch)      # argument checks before any launch
@@ -174,6 +182,13 @@ def augment_patch(case, p, patch_size=None):
     soft = getattr(case, "soft", None)
     gain = [float(v) for v in p["gain"]] if direct else [1.0] * c
     bias = [float(v) for v in p["bias"]] if direct else [0.0] * c
+    if resident:
+        _packed_gather([case], [_patch_desc(flags, gain, bias, crop_lo=p["crop_lo"], scale=p["scale"], affine=affine)], patch, data, target)
+        if direct:
+            return data, target
+        if noise is None:
+            noise = elastic_noise(int(el["seed"]), patch, case.image.device)
+        return elastic_warp(data, target, elastic_field(noise, sigma, alpha), p["flips"], p["transpose"], p["gain"], p["bias"])
     if affine is not None:
         matrix, offset, mapping = affine
         L.check(lib.ru_augment_patch_affine(L.f32(case.image), L.ptr(case.label), None if soft is None else L.f32(soft),
@@ -201,6 +216,209 @@ def augment_patch(case, p, patch_size=None):
         noise = elastic_noise(int(el["seed"]), patch, case.image.device)
     disp = elastic_field(noise, sigma, alpha)
     return elastic_warp(data, target, disp, p["flips"], p["transpose"], p["gain"], p["bias"])
+
+
+# ---------------------------------------------------------------------------------------------------------------- resident training set
+# csrc/resident.hip: packed cases (`ru_case_probe` / `ru_case_pack` / `ru_case_unpack`) and the batched gather (`ru_augment_batch_packed`).
+def pack_case_host(image, label, soft=None):
+    """(box_lo, box_size, kind) of a case, the numpy restatement of `ru_case_probe`: the box bounds every voxel where the bit pattern of any image
+    or soft channel is not that of +0.0f (so -0.0 and NaN are inside) or the label is not 0 -- (0,0,0) / (1,1,1) for an all-zero case -- and kind
+    is "uint16" if every image value x (as float32) satisfies bits(float32(uint16(x))) == bits(x), else "float32": a negative, fractional,
+    above-65535, -0.0 or NaN value anywhere makes the case float32."""
+    x = np.ascontiguousarray(image, dtype=np.float32)
+    if x.ndim != 4:
+        raise ValueError("resident: image must be [C,D,H,W], got shape %s" % (x.shape,))
+    lab = np.asarray(label)
+    if lab.shape != x.shape[1:]:
+        raise ValueError("resident: label must be [D,H,W] = %s, got %s" % (x.shape[1:], lab.shape))
+    bits = x.view(np.uint32)
+    occupied = (bits != 0).any(axis=0) | (lab != 0)
+    if soft is not None:
+        sf = np.ascontiguousarray(soft.detach().cpu().numpy() if isinstance(soft, torch.Tensor) else soft, dtype=np.float32)
+        if sf.shape != (3,) + x.shape[1:]:
+            raise ValueError("resident: soft targets must be [3,D,H,W] = %s, got %s" % ((3,) + x.shape[1:], sf.shape))
+        occupied |= (sf.view(np.uint32) != 0).any(axis=0)
+    box = _bbox3(occupied)
+    if box[0][0] < 0:
+        lo, size = (0, 0, 0), (1, 1, 1)
+    else:
+        lo, size = tuple(int(v) for v in box[0]), tuple(int(v) for v in box[1] - box[0] + 1)
+    with np.errstate(invalid="ignore"):
+        ranged = (x >= 0) & (x <= 65535)
+    back = np.where(ranged, x, 0).astype(np.uint16).astype(np.float32)
+    exact = bool(ranged.all() and (back.view(np.uint32) == bits).all())
+    return lo, size, ("uint16" if exact else "float32")
+
+
+class ResidentCase(object):
+    """One case of a `ResidentCases` store: a view, nothing is copied.  `image` / `label` / `soft` are the PACKED device tensors (the crop of the
+    case to `box` = (lo, size); `image` uint16 or float32 by `kind`); `mean`, `std`, `bbox`, `patch_size` are `DeviceCase`'s, `channels` and
+    `shape` = (D, H, W) those of the whole case.  `augment_patch` takes it in place of a `DeviceCase`."""
+
+    def __init__(self, image, label, soft, kind, box, shape, mean, std, bbox, patch_size):
+        self.image, self.label, self.soft = image, label, soft
+        self.kind, self.box, self.shape = kind, box, tuple(int(v) for v in shape)
+        self.channels = int(image.shape[0])
+        self.mean, self.std, self.bbox, self.patch_size = mean, std, bbox, patch_size
+        self.nbytes = sum(int(t.numel()) * t.element_size() for t in (image, label, soft) if t is not None)
+        d = L.CaseDesc()
+        d.image, d.label, d.soft = image.data_ptr(), label.data_ptr(), (None if soft is None else soft.data_ptr())
+        d.kind, d.C = L.PACK_KINDS[kind], self.channels
+        d.dims[:], d.box_lo[:], d.box_size[:] = self.shape, box[0], box[1]
+        d.mean[:self.channels] = [float(v) for v in mean]                      # the values `augment_patch` hands to ru_augment_patch
+        with np.errstate(all="ignore"):                                        # an all-zero case has no statistics, here as in a DeviceCase
+            d.inv_std[:self.channels] = [float(1.0 / v) for v in std]
+        self._desc = d
+
+
+class ResidentCases(object):
+    """The training set resident in HBM.  `cases` is what `SimpleReader` takes: (image [C,D,H,W], label [D,H,W][, soft [3,D,H,W]]) arrays or
+    callables returning them, each called ONCE, here.  Per case, in order: the float32 upload to a transient buffer, `remap_labels`,
+    `zscore_stats` on the full upload (so `mean` / `std` are `DeviceCase`'s bit for bit), `label_bbox` on the host, `ru_case_probe` and
+    `ru_case_pack` (see `pack_case_host` for the rules); the transient buffer is then freed.  `dtype`: "auto" stores a case as uint16 where that is
+    exact and as float32 otherwise, "float32" forces float32, "uint16" raises on a case that is not exact.  `max_bytes` (optional) bounds the
+    store: the case that would exceed it raises before its allocation.  `store[i]` is a `ResidentCase`, `store.nbytes` the bytes held,
+    `store.unpack(i)` the full (image, label, soft or None) device tensors back, byte for byte."""
+
+    def __init__(self, cases, patch_size, device="cuda", dtype="auto", max_bytes=None):
+        if dtype not in ("auto", "float32", "uint16"):
+            raise ValueError("resident: dtype must be 'auto', 'float32' or 'uint16', got %r" % (dtype,))
+        if max_bytes is not None and (isinstance(max_bytes, bool) or not isinstance(max_bytes, (int, np.integer)) or max_bytes < 0):
+            raise ValueError("resident: max_bytes must be a non-negative integer or None, got %r" % (max_bytes,))
+        self.patch_size = tuple(int(p) for p in patch_size)
+        if len(self.patch_size) != 3 or min(self.patch_size) < 1:
+            raise ValueError("resident: patch_size must hold three positive extents, got %r" % (patch_size,))
+        self.device, self.dtype, self.max_bytes = device, dtype, max_bytes
+        self.nbytes = 0
+        self._views = []
+        cases = list(cases)
+        if cases:
+            L.require_gpu()
+        for index, src in enumerate(cases):
+            item = src() if callable(src) else src
+            self._views.append(self._pack(index, item[0], item[1], item[2] if len(item) > 2 else None))
+            self.nbytes += self._views[-1].nbytes
+
+    def _pack(self, index, image, label, soft):
+        lib = L.load()
+        label = remap_labels(label)
+        full = torch.as_tensor(np.ascontiguousarray(image, dtype=np.float32)).to(self.device)
+        if full.dim() != 4 or tuple(full.shape[1:]) != tuple(label.shape):
+            raise ValueError("resident: case %d: image must be [C,D,H,W] over the label's %s, got %s" % (index, tuple(label.shape), tuple(full.shape)))
+        c, d, h, w = (int(v) for v in full.shape)
+        lab = torch.as_tensor(label).to(self.device)
+        sft = None
+        if soft is not None:
+            if isinstance(soft, torch.Tensor):
+                sft = soft.detach().to(device=self.device, dtype=torch.float32).contiguous()
+            else:
+                sft = torch.as_tensor(np.ascontiguousarray(soft, dtype=np.float32)).to(self.device)
+            if tuple(sft.shape) != (3, d, h, w):
+                raise ValueError("soft targets must be [3,D,H,W] = %s, got %s" % ((3, d, h, w), tuple(sft.shape)))
+        mean, std = zscore_stats(full)
+        bbox = label_bbox(label, self.patch_size)
+        probe = torch.empty(8, dtype=torch.int32, device=full.device)
+        L.check(lib.ru_case_probe(L.f32(full), L.ptr(lab), None if sft is None else L.f32(sft), c, d, h, w, L.ptr(probe), L.stream()), "ru_case_probe")
+        probe = [int(v) for v in probe.cpu()]
+        lo, size, exact = tuple(probe[0:3]), tuple(probe[3:6]), bool(probe[6])
+        if self.dtype == "uint16" and not exact:
+            raise ValueError("resident: case %d is not exact in uint16 (a negative, fractional, above-65535, -0.0 or NaN value) and dtype='uint16'" % index)
+        kind = "uint16" if (exact and self.dtype != "float32") else "float32"
+        voxels = size[0] * size[1] * size[2]
+        need = voxels * (c * (2 if kind == "uint16" else 4) + 1 + (12 if sft is not None else 0))
+        if self.max_bytes is not None and self.nbytes + need > self.max_bytes:
+            raise ValueError("resident: case %d needs %d bytes; with the %d already held that exceeds max_bytes = %d" % (index, need, self.nbytes, self.max_bytes))
+        pimage = torch.empty((c,) + size, dtype=torch.uint16 if kind == "uint16" else torch.float32, device=full.device)
+        plabel = torch.empty(size, dtype=torch.uint8, device=full.device)
+        psoft = None if sft is None else torch.empty((3,) + size, dtype=torch.float32, device=full.device)
+        L.check(lib.ru_case_pack(L.f32(full), L.ptr(lab), None if sft is None else L.f32(sft), c, d, h, w, _arr(C.c_int, list(lo)), _arr(C.c_int, list(size)),
+                                 L.PACK_KINDS[kind], L.ptr(pimage), L.ptr(plabel), None if psoft is None else L.f32(psoft), L.stream()), "ru_case_pack")
+        return ResidentCase(pimage, plabel, psoft, kind, (lo, size), (d, h, w), mean, std, bbox, self.patch_size)
+
+    def __len__(self):
+        return len(self._views)
+
+    def __getitem__(self, index):
+        return self._views[index]
+
+    def unpack(self, index):
+        """(image [C,D,H,W] float32, label [D,H,W] uint8, soft [3,D,H,W] float32 or None): `ru_case_unpack`, the arrays the case was built from"""
+        v = self._views[index]
+        d, h, w = v.shape
+        image = torch.empty((v.channels, d, h, w), dtype=torch.float32, device=v.image.device)
+        label = torch.empty((d, h, w), dtype=torch.uint8, device=v.image.device)
+        soft = None if v.soft is None else torch.empty((3, d, h, w), dtype=torch.float32, device=v.image.device)
+        L.check(L.load().ru_case_unpack(L.ptr(v.image), L.ptr(v.label), None if v.soft is None else L.f32(v.soft), L.PACK_KINDS[v.kind], v.channels, d, h, w,
+                                        _arr(C.c_int, list(v.box[0])), _arr(C.c_int, list(v.box[1])), L.f32(image), L.ptr(label),
+                                        None if soft is None else L.f32(soft), L.stream()), "ru_case_unpack")
+        return image, label, soft
+
+
+def _patch_desc(flags, gain, bias, crop_lo=None, scale=None, affine=None):
+    """the `ru_patch_desc` (ctypes) of one sample: the affine pass for affine = (matrix, offset, mapping code), else the zoom pass"""
+    q = L.PatchDesc()
+    q.flags = int(flags)
+    if affine is None:
+        q.mode = L.AUG_ZOOM
+        q.crop_lo[:] = [int(v) for v in crop_lo]
+        q.scale[:] = [float(v) for v in scale]
+    else:
+        matrix, offset, mapping = affine
+        q.mode, q.mapping = L.AUG_AFFINE, int(mapping)
+        q.matrix[:] = [float(v) for v in matrix.reshape(-1)]
+        q.offset[:] = [float(v) for v in offset]
+    q.gain[:len(gain)] = [float(v) for v in gain]
+    q.bias[:len(bias)] = [float(v) for v in bias]
+    return q
+
+
+def _packed_gather(views, descs, patch, data, target):
+    """one `ru_augment_batch_packed` call: sample n = (views[n], descs[n]) into data[n] / target[n] (or into data / target for a single sample)"""
+    n = len(views)
+    L.check(L.load().ru_augment_batch_packed((L.CaseDesc * n)(*[v._desc for v in views]), (L.PatchDesc * n)(*descs), n, _arr(C.c_int, list(patch)),
+                                             L.f32(data), L.f32(target), L.stream()), "ru_augment_batch_packed")
+
+
+def _check_batch(patch, params_list):
+    """argument checks of a batch, ValueError before any launch; returns the `ru_patch_desc` list"""
+    descs = []
+    for n, p in enumerate(params_list):
+        if p.get("elastic") is not None:
+            raise ValueError("resident: sample %d has an elastic entry: elastic deformation stays on the per-sample path (augment_patch)" % n)
+        if p["transpose"] and len(params_list) > 1 and patch[0] != patch[1]:
+            raise ValueError("resident: sample %d is transposed: a batch needs P0 == P1, got patch %s" % (n, tuple(patch)))
+        rot = p.get("rotation")
+        affine = None if rot is None else _rotation_transform(rot, p["crop_lo"], p["scale"], patch)
+        descs.append(_patch_desc(_flags(p["flips"], p["transpose"]), p["gain"], p["bias"], crop_lo=p["crop_lo"], scale=p["scale"], affine=affine))
+    return descs
+
+
+def _augment_views(views, params_list, patch, descs=None):
+    descs = _check_batch(patch, params_list) if descs is None else descs
+    n, c = len(views), views[0].channels
+    out_sp = (patch[1], patch[0], patch[2]) if (n == 1 and params_list[0]["transpose"]) else patch
+    data = torch.empty((n, c) + tuple(out_sp), dtype=torch.float32, device=views[0].image.device)
+    target = torch.empty((n, 3) + tuple(out_sp), dtype=torch.float32, device=views[0].image.device)
+    _packed_gather(views, descs, patch, data, target)
+    return data, target
+
+
+def augment_batch(store, indices, params_list):
+    """(data [N,C,Q0,Q1,P2], target [N,3,Q0,Q1,P2]) float32 device tensors: sample n is `augment_patch(store[indices[n]], params_list[n])`, bit for
+    bit, all N from ONE `ru_augment_batch_packed` call (chunks of `RU_AUG_BATCH_MAX` samples per launch) written straight into the batch: no
+    per-sample tensors, no `torch.stack`.  Zoom and rotated samples, uint16 and float32 cases, hard and soft targets mix freely.  Refused
+    (ValueError, before any launch): a sample with an `elastic` entry (elastic deformation stays on the per-sample path), a transposed sample in
+    a batch of more than one unless P0 == P1, an index outside the store."""
+    indices, params_list = [int(i) for i in indices], list(params_list)
+    if len(indices) != len(params_list) or not indices:
+        raise ValueError("resident: one parameter dict per index and at least one sample, got %d indices and %d dicts" % (len(indices), len(params_list)))
+    for i in indices:
+        if not 0 <= i < len(store):
+            raise ValueError("resident: index %d outside the store of %d cases" % (i, len(store)))
+    patch = tuple(int(v) for v in store.patch_size)
+    descs = _check_batch(patch, params_list)
+    L.require_gpu()
+    return _augment_views([store[i] for i in indices], params_list, patch, descs)
 
 
 # ---------------------------------------------------------------------------------------------------------------- rotation
@@ -798,13 +1016,18 @@ class SimpleReader(torch.utils.data.Dataset):
     parameters drawn from a private `random.Random(intensity_seed)`; targets and the global streams are those of `intensity=False`.
     `rotation=True` (nnU-Net's defaults) or a `RotationConfig` rotates a patch with probability `p_rotation` about its own centre (see augment_patch),
     the angles drawn from a private `random.Random(rotation_seed)`: a patch that draws no rotation takes the path above bit for bit, one that does
-    keeps its crop, scale, flip, transpose, gain and bias draws, and the global streams are those of `rotation=False`."""
+    keeps its crop, scale, flip, transpose, gain and bias draws, and the global streams are those of `rotation=False`.
+    `cases` may be a `ResidentCases` store (built for the same `patch_size`): a change of case then selects a view -- no upload, no host numpy, no
+    synchronisation -- and the draws, their order and the items are those of the list reader over the same cases, bit for bit."""
 
     def __init__(self, cases, patch_size, images_in_epoch=4000, patches_from_single_image=1, device="cuda", elastic=False, elastic_seed=None,
                  intensity=False, intensity_seed=None, rotation=False, rotation_seed=None):
         super(SimpleReader, self).__init__()
-        self.cases = list(cases)
+        self.store = cases if isinstance(cases, ResidentCases) else None
+        self.cases = cases if self.store is not None else list(cases)
         self.patch_size = tuple(patch_size)
+        if self.store is not None and tuple(int(v) for v in self.patch_size) != self.store.patch_size:
+            raise ValueError("SimpleReader: the store was built for patch %s, the reader asks for %s" % (self.store.patch_size, self.patch_size))
         self.images_in_epoch = images_in_epoch
         self.patches_from_single_image = patches_from_single_image
         self.device = device
@@ -823,13 +1046,17 @@ class SimpleReader(torch.utils.data.Dataset):
         if self.patches_from_current_image > self.patches_from_single_image or self.case is None:      # dataloader.py:119-121
             self.patches_from_current_image = 0
             self.current_image_index = index
-            src = self.cases[index]
-            item = src() if callable(src) else src
-            image, label = item[0], item[1]
-            self.case = DeviceCase(image, label, self.patch_size, self.device, soft=item[2] if len(item) > 2 else None)
+            if self.store is not None:
+                self.case = self.store[index]
+            else:
+                src = self.cases[index]
+                item = src() if callable(src) else src
+                image, label = item[0], item[1]
+                self.case = DeviceCase(image, label, self.patch_size, self.device, soft=item[2] if len(item) > 2 else None)
         self.patches_from_current_image += 1
 
-    def __getitem__(self, index):
+    def _draw(self, index):
+        """selects the case of item `index` (`self.case`) and makes the item's draws, in the reference's order; returns the parameters"""
         index = index % self.real_length
         self._load(index)
         p = draw_augment_params(self.case.bbox, self.patch_size, int(self.case.image.shape[0]), elastic=self.elastic, elastic_rng=self.elastic_rng)
@@ -837,6 +1064,10 @@ class SimpleReader(torch.utils.data.Dataset):
             rot = draw_rotation_params(self.rotation_rng, self.rotation)
             if rot is not None:
                 p["rotation"] = rot
+        return p
+
+    def __getitem__(self, index):
+        p = self._draw(index)
         data, target = augment_patch(self.case, p)
         if self.intensity is not None:
             data = intensity_augment(data, draw_intensity_params(int(data.shape[0]), self.intensity_rng, self.intensity))
@@ -844,6 +1075,42 @@ class SimpleReader(torch.utils.data.Dataset):
 
     def __len__(self):
         return int(self.images_in_epoch)
+
+
+class ResidentLoader(object):
+    """Stands in for `torch.utils.data.DataLoader` over a `SimpleReader` on a `ResidentCases` store (`Trainer.train` only iterates it and reads
+    `len()`): for every index batch of `batch_sampler` -- default `BatchSampler(RandomSampler(reader), batch_size, drop_last)` -- the reader's draws
+    are made sample by sample in `__getitem__`'s order, ONE `augment_batch` launch writes the batch (a batch with an elastic sample falls back to
+    per-sample `augment_patch` calls and `torch.stack`), `intensity_augment` runs per sample, and ([data], [target]) is yielded: the batches of
+    `DataLoader(reader, batch_sampler=..., num_workers=0)` under the same seeds, bit for bit, without the per-sample tensors and the stack."""
+
+    def __init__(self, reader, batch_size=1, batch_sampler=None, drop_last=True):
+        if not isinstance(reader, SimpleReader) or reader.store is None:
+            raise ValueError("ResidentLoader: the reader must be a SimpleReader over a ResidentCases store")
+        self.reader = reader
+        if batch_sampler is None:
+            batch_sampler = torch.utils.data.BatchSampler(torch.utils.data.RandomSampler(reader), int(batch_size), bool(drop_last))
+        self.batch_sampler = batch_sampler
+
+    def __len__(self):
+        return len(self.batch_sampler)
+
+    def __iter__(self):
+        r = self.reader
+        for batch in self.batch_sampler:
+            views, params = [], []
+            for index in batch:
+                params.append(r._draw(index))
+                views.append(r.case)
+            if any(p.get("elastic") is not None for p in params):
+                items = [augment_patch(v, p) for v, p in zip(views, params)]
+                data, target = torch.stack([d for d, _ in items]), torch.stack([t for _, t in items])
+            else:
+                data, target = _augment_views(views, params, tuple(int(v) for v in r.patch_size))
+            if r.intensity is not None:
+                data = torch.stack([intensity_augment(data[n], draw_intensity_params(int(data.shape[1]), r.intensity_rng, r.intensity))
+                                    for n in range(int(data.shape[0]))])
+            yield [data], [target]
 
 
 class FullReader(torch.utils.data.Dataset):

@@ -908,6 +908,64 @@ size_t ru_intensity_workspace_bytes(int C, int P0, int P1, int P2);
 int ru_intensity_augment(const float* in, float* out, int C, int P0, int P1, int P2, const ru_intensity_params* p, void* ws, size_t ws_bytes,
                          ru_stream_t stream);
 
+/* ---------------------------------------------------------------- the training set resident in HBM (csrc/resident.hip).  Opt-in; the entry points
+ * above are not touched.
+ * A PACKED case is the bounding box [box_lo, box_lo + box_size) of every voxel of image [C][D][H][W] float32, label [D][H][W] uint8 and (optional)
+ * soft [3][D][H][W] float32 that is not zero: a voxel is inside if the BIT PATTERN of any image or soft channel is not that of +0.0f (so -0.0f and
+ * NaN are inside) or its label is not 0.  Inside the box the image is stored as [C][b0][b1][b2] uint16 (RU_PACK_U16) or float32 (RU_PACK_F32), the
+ * label as [b0][b1][b2] uint8, soft as [3][b0][b1][b2] float32.  Outside the box the case is +0.0f / label 0 bit for bit and inside it every value
+ * is stored exactly, so ru_case_unpack(ru_case_pack(x)) == x byte for byte.
+ * ru_case_probe: one pass; out8 (DEVICE, 8 ints) = box_lo[3], box_size[3], exact, 0.  exact = 1 if every image value x satisfies
+ *   bits((float)(uint16)x) == bits(x) -- negative, fractional, above 65535, -0.0f and NaN values clear it; only then may the case be packed as
+ *   RU_PACK_U16.  An all-zero case gets box_lo = (0,0,0), box_size = (1,1,1).  Integer min / max atomics only: two calls give the same bytes.
+ * ru_case_pack: crops to the box (the caller passes what the probe wrote); kind RU_PACK_U16 on a case that is not exact is not detected here.
+ * ru_case_unpack: the inverse, +0.0f / label 0 outside the box.  soft and soft_out are both NULL or both set.
+ * All three only enqueue.  Refused (RU_EINVAL, before any launch): a null pointer, C outside 1..8, an extent <= 0, an unknown kind, a box that does
+ * not lie inside the volume.
+ *
+ * ru_augment_batch_packed: ONE launch cuts N patches from N packed cases (the same case may appear more than once) straight into
+ *   data_out [N][C][Q0][Q1][P2] and target_out [N][3][Q0][Q1][P2]; N = 1 is the single-patch entry.  Sample n is cases[n] + patches[n] (HOST arrays,
+ *   read at launch: the descriptors travel as kernel arguments, at most RU_AUG_BATCH_MAX samples per launch, more are sent in chunks).  A sample of
+ *   mode RU_AUG_ZOOM computes what ru_augment_patch / ru_augment_patch_soft compute on the unpacked case for (crop_lo, patch, scale, flags, gain,
+ *   bias), one of mode RU_AUG_AFFINE what ru_augment_patch_affine computes for (patch, matrix, offset, flags, gain, bias, mapping), bit for bit:
+ *   the kernels instantiate one per-voxel function (csrc/augment_voxel.hpp) on different sources.  A case with soft != NULL gets its targets from
+ *   soft.  Every sample has the same channel count and the same patch; a transposed sample (flags bit 3) in a batch of more than one needs
+ *   P0 == P1.  No workspace, no atomics, no synchronisation: the call only enqueues.  Refused (RU_EINVAL, before any launch): what the
+ *   single-patch entry points refuse (crop outside the volume or scale <= 0 for zoom; matrix or offset not finite, |det| < 1e-6, unknown
+ *   mapping for affine; flags outside bits 0..3; C outside 1..8; patch extents <= 0 or P0 P1 P2 >= 2^31 - 1), N < 1, an unknown kind or mode, a
+ *   box outside its volume, differing channel counts, a transposed sample with P0 != P1 and N > 1. */
+#define RU_PACK_F32 0
+#define RU_PACK_U16 1
+#define RU_AUG_ZOOM 0
+#define RU_AUG_AFFINE 1
+#define RU_AUG_BATCH_MAX 8                /* samples per launch: 8 x 352 bytes of descriptors stay well under HIP's 4 KB of kernel arguments */
+typedef struct ru_case_desc {
+    const void* image;                    /* packed image, DEVICE: uint16 or float32 by `kind` */
+    const unsigned char* label;           /* packed label, DEVICE */
+    const float* soft;                    /* packed soft targets, DEVICE, or NULL */
+    int kind;                             /* RU_PACK_F32 / RU_PACK_U16 */
+    int C;
+    int dims[3];                          /* D, H, W of the whole case */
+    int box_lo[3], box_size[3];
+    float mean[8], inv_std[8];            /* z-score constants per channel */
+} ru_case_desc;
+typedef struct ru_patch_desc {
+    int mode;                             /* RU_AUG_ZOOM / RU_AUG_AFFINE */
+    int flags;                            /* bit 0/1/2: flip D/H/W, bit 3: transpose D <-> H */
+    int mapping;                          /* affine: RU_AFFINE_MAP_*; zoom: ignored */
+    int crop_lo[3];                       /* zoom */
+    double scale[3];                      /* zoom */
+    double matrix[9], offset[3];          /* affine */
+    float gain[8], bias[8];
+} ru_patch_desc;
+int ru_case_probe(const float* image, const unsigned char* label, const float* soft, int C, int D, int H, int W, int* out8, ru_stream_t stream);
+int ru_case_pack(const float* image, const unsigned char* label, const float* soft, int C, int D, int H, int W, const int* box_lo,
+                 const int* box_size, int kind, void* image_out, unsigned char* label_out, float* soft_out, ru_stream_t stream);
+int ru_case_unpack(const void* image, const unsigned char* label, const float* soft, int kind, int C, int D, int H, int W, const int* box_lo,
+                   const int* box_size, float* image_out, unsigned char* label_out, float* soft_out, ru_stream_t stream);
+int ru_augment_batch_packed(const ru_case_desc* cases, const ru_patch_desc* patches, int N, const int* patch, float* data_out, float* target_out,
+                            ru_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
