@@ -1,4 +1,4 @@
-// engine.hip -- C-ABI entry points of libresunet_hip.so and the whole-network executor (ru_unet_*).
+// engine.hip -- the whole-network executor (ru_unet_*) of libresunet_hip.so and the library's error state (ru_last_error).
 //
 // The executor walks the topology of model.UNet (model.py:309-433) once per call and enqueues every kernel on
 // the caller's stream; all scratch (activations kept for backward, packed weights, reduction partials) is
@@ -11,6 +11,7 @@
 //   out = x + lrelu(y2*scale2+shift2)                               (one streaming pass)
 // i.e. the GroupNorm-apply + LeakyReLU between the two convolutions never touches HBM.
 #include "ru_common.h"
+#include "arena.hpp"
 
 #include <vector>
 #include <math.h>
@@ -38,34 +39,6 @@ constexpr float kSlope = 1e-2f;   // LeakyReLU(1e-2), model.py:93-94,352
 constexpr int kGroups = 8;        // GroupNorm(8, C), model.py:95-96,338
 constexpr float kEps = 1e-5f;
 constexpr int kInCh = 4;          // model.py:336
-
-// Bump allocator over the caller's workspace.  Tensors grow from the bottom (`off`); an inference forward REWINDS to a mark when a
-// block's temporaries are dead (everything runs on one stream, so a later kernel may overwrite them), `peak` is the high-water mark.
-// Small per-layer arrays that must outlive those rewinds (GroupNorm mean / rstd / scale / shift, read by ru_unet_gn_stats and by the
-// backward) are taken from the TOP of the workspace (`keep`).  The dry walk of ru_unet_workspace_bytes mirrors the real one call for call.
-struct Arena {
-    char* base = nullptr;
-    size_t cap = 0, off = 0, peak = 0, keep = 0;
-    bool dry = true, failed = false;
-    float* alloc(size_t nfloats) {
-        const size_t bytes = align_up(nfloats * sizeof(float), 256);
-        const size_t o = off;
-        off += bytes;
-        if (off > peak) peak = off;
-        if (dry) return nullptr;
-        if (off + keep > (cap & ~(size_t)255)) { failed = true; return nullptr; }
-        return reinterpret_cast<float*>(base + o);
-    }
-    float* alloc_keep(size_t nfloats) {
-        keep += align_up(nfloats * sizeof(float), 256);
-        if (dry) return nullptr;
-        const size_t top = cap & ~(size_t)255;           // (a caller may pass any size: the top region stays 256-byte aligned)
-        if (off + keep > top) { failed = true; return nullptr; }
-        return reinterpret_cast<float*>(base + top - keep);
-    }
-    void rewind(size_t mark) { off = mark; }
-    size_t need() const { return peak + keep; }
-};
 
 // ---------------------------------------------------------------------- the environment (switches.hpp: the table of every variable)
 static bool env_is(const char* name, char c) { const char* e = getenv(name); return e && *e == c; }
@@ -152,27 +125,16 @@ static void sink_end(hipStream_t s) {
     k.used += 2;
 }
 
-#define RU_RUN(call)                      \
-    do {                                  \
-        if (!A.dry) {                     \
-            if (A.failed) { set_error("workspace too small"); return RU_ENOMEM; } \
-            if (t_sink) sink_begin(#call, s); \
-            const int rc__ = (call);      \
-            if (t_sink) sink_end(s);      \
-            if (rc__ != RU_OK) return rc__; \
-            if (env_trace()) { const int rt__ = trace_sync(#call, s); if (rt__ != RU_OK) return rt__; } \
-        }                                 \
-    } while (0)
-
-__global__ void gn_scale_shift_kernel(const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
-                                      const float* __restrict__ rstd, float* __restrict__ scale, float* __restrict__ shift, int N, int C, int G) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N * C) return;
-    const int n = i / C, c = i % C, g = c / (C / G);
-    const float a = gamma[c] * rstd[n * G + g];
-    scale[i] = a;
-    shift[i] = beta[c] - mean[n * G + g] * a;
+// one launch of the executor: the family sink's event pair around it, RU_TRACE's synchronisation behind it
+template <class F>
+static int run_probed(const char* call, hipStream_t s, F&& launch) {
+    if (t_sink) sink_begin(call, s);
+    const int rc = launch();
+    if (t_sink) sink_end(s);
+    if (rc != RU_OK) return rc;
+    return env_trace() ? trace_sync(call, s) : RU_OK;
 }
+#define RU_RUN(call) RU_ARENA_RUN(run_probed(#call, s, [&] { return (call); }))
 
 }  // namespace ru
 
@@ -1452,563 +1414,10 @@ extern "C" int ru_unet_gn_stats(ru_unet_t h, int idx, float* mean, float* rstd, 
     return RU_OK;
 }
 
-// ====================================================================== op-level C-ABI
+// ====================================================================== library state (the op-level C-ABI is op_abi.hip)
 extern "C" const char* ru_last_error(void) { return g_err; }
 extern "C" int ru_version(void) { return 100; }
 extern "C" int ru_device_ok(void) {
     int n = 0;
     return (hipGetDeviceCount(&n) == hipSuccess && n > 0) ? 1 : 0;
-}
-
-struct WsCarver {
-    char* base; size_t cap, off = 0; bool failed = false;
-    WsCarver(void* b, size_t c) : base((char*)b), cap(c) {}
-    float* take(size_t nfloats) {
-        const size_t bytes = align_up(nfloats * sizeof(float), 256);
-        if (!base || off + bytes > cap) { failed = true; return nullptr; }
-        float* p = (float*)(base + off);
-        off += bytes;
-        return p;
-    }
-};
-#define RU_WS_OK(w) do { if ((w).failed) { set_error("workspace too small"); return RU_ENOMEM; } } while (0)
-
-extern "C" size_t ru_conv3d_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W, int k) {
-    size_t b = 4096;
-    if (k == 3) {
-        b += align_up(conv3_packed_floats(Cin, Cout) * 4, 256) + align_up(conv3_packed_floats(Cout, Cin) * 4, 256);
-        b += align_up(conv3_sb_frag_bytes(Cin, Cout), 256) + align_up(conv3_sb_frag_bytes(Cout, Cin), 256);
-        b += align_up(wgrad3_workspace_bytes(N, Cin, Cout, D, H, W), 256) + align_up(bias_grad_workspace_bytes(N, Cout, (size_t)D * H * W), 256);
-    } else if (k == 1) {
-        b += align_up((size_t)Cin * Cout * 4, 256) + align_up(wgrad1_workspace_bytes(N, Cin, Cout, (size_t)D * H * W), 256);
-    } else if (k == 2) {
-        const size_t Vo = (size_t)(D / 2) * (H / 2) * (W / 2);
-        b += align_up((size_t)N * 8 * Cin * Vo * 4, 256) + align_up((size_t)8 * Cin * Cout * 4, 256) + align_up(wgrad1_workspace_bytes(N, 8 * Cin, Cout, Vo), 256);
-    }
-    return b;
-}
-
-extern "C" int ru_conv3d_fwd(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Cout, int D, int H, int W, int k,
-                             void* ws, size_t ws_bytes, ru_stream_t stream) {
-    return ru_conv3d_fwd_p(x, w, bias, y, N, Cin, Cout, D, H, W, k, RU_PREC_F32, ws, ws_bytes, stream);
-}
-
-// pack one 3x3x3 weight for `precision` into the workspace and fill the weight fields of `a`
-static int prep_conv3_weights(Conv3Args& a, const float* w, int Cin_f, int Cout_f, int mode, int precision, int W, WsCarver& C, hipStream_t s) {
-    const int cin_conv = mode == 0 ? Cin_f : Cout_f, cout_conv = mode == 0 ? Cout_f : Cin_f;
-    a.mode = precision;
-    if (conv3_effective_mode(precision, W) == RU_PREC_BF16X3) {
-        void* wf = C.take(conv3_sb_frag_bytes(cin_conv, cout_conv) / 4 + 64);
-        RU_WS_OK(C);
-        a.wfrag = wf;
-        return conv3_sb_pack_weights(w, wf, Cin_f, Cout_f, mode, s);
-    }
-    float* wp = C.take(conv3_packed_floats(cin_conv, cout_conv));
-    RU_WS_OK(C);
-    a.wp = wp;
-    return conv3_pack_weights(w, wp, Cin_f, Cout_f, mode, s);
-}
-
-extern "C" int ru_conv3d_fwd_p(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Cout, int D, int H, int W, int k,
-                               int precision, void* ws, size_t ws_bytes, ru_stream_t stream) {
-    RU_REQUIRE(x && w && y, "ru_conv3d_fwd: null argument");
-    RU_REQUIRE(precision == RU_PREC_F32 || precision == RU_PREC_BF16X3, "ru_conv3d_fwd: bad precision");
-    hipStream_t s = (hipStream_t)stream;
-    WsCarver C(ws, ws_bytes);
-    if (k == 3) {
-        Conv3Args a{};
-        int rc = prep_conv3_weights(a, w, Cin, Cout, 0, precision, W, C, s);
-        if (rc) return rc;
-        a.x = x; a.bias = bias; a.y = y; a.N = N; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W;
-        return conv3_launch(a, switches_from_env(), s);
-    }
-    RU_REQUIRE(!bias, "ru_conv3d_fwd: bias only supported for k=3 (model.py:348)");
-    if (k == 1) {
-        float* wT = C.take((size_t)Cin * Cout);
-        RU_WS_OK(C);
-        int rc = transpose_launch(w, wT, Cout, Cin, s);
-        if (rc) return rc;
-        Conv1Args a{};
-        a.x0 = x; a.C0 = Cin; a.wT = wT; a.ldw = Cout; a.y = y; a.out_slope = 1.f; a.N = N; a.Cout = Cout; a.V = (size_t)D * H * W;
-        return conv1_launch(a, s);
-    }
-    if (k == 2) {
-        RU_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, "ru_conv3d_fwd: k=2 needs even extents");
-        const size_t Vo = (size_t)(D / 2) * (H / 2) * (W / 2);
-        float* xs = C.take((size_t)N * 8 * Cin * Vo);
-        float* wT = C.take((size_t)8 * Cin * Cout);
-        RU_WS_OK(C);
-        int rc = s2d_launch(x, xs, N, Cin, D, H, W, s);
-        if (rc) return rc;
-        rc = transpose_launch(w, wT, Cout, 8 * Cin, s);
-        if (rc) return rc;
-        Conv1Args a{};
-        a.x0 = xs; a.C0 = 8 * Cin; a.wT = wT; a.ldw = Cout; a.y = y; a.out_slope = 1.f; a.N = N; a.Cout = Cout; a.V = Vo;
-        return conv1_launch(a, s);
-    }
-    set_error("ru_conv3d_fwd: unsupported kernel size %d", k);
-    return RU_EINVAL;
-}
-
-extern "C" int ru_conv3d_bwd_data(const float* dy, const float* w, float* dx, int N, int Cin, int Cout, int D, int H, int W, int k,
-                                  void* ws, size_t ws_bytes, ru_stream_t stream) {
-    return ru_conv3d_bwd_data_p(dy, w, dx, N, Cin, Cout, D, H, W, k, RU_PREC_F32, ws, ws_bytes, stream);
-}
-
-extern "C" int ru_conv3d_bwd_data_p(const float* dy, const float* w, float* dx, int N, int Cin, int Cout, int D, int H, int W, int k,
-                                    int precision, void* ws, size_t ws_bytes, ru_stream_t stream) {
-    RU_REQUIRE(dy && w && dx, "ru_conv3d_bwd_data: null argument");
-    RU_REQUIRE(precision == RU_PREC_F32 || precision == RU_PREC_BF16X3, "ru_conv3d_bwd_data: bad precision");
-    hipStream_t s = (hipStream_t)stream;
-    WsCarver C(ws, ws_bytes);
-    if (k == 3) {
-        Conv3Args a{};
-        int rc = prep_conv3_weights(a, w, Cin, Cout, 1, precision, W, C, s);
-        if (rc) return rc;
-        a.x = dy; a.y = dx; a.N = N; a.Cin = Cout; a.Cout = Cin; a.D = D; a.H = H; a.W = W;
-        return conv3_launch(a, switches_from_env(), s);
-    }
-    if (k == 1) {
-        Conv1Args a{};
-        a.x0 = dy; a.C0 = Cout; a.wT = w; a.ldw = Cin; a.y = dx; a.out_slope = 1.f; a.N = N; a.Cout = Cin; a.V = (size_t)D * H * W;
-        return conv1_launch(a, s);
-    }
-    if (k == 2) {
-        RU_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, "ru_conv3d_bwd_data: k=2 needs even extents");
-        const size_t Vo = (size_t)(D / 2) * (H / 2) * (W / 2);
-        float* t = C.take((size_t)N * 8 * Cin * Vo);
-        RU_WS_OK(C);
-        Conv1Args a{};
-        a.x0 = dy; a.C0 = Cout; a.wT = w; a.ldw = 8 * Cin; a.y = t; a.out_slope = 1.f; a.N = N; a.Cout = 8 * Cin; a.V = Vo;
-        int rc = conv1_launch(a, s);
-        if (rc) return rc;
-        return d2s_launch(t, dx, N, Cin, D, H, W, s);
-    }
-    set_error("ru_conv3d_bwd_data: unsupported kernel size %d", k);
-    return RU_EINVAL;
-}
-
-extern "C" int ru_conv3d_bwd_weight(const float* x, const float* dy, float* dw, float* db, int N, int Cin, int Cout, int D, int H, int W, int k,
-                                    void* ws, size_t ws_bytes, ru_stream_t stream) {
-    return ru_conv3d_bwd_weight_p(x, dy, dw, db, N, Cin, Cout, D, H, W, k, RU_PREC_F32, ws, ws_bytes, stream);
-}
-
-extern "C" int ru_conv3d_bwd_weight_p(const float* x, const float* dy, float* dw, float* db, int N, int Cin, int Cout, int D, int H, int W, int k,
-                                      int precision, void* ws, size_t ws_bytes, ru_stream_t stream) {
-    RU_REQUIRE(x && dy && dw, "ru_conv3d_bwd_weight: null argument");
-    RU_REQUIRE(precision == RU_PREC_F32 || precision == RU_PREC_BF16X3, "ru_conv3d_bwd_weight: bad precision");
-    hipStream_t s = (hipStream_t)stream;
-    WsCarver C(ws, ws_bytes);
-    if (k == 3) {
-        Wgrad3Args a{};
-        a.x = x; a.dy = dy; a.dw = dw; a.N = N; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W; a.mode = precision;
-        a.ws_bytes = wgrad3_workspace_bytes(N, Cin, Cout, D, H, W);
-        a.ws = C.take(a.ws_bytes / 4);
-        RU_WS_OK(C);
-        int rc = wgrad3_launch(a, s);
-        if (rc) return rc;
-        if (db) {
-            const size_t b = bias_grad_workspace_bytes(N, Cout, (size_t)D * H * W);
-            float* p = C.take(b / 4 + 1);
-            RU_WS_OK(C);
-            return bias_grad_launch(dy, db, N, Cout, (size_t)D * H * W, p, b, s);
-        }
-        return RU_OK;
-    }
-    RU_REQUIRE(!db, "ru_conv3d_bwd_weight: bias only supported for k=3");
-    if (k == 1) {
-        Wgrad1Args a{};
-        a.x = x; a.dy = dy; a.dw = dw; a.ldw = Cin; a.N = N; a.Cin = Cin; a.Cout = Cout; a.V = (size_t)D * H * W;
-        a.ws_bytes = wgrad1_workspace_bytes(N, Cin, Cout, a.V);
-        a.ws = C.take(a.ws_bytes / 4);
-        RU_WS_OK(C);
-        return wgrad1_launch(a, s);
-    }
-    if (k == 2) {
-        RU_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, "ru_conv3d_bwd_weight: k=2 needs even extents");
-        const size_t Vo = (size_t)(D / 2) * (H / 2) * (W / 2);
-        float* xs = C.take((size_t)N * 8 * Cin * Vo);
-        RU_WS_OK(C);
-        int rc = s2d_launch(x, xs, N, Cin, D, H, W, s);
-        if (rc) return rc;
-        Wgrad1Args a{};
-        a.x = xs; a.dy = dy; a.dw = dw; a.ldw = 8 * Cin; a.N = N; a.Cin = 8 * Cin; a.Cout = Cout; a.V = Vo;
-        a.ws_bytes = wgrad1_workspace_bytes(N, 8 * Cin, Cout, Vo);
-        a.ws = C.take(a.ws_bytes / 4);
-        RU_WS_OK(C);
-        return wgrad1_launch(a, s);
-    }
-    set_error("ru_conv3d_bwd_weight: unsupported kernel size %d", k);
-    return RU_EINVAL;
-}
-
-extern "C" size_t ru_groupnorm_workspace_bytes(int N, int C, size_t V) {
-    return 4096 + align_up((size_t)N * C * gn_stats_tiles(V) * 2 * 4, 256) + 5 * align_up((size_t)N * C * 4, 256) + align_up((size_t)N * C * 3 * 4, 256);
-}
-
-extern "C" int ru_groupnorm_fwd(const float* x, const float* gamma, const float* beta, const float* residual, float* y, float* mean, float* rstd,
-                                int N, int C, size_t V, int G, float eps, float slope, void* ws, size_t ws_bytes, ru_stream_t stream) {
-    RU_REQUIRE(x && gamma && beta && y && mean && rstd, "ru_groupnorm_fwd: null argument");
-    hipStream_t s = (hipStream_t)stream;
-    WsCarver Cw(ws, ws_bytes);
-    const int nblk = gn_stats_tiles(V);
-    float* part = Cw.take((size_t)N * C * nblk * 2);
-    float* scale = Cw.take((size_t)N * C);
-    float* shift = Cw.take((size_t)N * C);
-    RU_WS_OK(Cw);
-    int rc = gn_stats_launch(x, part, N, C, V, s);
-    if (rc) return rc;
-    rc = gn_finalize_launch(part, nblk, gamma, beta, mean, rstd, scale, shift, N, C, V, G, eps, s, nullptr, true);
-    if (rc) return rc;
-    return gn_apply_launch(x, scale, shift, residual, y, N, C, V, slope, s);
-}
-
-extern "C" int ru_groupnorm_bwd(const float* x, const float* gamma, const float* beta, const float* mean, const float* rstd, const float* dy,
-                                float* dx, float* dgamma, float* dbeta, int N, int C, size_t V, int G, float slope,
-                                void* ws, size_t ws_bytes, ru_stream_t stream) {
-    RU_REQUIRE(x && gamma && beta && mean && rstd && dy && dx, "ru_groupnorm_bwd: null argument");
-    RU_REQUIRE(C % G == 0, "ru_groupnorm_bwd: C %% G != 0");
-    hipStream_t s = (hipStream_t)stream;
-    WsCarver Cw(ws, ws_bytes);
-    const int nblk = gn_bwd_tiles(V);
-    float* part = Cw.take((size_t)N * C * nblk * 2);
-    float* scale = Cw.take((size_t)N * C);
-    float* shift = Cw.take((size_t)N * C);
-    float* coef = Cw.take((size_t)N * C * 3);
-    RU_WS_OK(Cw);
-    hipLaunchKernelGGL(gn_scale_shift_kernel, dim3(cdiv(N * C, 256)), dim3(256), 0, s, gamma, beta, mean, rstd, scale, shift, N, C, G);
-    RU_CHECK_LAUNCH("gn_scale_shift_kernel");
-    int rc = gn_bwd_reduce_launch(x, dy, scale, shift, mean, rstd, slope, part, N, C, V, G, s);
-    if (rc) return rc;
-    rc = gn_bwd_finalize_launch(part, nblk, gamma, mean, rstd, coef, dgamma, dbeta, N, C, V, G, s);
-    if (rc) return rc;
-    return gn_bwd_apply_launch(x, dy, scale, shift, coef, slope, dx, N, C, V, s);
-}
-
-extern "C" int ru_leaky_relu_fwd(const float* x, float* y, size_t n, float slope, ru_stream_t stream) { return lrelu_fwd_launch(x, y, n, slope, (hipStream_t)stream); }
-extern "C" int ru_leaky_relu_bwd(const float* y, const float* dy, float* dx, size_t n, float slope, ru_stream_t stream) { return lrelu_bwd_launch(y, dy, dx, n, slope, (hipStream_t)stream); }
-extern "C" int ru_upsample2x_trilinear_fwd(const float* x, float* y, int N, int C, int D, int H, int W, ru_stream_t stream) { return up2_fwd_launch(x, y, N, C, D, H, W, (hipStream_t)stream); }
-extern "C" int ru_upsample2x_trilinear_bwd(const float* dy, float* dx, int N, int C, int D, int H, int W, ru_stream_t stream) { return up2_bwd_launch(dy, dx, N, C, D, H, W, (hipStream_t)stream); }
-extern "C" int ru_sigmoid_fwd(const float* x, float* y, size_t n, ru_stream_t stream) { return sigmoid_launch(x, y, n, (hipStream_t)stream); }
-
-extern "C" size_t ru_criterion_workspace_bytes(int N, int C, size_t V) { return 4096 + (size_t)N * C * crit_tiles(V) * 3 * sizeof(float); }
-extern "C" int ru_criterion_sums(const float* p, const float* g, double* sums, int N, int C, size_t V, float bg_weight, void* ws, size_t ws_bytes, ru_stream_t stream) {
-    RU_REQUIRE(p && g && sums, "ru_criterion_sums: null argument");
-    return crit_sums_launch(p, g, sums, N, C, V, bg_weight, ws, ws_bytes, (hipStream_t)stream);
-}
-extern "C" int ru_criterion_grad(const float* p, const float* g, const double* sums, double count, float w_dice, float w_bce, float bg_weight,
-                                 float priority, float* dp, int N, int C, size_t V, ru_stream_t stream) {
-    RU_REQUIRE(p && g && sums && dp && count > 0, "ru_criterion_grad: bad argument");
-    return crit_grad_launch(p, g, sums, count, w_dice, w_bce, bg_weight, priority, dp, N, C, V, (hipStream_t)stream);
-}
-extern "C" int ru_criterion_value(const double* sums_host, int C, double count, double priority, double* dice, double* bce) {
-    RU_REQUIRE(sums_host && C > 0 && count > 0, "ru_criterion_value: bad argument");
-    double acc = 0.0;
-    for (int c = 0; c < C; ++c) acc += 2.0 * (sums_host[c] + 1e-6) / (sums_host[C + c] + 2e-6);   // loss.py:114-117
-    if (dice) *dice = priority * (1.0 - acc / C);                                                  // loss.py:122
-    if (bce) *bce = -sums_host[2 * C] / count;                                                     // loss.py:79
-    return RU_OK;
-}
-extern "C" int ru_criterion_value_device(const double* sums, int C, double count, double priority, double w_dice, double w_bce, double* out3,
-                                         ru_stream_t stream) {
-    RU_REQUIRE(sums && out3 && C > 0 && C <= 64 && count > 0, "ru_criterion_value_device: bad argument");
-    return crit_value_launch(sums, C, count, priority, w_dice, w_bce, out3, (hipStream_t)stream);
-}
-extern "C" int ru_adam_amsgrad_step(float* w, const float* g, float* m, float* v, float* vmax, size_t n, float lr, float beta1, float beta2,
-                                    float eps, float weight_decay, int step, ru_stream_t stream) {
-    RU_REQUIRE(w && g && m && v && vmax, "ru_adam_amsgrad_step: null argument");
-    return adam_launch(w, g, m, v, vmax, n, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
-}
-
-extern "C" int ru_adam_step(float* w, const float* g, float* m, float* v, float* vmax_or_null, size_t n, float lr, float beta1, float beta2,
-                            float eps, float weight_decay, int step, ru_stream_t stream) {
-    RU_REQUIRE(w && g && m && v, "ru_adam_step: null argument");
-    return adam_launch(w, g, m, v, vmax_or_null, n, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream);
-}
-
-// ---------------------------------------------------------------- inference post-processing
-extern "C" int ru_tta_merge(const float* probs, int K, unsigned flips, float* mean_out, unsigned char* mask, unsigned long long* counts,
-                            int C, int D, int H, int W, ru_stream_t stream) {
-    RU_REQUIRE(probs && mask && counts, "ru_tta_merge: null argument");
-    return tta_merge_launch(probs, K, flips, mean_out, mask, counts, C, D, H, W, (hipStream_t)stream);
-}
-extern "C" int ru_compose_labels(const unsigned char* mask, const unsigned long long* counts, unsigned long long et_min, unsigned char* labels,
-                                 size_t V, ru_stream_t stream) {
-    RU_REQUIRE(mask && counts && labels, "ru_compose_labels: null argument");
-    return compose_labels_launch(mask, counts, et_min, labels, V, (hipStream_t)stream);
-}
-
-extern "C" int ru_dice_accumulate(const unsigned long long* counts, double* acc, int N, int C, int nacc, ru_stream_t stream) {
-    return dice_accumulate_launch(counts, acc, N, C, nacc, (hipStream_t)stream);
-}
-extern "C" int ru_dice_counts(const float* p, const float* g, unsigned long long* counts, int N, int C, size_t V, ru_stream_t stream) {
-    RU_REQUIRE(p && g && counts && N > 0 && C > 0, "ru_dice_counts: bad argument");
-    return dice_counts_launch(p, g, counts, N * C, V, (hipStream_t)stream);
-}
-
-// ====================================================================== C16 layout hooks (tests / probes)
-extern "C" int ru_layout_convert(const float* src, float* dst, int N, int C, size_t V, int to_c16, ru_stream_t stream) {
-    RU_REQUIRE(src && dst && N > 0, "ru_layout_convert: bad argument");
-    return layout_convert_launch(src, dst, N, C, V, to_c16, (hipStream_t)stream);
-}
-
-extern "C" int ru_upsample2x_trilinear_fwd_l(const float* x, float* y, int N, int C, int D, int H, int W, float out_slope, ru_stream_t stream) {
-    RU_REQUIRE(x && y && N > 0 && C > 0 && D > 0 && H > 0 && W > 0, "ru_upsample2x_trilinear_fwd_l: bad argument");
-    return up2_fwd16_launch(x, y, N, C, D, H, W, out_slope, (hipStream_t)stream);
-}
-extern "C" int ru_upsample2x_trilinear_bwd_l(const float* dy, float* dx, int N, int C, int D, int H, int W, ru_stream_t stream) {
-    RU_REQUIRE(dy && dx && N > 0 && C > 0 && D > 0 && H > 0 && W > 0, "ru_upsample2x_trilinear_bwd_l: bad argument");
-    return up2_bwd16_launch(dy, dx, N, C, D, H, W, (hipStream_t)stream);
-}
-extern "C" int ru_conv3d_fwd_l(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Cout, int D, int H, int W,
-                               int flags, void* ws, size_t ws_bytes, ru_stream_t stream) {
-    RU_REQUIRE(x && w && y, "ru_conv3d_fwd_l: null argument");
-    const Switches sw = switches_from_env();
-    hipStream_t s = (hipStream_t)stream;
-    WsCarver C(ws, ws_bytes);
-    Conv3Args a{};
-    void* wf = C.take(conv3_sb_frag_bytes(Cin, Cout) / 4 + 64);
-    RU_WS_OK(C);
-    const bool f32 = (flags & 16) != 0;                          // exact-f32 arithmetic on voxel-major tensors (conv3_f32c_kernel)
-    a.products = (flags & 32) ? 2 : 0;                           // the input is an activation tensor: fp16 + MX-fp8 products where the shape has that kernel (conv3_mx.hpp)
-    RU_REQUIRE(!f32 || ((flags & 3) != 0 && !(flags & (4 | 8))), "ru_conv3d_fwd_l: the exact-f32 form needs a voxel-major side and takes neither the 4-channel copy nor a split-form input");
-    // flag bit 6: x (float32, voxel-major) is a GRADIENT -- where conv3_mx_kernel<GRAD> takes the shape it is converted to the gradient-operand form of the MX scheme
-    // (conv3_mxg_split_launch; in a training step wgrad3_tz<1,0,3,3> writes that form) and convolved with bf16 main + MX cross products; elsewhere the bit is ignored
-    const bool gop = (flags & 64) && !f32 && (flags & 3) == 3 && !(flags & (4 | 8)) && !bias && conv3_mxg_usable(sw, N, Cin, Cout, D, H, W);
-    int rc = f32 ? conv3_f32c_pack_weights(w, wf, Cin, Cout, 0, s) : conv3_sb_pack_weights(w, wf, Cin, Cout, 0, s, gop);
-    if (rc) return rc;
-    a.mode = f32 ? RU_PREC_F32 : RU_PREC_BF16X3; a.wfrag = wf;
-    a.in_c16 = flags & 1; a.out_c16 = (flags >> 1) & 1;
-    a.in_s16 = (flags >> 3) & 1;                                 // x is voxel-major in SPLIT form (hi / lo bf16 packets, as gn_bwd_apply16 publishes it)
-    RU_REQUIRE(!a.in_s16 || a.in_c16, "ru_conv3d_fwd_l: the split form is a voxel-major layout");
-    a.x = x; a.bias = bias; a.y = y; a.N = N; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W;
-    if (gop) {
-        const size_t nvox = (size_t)N * D * H * W;
-        float* g16 = C.take(nvox * 16);
-        RU_WS_OK(C);
-        rc = conv3_mxg_split_launch(x, g16, nvox, s);
-        if (rc) return rc;
-        a.x = g16; a.in_s16 = 1; a.in_g16 = 1; a.products = 0;
-    }
-    if (flags & 4) {                                             // x NCDHW with Cin <= 4: 4-channel copy + tap-pair kernel
-        RU_REQUIRE(!(flags & 1) && conv3_sb4_usable(N, Cin, Cout, D, H, W), "ru_conv3d_fwd_l: shape does not fit the 4-channel kernel");
-        const size_t V = (size_t)D * H * W;
-        float* x4 = C.take((size_t)N * 4 * V);
-        void* wf4 = C.take(conv3_sb4_frag_bytes(Cout) / 4 + 64);
-        RU_WS_OK(C);
-        rc = pad_to_c4_launch(x, x4, N, Cin, V, s);
-        if (rc) return rc;
-        rc = conv3_sb4_pack_weights(w, wf4, Cin, Cout, 0, s);
-        if (rc) return rc;
-        a.x = x4; a.wfrag = wf4; a.in_c4 = 1;
-    }
-    return f32 ? conv3_launch(a, sw, s) : conv3_sb_launch(a, sw, s);
-}
-
-extern "C" int ru_conv3d_bwd_weight_l(const float* x, const float* dy, float* dw, int N, int Cin, int Cout, int D, int H, int W,
-                                      int flags, void* ws, size_t ws_bytes, ru_stream_t stream) {
-    RU_REQUIRE(x && dy && dw, "ru_conv3d_bwd_weight_l: null argument");
-    WsCarver C(ws, ws_bytes);
-    Wgrad3Args a{};
-    a.x = x; a.dy = dy; a.dw = dw; a.mode = RU_PREC_BF16X3; a.x_c16 = flags & 1; a.dy_c16 = (flags >> 1) & 1;
-    a.N = N; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W;
-    a.ws_bytes = wgrad3_workspace_bytes(N, Cin, Cout, D, H, W);
-    a.ws = C.take(a.ws_bytes / 4);
-    RU_WS_OK(C);
-    return wgrad3_launch(a, (hipStream_t)stream);
-}
-
-// The voxel-major pointwise family, one launch at a time: thin fillers of Conv1Args / Wgrad1Args (no kernels, no arithmetic of their own).
-extern "C" size_t ru_conv1_l_workspace_bytes(int C0, int Cout, int s2d) {
-    return 4096 + (s2d ? 2 * align_up((size_t)C0 * Cout * sizeof(float), 256) : 0);      // both packs of the 2x2x2 weight
-}
-extern "C" int ru_conv1_l(const float* x0, int C0, const float* x1, int C1, const float* w, int ldw, float* y, float* y1, int Cout0,
-                          const float* add, float out_slope, const float* mask, float mask_slope, int N, int Cout, size_t V,
-                          int s2d, int Dc, int Hc, int Wc, const float* bst_y, const float* bst_k, float bst_slope,
-                          float* stat_partials, size_t stat_floats, int* nblk, int* inst, void* ws, size_t ws_bytes, ru_stream_t stream) {
-    RU_REQUIRE(x0 && w && y, "ru_conv1_l: null argument");
-    RU_REQUIRE(s2d >= 0 && s2d <= 2, "ru_conv1_l: s2d is 0 (plain), 1 (gather) or 2 (scatter)");
-    hipStream_t s = (hipStream_t)stream;
-    WsCarver C(ws, ws_bytes);
-    Conv1Args a{};
-    a.x0 = x0; a.C0 = C0; a.x1 = x1; a.C1 = C1; a.wT = w; a.ldw = ldw; a.y = y; a.add = add; a.out_slope = out_slope;
-    a.N = N; a.Cout = Cout; a.V = V; a.s2d = s2d; a.Dc = Dc; a.Hc = Hc; a.Wc = Wc; a.mask = mask; a.mask_slope = mask_slope;
-    a.y1 = y1; a.Cout0 = Cout0; a.bst_y = bst_y; a.bst_k = bst_k; a.bst_slope = bst_slope; a.stat_partials = stat_partials;
-    if (s2d) {
-        // w is the reference's [Cconv_out][Cconv_in][2][2][2]; the engine's pack gives the gather its [Cout][tap*Cin + c] and the scatter its [tap*Cin + c][C0]
-        RU_REQUIRE(C0 > 0 && Cout > 0 && (s2d == 1 ? C0 : Cout) % 8 == 0, "ru_conv1_l: stride-2 modes need 8 x channels on the gathered side");
-        const int co = s2d == 1 ? Cout : C0, ci = (s2d == 1 ? C0 : Cout) / 8;
-        float* wd = C.take((size_t)8 * ci * co);
-        float* wdT = C.take((size_t)8 * ci * co);
-        RU_WS_OK(C);
-        int rc = pack_down16_launch(w, wd, wdT, co, ci, s);
-        if (rc) return rc;
-        a.wT = s2d == 1 ? wd : wdT;
-        a.ldw = C0;
-    }
-    if (inst) *inst = conv1_16_choose(a).packed();
-    if (nblk) *nblk = 0;
-    if (bst_y) {
-        const int nb = conv1_16_bst_nblk(a);             // 0: no fused form -- conv1_16_launch refuses below, with its own message
-        RU_REQUIRE(nb == 0 || (stat_partials && stat_floats >= (size_t)N * (s2d == 2 ? Cout / 8 : Cout) * nb * 2), "ru_conv1_l: statistics buffer too small");
-        if (nblk) *nblk = nb;
-    }
-    return conv1_16_launch(a, s);
-}
-
-// The 3x3x3 family, one launch at a time with every fused operand of Conv3Args (except the tail finalize `fin`, whose ticket is the engine's, and ksplit): a thin
-// filler like ru_conv1_l.  Weights are packed as ru_conv3d_fwd_l packs them; weight_mode = 1 packs the data-gradient form of w = [Cout][Cin][3][3][3] OF THE FORWARD
-// CONVOLUTION (channels swapped, taps mirrored), so that the launch maps x's Cin channels (the forward's outputs) to y's Cout channels as the engine's backward does.
-static size_t c3l_frag_bytes(int Cin, int Cout) { const size_t sb = conv3_sb_frag_bytes(Cin, Cout), f = conv3_f32c_frag_bytes(Cin, Cout); return sb > f ? sb : f; }
-extern "C" size_t ru_conv3_l_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W, int flags) {
-    const size_t nvox = (size_t)N * D * H * W;
-    return 4096 + align_up(c3l_frag_bytes(Cin, Cout) + 256, 256) + ((flags & 4) ? align_up(nvox * 16, 256) + align_up(conv3_sb4_frag_bytes(Cout) + 256, 256) : 0) +
-           ((flags & 64) ? align_up(nvox * 64, 256) : 0);
-}
-extern "C" int ru_conv3_l(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Cout, int D, int H, int W, int flags, int weight_mode,
-                          const float* add, const float* in_scale, const float* in_shift, float in_slope, const float* in_res, float* in_sum_out,
-                          int sigmoid, int products, const float* bst_y, const float* bst_k, float bst_slope, float* stat_partials, size_t stat_floats,
-                          int* nblk, int* route, void* ws, size_t ws_bytes, ru_stream_t stream) {
-    RU_REQUIRE(x && w && y, "ru_conv3_l: null argument");
-    RU_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, "ru_conv3_l: bad shape");
-    RU_REQUIRE(weight_mode == 0 || weight_mode == 1, "ru_conv3_l: weight_mode is 0 (forward packing) or 1 (data-gradient packing)");
-    const Switches sw = switches_from_env();
-    hipStream_t s = (hipStream_t)stream;
-    WsCarver C(ws, ws_bytes);
-    Conv3Args a{};
-    void* wf = C.take(c3l_frag_bytes(Cin, Cout) / 4 + 64);
-    RU_WS_OK(C);
-    const bool f32 = (flags & 16) != 0;
-    a.products = (flags & 32) ? 2 : products;
-    RU_REQUIRE(!f32 || ((flags & 3) != 0 && !(flags & (4 | 8))), "ru_conv3_l: the exact-f32 form needs a voxel-major side and takes neither the 4-channel copy nor a split-form input");
-    const bool gop = (flags & 64) && !f32 && (flags & 3) == 3 && !(flags & (4 | 8)) && !bias && conv3_mxg_usable(sw, N, Cin, Cout, D, H, W);
-    const int Cin_f = weight_mode ? Cout : Cin, Cout_f = weight_mode ? Cin : Cout;       // w's own extents [Cout_f][Cin_f][27]
-    int rc = f32 ? conv3_f32c_pack_weights(w, wf, Cin_f, Cout_f, weight_mode, s) : conv3_sb_pack_weights(w, wf, Cin_f, Cout_f, weight_mode, s, gop);
-    if (rc) return rc;
-    a.mode = f32 ? RU_PREC_F32 : RU_PREC_BF16X3; a.wfrag = wf;
-    a.in_c16 = flags & 1; a.out_c16 = (flags >> 1) & 1; a.in_s16 = (flags >> 3) & 1;
-    RU_REQUIRE(!a.in_s16 || a.in_c16, "ru_conv3_l: the split form is a voxel-major layout");
-    a.x = x; a.bias = bias; a.y = y; a.N = N; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W;
-    a.add = add; a.in_scale = in_scale; a.in_shift = in_shift; a.in_slope = in_slope; a.in_res = in_res; a.in_sum_out = in_sum_out; a.sigmoid = sigmoid;
-    a.bst_y = bst_y; a.bst_k = bst_k; a.bst_slope = bst_slope; a.stat_partials = stat_partials;
-    if (gop) {
-        const size_t nvox = (size_t)N * D * H * W;
-        float* g16 = C.take(nvox * 16);
-        RU_WS_OK(C);
-        rc = conv3_mxg_split_launch(x, g16, nvox, s);
-        if (rc) return rc;
-        a.x = g16; a.in_s16 = 1; a.in_g16 = 1; a.products = 0;
-    }
-    if (flags & 4) {                                             // x NCDHW with Cin <= 4: 4-channel copy + tap-pair kernel
-        RU_REQUIRE(!(flags & 1) && conv3_sb4_usable(N, Cin, Cout, D, H, W), "ru_conv3_l: shape does not fit the 4-channel kernel");
-        const size_t V = (size_t)D * H * W;
-        float* x4 = C.take((size_t)N * 4 * V);
-        void* wf4 = C.take(conv3_sb4_frag_bytes(Cout) / 4 + 64);
-        RU_WS_OK(C);
-        rc = pad_to_c4_launch(x, x4, N, Cin, V, s);
-        if (rc) return rc;
-        rc = conv3_sb4_pack_weights(w, wf4, Cin_f, Cout_f, weight_mode, s);
-        if (rc) return rc;
-        a.x = x4; a.wfrag = wf4; a.in_c4 = 1;
-    }
-    const int r = f32 ? conv3_f32c_route(a) : conv3_sb_route(a, sw);
-    if (route) *route = r;
-    const int nb = f32 ? conv3_f32c_tiles_per_sample(N, Cin, Cout, D, H, W) : conv3_sb_route_nblk(r, N, Cout, D, H, W);     // partials per (sample, channel)
-    if (nblk) *nblk = nb;
-    RU_REQUIRE(!stat_partials || stat_floats >= (size_t)N * Cout * nb * 2, "ru_conv3_l: statistics buffer too small");
-    return f32 ? conv3_launch(a, sw, s) : conv3_sb_launch(a, sw, s);
-}
-
-extern "C" size_t ru_wgrad1_l_workspace_bytes(int N, int Cin, int Cout, size_t V) { return 4096 + align_up(wgrad1_workspace_bytes(N, Cin, Cout, V), 256); }
-extern "C" int ru_wgrad1_l(const float* x, const float* x1, int C0, const float* dy, float* dw, int ldw, int N, int Cin, int Cout, size_t V,
-                           int c16, int s2d, int Dc, int Hc, int Wc, int tap_split, const float* dg_w, int dg_ldw, float* dg_y0, float* dg_y1,
-                           float dg_mask_slope, int* inst, void* ws, size_t ws_bytes, ru_stream_t stream) {
-    RU_REQUIRE(x && dy && dw, "ru_wgrad1_l: null argument");
-    WsCarver C(ws, ws_bytes);
-    Wgrad1Args a{};
-    a.x = x; a.x1 = x1; a.C0 = C0; a.dy = dy; a.dw = dw; a.ldw = ldw; a.N = N; a.Cin = Cin; a.Cout = Cout; a.V = V;
-    a.c16 = c16; a.s2d = s2d; a.Dc = Dc; a.Hc = Hc; a.Wc = Wc; a.tap_split = tap_split;
-    a.dg_w = dg_w; a.dg_ldw = dg_ldw; a.dg_y0 = dg_y0; a.dg_y1 = dg_y1; a.dg_mask_slope = dg_mask_slope;
-    RU_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && V > 0, "ru_wgrad1_l: bad shape");
-    a.ws_bytes = wgrad1_workspace_bytes(N, Cin, Cout, V);
-    a.ws = C.take(a.ws_bytes / 4);
-    RU_WS_OK(C);
-    if (inst) *inst = wgrad1_inst(a);
-    return wgrad1_launch(a, (hipStream_t)stream);
-}
-
-// The transpose-read 3x3x3 weight gradient, one launch at a time with every operand of Wgrad3Args the engine sets: a thin filler like ru_conv3_l (no kernels,
-// no arithmetic of its own).  flags: 1 dy is in split form, 2 x is NCDHW with dw_cin <= 4 channels (4-channel copy made here), 4 dy is NCDHW with dw_cout <= 4
-// channels (likewise), 8 swapped, 16 gb_g16, 32 the reduction of the partials is deferred to a list of this call's own and flushed behind the kernel.
-extern "C" size_t ru_wgrad3_l_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W, int flags) {
-    return 4096 + align_up(wgrad3_tr_workspace_bytes(N, Cin, Cout, D, H, W), 256) + ((flags & 2) ? align_up((size_t)N * D * H * W * 16, 256) : 0) + ((flags & 4) ? align_up((size_t)N * D * H * W * 16, 256) : 0);
-}
-extern "C" int ru_wgrad3_l(const float* x, const float* dy, float* dw, int N, int Cin, int Cout, int D, int H, int W, int flags, int products,
-                           const float* in_scale, const float* in_shift, float in_slope, int dw_cin, int dw_cout,
-                           const float* gb_y, const float* gb_d, const float* gb_scale, const float* gb_shift, const float* gb_coef, float gb_slope, float* gb_out,
-                           int* inst, void* ws, size_t ws_bytes, ru_stream_t stream) {
-    RU_REQUIRE(x && (dy || gb_y) && dw, "ru_wgrad3_l: null argument");
-    RU_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, "ru_wgrad3_l: bad shape");
-    hipStream_t s = (hipStream_t)stream;
-    WsCarver C(ws, ws_bytes);
-    Wgrad3Args a{};
-    a.x = x; a.dy = dy ? dy : gb_y; a.dw = dw; a.mode = RU_PREC_BF16X3; a.x_c16 = 1; a.dy_c16 = 1;
-    a.N = N; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W;
-    a.in_scale = in_scale; a.in_shift = in_shift; a.in_slope = in_slope; a.dw_cin = dw_cin; a.dw_cout = dw_cout;
-    a.dy_s16 = flags & 1; a.x_c4 = (flags >> 1) & 1; a.dy_c4 = (flags >> 2) & 1; a.swapped = (flags >> 3) & 1; a.gb_g16 = (flags >> 4) & 1; a.products = products;
-    a.gb_y = gb_y; a.gb_d = gb_d; a.gb_scale = gb_scale; a.gb_shift = gb_shift; a.gb_coef = gb_coef; a.gb_slope = gb_slope; a.gb_out = gb_out;
-    a.ws_bytes = wgrad3_tr_workspace_bytes(N, Cin, Cout, D, H, W);
-    a.ws = C.take(a.ws_bytes / 4);
-    RU_WS_OK(C);
-    for (int side = 0; side < 2; ++side) {                       // a few-channel side arrives NCDHW and is copied as the engine's stem and head copy it
-        if (!(side == 0 ? a.x_c4 : a.dy_c4)) continue;
-        const int cfew = side == 0 ? dw_cin : dw_cout;
-        const size_t V = (size_t)D * H * W;
-        RU_REQUIRE(cfew > 0 && cfew <= 4 && (side == 0 || dy), "ru_wgrad3_l: a 4-channel copy holds 1..4 channels (dw_cin / dw_cout)");
-        float* c4 = C.take((size_t)N * 4 * V);
-        RU_WS_OK(C);
-        const int rc = pad_to_c4_launch(side == 0 ? x : dy, c4, N, cfew, V, s);
-        if (rc) return rc;
-        if (side == 0) a.x = c4; else a.dy = c4;
-    }
-    if (inst) *inst = wgrad3_tr_inst(a);
-    WgradRedList own;
-    if (flags & 32) a.defer = &own;
-    const int rc = wgrad3_tr_launch(a, s);
-    if (rc) return rc;
-    return (flags & 32) ? wgrad_reduce_flush(own, s) : RU_OK;
-}
-
-// ====================================================================== training input pipeline (dataloader.py)
-extern "C" size_t ru_zscore_workspace_bytes(int C, size_t V) { return zscore_workspace_bytes(C, V) + 256; }
-extern "C" int ru_zscore_stats(const float* image, double* stats, int C, size_t V, void* ws, size_t ws_bytes, ru_stream_t stream) {
-    RU_REQUIRE(image && stats && C > 0 && V > 0, "ru_zscore_stats: bad argument");
-    return zscore_stats_launch(image, stats, C, V, ws, ws_bytes, (hipStream_t)stream);
-}
-static int augment_patch_impl(const float* image, const unsigned char* label, const float* soft, const float* mean, const float* inv_std, int C, int D, int H, int W,
-                              const int* crop_lo, const int* patch, const double* scale, int flags, const float* gain, const float* bias,
-                              float* data_out, float* target_out, ru_stream_t stream) {
-    RU_REQUIRE(image && (label || soft) && mean && inv_std && crop_lo && patch && scale && gain && bias && data_out && target_out, "ru_augment_patch: null argument");
-    RU_REQUIRE(C > 0 && C <= RU_AUG_MAXC, "ru_augment_patch: 1..%d channels", RU_AUG_MAXC);
-    const int dims[3] = {D, H, W};
-    AugmentArgs a{};
-    a.image = image; a.label = label; a.soft = soft; a.data = data_out; a.target = target_out; a.C = C; a.D = D; a.H = H; a.W = W; a.flags = flags;
-    for (int i = 0; i < 3; ++i) {
-        RU_REQUIRE(patch[i] > 0 && crop_lo[i] >= 0 && crop_lo[i] + patch[i] <= dims[i], "ru_augment_patch: the crop must lie inside the volume");
-        RU_REQUIRE(scale[i] > 0.0, "ru_augment_patch: scale must be positive");
-        a.lo[i] = crop_lo[i]; a.P[i] = patch[i]; a.scale[i] = scale[i];
-    }
-    for (int c = 0; c < C; ++c) { a.mean[c] = mean[c]; a.istd[c] = inv_std[c]; a.gain[c] = gain[c]; a.bias[c] = bias[c]; }
-    return augment_patch_launch(a, (hipStream_t)stream);
-}
-extern "C" int ru_augment_patch(const float* image, const unsigned char* label, const float* mean, const float* inv_std, int C, int D, int H, int W,
-                                const int* crop_lo, const int* patch, const double* scale, int flags, const float* gain, const float* bias,
-                                float* data_out, float* target_out, ru_stream_t stream) {
-    RU_REQUIRE(label, "ru_augment_patch: null argument");
-    return augment_patch_impl(image, label, nullptr, mean, inv_std, C, D, H, W, crop_lo, patch, scale, flags, gain, bias, data_out, target_out, stream);
-}
-extern "C" int ru_augment_patch_soft(const float* image, const unsigned char* label, const float* soft, const float* mean, const float* inv_std, int C, int D, int H,
-                                     int W, const int* crop_lo, const int* patch, const double* scale, int flags, const float* gain, const float* bias,
-                                     float* data_out, float* target_out, ru_stream_t stream) {
-    return augment_patch_impl(image, label, soft, mean, inv_std, C, D, H, W, crop_lo, patch, scale, flags, gain, bias, data_out, target_out, stream);
 }

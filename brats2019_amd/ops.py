@@ -1079,11 +1079,9 @@ def conv3d_layout(x, w, bias=None, in_c16=False, out_c16=False, few_channels=Fal
     cout = int(w.shape[0])
     y = torch.empty((n, cout // 16, d, h, wd, 16) if out_c16 else (n, cout, d, h, wd), dtype=torch.float32, device=x.device)
     lib = L.load()
-    ws = L.workspace(lib.ru_conv3d_workspace_bytes(n, cin, cout, d, h, wd, 3) + (n * d * h * wd * 16 + 65536 if few_channels else 0)
-                     + (n * d * h * wd * 64 + 65536 if gradient else 0), x.device)
-    L.check(lib.ru_conv3d_fwd_l(L.f32(x), L.f32(w), L.ptr(bias, True), L.f32(y), n, cin, cout, d, h, wd,
-                                int(in_c16) | (int(out_c16) << 1) | (int(few_channels) << 2) | (int(in_split) << 3) | (int(exact_f32) << 4) | (int(activations) << 5) | (int(gradient) << 6),
-                                L.ptr(ws), ws.numel(), L.stream()), "ru_conv3d_fwd_l")
+    flags = int(in_c16) | (int(out_c16) << 1) | (int(few_channels) << 2) | (int(in_split) << 3) | (int(exact_f32) << 4) | (int(activations) << 5) | (int(gradient) << 6)
+    ws = L.workspace(lib.ru_conv3_l_workspace_bytes(n, cin, cout, d, h, wd, flags), x.device)
+    L.check(lib.ru_conv3d_fwd_l(L.f32(x), L.f32(w), L.ptr(bias, True), L.f32(y), n, cin, cout, d, h, wd, flags, L.ptr(ws), ws.numel(), L.stream()), "ru_conv3d_fwd_l")
     return y
 
 

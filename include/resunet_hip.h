@@ -51,7 +51,10 @@ int ru_device_ok(void);
  * nn.Conv3d as the reference constructs it: (k=3,stride=1,pad=1) model.py:72-73,336,348;
  * (k=2,stride=2,pad=0) model.py:361-363; (k=1,stride=1,pad=0) model.py:393,401.  Cross-correlation,
  * zero padding, weight layout [Cout][Cin][k][k][k].  D,H,W are the INPUT extents; for k=2 they must be even.
- * `bias` may be NULL.  Exact-f32 arithmetic (v_mfma_f32_16x16x4_f32 / v_fmac_f32).  */
+ * `bias` may be NULL.  Exact-f32 arithmetic (v_mfma_f32_16x16x4_f32 / v_fmac_f32).
+ * ru_conv3d_workspace_bytes is the largest of the dry walks (the entry's own carve, run on the host without launches) it covers, plus 4096:
+ * ru_conv3d_fwd / _bwd_data / _bwd_weight and their _p forms at both precisions, db included; for k = 3 also ru_conv3d_bwd_weight_l and
+ * ru_conv3d_fwd_l / ru_conv3_l for every `flags` without bits 2 and 6 (those two take more: ru_conv3_l_workspace_bytes).  */
 size_t ru_conv3d_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W, int k);
 int ru_conv3d_fwd(const float* x, const float* w, const float* bias, float* y,
                   int N, int Cin, int Cout, int D, int H, int W, int k,
@@ -78,7 +81,8 @@ int ru_conv3d_bwd_weight(const float* x, const float* dy, float* dw, float* db,
 /* ---------------------------------------------------------------- GroupNorm (+ fused LeakyReLU / residual)
  * nn.GroupNorm(G, C), eps, affine (model.py:95-96,338) followed by LeakyReLU(slope) (model.py:93-94; pass
  * slope = 1 for "no activation", as after norm_input, model.py:413) and, if residual != NULL, the Residual
- * skip add `x + out` (model.py:115).  V = D*H*W.  mean/rstd: [N*G] outputs (saved for backward).  */
+ * skip add `x + out` (model.py:115).  V = D*H*W.  mean/rstd: [N*G] outputs (saved for backward).
+ * ru_groupnorm_workspace_bytes: the larger of the dry walks of ru_groupnorm_fwd and ru_groupnorm_bwd, plus 4096.  */
 size_t ru_groupnorm_workspace_bytes(int N, int C, size_t V);
 int ru_groupnorm_fwd(const float* x, const float* gamma, const float* beta, const float* residual, float* y,
                      float* mean, float* rstd, int N, int C, size_t V, int G, float eps, float slope,
@@ -585,12 +589,14 @@ int ru_paste_u8c(const unsigned char* src, unsigned char* full, int C, int D, in
  * chip) take the fp16 + MX-fp8 product scheme the engine's forward convolutions take (f16*f16 + two e4m3 cross terms, RU_MX=0: off); never set for gradients;
  * bit 6 = x (float32, voxel-major both sides, 16 -> 16 channels) is a GRADIENT: where the kernel takes the shape it is converted to the gradient-operand form (bf16 + two
  * e4m3 planes + one exponent byte per voxel) and convolved with bf16 main + MX-fp8 cross products, as the engine's 16-channel data-gradient convolutions are (RU_MXG=0:
- * off; needs 64 more workspace bytes per input voxel); ignored elsewhere.  k = 3. */
+ * off; needs 64 more workspace bytes per input voxel); ignored elsewhere.  k = 3.
+ * ru_conv3d_fwd_l is ru_conv3_l (below) with weight_mode 0 and no fused operands or reports: ru_conv3_l_workspace_bytes(..., flags) sizes it for any flags,
+ * ru_conv3d_workspace_bytes(..., 3) for flags without bits 2 and 6. */
 int ru_layout_convert(const float* src, float* dst, int N, int C, size_t V, int to_c16, ru_stream_t stream);
 int ru_conv3d_fwd_l(const float* x, const float* w, const float* bias, float* y,
                     int N, int Cin, int Cout, int D, int H, int W, int flags,
                     void* ws, size_t ws_bytes, ru_stream_t stream);
-/* weight gradient; flags: bit 0 = x is C16, bit 1 = dy is C16 */
+/* weight gradient; flags: bit 0 = x is C16, bit 1 = dy is C16.  ws: ru_conv3d_workspace_bytes(..., 3) */
 int ru_conv3d_bwd_weight_l(const float* x, const float* dy, float* dw,
                            int N, int Cin, int Cout, int D, int H, int W, int flags,
                            void* ws, size_t ws_bytes, ru_stream_t stream);
@@ -610,7 +616,9 @@ int ru_conv3d_bwd_weight_l(const float* x, const float* dy, float* dw,
  *   of a stride-2 conv (Cin = 8 x its channels, channel tap*(Cin/8) + c at fine voxel (2z+i, 2y+j, 2x+k), tap = 4i + 2j + k); tap_split = Cin/8 writes
  *   dw[o*ldw + c*8 + tap], the reference's [Cout][Cin/8][2][2][2].  dg_w (optional, [Cout][dg_ldw], Cout <= 32): the data gradient in the same pass,
  *   dx[v][c] = sum_o dg_w[o][c] * dy[v][o], channels < C0 (or all) to dg_y0, the others to dg_y1 times (x1 > 0 ? 1 : dg_mask_slope).
- *   *inst (optional): OT | CT << 4 of wgrad1_f32_kernel<OT, CT>, bit 8 = the stride-2 kernel instead, bit 9 = fused data gradient. */
+ *   *inst (optional): OT | CT << 4 of wgrad1_f32_kernel<OT, CT>, bit 8 = the stride-2 kernel instead, bit 9 = fused data gradient.
+ * ru_conv1_l_workspace_bytes / ru_wgrad1_l_workspace_bytes: the dry walk of ru_conv1_l (both packs of the 2x2x2 weight with s2d, nothing without) /
+ *   of ru_wgrad1_l (the partials), plus 4096. */
 size_t ru_conv1_l_workspace_bytes(int C0, int Cout, int s2d);
 int ru_conv1_l(const float* x0, int C0, const float* x1, int C1, const float* w, int ldw, float* y, float* y1, int Cout0,
                const float* add, float out_slope, const float* mask, float mask_slope, int N, int Cout, size_t V,
@@ -628,7 +636,10 @@ int ru_conv1_l(const float* x0, int C0, const float* x1, int C1, const float* w,
  *   *route (optional): the kernel taken -- family (1 one-stage sb, 2 persistent sb2, 3 sb2c4, 4 wz32, 5 wz32mx, 6 mx, 7 f32c; 8 wz16, the
  *   16x16 Winograd-z kernel, which only a build with the developer switch RU_SB2_DBG can route to) | TZ << 4 | TY << 8 | IN16 << 12 |
  *   OUT16 << 13 | MULTI << 14 | BST << 15 | ADD << 16 | HEAD << 17 | GRAD << 18 | products per operand pair << 20.
- * The tail finalize of the statistics (the engine's ticket) and split-K are not reachable from here. */
+ * The tail finalize of the statistics (the engine's ticket) and split-K are not reachable from here.
+ * ru_conv3_l_workspace_bytes(..., flags): the dry walk of ru_conv3_l (and of ru_conv3d_fwd_l) for these flags with bias == NULL and weight_mode 0, under the
+ * RU_* switches of the calling process, plus 4096 -- the weight fragments, the 4-channel copy and its fragments (bit 2), the gradient-operand tensor (bit 6,
+ * where the shape and RU_MXG take it; a bias turns that form off and needs no more). */
 size_t ru_conv3_l_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W, int flags);
 int ru_conv3_l(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Cout, int D, int H, int W, int flags, int weight_mode,
                const float* add, const float* in_scale, const float* in_shift, float in_slope, const float* in_res, float* in_sum_out,
@@ -653,7 +664,9 @@ int ru_wgrad1_l(const float* x, const float* x1, int C0, const float* dy, float*
  *   gb_d (voxel-major), gb_scale / gb_shift [N][Cout], gb_coef [N][Cout][3] and gb_slope,
  *       dy = cA * ((y*scale + shift) > 0 ? d : d*slope) + (cB*y + cC),
  *   and is written to gb_out (voxel-major, 64 bytes per voxel and block; may be null with flag 2 only) in the form flag 16 names.
- *   *inst (optional): the instantiation taken, OT | XS << 4 | DS << 8 | NP << 12 of wgrad3_tz_kernel<OT, XS, DS, NP>; negative: the launch is refused. */
+ *   *inst (optional): the instantiation taken, OT | XS << 4 | DS << 8 | NP << 12 of wgrad3_tz_kernel<OT, XS, DS, NP>; negative: the launch is refused.
+ * ru_wgrad3_l_workspace_bytes(..., flags): the dry walk of ru_wgrad3_l, plus 4096 -- the partials and one 4-channel copy each for flags 2 and 4 (the other
+ *   flags take nothing). */
 size_t ru_wgrad3_l_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W, int flags);
 int ru_wgrad3_l(const float* x, const float* dy, float* dw, int N, int Cin, int Cout, int D, int H, int W, int flags, int products,
                 const float* in_scale, const float* in_shift, float in_slope, int dw_cin, int dw_cout,

@@ -1,0 +1,107 @@
+"""What tests/test_op_workspace.py and tools/op_abi_bytes.py share: one case per op-level entry that takes a workspace and per branch of its carve, on
+seeded inputs, at the smallest shapes the other suites use to reach those branches.  A case is (name, short, run): run() calls the entry through
+brats2019_amd.ops -- which sizes the workspace with the entry's query and allocates it with _lib.workspace -- and returns its output tensors; short says
+that the query is ONE walk that takes something, so that a workspace one 256-byte unit below it must be refused.  GuardedWorkspace stands in for
+_lib.workspace and decides how many bytes the entry really gets, with a guard behind them."""
+import torch
+
+GUARD = 4096
+PATTERN = 0xA5
+
+
+class GuardedWorkspace:
+    """_lib.workspace(nbytes, device) -> the first size_of(nbytes) bytes of an allocation that goes on for GUARD bytes of PATTERN"""
+
+    def __init__(self, size_of=lambda nbytes: nbytes):
+        self.size_of, self.bufs = size_of, []
+
+    def __call__(self, nbytes, device):
+        n = max(int(self.size_of(int(nbytes))), 0)
+        buf = torch.full((n + GUARD,), 0xFF, dtype=torch.uint8, device=device)       # (stale workspace bytes read as NaN)
+        buf[n:] = PATTERN
+        self.bufs.append((buf, n))
+        return buf[:n]
+
+    def intact(self):
+        torch.cuda.synchronize()
+        return len(self.bufs) > 0 and all(bool((buf[n:] == PATTERN).all()) for buf, n in self.bufs)
+
+
+def _rand(*shape, seed, scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(*shape, generator=g) * scale).cuda()
+
+
+def _c16(n, c, d, h, w, seed):
+    return _rand(n, c // 16, d, h, w, 16, seed=seed)
+
+
+def cases():
+    from brats2019_amd import ops
+    out = []
+    add = lambda name, short, run: out.append((name, short, run))
+    as_list = lambda r: [t for t in (r if isinstance(r, (tuple, list)) else (r,)) if isinstance(t, torch.Tensor)]
+
+    # ---- ru_conv3d_fwd_p / _bwd_data_p / _bwd_weight_p, k = 1, 2, 3: 1 x 8 -> 8 at 8 x 8 x 8 (one query serves all of them: no short case)
+    n, c, s = 1, 8, 8
+    for k in (1, 2, 3):
+        for prec in (("f32", "bf16x3") if k == 3 else ("f32",)):
+            x, w = _rand(n, c, s, s, s, seed=10 + k), _rand(c, c, k, k, k, seed=20 + k, scale=0.2)
+            so = s // 2 if k == 2 else s
+            dy, b = _rand(n, c, so, so, so, seed=30 + k), (_rand(c, seed=40) if k == 3 else None)
+            add("conv3d_fwd_k%d_%s" % (k, prec), False, lambda x=x, w=w, b=b, prec=prec: as_list(ops.conv3d(x, w, b, precision=prec)))
+            add("conv3d_bwd_data_k%d_%s" % (k, prec), False, lambda dy=dy, w=w, prec=prec: as_list(ops.conv3d_bwd_data(dy, w, (s, s, s), precision=prec)))
+            add("conv3d_bwd_weight_k%d_%s" % (k, prec), False, lambda x=x, dy=dy, k=k, prec=prec: as_list(ops.conv3d_bwd_weight(x, dy, k, with_bias=(k == 3), precision=prec)))
+
+    # ---- GroupNorm: N = 1, C = 16, V = 8192 + 1 -- two tiles
+    x, dy = _rand(1, 16, 1, 1, 8193, seed=50), _rand(1, 16, 1, 1, 8193, seed=51)
+    gamma, beta = _rand(16, seed=52) + 1.0, _rand(16, seed=53)
+
+    def gn_bwd():
+        _, mean, rstd = ops.group_norm(x, gamma, beta, slope=0.01)
+        return as_list(ops.group_norm_bwd(x, gamma, beta, mean, rstd, dy, slope=0.01))
+    add("groupnorm_fwd", False, lambda: as_list(ops.group_norm(x, gamma, beta, slope=0.01, residual=dy)))
+    add("groupnorm_bwd", False, gn_bwd)
+
+    # ---- the 3x3x3 layout launch, 1 x 16 -> 16 at 8 x 8 x 16: plain, split-form input, exact f32, activations; bit 6 where the shape does not take it
+    n, d, h, w_ = 1, 8, 8, 16
+    xv, xn = _c16(n, 16, d, h, w_, seed=60), _rand(n, 16, d, h, w_, seed=61)
+    wt, bias = _rand(16, 16, 3, 3, 3, seed=62, scale=0.1), _rand(16, seed=63)
+    for tag, kw in (("ncdhw", {}), ("in16", dict(in_c16=True)), ("out16", dict(out_c16=True)), ("c16", dict(in_c16=True, out_c16=True)),
+                    ("c16_split", dict(in_c16=True, out_c16=True, in_split=True)), ("c16_f32", dict(in_c16=True, out_c16=True, exact_f32=True)),
+                    ("c16_act", dict(in_c16=True, out_c16=True, activations=True)), ("c16_grad_small", dict(in_c16=True, out_c16=True, gradient=True))):
+        xin = (ops.to_split_c16(xv) if kw.get("in_split") else xv) if kw.get("in_c16") else xn
+        add("conv3_l_" + tag, True, lambda xin=xin, kw=kw: as_list(ops.conv3_fused(xin, wt, **kw).y))
+        add("conv3d_fwd_l_" + tag, True, lambda xin=xin, kw=kw: as_list(ops.conv3d_layout(xin, wt, **kw)))
+    add("conv3_l_c16_bias", True, lambda: as_list(ops.conv3_fused(xv, wt, bias=bias, in_c16=True, out_c16=True).y))
+    add("conv3d_bwd_weight_l_ncdhw", False, lambda: as_list(ops.conv3d_bwd_weight_layout(xn, xn)))
+    add("conv3d_bwd_weight_l_c16", False, lambda: as_list(ops.conv3d_bwd_weight_layout(xv, xv, x_c16=True, dy_c16=True)))
+    # flag bit 2, the 4-channel copy: 2 x 4 -> 16 at 32 x 32 x 64 (the shape must fit the 4-channel kernel)
+    x4, w4 = _rand(2, 4, 32, 32, 64, seed=64), _rand(16, 4, 3, 3, 3, seed=65, scale=0.2)
+    for tag, kw in (("c4_out16", dict(few_channels=True, out_c16=True)), ("c4", dict(few_channels=True))):
+        add("conv3_l_" + tag, True, lambda kw=kw: as_list(ops.conv3_fused(x4, w4, **kw).y))
+        add("conv3d_fwd_l_" + tag, True, lambda kw=kw: as_list(ops.conv3d_layout(x4, w4, **kw)))
+    # flag bit 6, the gradient-operand tensor: 2 x 16 -> 16 at 30 x 44 x 40
+    xg = _c16(2, 16, 30, 44, 40, seed=66)
+    add("conv3_l_c16_grad", True, lambda: as_list(ops.conv3_fused(xg, wt, in_c16=True, out_c16=True, gradient=True).y))
+    add("conv3d_fwd_l_c16_grad", True, lambda: as_list(ops.conv3d_layout(xg, wt, in_c16=True, out_c16=True, gradient=True)))
+
+    # ---- ru_conv1_l: plain (takes nothing), gather and scatter of 1 x 16 -> 32 at one coarse voxel
+    xf, xc = _c16(1, 16, 2, 2, 2, seed=70), _c16(1, 32, 1, 1, 1, seed=71)
+    wg, wsc, wp = _rand(32, 16, 2, 2, 2, seed=72, scale=0.3), _rand(32, 16, 2, 2, 2, seed=73, scale=0.3), _rand(32, 16, seed=74, scale=0.3)
+    add("conv1_l_plain", False, lambda: as_list(ops.conv1x1_c16(xf, wp).y))
+    add("conv1_l_gather", True, lambda: as_list(ops.conv1x1_c16(xf, wg, s2d=1).y))
+    add("conv1_l_scatter", True, lambda: as_list(ops.conv1x1_c16(xc, wsc, s2d=2).y))
+    # ---- ru_wgrad1_l: 1 x 16 -> 32
+    x1, dy1 = _c16(1, 16, 2, 3, 5, seed=75), _c16(1, 32, 2, 3, 5, seed=76)
+    add("wgrad1_l", True, lambda: as_list(ops.conv1x1_bwd_weight_c16(x1, dy1).dw))
+
+    # ---- ru_wgrad3_l at the ragged shape of tests/test_wgrad3_fused_host.py (RAG): plain, x as a 4-channel copy, dy as a 4-channel copy, deferred reduction
+    n, (d, h, w_) = 2, (5, 11, 19)
+    x3, dy3 = _c16(n, 16, d, h, w_, seed=80), _c16(n, 16, d, h, w_, seed=81)
+    xs, dys = _rand(n, 4, d, h, w_, seed=82), _rand(n, 3, d, h, w_, seed=83)
+    add("wgrad3_l", True, lambda: as_list(ops.wgrad3_fused(x3, dy3).dw))
+    add("wgrad3_l_deferred", True, lambda: as_list(ops.wgrad3_fused(x3, dy3, deferred=True).dw))
+    add("wgrad3_l_xc4", True, lambda: as_list(ops.wgrad3_fused(xs, dy3, x_c4=True, dw_cin=4).dw))
+    add("wgrad3_l_dyc4", True, lambda: as_list(ops.wgrad3_fused(x3, dys, dy_c4=True, dw_cout=3).dw))
+    return out

@@ -241,6 +241,27 @@ def test_inference_workspace_recycles_block_temporaries():
     assert ws(1, 36, 0) == 0                      # extents must be divisible by 8 (three stride-2 levels): size query says 0
 
 
+def test_op_level_workspace_queries_are_walks_of_their_entries(lib):
+    """The op-level size queries are dry walks of the entries' own carve (host only, null tensors), so what one query promises about another holds
+    by construction: ru_conv3d_workspace_bytes(..., 3) covers the 3x3x3 layout launch for every flag set without bits 2 and 6 -- bench.py sizes
+    ru_conv3d_fwd_l(flags = 3 | 32) with it -- and bit 2 (the 4-channel copy) or bit 6 (the gradient-operand tensor) never lowers
+    ru_conv3_l_workspace_bytes.  The grid holds a shape the 4-channel kernel takes (2 x 4 -> 16 at 32 x 32 x 64) and one the gradient-operand form
+    takes (2 x 16 -> 16 at 30 x 44 x 40), where those bits must cost their tensor."""
+    plain = [f for f in range(128) if not f & (4 | 64)]
+    for n, d, h, w in ((1, 8, 8, 16), (1, 5, 6, 7), (2, 32, 32, 64), (2, 30, 44, 40)):
+        for cin, cout in ((4, 16), (16, 16), (32, 32), (16, 3)):
+            q = lambda flags: int(lib.ru_conv3_l_workspace_bytes(n, cin, cout, d, h, w, flags))
+            whole = int(lib.ru_conv3d_workspace_bytes(n, cin, cout, d, h, w, 3))
+            for flags in plain:
+                assert whole >= q(flags) > 4096, (n, cin, cout, d, h, w, flags)
+                # (the two bits exclude each other -- bit 2 is an NCDHW input, bit 6 a voxel-major one -- so each is set on a flag set without them)
+                assert min(q(flags | 4), q(flags | 64), q(flags | 4 | 64)) >= q(flags), (n, cin, cout, d, h, w, flags)
+    nvox = 2 * 32 * 32 * 64
+    assert lib.ru_conv3_l_workspace_bytes(2, 4, 16, 32, 32, 64, 2 | 4) >= lib.ru_conv3_l_workspace_bytes(2, 4, 16, 32, 32, 64, 2) + nvox * 16
+    nvox = 2 * 30 * 44 * 40                       # (the walk reads the process's switches, as the call does: RU_MXG=0 turns the form off)
+    assert os.environ.get("RU_MXG") == "0" or lib.ru_conv3_l_workspace_bytes(2, 16, 16, 30, 44, 40, 3 | 64) >= lib.ru_conv3_l_workspace_bytes(2, 16, 16, 30, 44, 40, 3) + nvox * 64
+
+
 def _module_with_state_layout(names, shapes):
     """An nn.Module whose state_dict has exactly these names (in order) and shapes: the stand-in for the reference model whose layout
     tests/golden/state_layout.npz records (module tree from the dotted names, one Parameter per leaf)."""

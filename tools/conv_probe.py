@@ -19,7 +19,7 @@ x = torch.randn(n, c, size, size, size, device=dev)
 w = torch.randn(c, c, 3, 3, 3, device=dev) * 0.05
 y = torch.empty_like(x)
 dw = torch.empty_like(w)
-ws = L.workspace(lib.ru_conv3d_workspace_bytes(n, c, c, size, size, size, 3) + (n * size ** 3 * 64 + 65536 if flags & 64 else 0), dev)
+ws = L.workspace(lib.ru_conv3_l_workspace_bytes(n, c, c, size, size, size, flags) if kind == "fwd" and flags else lib.ru_conv3d_workspace_bytes(n, c, c, size, size, size, 3), dev)
 for _ in range(launches):
     if kind == "fwd" and flags:
         L.check(lib.ru_conv3d_fwd_l(L.f32(x), L.f32(w), None, L.f32(y), n, c, c, size, size, size, flags, L.ptr(ws), ws.numel(), L.stream()), "fwd_l")

@@ -16,7 +16,7 @@ x = torch.randn(n, c // 16, size, size, size, 16, device=dev)
 x = torch.where(x > 0, x, 0.01 * x)                 # an activation tensor
 w = torch.randn(c, c, 3, 3, 3, device=dev) * 0.05
 y = torch.empty_like(x)
-ws = L.workspace(lib.ru_conv3d_workspace_bytes(n, c, c, size, size, size, 3), dev)
+ws = L.workspace(lib.ru_conv3_l_workspace_bytes(n, c, c, size, size, size, FLAGS), dev)
 run = lambda: L.check(lib.ru_conv3d_fwd_l(L.f32(x), L.f32(w), None, L.f32(y), n, c, c, size, size, size, FLAGS, L.ptr(ws), ws.numel(), L.stream()), "conv")
 for _ in range(3):
     run()
