@@ -15,14 +15,10 @@ constexpr int MX_SCALE_W = (127 - MX_SWH) * 0x01010101;        // 2^-8
 constexpr int MXG_SX = 8, MXG_SWH = 8, MXG_SWL = 16;
 static_assert(MXG_SX + MXG_SWH == MXG_SWL, "one weight-side scale serves both cross terms");
 constexpr int MXG_SCALE_W = (127 - MXG_SWL) * 0x01010101;      // 2^-16; the data side's byte is 127 + e per voxel
-constexpr int MX_UNITS = 28;                                   // 16-byte x 64-lane units per 16-cout group: 14 fp16 K-steps, 2 x 3 x 2 cross, 2 ninth chain
 
 typedef _Float16 mx_f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 mx_f16x2 __attribute__((ext_vector_type(2)));
 typedef int mx_i32x8 __attribute__((ext_vector_type(8)));
-
-__host__ __device__ constexpr bool mx_channels_ok(int Cin_conv, int Cout_conv) { return Cin_conv == 16 && Cout_conv % 16 == 0; }
-static inline size_t mx_frag_bytes(int Cin_conv, int Cout_conv) { return mx_channels_ok(Cin_conv, Cout_conv) ? (size_t)(Cout_conv / 16) * MX_UNITS * 64 * 16 : 0; }
 
 // tap (dz*9 + dy*3 + dx) of cross fragment X(h, .) for row tap dy, tap pair j = g >> 1, slot
 __host__ __device__ constexpr int mx_cross_tap(int h, int j, int slot, int dy) {
@@ -92,7 +88,7 @@ __device__ __forceinline__ void mx_split4(const float (&t)[4], uint2& h16, unsig
     x8 = mx_cvt4(t[0], t[1], t[2], t[3]);
 }
 
-// ------------------------------------------------------------------ weight fragments (packed behind the direct ones of the same weight)
+// ------------------------------------------------------------------ weight fragments (form PF_MX of the pack: conv3_pack_layout.hpp has MX_UNITS, mx_channels_ok and the place)
 // unit u of 16-cout group cog, lane l (col = l & 15 = output channel, k-group g = l >> 4):
 //   u < 14            fp16 K-step u: 8 x fp16 of W[co][ci = (g&1)*8 + e][sb_tap(u, g>>1)]                       (the direct kernel's fragment in fp16)
 //   u = 14 + (3h+dy)*2 + slot   cross: 16 x e4m3 over ci = 0..15 of tap mx_cross_tap(h, g>>1, slot, dy): (g&1) == 0 ? w * 2^8 : (w - f16(w)) * 2^19

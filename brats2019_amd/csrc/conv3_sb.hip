@@ -592,7 +592,7 @@ __device__ __forceinline__ void sb_pack_one(const float* __restrict__ w, u32x4* 
     wfrag[(unit + 0) * 64 + lane] = hi;
     wfrag[(unit + 1) * 64 + lane] = lo;
 }
-// head-form unit u = f*2 + hl (f = 0..4), behind the direct fragments: lane l (col = l&15 = 4 dy + co, k-group g = l>>4) holds, for e = 0..7,
+// head-form unit u = f*2 + hl (f = 0..4) of form PF_HEAD: lane l (col = l&15 = 4 dy + co, k-group g = l>>4) holds, for e = 0..7,
 // W[cout = co][cin = (g&1)*8 + e][tap = sb_head_tap(f, g>>1, dy)] (conv3_sb_common.hpp, sb_head_shape)
 __device__ __forceinline__ void sb_pack_head_one(const float* __restrict__ w, u32x4* __restrict__ hfrag, int Cin_f, int Cout_f, int mode, int i) {
     if (i >= SB_HEAD_KSTEPS * 64) return;
@@ -614,44 +614,25 @@ __device__ __forceinline__ void sb_pack_head_one(const float* __restrict__ w, u3
     hfrag[((size_t)f * 2 + 0) * 64 + lane] = hi;
     hfrag[((size_t)f * 2 + 1) * 64 + lane] = lo;
 }
-// Every weight is packed in ALL forms where the channel counts allow the Winograd-z kernels (conv3_wz.hpp, conv3_wz32.hpp): the direct fragments, and right
-// behind them (conv3_sb_frag_bytes_direct) the transformed ones of the 16x16x32 form, then (wz_frag_bytes further) those of the 32x32x16 form -- which kernel a launch takes depends on its SHAPE, and frozen packs (inference) must serve
-// every shape.  Threads [0, direct) pack direct units, [direct, direct + wz) transformed ones, [direct + wz, direct + wz + wz32) the 32x32x16 ones.
-// forms: bit 0 = the 16x16x32 Winograd-z fragments, bit 1 = the 32x32x16 ones (SB_FORMS_ALL: op-level packs and inference, whose frozen packs must serve
-// every later launch; a training step repacks per forward and packs what that forward's launches take -- sb_pack_forms); bit 2 = the fp16 + MX-fp8 fragments of
-// conv3_mx_kernel (16 input channels, whole 16-channel output blocks: shapes that have neither a Winograd-z nor a head form, so they sit right behind the direct ones)
-constexpr int SB_FORMS_ALL = 15;                        // (bit 3: the same scheme's Winograd-z fragments, conv3_wz32mx.hpp, behind the two bf16 Winograd-z forms)
+// one pack thread of one weight: the form whose thread range holds i (conv3_pack_layout.hpp has the layout, the ranges and the request bits of `forms`)
 __device__ __forceinline__ void sb_pack_both(const float* __restrict__ w, u32x4* __restrict__ wfrag, int Cin_f, int Cout_f, int mode, int nchunk, int ncog, int forms, int i) {
-    const int direct = ncog * nchunk * SB_KSTEPS * 64;
-    if (i < direct) { if (!(forms & 16)) sb_pack_one(w, wfrag, Cin_f, Cout_f, mode, nchunk, ncog, i); return; }      // (bit 4: the direct fragments are not needed -- conv3_sb_pack_add)
     const int cin_conv = mode == 0 ? Cin_f : Cout_f, cout_conv = mode == 0 ? Cout_f : Cin_f;
-    if (sb_head_shape(cin_conv, cout_conv)) { sb_pack_head_one(w, wfrag + (size_t)direct * 2, Cin_f, Cout_f, mode, i - direct); return; }
-    if (mx_channels_ok(cin_conv, cout_conv)) { if (forms & 4) mx_pack_one(w, wfrag + (size_t)direct * 2, Cin_f, Cout_f, mode, ncog, i - direct, (forms & 32) != 0); return; }     // (bit 5: the gradient-operand variant in the same place)
-    if (!wz_channels_ok(cin_conv, cout_conv)) return;
-    const int wz = WZ16_FORM ? (cout_conv / 32) * nchunk * 4 * 2 * WZ_KSTEPS * 64 : 0;      // (the fragments keep their places whatever `forms` says: a skipped form leaves its bytes as they are)
-    int r = i - direct;
-    if (WZ16_FORM && (forms & 1)) {
-        if (r < wz) { wz_pack_one(w, reinterpret_cast<wz_u32x4*>(wfrag + (size_t)direct * 2), Cin_f, Cout_f, mode, nchunk, cout_conv / 32, r); return; }
-        r -= wz;
-    }
-    const int wz32 = (cout_conv / 32) * nchunk * 4 * 9 * 64;
-    if (forms & 2) {
-        if (r < wz32) { wz32_pack_one(w, reinterpret_cast<wz_u32x4*>(wfrag + ((size_t)direct + wz) * 2), Cin_f, Cout_f, mode, nchunk, cout_conv / 32, r); return; }
-        r -= wz32;
-    }
-    if (forms & 8) wz32mx_pack_one(w, reinterpret_cast<wz_u32x4*>(wfrag + ((size_t)direct + wz + wz32) * 2), Cin_f, Cout_f, mode, nchunk, cout_conv / 32, r);
+    const PackLayout L = pack_layout(cin_conv, cout_conv);
+    const PackThreads T = pack_threads(cin_conv, cout_conv, forms);
+    if (i < T.count[PF_DIRECT]) { if (!(forms & PACK_SKIP_DIRECT)) sb_pack_one(w, wfrag, Cin_f, Cout_f, mode, nchunk, ncog, i); return; }
+    auto mine = [&](PackForm f) { return i >= T.begin[f] && i < T.begin[f] + T.count[f]; };
+    auto at = [&](PackForm f) { return wfrag + L.start[f] * 64; };
+    if (mine(PF_HEAD)) sb_pack_head_one(w, at(PF_HEAD), Cin_f, Cout_f, mode, i - T.begin[PF_HEAD]);
+    else if (mine(PF_MX)) mx_pack_one(w, at(PF_MX), Cin_f, Cout_f, mode, ncog, i - T.begin[PF_MX], (forms & PACK_MX_GRAD) != 0);
+    else if (mine(PF_WZ16)) wz_pack_one(w, reinterpret_cast<wz_u32x4*>(at(PF_WZ16)), Cin_f, Cout_f, mode, nchunk, cout_conv / 32, i - T.begin[PF_WZ16]);
+    else if (mine(PF_WZ32)) wz32_pack_one(w, reinterpret_cast<wz_u32x4*>(at(PF_WZ32)), Cin_f, Cout_f, mode, nchunk, cout_conv / 32, i - T.begin[PF_WZ32]);
+    else if (mine(PF_WZ32MX)) wz32mx_pack_one(w, reinterpret_cast<wz_u32x4*>(at(PF_WZ32MX)), Cin_f, Cout_f, mode, nchunk, cout_conv / 32, i - T.begin[PF_WZ32MX]);
 }
-static inline int sb_pack_threads(int cin_conv, int cout_conv, int forms) {
-    const int nchunk = cdiv(cin_conv, 16), ncog = cdiv(cout_conv, 16);
-    return ncog * nchunk * SB_KSTEPS * 64 + (wz_channels_ok(cin_conv, cout_conv) ? (cout_conv / 32) * nchunk * (((WZ16_FORM && (forms & 1)) ? 4 * 2 * WZ_KSTEPS : 0) + ((forms & 2) ? 4 * 9 : 0) + ((forms & 8) ? WZ32MX_UNITS_XI : 0)) * 64 : 0)
-         + (sb_head_shape(cin_conv, cout_conv) ? SB_HEAD_KSTEPS * 64 : 0) + (((forms & 4) && mx_channels_ok(cin_conv, cout_conv)) ? ncog * MX_UNITS * 64 : 0);
-}
-// what the launches of a TRAINING forward + backward under `sw` read of a weight packed in `mode` (0: forward, 1: data gradient)
-static int sb_pack_forms(const Switches& sw, int mode) {
-    if (mode == 1) return sw.mxg ? (4 | 32) : 0;            // data-gradient launches (split-form inputs) take the direct kernels; 16 -> 16: the gradient-operand MX form beside them
-    if (!sw.wz) return sw.mx ? 4 : 0;                       // forward convolutions only: gradients never take the fp16 + MX-fp8 scheme
-    if (sw.mx && sw.mx_wz) return 4 | 8;                    // forward launches take the MX kernel of their shape: direct (16 channels) or Winograd-z (32..)
-    return (sw.mx ? 4 : 0) | (sw.wz32 ? 2 : 1);             // ... or ONE three-product Winograd-z form
+int sb_pack_forms(const Switches& sw, int mode) {
+    if (mode == 1) return sw.mxg ? (PACK_MX | PACK_MX_GRAD) : 0;      // data-gradient launches (split-form inputs) take the direct kernels; 16 -> 16: the gradient-operand MX form beside them
+    if (!sw.wz) return sw.mx ? PACK_MX : 0;                          // forward convolutions only: gradients never take the fp16 + MX-fp8 scheme
+    if (sw.mx && sw.mx_wz) return PACK_MX | PACK_WZ32MX;              // forward launches take the MX kernel of their shape: direct (16 channels) or Winograd-z (32..)
+    return (sw.mx ? PACK_MX : 0) | (sw.wz32 ? PACK_WZ32 : PACK_WZ16); // ... or ONE three-product Winograd-z form
 }
 __global__ void conv3_sb_pack_kernel(const float* __restrict__ w, u32x4* __restrict__ wfrag, int Cin_f, int Cout_f, int mode, int nchunk, int ncog, int forms) {
     sb_pack_both(w, wfrag, Cin_f, Cout_f, mode, nchunk, ncog, forms, blockIdx.x * blockDim.x + threadIdx.x);
@@ -667,7 +648,7 @@ int conv3_sb_pack_batch(SbPackBatch& b, hipStream_t s) {
     int maxtotal = 0;
     for (int i = 0; i < b.n; ++i) {
         const SbPackEntry& e = b.e[i];
-        const int t = sb_pack_threads(e.mode == 0 ? e.Cin_f : e.Cout_f, e.mode == 0 ? e.Cout_f : e.Cin_f, e.forms);
+        const int t = pack_threads(e.mode == 0 ? e.Cin_f : e.Cout_f, e.mode == 0 ? e.Cout_f : e.Cin_f, e.forms).total;
         if (t > maxtotal) maxtotal = t;
     }
     hipLaunchKernelGGL(conv3_sb_pack_batch_kernel, dim3(cdiv(maxtotal, 256), b.n), dim3(256), 0, s, b);
@@ -675,26 +656,16 @@ int conv3_sb_pack_batch(SbPackBatch& b, hipStream_t s) {
     b.n = 0;
     return RU_OK;
 }
-bool conv3_sb_forward_skips_direct(const Switches& sw, int N, int Cin, int Cout, int D, int H, int W) {
-    if (sw.wz && conv3_wz_shape_ok(N, Cin, Cout, D, H, W)) return true;             // conv3_wz32mx_kernel or conv3_wz32_kernel
-    return sw.mx && conv3_mx_shape_ok(N, Cin, Cout, D, H, W);                       // conv3_mx_kernel
-}
-int conv3_sb_pack_add(SbPackBatch& b, const Switches& sw, const float* w, void* wfrag, int Cin_f, int Cout_f, int mode, bool all_forms, hipStream_t s, bool skip_direct) {
+int conv3_sb_pack_add(SbPackBatch& b, const float* w, void* wfrag, int Cin_f, int Cout_f, int mode, int forms, hipStream_t s, unsigned* wforms) {
     if (b.n == RU_PACK_BATCH) { const int rc = conv3_sb_pack_batch(b, s); if (rc) return rc; }
     const int cin_conv = mode == 0 ? Cin_f : Cout_f, cout_conv = mode == 0 ? Cout_f : Cin_f;
     SbPackEntry& e = b.e[b.n++];
-    e.w = w; e.wfrag = wfrag; e.Cin_f = Cin_f; e.Cout_f = Cout_f; e.mode = mode; e.nchunk = cdiv(cin_conv, 16); e.ncog = cdiv(cout_conv, 16);
-    e.forms = all_forms ? SB_FORMS_ALL : (sb_pack_forms(sw, mode) | ((skip_direct && mode == 0) ? 16 : 0));
+    e.w = w; e.wfrag = wfrag; e.Cin_f = Cin_f; e.Cout_f = Cout_f; e.mode = mode; e.nchunk = cdiv(cin_conv, 16); e.ncog = cdiv(cout_conv, 16); e.forms = forms;
+    *wforms = pack_forms_present(cin_conv, cout_conv, forms);
     return RU_OK;
 }
 
-size_t conv3_sb_frag_bytes_direct(int Cin_conv, int Cout_conv) {
-    return (size_t)cdiv(Cout_conv, 16) * cdiv(Cin_conv, 16) * SB_KSTEPS * 2 * 64 * 16;
-}
-size_t conv3_sb_frag_bytes(int Cin_conv, int Cout_conv) {          // direct fragments + (32..: the Winograd-z fragments | <= 4 couts: the head form) behind them
-    return conv3_sb_frag_bytes_direct(Cin_conv, Cout_conv) + wz_frag_bytes(Cin_conv, Cout_conv) + wz32_frag_bytes(Cin_conv, Cout_conv) + wz32mx_frag_bytes(Cin_conv, Cout_conv)
-         + (sb_head_shape(Cin_conv, Cout_conv) ? (size_t)SB_HEAD_KSTEPS * 2 * 64 * 16 : 0) + mx_frag_bytes(Cin_conv, Cout_conv);
-}
+size_t conv3_sb_frag_bytes(int Cin_conv, int Cout_conv) { return pack_layout(Cin_conv, Cout_conv).total * PACK_UNIT_BYTES; }
 // The inference head: the last Residual block's output x + lrelu(norm2(conv2)) (model.py:112-116) is formed in the head conv's staging instead of a pass of its
 // own (Conv3Args::in_res).  Exists in the head-form variant of the persistent kernel only: the same tests as conv3_sb_launch's way there.  Switches::head_res off: never (A/B).
 bool conv3_sb_head_takes_residual(const Switches& sw, int N, int Cin, int Cout, int D, int H, int W) {
@@ -702,11 +673,11 @@ bool conv3_sb_head_takes_residual(const Switches& sw, int N, int Cin, int Cout, 
     if ((size_t)D * H * W * 64 >= ((size_t)1 << 31)) return false;
     return sb_use_v2(sb_choose(N, Cout, D, H, W));
 }
-int conv3_sb_pack_weights(const float* w, void* wfrag, int Cin_f, int Cout_f, int mode, hipStream_t s, bool grad_operand) {
+int conv3_sb_pack_weights(const float* w, void* wfrag, int Cin_f, int Cout_f, int mode, hipStream_t s, int forms, unsigned* wforms) {
     const int cin_conv = mode == 0 ? Cin_f : Cout_f, cout_conv = mode == 0 ? Cout_f : Cin_f;
     const int nchunk = cdiv(cin_conv, 16), ncog = cdiv(cout_conv, 16);
-    const int forms = SB_FORMS_ALL | (grad_operand ? 32 : 0);    // (the MX fragments of a weight exist in ONE variant: activation or gradient operand)
-    const int total = sb_pack_threads(cin_conv, cout_conv, forms);
+    const int total = pack_threads(cin_conv, cout_conv, forms).total;
+    *wforms = pack_forms_present(cin_conv, cout_conv, forms);
     hipLaunchKernelGGL(conv3_sb_pack_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, w, (u32x4*)wfrag, Cin_f, Cout_f, mode, nchunk, ncog, forms);
     RU_CHECK_LAUNCH("conv3_sb_pack_kernel");
     return RU_OK;
@@ -801,6 +772,27 @@ int conv3_sb_route_nblk(int r, int N, int Cout, int D, int H, int W) {
     }
 }
 
+// the fragment form the kernel of route r reads (a PackForm, or the bit index of PACK_HAS_MX_GRAD / PACK_HAS_SB4), and the refusal of a pack that lacks it
+static int sb_route_form(int r) {
+    switch (c3r_family(r)) {
+    case C3F_WZ16: return PF_WZ16;
+    case C3F_WZ32: return PF_WZ32;
+    case C3F_WZ32MX: return PF_WZ32MX;
+    case C3F_MX: return c3r_grad(r) ? PF_COUNT : PF_MX;
+    case C3F_SB2C4: return PF_COUNT + 1;
+    case C3F_SB2: return c3r_head(r) ? PF_HEAD : PF_DIRECT;
+    default: return PF_DIRECT;
+    }
+}
+static int sb_require_form(const Conv3Args& a, int r) {
+    static const char* const family[9] = {"?", "sb", "sb2", "sb2c4", "wz32", "wz32mx", "mx", "f32c", "wz16"};
+    const int f = sb_route_form(r);
+    RU_REQUIRE(a.wforms != 0, "conv3_sb: the launch does not say which fragment forms its pack holds (Conv3Args::wforms, conv3_set_pack)");
+    RU_REQUIRE((a.wforms >> f) & 1u, "conv3_sb: the pack does not hold the %s fragments that route %s (0x%x) reads (forms present: 0x%x)",
+               pack_form_name(f), family[c3r_family(r) <= 8 ? c3r_family(r) : 0], r, a.wforms);
+    return RU_OK;
+}
+
 int conv3_sb_launch(const Conv3Args& a, const Switches& sw, hipStream_t s) {
     RU_REQUIRE(!(a.sigmoid && a.out_c16), "conv3_sb: the fused sigmoid exists for NCDHW output only");
     RU_REQUIRE(!a.bst_y || (a.bst_k && a.stat_partials && (a.in_c16 || a.in_c4) && a.out_c16 && !a.bias && !a.sigmoid && (!a.add || !a.in_c4) &&
@@ -814,6 +806,7 @@ int conv3_sb_launch(const Conv3Args& a, const Switches& sw, hipStream_t s) {
         const SBChoice c4 = sb_choose(a.N, a.Cout, a.D, a.H, a.W);
         RU_REQUIRE(sb_use_v2(c4), "conv3_sb: the 4-channel kernel needs at least 256 (4,8,16) tiles x cout groups");
         const int r4 = conv3_sb_route(a, sw);
+        { const int rc = sb_require_form(a, r4); if (rc) return rc; }
         if (c3r_bst(r4)) return sb2c4_cfg<true, true>(a, s);
         return c3r_out16(r4) ? sb2c4_cfg<true>(a, s) : sb2c4_cfg<false>(a, s);
     }
@@ -823,16 +816,16 @@ int conv3_sb_launch(const Conv3Args& a, const Switches& sw, hipStream_t s) {
     RU_REQUIRE(!a.out_c16 || a.Cout % 16 == 0, "conv3_sb: C16 output needs Cout %% 16 == 0");
     RU_REQUIRE(!(a.bias && a.out_c16 && a.stat_partials), "conv3_sb: bias + voxel-major output + statistics is not a path of the network");
     const int r = conv3_sb_route(a, sw);
-    const void* behind = static_cast<const char*>(a.wfrag) + conv3_sb_frag_bytes_direct(a.Cin, a.Cout);     // the non-direct fragments of the same weight
+    { const int rc = sb_require_form(a, r); if (rc) return rc; }
     switch (c3r_family(r)) {
     case C3F_WZ32: case C3F_WZ32MX: case C3F_WZ16:
-        return conv3_wz_launch(a, behind, r, s);
+        return conv3_wz_launch(a, r, s);
     case C3F_MX:
         // Conv3Args::in_g16: the input is a gradient in the operand form of the MX scheme (the caller asked conv3_mxg_usable before it wrote the tensor that way)
         if (c3r_grad(r))
             RU_REQUIRE(a.in_s16 && a.out_c16 && !a.bias && !a.sigmoid && !a.in_res && conv3_mxg_usable(sw, a.N, a.Cin, a.Cout, a.D, a.H, a.W),
                        "conv3_sb: a gradient-operand input is taken by conv3_mx_kernel<GRAD> only (16 -> 16 channels, persistent-kernel shapes)");
-        return conv3_mx_launch(a, behind, r, s);
+        return conv3_mx_launch(a, pack_form_ptr(a.wfrag, a.Cin, a.Cout, PF_MX), r, s);
     case C3F_SB2:
         if (c3r_in16(r) && c3r_out16(r)) return c3r_np(r) == 1 ? conv3_sb2_launch_c16_p1(a, r, s) : conv3_sb2_launch_c16(a, r, s);
         return conv3_sb2_launch_mixed(a, r, s);          // (three products whatever a.products says: the NCDHW-side variants have no one-product form)

@@ -14,8 +14,6 @@ namespace ru {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int SB_KSTEPS = 14;       // ceil(27 taps / 2)
-
 // Tap (dz*9 + dy*3 + dx, or -1 = phantom with zero weights) in K-slot `slot` (k-groups 0-1 / 2-3 of the A fragment) of K-step ks.
 // The 27 taps are 9 chains (dz, dx) of three dy taps each.  K-step 3f + dy (f < 4) pairs the dy-th taps of chains 2f and 2f+1, so the
 // A fragment of (K-step 3f + dy, output row i) is the fragment of (K-step 3f + dy', output row i + dy - dy'): one LDS read serves the
@@ -33,15 +31,13 @@ __host__ __device__ constexpr int sb_tap(int ks, int slot) {
 // matrix work, so the N columns carry (dy, cout) pairs: column n = 4 dy + co.  The fragment F(f, r) of halo row r then feeds, in ONE MFMA per product,
 // the three output rows r, r-1, r-2 -- 5 fragments x 10 halo rows x 3 products = 150 MFMAs per wave and item instead of 336 -- into the accumulator of
 // HALO row r; an output row is the sum of three accumulators' column groups, taken across lanes in the epilogue.  K-step f (f < 4) holds chains 2f and
-// 2f+1 as in sb_tap; K-step 4 the ninth chain in slot 0 (slot 1 zero).  The fragments sit behind the direct (and Winograd-z) ones of the same weight.
-constexpr int SB_HEAD_KSTEPS = 5;
+// 2f+1 as in sb_tap; K-step 4 the ninth chain in slot 0 (slot 1 zero).  (SB_HEAD_KSTEPS, sb_head_shape and the fragments' place in the pack: conv3_pack_layout.hpp)
 // lane l takes the value of lane l + SH of its 16-lane row (zero past the row's end): a DPP row shift -- one VALU move, no LDS.  The value goes through a
 // scalar argument on purpose: __builtin_bit_cast applied to a vector ELEMENT (v[e]) reads element 0 whatever the index (hipcc 7.2).
 template <int SH>
 __device__ __forceinline__ float sb_row_shl(float x) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x100 + SH, 0xf, 0xf, true));
 }
-__host__ __device__ constexpr bool sb_head_shape(int Cin_conv, int Cout_conv) { return Cout_conv <= 4 && Cin_conv <= 16; }
 __host__ __device__ constexpr int sb_head_tap(int f, int slot, int dy) {
     if (dy > 2) return -1;
     if (f < 4) return sb_tap(3 * f + dy, slot);
@@ -1084,8 +1080,7 @@ static int sb2_cfg_m(const Conv3Args& a, hipStream_t s) {
     RU_REQUIRE(!a.fin.ticket || (a.stat_partials && a.fin.nblk == (int)grid.x && a.fin.N == a.N && a.fin.C == a.Cout && fin_tail_lds_bytes(a.fin) <= (size_t)LDS2),
                "conv3_sb2: tail descriptor does not match the launch");
     RU_REQUIRE(!IN16 || (size_t)a.D * a.H * a.W * 64 < ((size_t)1 << 31), "conv3_sb2: a 16-channel block of the voxel-major input must be smaller than 2 GiB (buffer addressing)");
-    // head form: its fragments sit behind the direct ones of the same weight (conv3_sb_frag_bytes_direct; channel counts below 32 have no Winograd-z form)
-    const u32x4* wfr = (const u32x4*)a.wfrag + (HEAD ? (size_t)cdiv(a.Cout, 16) * cdiv(a.Cin, 16) * SB_KSTEPS * 2 * 64 : 0);
+    const u32x4* wfr = pack_form_ptr((const u32x4*)a.wfrag, a.Cin, a.Cout, HEAD ? PF_HEAD : PF_DIRECT);
     hipLaunchKernelGGL((conv3_sb2_kernel<TZ, TY, IN16, OUT16, MULTI, BST, ADD, NP, HEAD>), grid, dim3(512), LDS2, s, a, wfr, ntz, nty, ntx, cdiv(a.Cin, 16), dbg);
     RU_CHECK_LAUNCH("conv3_sb2_kernel");
     return RU_OK;

@@ -25,16 +25,16 @@ static int wz_cfg16(const Conv3Args& a, const void* wzfrag, hipStream_t s) {
 }
 #endif
 
-int conv3_wz_launch(const Conv3Args& a, const void* wzfrag, int r, hipStream_t s) {       // r = conv3_sb_route(a): which of the Winograd-z kernels
+int conv3_wz_launch(const Conv3Args& a, int r, hipStream_t s) {       // r = conv3_sb_route(a): which of the Winograd-z kernels
     RU_REQUIRE(a.in_c16 && a.out_c16 && !a.bias && !a.sigmoid && !a.in_c4 && !a.in_s16 && !a.bst_y && !a.add && a.products != 1 && conv3_wz_shape_ok(a.N, a.Cin, a.Cout, a.D, a.H, a.W),
                "conv3_wz: the forward form -- voxel-major float32 tensors, >= 32 input channels, whole 32-channel output blocks, an even depth, no residual / GroupNorm-backward sums");
     RU_REQUIRE(a.N <= 32 || !a.stat_partials, "conv3_wz: at most 32 samples per call when statistics are requested");
-    if (c3r_family(r) == C3F_WZ32MX)                     // an activation tensor: fp16 + MX-fp8 products (conv3_wz32mx.hpp), fragments behind the three-product forms
-        return conv3_wz32mx_launch(a, static_cast<const char*>(wzfrag) + wz_frag_bytes(a.Cin, a.Cout) + wz32_frag_bytes(a.Cin, a.Cout), s);
+    if (c3r_family(r) == C3F_WZ32MX)                     // an activation tensor: fp16 + MX-fp8 products (conv3_wz32mx.hpp)
+        return conv3_wz32mx_launch(a, pack_form_ptr(a.wfrag, a.Cin, a.Cout, PF_WZ32MX), s);
 #ifdef RU_SB2_DBG
-    if (c3r_family(r) == C3F_WZ16) return wz_cfg16(a, wzfrag, s);
+    if (c3r_family(r) == C3F_WZ16) return wz_cfg16(a, pack_form_ptr(a.wfrag, a.Cin, a.Cout, PF_WZ16), s);
 #endif
-    return conv3_wz32_launch(a, static_cast<const char*>(wzfrag) + wz_frag_bytes(a.Cin, a.Cout), s);     // matrix waves on 32x32x16 MFMAs (conv3_wz32.hpp)
+    return conv3_wz32_launch(a, pack_form_ptr(a.wfrag, a.Cin, a.Cout, PF_WZ32), s);     // matrix waves on 32x32x16 MFMAs (conv3_wz32.hpp)
 }
 
 }  // namespace ru

@@ -1,6 +1,6 @@
-// conv3_wz_pack.hpp -- fragment conventions of the Winograd-z convolution (conv3_wz.hpp), the device function that packs one weight tensor into them
-// and the shape rule of the kernel: what conv3_sb.hip needs (its batched pack kernel packs every 3x3x3 weight of the network in both forms, its launch
-// routine routes by shape) without instantiating the kernel template.
+// conv3_wz_pack.hpp -- fragment conventions of the Winograd-z convolution (conv3_wz.hpp), the device functions that pack one weight tensor into them
+// and the shape rule of the kernel: what conv3_sb.hip needs without instantiating the kernel template.  Unit counts, channel rule and the forms' places in
+// the pack: conv3_pack_layout.hpp (PF_WZ16, PF_WZ32, PF_WZ32MX).
 #pragma once
 #include "conv3_sb_common.hpp"
 #include "conv3_mx_pack.hpp"
@@ -9,14 +9,12 @@ namespace ru {
 
 typedef unsigned int wz_u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int WZ_KSTEPS = 5;
 constexpr int WZ_HY = 10, WZ_HX = 18;
 constexpr int WZ_PLANE = WZ_HY * WZ_HX;                  // 180 halo positions per transformed plane
 constexpr int WZ_HVOLP = 4 * WZ_PLANE;                   // packets per [hi/lo][channel half] section: 4 transformed planes
 constexpr int WZ_BUF = 4 * WZ_HVOLP;                     // packets per image buffer (46 080 bytes)
 constexpr int WZ_SCRATCH_FLOATS = 4 * 2 * 8 * 64 * 4;    // [wave][group][row][lane] float4: the four waves' M accumulators of one tile
 constexpr int WZ_LDS_BYTES = 2 * WZ_BUF * 16 + WZ_SCRATCH_FLOATS * 4 + SB_STAT_LDS_FLOATS * 4 + 1024;      // images, M scratch, statistics scratch, 1 KB landing pad of the operand prefetch
-constexpr int WZ_UNITS = 4 * 2 * WZ_KSTEPS * 2;          // 16-byte x 64-lane fragment units per (32-cout block, 16-cin chunk): [xi][group][K-step][hi/lo]
 
 // tap dy*3 + dx (or -1: phantom, zero weights) in K-slot `slot` of K-step ks of one transformed plane
 __host__ __device__ constexpr int wz_tap(int ks, int slot) {
@@ -25,9 +23,6 @@ __host__ __device__ constexpr int wz_tap(int ks, int slot) {
     return slot == 0 ? 2 * 3 + 2 : -1;                   // (dy 2, dx 2) | phantom
 }
 
-
-// channel counts for which the transformed fragments exist beside the direct ones (whether a SHAPE takes the kernel: conv3_wz_shape_ok)
-__host__ __device__ constexpr bool wz_channels_ok(int Cin_conv, int Cout_conv) { return Cin_conv >= 32 && Cin_conv % 16 == 0 && Cout_conv % 32 == 0; }
 
 // thread i of ncog32 * nchunk * 4 * 2 * WZ_KSTEPS * 64: unit u = ((((cog32*nchunk + chunk)*4 + xi)*2 + g)*WZ_KSTEPS + ks)*2 + hl, 64 lanes x 16 bytes;
 // lane l (col = l&15, k-group kg = l>>4) holds, for e = 0..7, G_xi[cout = cog32*32 + g*16 + col][cin = chunk*16 + (kg&1)*8 + e][tap = wz_tap(ks, kg>>1)]
@@ -69,7 +64,6 @@ __device__ __forceinline__ void wz_pack_one(const float* __restrict__ w, wz_u32x
 }
 
 // ---- the 32x32x16 form of the matrix waves (conv3_wz32.hpp): one K-step per tap, 32 output channels per fragment row
-constexpr int WZ32_UNITS = 4 * 9 * 2;                    // 16-byte x 64-lane fragment units per (32-cout block, 16-cin chunk): [xi][tap dy*3+dx][hi/lo]
 // thread i of ncog32 * nchunk * 4 * 9 * 64: unit u = (((cog32*nchunk + chunk)*4 + xi)*9 + tap)*2 + hl; lane l (row = l&31, K half kh = l>>5) holds,
 // for e = 0..7, G_xi[cout = cog32*32 + row][cin = chunk*16 + kh*8 + e][tap] (G_xi as in wz_pack_one)
 __device__ __forceinline__ void wz32_pack_one(const float* __restrict__ w, wz_u32x4* __restrict__ frag, int Cin_f, int Cout_f, int mode, int nchunk, int ncog32, int i) {
@@ -100,14 +94,9 @@ __device__ __forceinline__ void wz32_pack_one(const float* __restrict__ w, wz_u3
     frag[(unit + 0) * 64 + lane] = hi;
     frag[(unit + 1) * 64 + lane] = lo;
 }
-static inline size_t wz32_frag_bytes(int Cin_conv, int Cout_conv) {
-    return wz_channels_ok(Cin_conv, Cout_conv) ? (size_t)(Cout_conv / 32) * (Cin_conv / 16) * WZ32_UNITS * 64 * 16 : 0;
-}
 
 // ---- the fp16 + MX-fp8 product scheme on the 32x32 matrix form (conv3_wz32mx.hpp): per transformed plane nine fp16 tap units and five CROSS units of two
 // 16-byte halves -- tap pairs (0,0)+(0,1), (0,2)+(1,0), (1,1)+(1,2), (2,0)+(2,1), (2,2)+phantom in the two slots of v_mfma_scale_f32_32x32x64_f8f6f4
-constexpr int WZ32MX_UNITS_XI = 9 + 5 * 2;               // 16-byte x 64-lane units per (32-cout block, 16-cin chunk, transformed plane)
-constexpr int WZ32MX_UNITS = 4 * WZ32MX_UNITS_XI;
 // tap dy*3 + dx (-1: phantom) in slot `slot` of cross pair p
 __host__ __device__ constexpr int wz32mx_pair_tap(int p, int slot) { return 2 * p + slot < 9 ? 2 * p + slot : -1; }
 // unit u = ((cog32*nchunk + chunk)*4 + xi)*19 + j.  j < 9: lane l (row = l&31, K half kh = l>>5) holds 8 x fp16 of
@@ -167,19 +156,6 @@ __device__ __forceinline__ void wz32mx_pack_one(const float* __restrict__ w, wz_
         frag[(((size_t)(cog32 * nchunk + chunk) * 4 + xi) * WZ32MX_UNITS_XI + j) * 64 + lane] = out;
     }
 }
-static inline size_t wz32mx_frag_bytes(int Cin_conv, int Cout_conv) {
-    return wz_channels_ok(Cin_conv, Cout_conv) ? (size_t)(Cout_conv / 32) * (Cin_conv / 16) * WZ32MX_UNITS * 64 * 16 : 0;
-}
-
-// (the 16x16x32 form's fragments -- conv3_wz_kernel -- exist in devtools builds only: the product library neither packs nor reserves them)
-#ifdef RU_SB2_DBG
-constexpr bool WZ16_FORM = true;
-#else
-constexpr bool WZ16_FORM = false;
-#endif
-static inline size_t wz_frag_bytes(int Cin_conv, int Cout_conv) {
-    return (WZ16_FORM && wz_channels_ok(Cin_conv, Cout_conv)) ? (size_t)(Cout_conv / 32) * (Cin_conv / 16) * WZ_UNITS * 64 * 16 : 0;
-}
 
 // shapes the kernel takes: voxel-major in and out, several input chunks, whole 32-channel output blocks, an even number of planes, and at least
 // one (2,8,16) tile x 32-cout block per CU (below that the one-stage kernel's smaller tiles fill the chip better)
@@ -197,7 +173,7 @@ static inline long wz_grid_x(int N, int Cout, int D, int H, int W) {
     return gx > ntile ? ntile : gx;
 }
 
-int conv3_wz_launch(const Conv3Args& a, const void* wzfrag, int r, hipStream_t s);
+int conv3_wz_launch(const Conv3Args& a, int r, hipStream_t s);                       // reads the form of route r from the pack a.wfrag
 int conv3_wz32_launch(const Conv3Args& a, const void* wz32frag, hipStream_t s);      // conv3_wz32.hip: forward form only (no residual, no GroupNorm-backward sums)
 int conv3_wz32mx_launch(const Conv3Args& a, const void* wz32mxfrag, hipStream_t s);  // conv3_wz32mx.hip: the forward form with fp16 + MX-fp8 products (Conv3Args::products == 2, Switches::mx_wz)
 

@@ -149,12 +149,14 @@ struct ParamInfo {
     bool dead;
 };
 
+struct PackRef { size_t off = 0; unsigned forms = 0; };      // a split-bf16 weight pack: byte offset in ru_unet::fpack, and the forms pack_all wrote there (conv3_pack_layout.hpp)
+
 struct BlockP {           // parameter indices of one Residual (model.py:81-97)
     int down = -1, conv1 = -1, conv2 = -1, n1w = -1, n1b = -1, n2w = -1, n2b = -1;
     int cin_down = 0, c = 0;
     // packed-weight slots (offsets in floats into the pack region)
     size_t pk_f1 = 0, pk_f2 = 0, pk_d1 = 0, pk_d2 = 0, pk_downT = 0, pk_down16 = 0;   // pk_down16: [C][8*cin] then [8*cin][C]
-    size_t fk_f1 = 0, fk_f2 = 0, fk_d1 = 0, fk_d2 = 0;     // byte offsets of the split-bf16 weight fragments
+    PackRef fk_f1, fk_f2, fk_d1, fk_d2;
 };
 
 struct GNSave {
@@ -193,7 +195,9 @@ struct ru_unet {
     std::vector<size_t> pk_upT, pk_decT;
     int conv_in = -1, nin_w = -1, nin_b = -1, conv_out_w = -1, conv_out_b = -1;
     size_t pk_in = 0, pk_out = 0, pk_out_d = 0, pk_total = 0;
-    size_t fk_in = 0, fk_out = 0, fk_out_d = 0, fk_total = 0;
+    PackRef fk_in, fk_out, fk_out_d;
+    size_t fk_total = 0;
+    void set_pack(Conv3Args& a, const PackRef& r) const { conv3_set_pack(a, fpack + r.off, r.forms); }
     int precision = RU_PREC_F32;
     unsigned fusion = RU_FUSE_GN_BWD_STATS | RU_FUSE_GN_BWD_APPLY | RU_FUSE_SIDE_STREAM | RU_FUSE_BATCH_WREDUCE | RU_FUSE_PW_DGRAD;     // (RU_FUSE_TAIL_FINALIZE: opt-in)
     int grad_precision = RU_PREC_BF16X3;   // ru_unet_set_grad_precision: RU_PREC_BF16 = one MFMA product in the 3x3x3 data / weight gradients
@@ -302,10 +306,7 @@ static void assign_block_packs(ru_unet* h, BlockP& b) {
         b.pk_down16 = h->pk_total; h->pk_total += (size_t)2 * 8 * b.cin_down * b.c;
     }
     const size_t f = conv3_sb_frag_bytes(b.c, b.c);
-    b.fk_f1 = h->fk_total; h->fk_total += f;
-    b.fk_f2 = h->fk_total; h->fk_total += f;
-    b.fk_d1 = h->fk_total; h->fk_total += f;
-    b.fk_d2 = h->fk_total; h->fk_total += f;
+    for (PackRef* r : {&b.fk_f1, &b.fk_f2, &b.fk_d1, &b.fk_d2}) { r->off = h->fk_total; h->fk_total += f; }
 }
 
 extern "C" ru_unet_t ru_unet_create(int depth, const int* encoder_layers, const int* decoder_layers,
@@ -353,9 +354,9 @@ extern "C" ru_unet_t ru_unet_create(int depth, const int* encoder_layers, const 
     h->pk_out = h->pk_total; h->pk_total += conv3_packed_floats(ch[0], number_of_outputs);
     h->pk_out_d = h->pk_total; h->pk_total += conv3_packed_floats(number_of_outputs, ch[0]);
     h->fk_total = 0;
-    h->fk_in = h->fk_total; h->fk_total += conv3_sb_frag_bytes(kInCh, ch[0]);
-    h->fk_out = h->fk_total; h->fk_total += conv3_sb_frag_bytes(ch[0], number_of_outputs);
-    h->fk_out_d = h->fk_total; h->fk_total += conv3_sb_frag_bytes(number_of_outputs, ch[0]);
+    h->fk_in.off = h->fk_total; h->fk_total += conv3_sb_frag_bytes(kInCh, ch[0]);
+    h->fk_out.off = h->fk_total; h->fk_total += conv3_sb_frag_bytes(ch[0], number_of_outputs);
+    h->fk_out_d.off = h->fk_total; h->fk_total += conv3_sb_frag_bytes(number_of_outputs, ch[0]);
     for (auto& b : h->first_blocks) assign_block_packs(h, b);
     for (auto& lv : h->enc_blocks) for (auto& b : lv) assign_block_packs(h, b);
     for (int i = 0; i < depth - 1; ++i) for (auto& b : h->dec_blocks[i]) assign_block_packs(h, b);
@@ -453,24 +454,28 @@ extern "C" int ru_unet_param_is_dead(ru_unet_t h, int i) { return (h && i >= 0 &
 static inline const float* P(const ru_unet* h, const float* params, int idx) { return params ? params + h->params[idx].offset : nullptr; }
 static inline float* G(const ru_unet* h, float* grads, int idx) { return grads ? grads + h->params[idx].offset : nullptr; }
 
+static Conv3Args conv3_gn_args(const ru_unet* h, int N, int Cin, int Cout, int D, int H, int W, bool x_c16, bool x_c4);
+
 static int pack_all(ru_unet* h, const float* params, Arena& A, hipStream_t s) {
     float* pk = h->pack;
     SbPackBatch batch;
     batch.n = 0;
     // one 3x3x3 weight -> the layout of the active precision (f32: K-major floats; bf16x3: hi/lo fragments, all in one launch)
-    // lvl >= 0 (training, voxel-major flow): the resolution level whose forward convolution reads this weight -- where that launch takes the Winograd-z / MX kernel
-    // of its shape, the direct fragments are not written
-    auto pack3 = [&](int pidx, size_t pk_off, size_t fk_off, int cin_f, int cout_f, int mode, int lvl = -1) -> int {
-        const bool skipd = h->training && h->c16 && mode == 0 && lvl >= 0 &&
-                           conv3_sb_forward_skips_direct(h->sw, h->N, cin_f, cout_f, h->D >> lvl, h->H >> lvl, h->W >> lvl);
-        if (h->precision == RU_PREC_BF16X3) RU_RUN(conv3_sb_pack_add(batch, h->sw, P(h, params, pidx), h->fpack + fk_off, cin_f, cout_f, mode, !h->training, s, skipd));
+    // lvl >= 0 (forward weights of the blocks): the resolution level of the conv3_gn launch that reads this pack.  Inference packs every form (frozen packs serve
+    // every later launch); a training step packs what its switches launch, without the direct fragments where the route of that very launch reads none
+    auto pack3 = [&](int pidx, size_t pk_off, PackRef& fk, int cin_f, int cout_f, int mode, int lvl = -1) -> int {
+        int forms = h->training ? sb_pack_forms(h->sw, mode) : PACK_ALL;
+        if (h->training && mode == 0 && lvl >= 0 &&
+            conv3_route_skips_direct(conv3_sb_route(conv3_gn_args(h, h->N, cin_f, cout_f, h->D >> lvl, h->H >> lvl, h->W >> lvl, true, false), h->sw)))
+            forms |= PACK_SKIP_DIRECT;
+        if (h->precision == RU_PREC_BF16X3) RU_RUN(conv3_sb_pack_add(batch, P(h, params, pidx), h->fpack + fk.off, cin_f, cout_f, mode, forms, s, &fk.forms));
         // exact-f32 voxel-major inference: per-lane f32 fragments in the same slot (never larger than the split-bf16 ones)
-        if (h->precision == RU_PREC_F32 && h->c16) RU_RUN(conv3_f32c_pack_weights(P(h, params, pidx), h->fpack + fk_off, cin_f, cout_f, mode, s));
+        if (h->precision == RU_PREC_F32 && h->c16) RU_RUN(conv3_f32c_pack_weights(P(h, params, pidx), h->fpack + fk.off, cin_f, cout_f, mode, s));
         // outside the voxel-major flow the f32 layout is always kept: ragged W falls back to the f32 kernel
         if (!h->c16) RU_RUN(conv3_pack_weights(P(h, params, pidx), pk + pk_off, cin_f, cout_f, mode, s));
         return RU_OK;
     };
-    auto blk = [&](const BlockP& b, int lvl) -> int {
+    auto blk = [&](BlockP& b, int lvl) -> int {
         int rc = pack3(b.conv1, b.pk_f1, b.fk_f1, b.c, b.c, 0, lvl); if (rc) return rc;
         rc = pack3(b.conv2, b.pk_f2, b.fk_f2, b.c, b.c, 0, lvl); if (rc) return rc;
         if (h->training) {
@@ -507,17 +512,24 @@ static int sb_nblk(const ru_unet* h, Conv3Args a) {
 }
 
 // y = conv3(x) with optional fused input transform, tile statistics -> GNSave (mean/rstd/scale/shift)
-static int conv3_gn(ru_unet* h, Arena& A, hipStream_t s, const float* x, const float* wp, const char* wf, float* y, const GNSave* in_gn,
-                    const float* gamma, const float* beta, GNSave& out_gn, int N, int Cin, int Cout, int D, int H, int W, bool x_c16 = true,
-                    bool x_c4 = false) {
+// what conv3_gn's launch is by the handle and the shape alone -- everything its route depends on (pack_all asks the route before the tensors exist)
+static Conv3Args conv3_gn_args(const ru_unet* h, int N, int Cin, int Cout, int D, int H, int W, bool x_c16, bool x_c4) {
     Conv3Args a{};
-    a.x = x; a.wp = wp; a.y = y; a.mode = h->precision; a.wfrag = wf;
-    a.in_scale = in_gn ? in_gn->scale : nullptr;
-    a.in_shift = in_gn ? in_gn->shift : nullptr;
-    a.in_slope = in_gn ? in_gn->act_slope : kSlope;
+    a.mode = h->precision;
     a.N = N; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W;
     a.in_c16 = h->c16 && x_c16; a.out_c16 = h->c16; a.in_c4 = x_c4;
     a.products = 2;          // a FORWARD convolution: its input is an activation tensor, so the shapes that have the kernel take the fp16 + MX-fp8 scheme (conv3_mx.hpp; Switches::mx)
+    return a;
+}
+static int conv3_gn(ru_unet* h, Arena& A, hipStream_t s, const float* x, const float* wp, const void* wf, unsigned wforms, float* y, const GNSave* in_gn,
+                    const float* gamma, const float* beta, GNSave& out_gn, int N, int Cin, int Cout, int D, int H, int W, bool x_c16 = true,
+                    bool x_c4 = false) {
+    Conv3Args a = conv3_gn_args(h, N, Cin, Cout, D, H, W, x_c16, x_c4);
+    a.x = x; a.wp = wp; a.y = y;
+    conv3_set_pack(a, wf, wforms);
+    a.in_scale = in_gn ? in_gn->scale : nullptr;
+    a.in_shift = in_gn ? in_gn->shift : nullptr;
+    a.in_slope = in_gn ? in_gn->act_slope : kSlope;
     const bool sb = h->c16 ? h->precision == RU_PREC_BF16X3 : conv3_effective_mode(h->precision, W) == RU_PREC_BF16X3;       // conv3_launch hands the launch to conv3_sb_launch
     const int nblk = sb ? sb_nblk(h, a) : (h->c16 ? conv3_f32c_tiles_per_sample(N, Cin, Cout, D, H, W) : conv3_f32_tiles_per_sample(N, Cin, Cout, D, H, W));
     t_hint_c = Cout;
@@ -613,10 +625,10 @@ static int block_fwd(ru_unet* h, const float* params, Arena& A, hipStream_t s, c
     const size_t V = (size_t)D * H * W;
     sv.x = x; sv.N = N; sv.C = C; sv.D = D; sv.H = H; sv.W = W;
     sv.y1 = A.alloc((size_t)N * C * V);
-    int rc = conv3_gn(h, A, s, x, h->pack + bp.pk_f1, h->fpack + bp.fk_f1, sv.y1, xin_gn, P(h, params, bp.n1w), P(h, params, bp.n1b), sv.g1, N, C, C, D, H, W);
+    int rc = conv3_gn(h, A, s, x, h->pack + bp.pk_f1, h->fpack + bp.fk_f1.off, bp.fk_f1.forms, sv.y1, xin_gn, P(h, params, bp.n1w), P(h, params, bp.n1b), sv.g1, N, C, C, D, H, W);
     if (rc) return rc;
     sv.y2 = A.alloc((size_t)N * C * V);
-    rc = conv3_gn(h, A, s, sv.y1, h->pack + bp.pk_f2, h->fpack + bp.fk_f2, sv.y2, &sv.g1, P(h, params, bp.n2w), P(h, params, bp.n2b), sv.g2, N, C, C, D, H, W);
+    rc = conv3_gn(h, A, s, sv.y1, h->pack + bp.pk_f2, h->fpack + bp.fk_f2.off, bp.fk_f2.forms, sv.y2, &sv.g1, P(h, params, bp.n2w), P(h, params, bp.n2b), sv.g2, N, C, C, D, H, W);
     if (rc) return rc;
     if (defer_out) {
         RU_REQUIRE(h->c16 && !xin_gn, "block_fwd: the deferred residual pass exists in the voxel-major flow only");
@@ -675,10 +687,10 @@ static int unet_forward_impl(ru_unet* h, const float* params, const float* x, fl
         h->x_in4_planned = true;
         RU_RUN(pad_to_c4_launch(x, x4, N, kInCh, Vl(0), s));
         if (!reuse_packs) RU_RUN(conv3_sb4_pack_weights(P(h, params, h->conv_in), wf4, kInCh, C0, 0, s));
-        rc = conv3_gn(h, A, s, x4, nullptr, reinterpret_cast<const char*>(wf4), h->y0, nullptr, P(h, params, h->nin_w), P(h, params, h->nin_b), h->g0,
+        rc = conv3_gn(h, A, s, x4, nullptr, wf4, PACK_HAS_SB4, h->y0, nullptr, P(h, params, h->nin_w), P(h, params, h->nin_b), h->g0,
                       N, kInCh, C0, Dl[0], Hl[0], Wl[0], false, true);
     } else {
-        rc = conv3_gn(h, A, s, x, h->pack + h->pk_in, h->fpack + h->fk_in, h->y0, nullptr, P(h, params, h->nin_w), P(h, params, h->nin_b), h->g0, N, kInCh, C0, Dl[0], Hl[0], Wl[0], false);
+        rc = conv3_gn(h, A, s, x, h->pack + h->pk_in, h->fpack + h->fk_in.off, h->fk_in.forms, h->y0, nullptr, P(h, params, h->nin_w), P(h, params, h->nin_b), h->g0, N, kInCh, C0, Dl[0], Hl[0], Wl[0], false);
     }
     if (rc) return rc;
     if (!h->training) A.rewind(stem_mark);                      // inference: the 4-channel copy and the statistics partials are dead (the weight gradient reuses the copy in training)
@@ -773,7 +785,7 @@ static int unet_forward_impl(ru_unet* h, const float* params, const float* x, fl
     h->probs = probs_out;
     Conv3Args a{};
     a.x = cur; a.wp = h->pack + h->pk_out; a.bias = P(h, params, h->conv_out_b); a.y = pdst; a.sigmoid = 1;
-    a.mode = h->precision; a.wfrag = h->fpack + h->fk_out; a.in_c16 = h->c16;
+    a.mode = h->precision; h->set_pack(a, h->fk_out); a.in_c16 = h->c16;
     a.N = N; a.Cin = C0; a.Cout = h->nout; a.D = Dl[0]; a.H = Hl[0]; a.W = Wl[0];
     if (head_block) {                                    // x + lrelu(norm2(conv2)) of the last block, formed in this conv's staging
         a.x = head_block->y2; a.in_scale = head_block->g2.scale; a.in_shift = head_block->g2.shift; a.in_slope = kSlope; a.in_res = head_block->x;
@@ -976,7 +988,7 @@ static int block_bwd(ru_unet* h, const float* params, float* grads, Arena& A, hi
     if (rc) return rc;
     float* da1 = A.alloc((size_t)N * C * V);
     Conv3Args d2{};
-    d2.x = dy2; d2.wp = h->pack + bp.pk_d2; d2.y = da1; d2.mode = h->precision; d2.products = h->grad_products(); d2.wfrag = h->fpack + bp.fk_d2; d2.in_c16 = c16; d2.out_c16 = c16; d2.in_s16 = ds16; d2.in_g16 = g16; d2.N = N; d2.Cin = C; d2.Cout = C; d2.D = D; d2.H = H; d2.W = W;
+    d2.x = dy2; d2.wp = h->pack + bp.pk_d2; d2.y = da1; d2.mode = h->precision; d2.products = h->grad_products(); h->set_pack(d2, bp.fk_d2); d2.in_c16 = c16; d2.out_c16 = c16; d2.in_s16 = ds16; d2.in_g16 = g16; d2.N = N; d2.Cin = C; d2.Cout = C; d2.D = D; d2.H = H; d2.W = W;
     // the data-gradient conv of conv2 takes the GroupNorm-backward sums of norm1 in its epilogue (its output IS the gradient w.r.t.
     // LeakyReLU(norm1(y1))): no separate reduce pass over (y1, da1)
     const bool fuse1 = c16 && h->precision == RU_PREC_BF16X3 && conv3_sb_bst_usable(N, C, D, H, W) && (h->fusion & RU_FUSE_GN_BWD_STATS);
@@ -1004,7 +1016,7 @@ static int block_bwd(ru_unet* h, const float* params, float* grads, Arena& A, hi
     if (rc) return rc;
     float* dx = A.alloc((size_t)N * C * V);
     Conv3Args d1{};
-    d1.x = dy1; d1.wp = h->pack + bp.pk_d1; d1.y = dx; d1.add = dout; d1.mode = h->precision; d1.products = h->grad_products(); d1.wfrag = h->fpack + bp.fk_d1;       // skip path: dx = dout + dgrad(conv1)
+    d1.x = dy1; d1.wp = h->pack + bp.pk_d1; d1.y = dx; d1.add = dout; d1.mode = h->precision; d1.products = h->grad_products(); h->set_pack(d1, bp.fk_d1);       // skip path: dx = dout + dgrad(conv1)
     d1.in_c16 = c16; d1.out_c16 = c16; d1.in_s16 = ds16; d1.in_g16 = g16;
     d1.N = N; d1.Cin = C; d1.Cout = C; d1.D = D; d1.H = H; d1.W = W;
     if (nx) nx->out = FusedSums();
@@ -1101,11 +1113,11 @@ static int unet_backward_impl(ru_unet* h, const float* params, const float* dpro
     if (rc) return rc;
     float* dcur_buf = A.alloc((size_t)N * C0 * Vl(0));
     Conv3Args dh{};
-    dh.x = dlog; dh.wp = h->pack + h->pk_out_d; dh.y = dcur_buf; dh.mode = h->precision; dh.wfrag = h->fpack + h->fk_out_d; dh.out_c16 = c16; dh.N = N; dh.Cin = h->nout; dh.Cout = C0; dh.D = Dl[0]; dh.H = Hl[0]; dh.W = Wl[0];
+    dh.x = dlog; dh.wp = h->pack + h->pk_out_d; dh.y = dcur_buf; dh.mode = h->precision; h->set_pack(dh, h->fk_out_d); dh.out_c16 = c16; dh.N = N; dh.Cin = h->nout; dh.Cout = C0; dh.D = Dl[0]; dh.H = Hl[0]; dh.W = Wl[0];
     if (head4) {                                                 // few input channels: tap-pair kernel on the 4-channel copy
         float* wf4 = A.alloc(conv3_sb4_frag_bytes(C0) / sizeof(float) + 64);
         RU_RUN(conv3_sb4_pack_weights(P(h, params, h->conv_out_w), wf4, C0, h->nout, 1, s));
-        dh.x = d4; dh.wfrag = wf4; dh.in_c4 = 1;
+        dh.x = d4; conv3_set_pack(dh, wf4, PACK_HAS_SB4); dh.in_c4 = 1;
     }
     // the head's data gradient is the gradient entering norm2 of the last decoder block: its GroupNorm-backward sums are taken here
     const bool no_bst = !(h->fusion & RU_FUSE_GN_BWD_STATS);
@@ -1293,8 +1305,9 @@ static int unet_backward_impl(ru_unet* h, const float* params, const float* dpro
         float* wfd = A.alloc(conv3_sb_frag_bytes(C0, kInCh) / sizeof(float) + 64);
         Conv3Args di{};
         if (c16) {                                               // dy0 is voxel-major: the split-bf16 kernel reads it
-            RU_RUN(conv3_sb_pack_weights(P(h, params, h->conv_in), wfd, kInCh, C0, 1, s));
-            di.mode = RU_PREC_BF16X3; di.wfrag = wfd; di.in_c16 = 1; di.in_s16 = split0 ? 1 : 0;
+            unsigned wfd_forms = 0;
+            RU_RUN(conv3_sb_pack_weights(P(h, params, h->conv_in), wfd, kInCh, C0, 1, s, PACK_ALL, &wfd_forms));
+            di.mode = RU_PREC_BF16X3; conv3_set_pack(di, wfd, wfd_forms); di.in_c16 = 1; di.in_s16 = split0 ? 1 : 0;
         } else {
             RU_RUN(conv3_pack_weights(P(h, params, h->conv_in), wpd, kInCh, C0, 1, s));
         }
@@ -1369,17 +1382,17 @@ extern "C" int ru_unet_forward(ru_unet_t h, const float* params, const float* x,
 
 static int backward_entry(ru_unet_t h, const float* params, const float* dprobs, const CritGradArgs* crit, float* grads, float* dx, ru_stream_t stream) {
     if (!h->have_fwd || !h->training) { set_error("ru_unet_backward: needs a preceding training-mode ru_unet_forward"); return RU_ESTATE; }
+    // a training forward packs only the fragment forms its switches launch (sb_pack_forms): a switch flipped between that forward and this backward would make
+    // a launch read fragments that were never packed -- refused here, before the handle is bound to anything
+    h->sw = switches_from_env();
+    RU_REQUIRE(h->precision != RU_PREC_BF16X3 || h->pack_sw.pack_bits() == h->sw.pack_bits(),
+               "ru_unet_backward: RU_WZ / RU_MX / RU_MXG changed since the forward whose packs this backward reads (signature %d then, %d now)", h->pack_sw.pack_bits(), h->sw.pack_bits());
     Arena A;
     A.dry = false; A.base = h->ws; A.cap = h->ws_bytes; A.off = h->fwd_end; A.keep = h->fwd_keep;
     ru::t_sink = h->probe_families ? h->sink : nullptr;
     h->red.main.e.clear();
     h->red.side.e.clear();
     ru::t_red = (h->fusion & RU_FUSE_BATCH_WREDUCE) && !env_trace() ? &h->red : nullptr;
-    // a training forward packs only the fragment forms its switches launch (sb_pack_forms): a switch flipped between that forward and this backward would make
-    // a launch read fragments that were never packed -- refused instead
-    h->sw = switches_from_env();
-    RU_REQUIRE(h->precision != RU_PREC_BF16X3 || h->pack_sw.pack_bits() == h->sw.pack_bits(),
-               "ru_unet_backward: RU_WZ / RU_MX / RU_MXG changed since the forward whose packs this backward reads (signature %d then, %d now)", h->pack_sw.pack_bits(), h->sw.pack_bits());
     int rc = unet_backward_impl(h, params, dprobs, grads, dx, A, (hipStream_t)stream, crit);
     ru::t_red = nullptr;
     ru::t_sink = nullptr;

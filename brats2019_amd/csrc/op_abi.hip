@@ -56,8 +56,9 @@ static int prep_conv3_weights(Conv3Args& a, const float* w, int Cin_f, int Cout_
     a.mode = precision;
     if (conv3_effective_mode(precision, W) == RU_PREC_BF16X3) {
         void* wf = A.alloc(conv3_sb_frag_bytes(cin_conv, cout_conv) / 4 + 64);
-        a.wfrag = wf;
-        RU_ARENA_RUN(conv3_sb_pack_weights(w, wf, Cin_f, Cout_f, mode, s));
+        unsigned wforms = 0;
+        RU_ARENA_RUN(conv3_sb_pack_weights(w, wf, Cin_f, Cout_f, mode, s, PACK_ALL, &wforms));
+        conv3_set_pack(a, wf, wforms);
         return RU_OK;
     }
     float* wp = A.alloc(conv3_packed_floats(cin_conv, cout_conv));
@@ -335,9 +336,20 @@ static int conv3_l_walk(const char* who, Conv3Args a, const float* w, int flags,
     // (conv3_mxg_split_launch; in a training step wgrad3_tz<1,0,3,3> writes that form) and convolved with bf16 main + MX cross products; elsewhere the bit is ignored
     const bool gop = (flags & 64) && !f32 && (flags & 3) == 3 && !(flags & (4 | 8)) && !a.bias && conv3_mxg_usable(sw, N, Cin, Cout, D, H, W);
     const int Cin_f = weight_mode ? Cout : Cin, Cout_f = weight_mode ? Cin : Cout;       // w's own extents [Cout_f][Cin_f][27]
-    RU_ARENA_RUN(f32 ? conv3_f32c_pack_weights(w, wf, Cin_f, Cout_f, weight_mode, s) : conv3_sb_pack_weights(w, wf, Cin_f, Cout_f, weight_mode, s, gop));
-    a.mode = f32 ? RU_PREC_F32 : RU_PREC_BF16X3; a.wfrag = wf;
+    a.mode = f32 ? RU_PREC_F32 : RU_PREC_BF16X3;
     a.in_c16 = flags & 1; a.out_c16 = (flags >> 1) & 1;
+    int forms = PACK_ALL | (gop ? PACK_MX_GRAD : 0);             // (the MX fragments of a weight exist in ONE variant: activation or gradient operand)
+    // flag bit 7: pack w as a training step does (engine.hip, pack_all) -- the forms the switches launch, and no direct fragments where a forward convolution of
+    // this shape and these layouts, without the fused operands of this call, takes a Winograd-z / MX route
+    if (flags & 128) {
+        Conv3Args fwd{};
+        fwd.mode = a.mode; fwd.N = N; fwd.Cin = Cin; fwd.Cout = Cout; fwd.D = D; fwd.H = H; fwd.W = W;
+        fwd.in_c16 = a.in_c16; fwd.out_c16 = a.out_c16; fwd.products = a.products;
+        forms = sb_pack_forms(sw, weight_mode) | ((weight_mode == 0 && conv3_route_skips_direct(conv3_sb_route(fwd, sw))) ? PACK_SKIP_DIRECT : 0);
+    }
+    unsigned wforms = 0;
+    RU_ARENA_RUN(f32 ? conv3_f32c_pack_weights(w, wf, Cin_f, Cout_f, weight_mode, s) : conv3_sb_pack_weights(w, wf, Cin_f, Cout_f, weight_mode, s, forms, &wforms));
+    conv3_set_pack(a, wf, wforms);
     a.in_s16 = (flags >> 3) & 1;                                 // x is voxel-major in SPLIT form (hi / lo bf16 packets, as gn_bwd_apply16 publishes it)
     RU_REQUIRE(!a.in_s16 || a.in_c16, "%s: the split form is a voxel-major layout", who);
     if (gop) {
@@ -353,7 +365,7 @@ static int conv3_l_walk(const char* who, Conv3Args a, const float* w, int flags,
         void* wf4 = A.alloc(conv3_sb4_frag_bytes(Cout) / 4 + 64);
         RU_ARENA_RUN(pad_to_c4_launch(a.x, x4, N, Cin, V, s));
         RU_ARENA_RUN(conv3_sb4_pack_weights(w, wf4, Cin_f, Cout_f, weight_mode, s));
-        a.x = x4; a.wfrag = wf4; a.in_c4 = 1;
+        a.x = x4; conv3_set_pack(a, wf4, PACK_HAS_SB4); a.in_c4 = 1;
     }
     if (route || nblk || a.stat_partials) {
         const int r = f32 ? conv3_f32c_route(a) : conv3_sb_route(a, sw);
@@ -424,7 +436,7 @@ extern "C" size_t ru_conv3d_workspace_bytes(int N, int Cin, int Cout, int D, int
         Wgrad3Args a{};
         a.N = N; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W;
         cover(dry_need([&](Arena& A) { return conv3d_bwd_weight_l_walk(a, A, nullptr); }));
-        for (int flags = 0; flags < 128; ++flags)
+        for (int flags = 0; flags < 256; ++flags)
             if (!(flags & (4 | 64))) cover(conv3_l_need(N, Cin, Cout, D, H, W, flags));       // bits 2 and 6 take more: ru_conv3_l_workspace_bytes
     }
     return kSlack + need;

@@ -10,6 +10,7 @@
 
 #include "../../include/resunet_hip.h"
 #include "switches.hpp"
+#include "conv3_pack_layout.hpp"
 
 namespace ru {
 
@@ -183,6 +184,9 @@ struct Conv3Args {
     // voxel's exponent implied by its hi values): conv3_mx_kernel<GRAD> (16 -> 16 channels; written by wgrad3_tz<1,0,3,3> or conv3_mxg_split_launch)
     int in_g16;
     int in_c4;               // x is a [N][D][H][W][4] copy (pad_to_c4) of a tensor with Cin <= 4: conv3_sb2c4_kernel, wfrag from conv3_sb4_pack_weights
+    // which fragment forms the pack at wfrag holds (conv3_pack_layout.hpp; set with wfrag by conv3_set_pack).  Read on the HOST only: conv3_sb_launch refuses a route
+    // whose form is absent.  (It sits in what was padding in front of the next pointer: no field a kernel reads moves.)
+    unsigned wforms;
     // Fused GroupNorm-BACKWARD statistics (persistent split-bf16 kernel, C16 in and out, no bias / sigmoid; a residual `add` is part of the
     // output and therefore of the sums): this conv's output is
     // the gradient d w.r.t. the activation that followed a GroupNorm of `bst_y` (same shape as y).  The epilogue then writes, instead
@@ -204,6 +208,7 @@ struct Conv3Args {
     int ksplit;
     FinTail fin;             // split-bf16 kernels: finalize stat_partials in the launch (ticket null = off)
 };
+static inline void conv3_set_pack(Conv3Args& a, const void* wfrag, unsigned wforms) { a.wfrag = wfrag; a.wforms = wforms; }
 int conv3_f32_ksplit(int N, int Cin, int Cout, int D, int H, int W);     // split factor the engine uses for an exact-f32 conv of this shape (1 = none)
 int sum_partials_launch(const float* part, int ksplit, size_t n, float* y, hipStream_t s);    // y[i] = part[0][i] + part[1][i] + ... (fixed order)
 int conv3_cin_pad(int Cin);                       // CinP for a given Cin
@@ -247,25 +252,26 @@ int conv3_sb_route_nblk(int r, int N, int Cout, int D, int H, int W);     // par
 bool conv3_wz16_form_built();                     // devtools builds only: the 16x16x32 Winograd-z matrix form is instantiated, so Switches::wz32 can be off
 bool conv3_sb_head_takes_residual(const Switches& sw, int N, int Cin, int Cout, int D, int H, int W);   // the 16 -> <=4 voxel-major-in / NCDHW-out conv of this shape takes the head-form kernel, which stages Conv3Args::in_res
 int conv3_sb_launch(const Conv3Args& a, const Switches& sw, hipStream_t s);
-size_t conv3_sb_frag_bytes(int Cin_conv, int Cout_conv);          // direct fragments + the Winograd-z fragments behind them (where the channel counts allow)
-size_t conv3_sb_frag_bytes_direct(int Cin_conv, int Cout_conv);
+size_t conv3_sb_frag_bytes(int Cin_conv, int Cout_conv);          // the whole pack of one weight (conv3_pack_layout.hpp)
 size_t conv3_sb4_frag_bytes(int Cout_conv);
-int conv3_sb4_pack_weights(const float* w, void* wfrag, int Cin_f, int Cout_f, int mode, hipStream_t s);
+int conv3_sb4_pack_weights(const float* w, void* wfrag, int Cin_f, int Cout_f, int mode, hipStream_t s);                 // its pack holds PACK_HAS_SB4
 bool conv3_sb4_usable(int N, int Cin, int Cout, int D, int H, int W);                                   // shape fits the 4-channel kernel
-int conv3_sb_pack_weights(const float* w, void* wfrag, int Cin_f, int Cout_f, int mode, hipStream_t s, bool grad_operand = false);   // mode 0 fwd, 1 data-gradient; grad_operand: the MX fragments in the gradient-operand variant
+// mode 0 fwd, 1 data-gradient; `forms`: a pack request (conv3_pack_layout.hpp); *wforms: what the pack then holds
+int conv3_sb_pack_weights(const float* w, void* wfrag, int Cin_f, int Cout_f, int mode, hipStream_t s, int forms, unsigned* wforms);
 // the same for many weights in one launch: add entries, then flush (add flushes by itself when the table is full)
 constexpr int RU_PACK_BATCH = 64;
 struct SbPackEntry { const float* w; void* wfrag; int Cin_f, Cout_f, mode, nchunk, ncog, forms; };
 struct SbPackBatch { SbPackEntry e[RU_PACK_BATCH]; int n; };
-// all_forms false: only the forms a training step launches (sb_pack_forms); skip_direct (training, forward weights): every launch that reads this pack takes the
-// Winograd-z / fp16 + MX-fp8 kernel of its shape, so the direct three-product fragments -- a third of a deep-level weight's bytes -- are not written
-int conv3_sb_pack_add(SbPackBatch& b, const Switches& sw, const float* w, void* wfrag, int Cin_f, int Cout_f, int mode, bool all_forms, hipStream_t s, bool skip_direct = false);
+// what the launches of a TRAINING forward + backward under `sw` read of a weight packed in `mode`, as a pack request
+int sb_pack_forms(const Switches& sw, int mode);
+// the route of a forward launch reads no direct fragments: a training step's pack of that launch's weight may leave them out (PACK_SKIP_DIRECT)
+static inline bool conv3_route_skips_direct(int r) { const int f = c3r_family(r); return f == C3F_WZ32 || f == C3F_WZ32MX || f == C3F_WZ16 || f == C3F_MX; }
+int conv3_sb_pack_add(SbPackBatch& b, const float* w, void* wfrag, int Cin_f, int Cout_f, int mode, int forms, hipStream_t s, unsigned* wforms);
 // the gradient-operand form of the MX product scheme (conv3_mx.hip; conv3_mx_pack.hpp MXG_*)
 bool conv3_mxg_usable(const Switches& sw, int N, int Cin, int Cout, int D, int H, int W);      // Switches::mxg and the shape is one conv3_mx_kernel<GRAD> takes: the producer of the gradient asks before it writes the operand form
 // fp32 voxel-major [N][1][D][H][W][16] -> the gradient operand form: per voxel 64 bytes [bf16 hi ch 0-7 | hi ch 8-15 | e4m3(lo * 2^(8-e)), e4m3(g * 2^-e) ch 0-7 | the same ch 8-15],
 // e from the voxel's largest |hi| (what wgrad3_tz<1,0,3,3> publishes in the step; this launch serves the op-level entry and the tests)
 int conv3_mxg_split_launch(const float* x, void* g16, size_t nvox, hipStream_t s);
-bool conv3_sb_forward_skips_direct(const Switches& sw, int N, int Cin, int Cout, int D, int H, int W);     // a forward launch of this shape on activations (products == 2) takes a non-direct kernel
 int conv3_sb_pack_batch(SbPackBatch& b, hipStream_t s);
 // pack [Cout][Cin][27] -> wp.  mode 0: forward; mode 1: data-gradient (taps flipped, in/out swapped:
 // the packed conv maps Cout_f input channels to Cin_f output channels).

@@ -1196,12 +1196,14 @@ def conv3_route(packed):
 
 def conv3_fused(x, w, bias=None, in_c16=False, out_c16=False, few_channels=False, in_split=False, exact_f32=False, activations=False, gradient=False,
                 add=None, in_scale=None, in_shift=None, in_slope=LEAKY_SLOPE, in_res=None, in_sum_out=None, sigmoid=False, products=0,
-                bst_y=None, bst_k=None, bst_slope=LEAKY_SLOPE, stats=None, weight_mode=0):
+                bst_y=None, bst_k=None, bst_slope=LEAKY_SLOPE, stats=None, weight_mode=0, pack_training=False, y=None):
     """One launch of the 3x3x3 family with the operands the engine fuses into it (ru_conv3_l; layout flags as conv3d_layout).  in_scale / in_shift [N, Cin]: the
     GroupNorm apply + LeakyReLU(in_slope) formed in the staging; in_res (voxel-major): added to the transformed input, the sum written to in_sum_out (a tensor
     like x, or True to allocate one); add: joined in the store; stats: per-workgroup (sum, sumsq) of the stored value before the sigmoid -- or, with bst_y /
     bst_k [N, 3, Cout], the GroupNorm-backward sums -- returned as partials [N, Cout, nblk, 2] (default: on with bst_y); weight_mode = 1: w is the FORWARD
-    convolution's [Cin, Cout, 3, 3, 3] and is packed as its data gradient.  route: decode with conv3_route."""
+    convolution's [Cin, Cout, 3, 3, 3] and is packed as its data gradient.  pack_training: w is packed as a training step packs it (flag bit 7: the forms the RU_*
+    switches launch, no direct fragments where a forward convolution of this shape takes a Winograd-z / MX route) -- a launch whose route reads a form the pack
+    lacks is refused.  y: the output tensor to write (default: a new one).  route: decode with conv3_route."""
     x, w, bias, add, in_scale, in_shift, in_res, bst_y, bst_k = (_prep(t) for t in (x, w, bias, add, in_scale, in_shift, in_res, bst_y, bst_k))
     if in_c16:
         n, cb, d, h, wd, _ = (int(v) for v in x.shape)
@@ -1210,7 +1212,8 @@ def conv3_fused(x, w, bias=None, in_c16=False, out_c16=False, few_channels=False
         n, cin, d, h, wd = _dims5(x)
     cout = int(w.shape[1 if weight_mode else 0])
     dev = x.device
-    y = torch.empty((n, cout // 16, d, h, wd, 16) if out_c16 else (n, cout, d, h, wd), dtype=torch.float32, device=dev)
+    if y is None:
+        y = torch.empty((n, cout // 16, d, h, wd, 16) if out_c16 else (n, cout, d, h, wd), dtype=torch.float32, device=dev)
     if in_sum_out is True:
         in_sum_out = torch.full_like(x, float("nan"))
     part, cap = None, 0
@@ -1220,7 +1223,7 @@ def conv3_fused(x, w, bias=None, in_c16=False, out_c16=False, few_channels=False
         cap = n * cout * max(((d + 1) // 2) * ((h + 1) // 2) * ((wd + 15) // 16), 1024) * 2      # nblk <= the (2,2,16) tiles of a sample, or one per workgroup
         part = torch.full((cap,), float("nan"), dtype=torch.float32, device=dev)
     flags = (int(in_c16) | (int(out_c16) << 1) | (int(few_channels) << 2) | (int(in_split) << 3) | (int(exact_f32) << 4) | (int(activations) << 5)
-             | (int(gradient) << 6))
+             | (int(gradient) << 6) | (int(pack_training) << 7))
     lib = L.load()
     ws = L.workspace(lib.ru_conv3_l_workspace_bytes(n, cin, cout, d, h, wd, flags), dev)
     nblk, route = C.c_int(0), C.c_int(0)

@@ -54,7 +54,7 @@ int ru_device_ok(void);
  * `bias` may be NULL.  Exact-f32 arithmetic (v_mfma_f32_16x16x4_f32 / v_fmac_f32).
  * ru_conv3d_workspace_bytes is the largest of the dry walks (the entry's own carve, run on the host without launches) it covers, plus 4096:
  * ru_conv3d_fwd / _bwd_data / _bwd_weight and their _p forms at both precisions, db included; for k = 3 also ru_conv3d_bwd_weight_l and
- * ru_conv3d_fwd_l / ru_conv3_l for every `flags` without bits 2 and 6 (those two take more: ru_conv3_l_workspace_bytes).  */
+ * ru_conv3d_fwd_l / ru_conv3_l for every `flags` (bits 0-7) without bits 2 and 6 (those two take more: ru_conv3_l_workspace_bytes).  */
 size_t ru_conv3d_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W, int k);
 int ru_conv3d_fwd(const float* x, const float* w, const float* bias, float* y,
                   int N, int Cin, int Cout, int D, int H, int W, int k,
@@ -589,7 +589,10 @@ int ru_paste_u8c(const unsigned char* src, unsigned char* full, int C, int D, in
  * chip) take the fp16 + MX-fp8 product scheme the engine's forward convolutions take (f16*f16 + two e4m3 cross terms, RU_MX=0: off); never set for gradients;
  * bit 6 = x (float32, voxel-major both sides, 16 -> 16 channels) is a GRADIENT: where the kernel takes the shape it is converted to the gradient-operand form (bf16 + two
  * e4m3 planes + one exponent byte per voxel) and convolved with bf16 main + MX-fp8 cross products, as the engine's 16-channel data-gradient convolutions are (RU_MXG=0:
- * off; needs 64 more workspace bytes per input voxel); ignored elsewhere.  k = 3.
+ * off; needs 64 more workspace bytes per input voxel); ignored elsewhere; bit 7 = pack `w` as a training step packs it instead of in every form: the fragment
+ * forms the RU_* switches of the process launch, and no direct fragments where a forward convolution of this shape and these layouts (bits 0, 1, 5; no fused
+ * residual / bias operand) takes a Winograd-z or fp16 + MX-fp8 kernel.  The launch itself is unchanged; if its route reads a form that pack does not hold -- a
+ * residual `add` keeps a launch of such a shape on the direct kernel -- it is refused with RU_EINVAL before anything of the convolution is launched.  k = 3.
  * ru_conv3d_fwd_l is ru_conv3_l (below) with weight_mode 0 and no fused operands or reports: ru_conv3_l_workspace_bytes(..., flags) sizes it for any flags,
  * ru_conv3d_workspace_bytes(..., 3) for flags without bits 2 and 6. */
 int ru_layout_convert(const float* src, float* dst, int N, int C, size_t V, int to_c16, ru_stream_t stream);

@@ -86,6 +86,31 @@ def cases():
     add("conv3_l_c16_grad", True, lambda: as_list(ops.conv3_fused(xg, wt, in_c16=True, out_c16=True, gradient=True).y))
     add("conv3d_fwd_l_c16_grad", True, lambda: as_list(ops.conv3d_layout(xg, wt, in_c16=True, out_c16=True, gradient=True)))
 
+    # ---- one launch per route family of the 3x3x3 split-bf16 kernels (each reads another form of the weight pack), at the smallest shapes
+    # tests/test_conv3_fused_host.py lists for them
+    s60 = (30, 30, 60)
+    x32, w32 = _c16(2, 32, 32, 32, 32, seed=100), _rand(32, 32, 3, 3, 3, seed=101, scale=0.06)
+    x32r = _c16(2, 32, 32, 30, 44, seed=102)
+    x16, a16 = _c16(2, 16, *s60, seed=103), _c16(2, 16, *s60, seed=104)
+    sc16, sh16 = _rand(2, 16, seed=105) + 1.5, _rand(2, 16, seed=106, scale=0.5)
+    w3, b3 = _rand(3, 16, 3, 3, 3, seed=107, scale=0.1), _rand(3, seed=108)
+    xs24, as24 = _c16(1, 16, 8, 16, 18, seed=109), _c16(1, 16, 8, 16, 18, seed=110)
+    for tag, want, xin, wgt, kw in (
+            ("wz32", ("wz32", False, False), x32, w32, dict(in_c16=True, out_c16=True)),
+            ("wz32mx", ("wz32mx", False, False), x32r, w32, dict(in_c16=True, out_c16=True, activations=True)),
+            ("mx_fwd", ("mx", False, False), x16, wt, dict(in_c16=True, out_c16=True, activations=True)),
+            ("mx_grad", ("mx", False, True), x16, wt, dict(in_c16=True, out_c16=True, gradient=True, weight_mode=1)),
+            ("head", ("sb2", True, False), x16, w3, dict(in_c16=True, bias=b3, sigmoid=True)),
+            ("head_res", ("sb2", True, False), x16, w3, dict(in_c16=True, bias=b3, sigmoid=True, in_scale=sc16, in_shift=sh16, in_res=a16, in_sum_out=True)),
+            ("sb2_add", ("sb2", False, False), x16, wt, dict(in_c16=True, out_c16=True, add=a16, stats=True)),
+            ("sb_add", ("sb", False, False), xs24, wt, dict(in_c16=True, out_c16=True, add=as24, stats=True))):
+        def run(xin=xin, wgt=wgt, kw=kw, want=want):
+            r = ops.conv3_fused(xin, wgt, **kw)
+            route = ops.conv3_route(r.route)
+            assert (route.family, route.head, route.grad) == want, (want, route)
+            return as_list([r.y, r.in_sum, r.partials])
+        add("conv3_l_route_" + tag, True, run)
+
     # ---- ru_conv1_l: plain (takes nothing), gather and scatter of 1 x 16 -> 32 at one coarse voxel
     xf, xc = _c16(1, 16, 2, 2, 2, seed=70), _c16(1, 32, 1, 1, 1, seed=71)
     wg, wsc, wp = _rand(32, 16, 2, 2, 2, seed=72, scale=0.3), _rand(32, 16, 2, 2, 2, seed=73, scale=0.3), _rand(32, 16, seed=74, scale=0.3)

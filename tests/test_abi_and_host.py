@@ -247,7 +247,7 @@ def test_op_level_workspace_queries_are_walks_of_their_entries(lib):
     ru_conv3d_fwd_l(flags = 3 | 32) with it -- and bit 2 (the 4-channel copy) or bit 6 (the gradient-operand tensor) never lowers
     ru_conv3_l_workspace_bytes.  The grid holds a shape the 4-channel kernel takes (2 x 4 -> 16 at 32 x 32 x 64) and one the gradient-operand form
     takes (2 x 16 -> 16 at 30 x 44 x 40), where those bits must cost their tensor."""
-    plain = [f for f in range(128) if not f & (4 | 64)]
+    plain = [f for f in range(256) if not f & (4 | 64)]
     for n, d, h, w in ((1, 8, 8, 16), (1, 5, 6, 7), (2, 32, 32, 64), (2, 30, 44, 40)):
         for cin, cout in ((4, 16), (16, 16), (32, 32), (16, 3)):
             q = lambda flags: int(lib.ru_conv3_l_workspace_bytes(n, cin, cout, d, h, w, flags))
@@ -260,6 +260,20 @@ def test_op_level_workspace_queries_are_walks_of_their_entries(lib):
     assert lib.ru_conv3_l_workspace_bytes(2, 4, 16, 32, 32, 64, 2 | 4) >= lib.ru_conv3_l_workspace_bytes(2, 4, 16, 32, 32, 64, 2) + nvox * 16
     nvox = 2 * 30 * 44 * 40                       # (the walk reads the process's switches, as the call does: RU_MXG=0 turns the form off)
     assert os.environ.get("RU_MXG") == "0" or lib.ru_conv3_l_workspace_bytes(2, 16, 16, 30, 44, 40, 3 | 64) >= lib.ru_conv3_l_workspace_bytes(2, 16, 16, 30, 44, 40, 3) + nvox * 64
+
+
+def test_conv3_pack_sizes_are_those_before_the_layout_table(lib):
+    """ru_conv3_l_workspace_bytes at 2 x 32 x 32 x 64 for the channel pairs of the network's levels, its stem (4 -> 16, and 3 / 4 input channels through the 4-channel
+    copy, flags 2 | 4), its head (16 -> 3, 16 -> 1) and their data gradients: the values the library gave when the pack's size was a hand sum of per-form helpers
+    (recorded from that build), now the total of csrc/conv3_pack_layout.hpp's table.  Bit 7 (pack as a training step does) takes the same buffer."""
+    recorded = {(16, 16, 3): 61696, (32, 32, 3): 422144, (64, 64, 3): 1675520, (128, 128, 3): 6689024, (4, 16, 0): 33024, (4, 16, 2 | 4): 2140672,
+                (3, 16, 2 | 4): 2140672, (16, 4, 3): 43264, (16, 3, 1): 43264, (3, 16, 2): 33024, (16, 1, 1): 43264, (16, 16, 0): 61696, (32, 32, 0): 422144,
+                (64, 64, 0): 1675520, (128, 128, 0): 6689024}
+    if os.environ.get("RU_MXG") != "0":
+        recorded[(16, 16, 3 | 64)] = 8450304      # + the gradient-operand tensor
+    for (cin, cout, flags), want in recorded.items():
+        assert int(lib.ru_conv3_l_workspace_bytes(2, cin, cout, 32, 32, 64, flags)) == want, (cin, cout, flags)
+        assert int(lib.ru_conv3_l_workspace_bytes(2, cin, cout, 32, 32, 64, flags | 128)) == want, (cin, cout, flags)
 
 
 def _module_with_state_layout(names, shapes):

@@ -141,3 +141,28 @@ def test_bst_on_the_four_channel_kernel_with_a_residual_is_refused():
     i, _ = shared(c)
     with pytest.raises(RuntimeError, match="fused GroupNorm-backward statistics need the persistent voxel-major kernel"):
         launch(c, dict(i, add=make_inputs(_by_name("sb2_16_add_stats_real"))["add"]))
+
+
+@pytest.mark.parametrize("cin, dhw, family", [(32, (16, 32, 128), "wz32mx"), (16, (32, 64, 64), "mx")], ids=["wz32mx_32", "mx_16"])
+def test_a_pack_without_its_direct_fragments_refuses_the_direct_route(cin, dhw, family):
+    """A pack says what it holds (csrc/conv3_pack_layout.hpp).  Flag bit 7 packs the weight as a training step does: a forward convolution on activations of this
+    shape takes the Winograd-z (32 -> 32 at 1 x 16 x 32 x 128: 8 x 4 x 8 x 1 = 256 items, one per CU) / fp16 + MX-fp8 (16 -> 16 at 1 x 32 x 64 x 64: 256 (4,8,16)
+    tiles, the smallest persistent-kernel shape) kernel, so the direct fragments are left out -- and the launch computes the bytes of the launch on a full pack.
+    The same launch with a residual `add` routes to the direct persistent kernel, whose fragments that pack lacks: refused as an argument error on the host, the
+    output untouched."""
+    from brats2019_amd import ops
+    g = torch.Generator().manual_seed(7 + cin)
+    x = torch.randn(1, cin // 16, *dhw, 16, generator=g).cuda()
+    w = (torch.randn(cin, cin, 3, 3, 3, generator=g) * (27 * cin) ** -0.5).cuda()
+    add = torch.randn(1, cin // 16, *dhw, 16, generator=g).cuda()
+    kw = dict(in_c16=True, out_c16=True, activations=True)
+    full, training = ops.conv3_fused(x, w, **kw), ops.conv3_fused(x, w, pack_training=True, **kw)
+    assert ops.conv3_route(full.route).family == family and training.route == full.route, (ops.conv3_route(full.route), ops.conv3_route(training.route))
+    assert torch.equal(full.y.view(torch.int32), training.y.view(torch.int32))
+    with_add = ops.conv3_route(ops.conv3_fused(x, w, add=add, **kw).route)           # the full pack serves the direct route
+    assert with_add.family == "sb2" and with_add.add, with_add
+    y = torch.full_like(full.y, 12345.0)
+    with pytest.raises(RuntimeError, match=r"\(-1\).*does not hold the direct fragments that route sb2"):
+        ops.conv3_fused(x, w, add=add, pack_training=True, y=y, **kw)
+    torch.cuda.synchronize()
+    assert bool((y == 12345.0).all())

@@ -40,6 +40,29 @@ xc = ops.to_c16(x)
 say("layout", [xc, ops.from_c16(xc)])
 say("upsample2x_c16", [ops.upsample2x_c16(xc, out_slope=0.01), ops.upsample2x_bwd_c16(ops.to_c16(_rand(1, 16, 6, 10, 12, seed=93)))])
 
+# one training step (loss, flat gradient) under the three sets of forward kernels: the smallest configuration of the suite on the NCDHW split-bf16 flow, and the
+# shipped one at the smallest batch that reaches the fp16 + MX-fp8, Winograd-z and direct kernels in one step (2 x 64^3: levels 0 / 1 / 2-3)
+from brats2019_amd import loss as loss_mod, model as model_mod
+from oracle import resunet_oracle as O
+SMALL = dict(depth=3, encoder_layers=[1, 1, 2], decoder_layers=[1, 1, 1], number_of_channels=[8, 16, 32], number_of_outputs=3)       # tests/test_hip_unet.py
+for cfg_name, cfg, n, size in (("small", SMALL, 1, 32), ("default", O.DEFAULT_CFG, 2, 64)):
+    for env_name, env in (("default", {}), ("RU_MX=0", {"RU_MX": "0"}), ("RU_MX=0_RU_WZ=0", {"RU_MX": "0", "RU_WZ": "0"})):
+        os.environ.update(env)
+        try:
+            net = model_mod.UNet(**cfg)
+            net.set_precision("bf16x3")
+            net.load_state_dict({k: torch.from_numpy(v) for k, v in O.make_params(41, **cfg).items()})
+            net.cuda().train()
+            out = net([torch.from_numpy(O.make_input(n, size, size, size, seed=41)).cuda()])
+            loss = loss_mod.FusedCriterion()(out, [torch.from_numpy(O.make_target(n, size, size, size, seed=41)).cuda()])
+            loss.backward()
+            say("train_step_%s_%s" % (cfg_name, env_name),
+                [loss.detach(), out[0].detach(), torch.cat([q.grad.reshape(-1) for _, q in net.named_parameters() if q.grad is not None])])
+        finally:
+            for k in env:
+                os.environ.pop(k, None)
+        del net
+
 if "--out" in sys.argv:
     with open(sys.argv[sys.argv.index("--out") + 1], "w") as f:
         f.write("\n".join(lines) + "\n")

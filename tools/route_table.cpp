@@ -35,16 +35,14 @@ int main() {
         for (int N : Ns) for (const auto& c : ch) for (const auto& d : shp) {
             const int Cin = c[0], Cout = c[1], D = d[0], H = d[1], W = d[2];
             // the plan: what the engine asks before it builds its arguments, and what a training step packs of this weight at this shape
-            SbPackBatch b;
-            int forms[3];
-            for (int k = 0; k < 3; ++k) {                 // forward weight without / with the engine's skip_direct, data-gradient weight
-                b.n = 0;
-                conv3_sb_pack_add(b, sw, nullptr, nullptr, Cin, Cout, k == 2, false, nullptr, k == 1 && conv3_sb_forward_skips_direct(sw, N, Cin, Cout, D, H, W));
-                forms[k] = b.e[0].forms;
-            }
+            Conv3Args fwd{};                              // the forward launch of the engine's voxel-major flow that reads the weight (engine.hip, conv3_gn_args)
+            fwd.mode = RU_PREC_BF16X3; fwd.N = N; fwd.Cin = Cin; fwd.Cout = Cout; fwd.D = D; fwd.H = H; fwd.W = W; fwd.in_c16 = 1; fwd.out_c16 = 1; fwd.products = 2;
+            const bool skip_direct = conv3_route_skips_direct(conv3_sb_route(fwd, sw));
+            // forward weight without / with the engine's PACK_SKIP_DIRECT, data-gradient weight
+            const int forms[3] = {sb_pack_forms(sw, 0), sb_pack_forms(sw, 0) | (skip_direct ? PACK_SKIP_DIRECT : 0), sb_pack_forms(sw, 1)};
             snprintf(buf, sizeof(buf), "N=%d %d->%d %dx%dx%d plan: head_res=%d mxg=%d skip_direct=%d forms=%d/%d/%d\n", N, Cin, Cout, D, H, W,
                      (int)conv3_sb_head_takes_residual(sw, N, Cin, Cout, D, H, W), (int)conv3_mxg_usable(sw, N, Cin, Cout, D, H, W),
-                     (int)conv3_sb_forward_skips_direct(sw, N, Cin, Cout, D, H, W), forms[0], forms[1], forms[2]);
+                     (int)skip_direct, forms[0], forms[1], forms[2]);
             emit(buf);
             // layouts: bit 0 voxel-major input, bit 1 voxel-major output; the 4-channel copy exists for NCDHW inputs of <= 4 channels, the split / gradient-operand
             // forms for voxel-major inputs
