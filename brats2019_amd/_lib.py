@@ -172,7 +172,13 @@ SIGNATURES = {
     "ru_conv1_l": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _f, _vp, _f, _i, _i, _sz, _i, _i, _i, _i, _vp, _vp, _f, _vp, _sz,
                         C.POINTER(_i), C.POINTER(_i), _vp, _sz, _vp]),
     "ru_conv3_l_workspace_bytes": (_sz, [_i] * 7),
-    "ru_conv3_l": (_i, [_vp, _vp, _vp, _vp] + [_i] * 8 + [_vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _vp, _f, _vp, _sz, C.POINTER(_i), C.POINTER(_i), _vp, _sz, _vp]),
+    "ru_conv3_l": (_i, [_vp, _vp, _vp, _vp] + [_i] * 8 + [_vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _vp, _f, _vp, _sz, C.POINTER(_i), C.POINTER(_i), _vp, _sz, _vp, _vp]),
+    "ru_gn_finalize_l": (_i, [_vp, _i] + [_vp] * 7 + [_i, _i, _sz, _i, _f, _i, _vp]),
+    "ru_gn_apply_l": (_i, [_vp] * 7 + [_i, _i, _sz, _f, _f, _vp]),
+    "ru_gn_bwd_finalize_l": (_i, [_vp, _i] + [_vp] * 6 + [_i, _i, _sz, _i, _i, _vp]),
+    "ru_gn_bwd_l_nblk": (_i, [_sz]),
+    "ru_gn_bwd_l_workspace_bytes": (_sz, [_i, _i, _sz]),
+    "ru_gn_bwd_l": (_i, [_vp] * 7 + [_f] + [_vp] * 5 + [_i, _i, _sz, _i, _i, _vp, _sz, _vp]),
     "ru_wgrad1_l_workspace_bytes": (_sz, [_i, _i, _i, _sz]),
     "ru_wgrad3_l_workspace_bytes": (_sz, [_i] * 7),
     "ru_wgrad3_l": (_i, [_vp, _vp, _vp] + [_i] * 8 + [_vp, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, C.POINTER(_i), _vp, _sz, _vp]),
@@ -221,6 +227,13 @@ PACK_F32, PACK_U16 = 0, 1
 PACK_KINDS = {"float32": PACK_F32, "uint16": PACK_U16}
 AUG_ZOOM, AUG_AFFINE = 0, 1
 AUG_BATCH_MAX = 8
+
+
+class FinDesc(C.Structure):
+    """ru_fin_desc (include/resunet_hip.h): what a kernel's in-launch tail finalizes, and where to"""
+    _fields_ = [("kind", _i), ("G", _i), ("s2_sign", _i), ("keep_ticket", _i), ("eps", _f), ("nblk", _i), ("N", _i), ("C", _i),
+                ("gamma", _vp), ("beta", _vp), ("mean", _vp), ("rstd", _vp), ("scale", _vp), ("shift", _vp), ("bst_k", _vp),
+                ("coef", _vp), ("dgamma", _vp), ("dbeta", _vp)]
 
 
 class CaseDesc(C.Structure):

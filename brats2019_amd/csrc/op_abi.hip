@@ -320,12 +320,28 @@ extern "C" int ru_upsample2x_trilinear_bwd_l(const float* dy, float* dx, int N, 
     return up2_bwd16_launch(dy, dx, N, C, D, H, W, (hipStream_t)stream);
 }
 
-// The 3x3x3 family, one launch at a time with every fused operand of Conv3Args (except the tail finalize `fin`, whose ticket is the engine's, and ksplit): a thin
-// filler.  The caller (`who`, for the messages) has put the tensors, the shape and the fused operands into `a`; the walk decodes `flags` (resunet_hip.h), packs w
-// and launches.  weight_mode = 1 packs the data-gradient form of w = [Cout][Cin][3][3][3] OF THE FORWARD CONVOLUTION (channels swapped, taps mirrored), so that the
-// launch maps x's Cin channels (the forward's outputs) to y's Cout channels as the engine's backward does.  ru_conv3d_fwd_l is this walk with weight_mode 0 and
-// no fused operands or reports.
-static int conv3_l_walk(const char* who, Conv3Args a, const float* w, int flags, int weight_mode, size_t stat_floats, int* nblk, int* route, Arena& A, hipStream_t s) {
+// ru_fin_desc -> FinTail (what the caller left 0 of nblk / N / C is the launch's own)
+static void fill_fin(FinTail& f, const ru_fin_desc& d, unsigned* ticket, int nblk, int N, int C, size_t V) {
+    f.ticket = ticket; f.kind = d.kind; f.nblk = d.nblk ? d.nblk : nblk; f.N = d.N ? d.N : N; f.C = d.C ? d.C : C; f.G = d.G; f.V = V; f.eps = d.eps; f.s2_sign = d.s2_sign;
+    f.gamma = d.gamma; f.beta = d.beta; f.mean = d.mean; f.rstd = d.rstd; f.scale = d.scale; f.shift = d.shift; f.bst_k = d.bst_k;
+    f.coef = d.coef; f.dgamma = d.dgamma; f.dbeta = d.dbeta;
+}
+static int fin_desc_check(const char* who, const ru_fin_desc& d, int C) {
+    RU_REQUIRE(d.kind == 1 || d.kind == 2, "%s: the tail's kind is 1 (statistics) or 2 (GroupNorm-backward sums)", who);
+    RU_REQUIRE(d.G > 0 && C % d.G == 0, "%s: the tail needs G groups with C %% G == 0", who);
+    RU_REQUIRE(d.gamma && d.mean && d.rstd, "%s: the tail needs gamma, mean and rstd", who);
+    RU_REQUIRE(d.kind != 1 || (d.beta && d.scale && d.shift), "%s: a kind-1 tail needs beta, scale and shift", who);
+    RU_REQUIRE(d.kind != 2 || d.coef, "%s: a kind-2 tail needs coef", who);
+    return RU_OK;
+}
+// The 3x3x3 family, one launch at a time with every fused operand of Conv3Args (except ksplit): a thin filler.  The caller (`who`, for the messages) has put the
+// tensors, the shape and the fused operands into `a`; the walk decodes `flags` (resunet_hip.h), packs w and launches.  weight_mode = 1 packs the data-gradient form of
+// w = [Cout][Cin][3][3][3] OF THE FORWARD CONVOLUTION (channels swapped, taps mirrored), so that the launch maps x's Cin channels (the forward's outputs) to y's Cout
+// channels as the engine's backward does.  ru_conv3d_fwd_l is this walk with weight_mode 0 and no fused operands or reports.  fd (flag bit 8 on a dry walk): the tail
+// finalize -- Conv3Args::fin filled as the engine's conv3_gn / fill_bwd_tail fill it, the ticket a word of the workspace, zeroed on the stream (a workspace arrives
+// with anything in it).
+static int conv3_l_walk(const char* who, Conv3Args a, const float* w, int flags, int weight_mode, size_t stat_floats, int* nblk, int* route, Arena& A, hipStream_t s,
+                        const ru_fin_desc* fd = nullptr) {
     const Switches sw = switches_from_env();
     const int N = a.N, Cin = a.Cin, Cout = a.Cout, D = a.D, H = a.H, W = a.W;
     const bool f32 = (flags & 16) != 0;                          // exact-f32 arithmetic on voxel-major tensors (conv3_f32c_kernel)
@@ -367,13 +383,16 @@ static int conv3_l_walk(const char* who, Conv3Args a, const float* w, int flags,
         RU_ARENA_RUN(conv3_sb4_pack_weights(w, wf4, Cin_f, Cout_f, weight_mode, s));
         a.x = x4; conv3_set_pack(a, wf4, PACK_HAS_SB4); a.in_c4 = 1;
     }
+    unsigned* ticket = (fd || (flags & 256)) ? reinterpret_cast<unsigned*>(A.alloc(64)) : nullptr;
     if (route || nblk || a.stat_partials) {
         const int r = f32 ? conv3_f32c_route(a) : conv3_sb_route(a, sw);
         if (route) *route = r;
         const int nb = f32 ? conv3_f32c_tiles_per_sample(N, Cin, Cout, D, H, W) : conv3_sb_route_nblk(r, N, Cout, D, H, W);     // partials per (sample, channel)
         if (nblk) *nblk = nb;
         RU_REQUIRE(!a.stat_partials || stat_floats >= (size_t)N * Cout * nb * 2, "%s: statistics buffer too small", who);
+        if (fd && a.stat_partials && !A.dry && !A.failed) fill_fin(a.fin, *fd, ticket, nb, N, Cout, (size_t)D * H * W);
     }
+    if (fd && !fd->keep_ticket) RU_ARENA_RUN(fill_launch(reinterpret_cast<float*>(ticket), 0.f, 1, s));
     RU_ARENA_RUN(f32 ? conv3_launch(a, sw, s) : conv3_sb_launch(a, sw, s));
     return RU_OK;
 }
@@ -387,8 +406,10 @@ extern "C" size_t ru_conv3_l_workspace_bytes(int N, int Cin, int Cout, int D, in
 extern "C" int ru_conv3_l(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Cout, int D, int H, int W, int flags, int weight_mode,
                           const float* add, const float* in_scale, const float* in_shift, float in_slope, const float* in_res, float* in_sum_out,
                           int sigmoid, int products, const float* bst_y, const float* bst_k, float bst_slope, float* stat_partials, size_t stat_floats,
-                          int* nblk, int* route, void* ws, size_t ws_bytes, ru_stream_t stream) {
+                          int* nblk, int* route, void* ws, size_t ws_bytes, ru_stream_t stream, const ru_fin_desc* fin) {
     RU_REQUIRE(x && w && y, "ru_conv3_l: null argument");
+    RU_REQUIRE(!fin || stat_partials, "ru_conv3_l: the tail finalizes the statistics of this launch (stat_partials)");
+    if (fin) { const int rc = fin_desc_check("ru_conv3_l", *fin, Cout); if (rc) return rc; }
     RU_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, "ru_conv3_l: bad shape");
     RU_REQUIRE(weight_mode == 0 || weight_mode == 1, "ru_conv3_l: weight_mode is 0 (forward packing) or 1 (data-gradient packing)");
     Conv3Args a{};
@@ -396,7 +417,7 @@ extern "C" int ru_conv3_l(const float* x, const float* w, const float* bias, flo
     a.add = add; a.in_scale = in_scale; a.in_shift = in_shift; a.in_slope = in_slope; a.in_res = in_res; a.in_sum_out = in_sum_out; a.sigmoid = sigmoid;
     a.products = products; a.bst_y = bst_y; a.bst_k = bst_k; a.bst_slope = bst_slope; a.stat_partials = stat_partials;
     Arena A = arena_over(ws, ws_bytes);
-    return walk_result(A, conv3_l_walk("ru_conv3_l", a, w, flags, weight_mode, stat_floats, nblk, route, A, (hipStream_t)stream));
+    return walk_result(A, conv3_l_walk("ru_conv3_l", a, w, flags, weight_mode, stat_floats, nblk, route, A, (hipStream_t)stream, fin));
 }
 extern "C" int ru_conv3d_fwd_l(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Cout, int D, int H, int W,
                                int flags, void* ws, size_t ws_bytes, ru_stream_t stream) {
@@ -440,6 +461,64 @@ extern "C" size_t ru_conv3d_workspace_bytes(int N, int Cin, int Cout, int D, int
             if (!(flags & (4 | 64))) cover(conv3_l_need(N, Cin, Cout, D, H, W, flags));       // bits 2 and 6 take more: ru_conv3_l_workspace_bytes
     }
     return kSlack + need;
+}
+
+// ====================================================================== the voxel-major GroupNorm chain, one link at a time (thin: the launchers' own checks refuse)
+extern "C" int ru_gn_finalize_l(const float* partials, int nblk, const float* gamma, const float* beta, float* mean, float* rstd, float* scale, float* shift, float* bst_k,
+                                int N, int C, size_t V, int G, float eps, int centred, ru_stream_t stream) {
+    RU_REQUIRE(partials && gamma && beta && mean && rstd && scale && shift, "ru_gn_finalize_l: null argument");
+    RU_REQUIRE(N > 0 && C > 0 && G > 0 && nblk > 0 && V > 0, "ru_gn_finalize_l: bad shape");
+    return gn_finalize_launch(partials, nblk, gamma, beta, mean, rstd, scale, shift, N, C, V, G, eps, (hipStream_t)stream, bst_k, centred != 0);
+}
+extern "C" int ru_gn_apply_l(const float* x, const float* scale, const float* shift, const float* res, const float* res_scale, const float* res_shift, float* y,
+                             int N, int C, size_t V, float slope, float res_slope, ru_stream_t stream) {
+    RU_REQUIRE(x && scale && shift && y, "ru_gn_apply_l: null argument");
+    RU_REQUIRE(N > 0 && C > 0 && V > 0, "ru_gn_apply_l: bad shape");
+    return gn_apply16_launch(x, scale, shift, res, y, N, C, V, slope, (hipStream_t)stream, res_scale, res_shift, res_slope);
+}
+extern "C" int ru_gn_bwd_finalize_l(const float* partials, int nblk, const float* gamma, const float* mean, const float* rstd, float* coef, float* dgamma, float* dbeta,
+                                    int N, int C, size_t V, int G, int s2_sign, ru_stream_t stream) {
+    RU_REQUIRE(partials && gamma && mean && rstd && coef, "ru_gn_bwd_finalize_l: null argument");
+    RU_REQUIRE(N > 0 && C > 0 && G > 0 && nblk > 0 && V > 0, "ru_gn_bwd_finalize_l: bad shape");
+    return gn_bwd_finalize_launch(partials, nblk, gamma, mean, rstd, coef, dgamma, dbeta, N, C, V, G, (hipStream_t)stream, s2_sign);
+}
+
+// the sequence of the engine's gn_bwd() on the voxel-major flow: reduce (with or without the kind-2 tail), finalize where there is no tail, apply (plain or split)
+static int copy_out(float* dst, const float* src, size_t nfloats, hipStream_t s) {
+    const hipError_t e = hipMemcpyAsync(dst, src, nfloats * sizeof(float), hipMemcpyDeviceToDevice, s);
+    return e == hipSuccess ? RU_OK : hip_fail(e, "hipMemcpyAsync(ru_gn_bwd_l)");
+}
+static int gn_bwd_l_walk(const float* x, const float* dact, const float* gamma, const float* scale, const float* shift, const float* mean, const float* rstd, float slope,
+                         float* dx, float* dgamma, float* dbeta, float* coef_out, float* partials_out, int N, int C, size_t V, int G, int flags, Arena& A, hipStream_t s) {
+    const int nblk = gn_bwd_tiles16(V);
+    float* part = A.alloc((size_t)N * C * nblk * 2);
+    float* coef = A.alloc((size_t)N * C * 3);
+    unsigned* ticket = reinterpret_cast<unsigned*>(A.alloc(64));
+    FinTail f{};
+    if ((flags & 1) && !A.dry && !A.failed) {
+        f.ticket = ticket; f.kind = 2; f.nblk = nblk; f.N = N; f.C = C; f.G = G; f.V = V; f.s2_sign = 0;
+        f.gamma = gamma; f.mean = const_cast<float*>(mean); f.rstd = const_cast<float*>(rstd); f.coef = coef; f.dgamma = dgamma; f.dbeta = dbeta;
+    }
+    if ((flags & 1) && !(flags & 8)) RU_ARENA_RUN(fill_launch(reinterpret_cast<float*>(ticket), 0.f, 1, s));
+    RU_ARENA_RUN(gn_bwd_reduce16_launch(x, dact, scale, shift, mean, rstd, slope, part, N, C, V, G, s, &f));
+    if (!(flags & 1)) RU_ARENA_RUN(gn_bwd_finalize_launch(part, nblk, gamma, mean, rstd, coef, dgamma, dbeta, N, C, V, G, s, 0));
+    if (coef_out) RU_ARENA_RUN(copy_out(coef_out, coef, (size_t)N * C * 3, s));
+    if (partials_out) RU_ARENA_RUN(copy_out(partials_out, part, (size_t)N * C * nblk * 2, s));
+    if (!(flags & 4)) RU_ARENA_RUN(gn_bwd_apply16_launch(x, dact, scale, shift, coef, slope, dx, N, C, V, (flags >> 1) & 1, s));
+    return RU_OK;
+}
+extern "C" int ru_gn_bwd_l_nblk(size_t V) { return gn_bwd_tiles16(V); }
+extern "C" size_t ru_gn_bwd_l_workspace_bytes(int N, int C, size_t V) {
+    return kSlack + dry_need([&](Arena& A) { return gn_bwd_l_walk(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                                  N, C, V, 8, 0, A, nullptr); });
+}
+extern "C" int ru_gn_bwd_l(const float* x, const float* dact, const float* gamma, const float* scale, const float* shift, const float* mean, const float* rstd, float slope,
+                           float* dx, float* dgamma, float* dbeta, float* coef_out, float* partials_out, int N, int C, size_t V, int G, int flags,
+                           void* ws, size_t ws_bytes, ru_stream_t stream) {
+    RU_REQUIRE(x && dact && gamma && scale && shift && mean && rstd && (dx || (flags & 4)), "ru_gn_bwd_l: null argument");
+    RU_REQUIRE(N > 0 && C > 0 && G > 0 && V > 0, "ru_gn_bwd_l: bad shape");
+    Arena A = arena_over(ws, ws_bytes);
+    return walk_result(A, gn_bwd_l_walk(x, dact, gamma, scale, shift, mean, rstd, slope, dx, dgamma, dbeta, coef_out, partials_out, N, C, V, G, flags, A, (hipStream_t)stream));
 }
 
 // The voxel-major pointwise family, one launch at a time: thin fillers of Conv1Args / Wgrad1Args (no kernels, no arithmetic of their own).

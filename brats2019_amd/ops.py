@@ -1182,7 +1182,10 @@ def conv1x1_bwd_weight_c16(x, dy, x1=None, ldw=None, s2d=False, tap_split=False,
     return Wgrad1Result(dw, dx0, dx1, inst.value)
 
 
-Conv3Result = collections.namedtuple("Conv3Result", "y in_sum partials nblk route")
+Conv3Result = collections.namedtuple("Conv3Result", "y in_sum partials nblk route fin", defaults=(None,))
+GnStats = collections.namedtuple("GnStats", "mean rstd scale shift bst_k")
+GnBwdCoef = collections.namedtuple("GnBwdCoef", "coef dgamma dbeta")
+GnBwdResult = collections.namedtuple("GnBwdResult", "dx dgamma dbeta coef partials")
 Conv3Route = collections.namedtuple("Conv3Route", "family tz ty in16 out16 multi bst add np head grad")
 CONV3_FAMILIES = {1: "sb", 2: "sb2", 3: "sb2c4", 4: "wz32", 5: "wz32mx", 6: "mx", 7: "f32c", 8: "wz16"}
 
@@ -1196,14 +1199,20 @@ def conv3_route(packed):
 
 def conv3_fused(x, w, bias=None, in_c16=False, out_c16=False, few_channels=False, in_split=False, exact_f32=False, activations=False, gradient=False,
                 add=None, in_scale=None, in_shift=None, in_slope=LEAKY_SLOPE, in_res=None, in_sum_out=None, sigmoid=False, products=0,
-                bst_y=None, bst_k=None, bst_slope=LEAKY_SLOPE, stats=None, weight_mode=0, pack_training=False, y=None):
+                bst_y=None, bst_k=None, bst_slope=LEAKY_SLOPE, stats=None, weight_mode=0, pack_training=False, y=None,
+                tail=0, tail_gamma=None, tail_beta=None, tail_mean=None, tail_rstd=None, tail_want_k=False, tail_s2_sign=1, tail_groups=8, tail_eps=1e-5,
+                tail_override=None, tail_workspace=None, tail_keep_ticket=False):
     """One launch of the 3x3x3 family with the operands the engine fuses into it (ru_conv3_l; layout flags as conv3d_layout).  in_scale / in_shift [N, Cin]: the
     GroupNorm apply + LeakyReLU(in_slope) formed in the staging; in_res (voxel-major): added to the transformed input, the sum written to in_sum_out (a tensor
     like x, or True to allocate one); add: joined in the store; stats: per-workgroup (sum, sumsq) of the stored value before the sigmoid -- or, with bst_y /
     bst_k [N, 3, Cout], the GroupNorm-backward sums -- returned as partials [N, Cout, nblk, 2] (default: on with bst_y); weight_mode = 1: w is the FORWARD
     convolution's [Cin, Cout, 3, 3, 3] and is packed as its data gradient.  pack_training: w is packed as a training step packs it (flag bit 7: the forms the RU_*
     switches launch, no direct fragments where a forward convolution of this shape takes a Winograd-z / MX route) -- a launch whose route reads a form the pack
-    lacks is refused.  y: the output tensor to write (default: a new one).  route: decode with conv3_route."""
+    lacks is refused.  y: the output tensor to write (default: a new one).  route: decode with conv3_route.
+    tail = 1 / 2: the launch's last workgroup finalizes the partials (ru_fin_desc): 1 with tail_gamma / tail_beta -> fin = GnStats (bst_k with tail_want_k); 2 (the
+    partials are the GroupNorm-backward sums of bst_*) with tail_gamma and the GroupNorm's tail_mean / tail_rstd -> fin = GnBwdCoef.  tail_override: dict of nblk / N / C
+    handed to the launcher in place of the launch's own.  With a tail, fin = (the finalized tensors, the workspace tensor used); tail_workspace: that tensor of an
+    earlier call of the same shape, to be used again -- with tail_keep_ticket its ticket word is NOT zeroed before the launch (the finisher left it at zero)."""
     x, w, bias, add, in_scale, in_shift, in_res, bst_y, bst_k = (_prep(t) for t in (x, w, bias, add, in_scale, in_shift, in_res, bst_y, bst_k))
     if in_c16:
         n, cb, d, h, wd, _ = (int(v) for v in x.shape)
@@ -1225,15 +1234,85 @@ def conv3_fused(x, w, bias=None, in_c16=False, out_c16=False, few_channels=False
     flags = (int(in_c16) | (int(out_c16) << 1) | (int(few_channels) << 2) | (int(in_split) << 3) | (int(exact_f32) << 4) | (int(activations) << 5)
              | (int(gradient) << 6) | (int(pack_training) << 7))
     lib = L.load()
-    ws = L.workspace(lib.ru_conv3_l_workspace_bytes(n, cin, cout, d, h, wd, flags), dev)
+    fd, fin = None, None
+    if tail:
+        tail_gamma, tail_beta, tail_mean, tail_rstd = (_prep(t) for t in (tail_gamma, tail_beta, tail_mean, tail_rstd))
+        new = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
+        fd = L.FinDesc(kind=int(tail), G=int(tail_groups), s2_sign=int(tail_s2_sign), keep_ticket=int(bool(tail_keep_ticket)), eps=float(tail_eps),
+                       gamma=L.f32(tail_gamma), **{k: int(v) for k, v in (tail_override or {}).items()})
+        if tail == 1:
+            fin = GnStats(new(n * tail_groups), new(n * tail_groups), new(n, cout), new(n, cout), new(n, 3, cout) if tail_want_k else None)
+            fd.beta, fd.mean, fd.rstd, fd.scale, fd.shift, fd.bst_k = (L.ptr(t, True) for t in (tail_beta,) + tuple(fin))
+        else:
+            fin = GnBwdCoef(new(n, cout, 3), new(cout), new(cout))
+            fd.mean, fd.rstd, fd.coef, fd.dgamma, fd.dbeta = (L.ptr(t, True) for t in (tail_mean, tail_rstd) + tuple(fin))
+    ws = tail_workspace if tail_workspace is not None else L.workspace(lib.ru_conv3_l_workspace_bytes(n, cin, cout, d, h, wd, flags | (256 if tail else 0)), dev)
     nblk, route = C.c_int(0), C.c_int(0)
     L.check(lib.ru_conv3_l(L.f32(x), L.f32(w), L.ptr(bias, True), L.f32(y), n, cin, cout, d, h, wd, flags, int(weight_mode), L.ptr(add, True),
                            L.ptr(in_scale, True), L.ptr(in_shift, True), float(in_slope), L.ptr(in_res, True), L.ptr(in_sum_out, True), int(bool(sigmoid)),
                            int(products), L.ptr(bst_y, True), L.ptr(bst_k, True), float(bst_slope), L.ptr(part, True), cap, C.byref(nblk), C.byref(route),
-                           L.ptr(ws), ws.numel(), L.stream()), "ru_conv3_l")
+                           L.ptr(ws), ws.numel(), L.stream(), C.byref(fd) if fd is not None else None), "ru_conv3_l")
     if part is not None:
         part = part[:n * cout * nblk.value * 2].view(n, cout, nblk.value, 2)
-    return Conv3Result(y, in_sum_out, part, nblk.value, route.value)
+    return Conv3Result(y, in_sum_out, part, nblk.value, route.value, (fin, ws) if fin is not None else None)
+
+
+def _c16_dims(x):
+    n, cb, d, h, w, _ = (int(v) for v in x.shape)
+    return n, cb * 16, d * h * w
+
+
+def gn_finalize(partials, gamma, beta, V, centred=False, want_k=False, groups=8, eps=1e-5):
+    """One launch of the GroupNorm finalize (ru_gn_finalize_l) on partials [N, C, nblk, 2] -- (sum, sumsq) pairs as the convolution epilogues publish them, or with
+    centred the (sum, M2) pairs of the NCDHW statistics pass: GnStats(mean [N*G], rstd [N*G], scale [N, C], shift [N, C], bst_k [N, 3, C] or None)."""
+    partials, gamma, beta = _prep(partials), _prep(gamma), _prep(beta)
+    n, c, nblk, _ = (int(v) for v in partials.shape)
+    new = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=partials.device)
+    r = GnStats(new(n * groups), new(n * groups), new(n, c), new(n, c), new(n, 3, c) if want_k else None)
+    L.check(L.load().ru_gn_finalize_l(L.f32(partials), nblk, L.f32(gamma), L.f32(beta), L.f32(r.mean), L.f32(r.rstd), L.f32(r.scale), L.f32(r.shift),
+                                      L.ptr(r.bst_k, True), n, c, int(V), int(groups), float(eps), int(bool(centred)), L.stream()), "ru_gn_finalize_l")
+    return r
+
+
+def gn_apply_c16(x, scale, shift, slope, res=None, res_scale=None, res_shift=None, res_slope=1.0):
+    """One launch of the voxel-major GroupNorm apply (ru_gn_apply_l): y = res' + lrelu(x*scale + shift, slope) on x [N, C/16, D, H, W, 16]; res' is nothing, res, or
+    lrelu(res*res_scale + res_shift, res_slope) -- a GroupNorm output that was never written."""
+    x, scale, shift, res, res_scale, res_shift = (_prep(t) for t in (x, scale, shift, res, res_scale, res_shift))
+    n, c, v = _c16_dims(x)
+    y = torch.full_like(x, float("nan"))
+    L.check(L.load().ru_gn_apply_l(L.f32(x), L.f32(scale), L.f32(shift), L.ptr(res, True), L.ptr(res_scale, True), L.ptr(res_shift, True), L.f32(y), n, c, v,
+                                   float(slope), float(res_slope), L.stream()), "ru_gn_apply_l")
+    return y
+
+
+def gn_bwd_finalize(partials, gamma, mean, rstd, V, s2_sign, groups=8):
+    """One launch of the GroupNorm-backward finalize (ru_gn_bwd_finalize_l) on partials [N, C, nblk, 2] of (S1, S2): GnBwdCoef(coef [N, C, 3], dgamma [C], dbeta [C])."""
+    partials, gamma, mean, rstd = _prep(partials), _prep(gamma), _prep(mean), _prep(rstd)
+    n, c, nblk, _ = (int(v) for v in partials.shape)
+    new = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=partials.device)
+    r = GnBwdCoef(new(n, c, 3), new(c), new(c))
+    L.check(L.load().ru_gn_bwd_finalize_l(L.f32(partials), nblk, L.f32(gamma), L.f32(mean), L.f32(rstd), L.f32(r.coef), L.f32(r.dgamma), L.f32(r.dbeta),
+                                          n, c, int(V), int(groups), int(s2_sign), L.stream()), "ru_gn_bwd_finalize_l")
+    return r
+
+
+def gn_bwd_c16(x, dact, gamma, scale, shift, mean, rstd, slope, tail=False, split=False, stop_after_finalize=False, groups=8, workspace=None, keep_ticket=False):
+    """The voxel-major GroupNorm backward as the engine chains it (ru_gn_bwd_l): the reduction over (x, dact), the finalize -- in the reduction's tail or as its own
+    launch -- and the apply, plain or in split form (to_split_c16's).  GnBwdResult(dx or None, dgamma, dbeta, coef [N, C, 3], partials [N, C, nblk, 2]).  workspace:
+    a uint8 tensor of ru_gn_bwd_l_workspace_bytes(N, C, V) to use (default: a new one); keep_ticket: its ticket word is NOT zeroed before the launch (the finisher
+    of an earlier call on the same workspace left it at zero)."""
+    x, dact, gamma, scale, shift, mean, rstd = (_prep(t) for t in (x, dact, gamma, scale, shift, mean, rstd))
+    n, c, v = _c16_dims(x)
+    lib = L.load()
+    new = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=x.device)
+    dx = None if stop_after_finalize else torch.full_like(x, float("nan"))
+    r = GnBwdResult(dx, new(c), new(c), new(n, c, 3), new(n, c, lib.ru_gn_bwd_l_nblk(v), 2))
+    ws = workspace if workspace is not None else L.workspace(lib.ru_gn_bwd_l_workspace_bytes(n, c, v), x.device)
+    flags = int(bool(tail)) | (int(bool(split)) << 1) | (int(bool(stop_after_finalize)) << 2) | (int(bool(keep_ticket)) << 3)
+    L.check(lib.ru_gn_bwd_l(L.f32(x), L.f32(dact), L.f32(gamma), L.f32(scale), L.f32(shift), L.f32(mean), L.f32(rstd), float(slope), L.ptr(dx, True),
+                            L.f32(r.dgamma), L.f32(r.dbeta), L.f32(r.coef), L.f32(r.partials), n, c, v, int(groups), flags, L.ptr(ws), ws.numel(), L.stream()),
+            "ru_gn_bwd_l")
+    return r
 
 
 Wgrad3Result = collections.namedtuple("Wgrad3Result", "dw gb_out inst")

@@ -639,15 +639,57 @@ int ru_conv1_l(const float* x0, int C0, const float* x1, int C1, const float* w,
  *   *route (optional): the kernel taken -- family (1 one-stage sb, 2 persistent sb2, 3 sb2c4, 4 wz32, 5 wz32mx, 6 mx, 7 f32c; 8 wz16, the
  *   16x16 Winograd-z kernel, which only a build with the developer switch RU_SB2_DBG can route to) | TZ << 4 | TY << 8 | IN16 << 12 |
  *   OUT16 << 13 | MULTI << 14 | BST << 15 | ADD << 16 | HEAD << 17 | GRAD << 18 | products per operand pair << 20.
- * The tail finalize of the statistics (the engine's ticket) and split-K are not reachable from here.
+ *   fin (optional; needs stat_partials): the launch's LAST workgroup finalizes the partials it published (the engine's RU_FUSE_TAIL_FINALIZE), see ru_fin_desc.
+ *   The ticket is a word of the workspace, zeroed on the stream before the launch.  Null: no tail.  Split-K is not reachable from here.
  * ru_conv3_l_workspace_bytes(..., flags): the dry walk of ru_conv3_l (and of ru_conv3d_fwd_l) for these flags with bias == NULL and weight_mode 0, under the
  * RU_* switches of the calling process, plus 4096 -- the weight fragments, the 4-channel copy and its fragments (bit 2), the gradient-operand tensor (bit 6,
- * where the shape and RU_MXG take it; a bias turns that form off and needs no more). */
+ * where the shape and RU_MXG take it; a bias turns that form off and needs no more); bit 8 (the query's alone): a ru_fin_desc will be passed (the ticket). */
+/* What a kernel's in-launch tail finalizes, and where to (fin_tail.hpp).  kind 1: (sum, sumsq) partials -> mean / rstd [N][G], scale / shift [N][C] and, optionally,
+ * bst_k [N][3][C] -- what ru_gn_finalize_l writes.  kind 2: GroupNorm-backward sums -> coef [N][C][3], dgamma / dbeta [C] -- what ru_gn_bwd_finalize_l writes --
+ * from the INPUTS mean / rstd [N][G]; s2_sign as there.  nblk / N / C: 0 = the launch's own; another value is handed to the launcher as it is (which refuses a
+ * descriptor that does not match its grid).  keep_ticket: the workspace is the one a previous call of the same shape left, and its ticket word is NOT zeroed. */
+typedef struct ru_fin_desc {
+    int kind, G, s2_sign, keep_ticket;
+    float eps;
+    int nblk, N, C;
+    const float* gamma;
+    const float* beta;
+    float* mean;
+    float* rstd;
+    float* scale;
+    float* shift;
+    float* bst_k;
+    float* coef;
+    float* dgamma;
+    float* dbeta;
+} ru_fin_desc;
 size_t ru_conv3_l_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W, int flags);
 int ru_conv3_l(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Cout, int D, int H, int W, int flags, int weight_mode,
                const float* add, const float* in_scale, const float* in_shift, float in_slope, const float* in_res, float* in_sum_out,
                int sigmoid, int products, const float* bst_y, const float* bst_k, float bst_slope, float* stat_partials, size_t stat_floats,
-               int* nblk, int* route, void* ws, size_t ws_bytes, ru_stream_t stream);
+               int* nblk, int* route, void* ws, size_t ws_bytes, ru_stream_t stream, const ru_fin_desc* fin);
+
+/* The voxel-major GroupNorm chain, one link at a time (G groups, C % G == 0; x / res / dact / dx voxel-major [N][C/16][V][16]).
+ * ru_gn_finalize_l: partials [N][C][nblk][2] -> mean / rstd [N][G], scale / shift [N][C] (y = x*scale + shift), bst_k [N][3][C] (optional) = (sign(gamma)*rstd,
+ *   -sign(gamma)*mean*rstd, -beta/|gamma|; gamma == 0: -inf where beta > 0, else +inf).  centred = 0: (sum, sumsq) pairs; 1: the (sum, M2) pairs of the NCDHW statistics pass.
+ * ru_gn_apply_l: y = res' + lrelu(x*scale[n][c] + shift[n][c], slope); res' = nothing (res null), res, or lrelu(res*res_scale + res_shift, res_slope).
+ * ru_gn_bwd_finalize_l: partials [N][C][nblk][2] of (S1 = sum dh, S2 = sum dh*xhat; s2_sign = 1: S2 carries sign(gamma)) -> coef [N][C][3] (dx = cA*dh + cB*x + cC),
+ *   dgamma / dbeta [C].
+ * ru_gn_bwd_l: the chain of one GroupNorm backward -- the reduction over (x, dact), its finalize (flags bit 0: in the reduction's tail, else the separate launch),
+ *   the apply to dx (bit 1: in split form; bit 2: no apply, dx may be null).  bit 3: the ticket word of the workspace is not zeroed (see ru_fin_desc).  coef_out
+ *   [N][C][3] / partials_out [N][C][nblk][2], nblk = ru_gn_bwd_l_nblk(V) (optional): copies of what the chain left in the workspace.
+ *   ru_gn_bwd_l_workspace_bytes: its dry walk (partials, coef, ticket) plus 4096. */
+int ru_gn_finalize_l(const float* partials, int nblk, const float* gamma, const float* beta, float* mean, float* rstd, float* scale, float* shift, float* bst_k,
+                     int N, int C, size_t V, int G, float eps, int centred, ru_stream_t stream);
+int ru_gn_apply_l(const float* x, const float* scale, const float* shift, const float* res, const float* res_scale, const float* res_shift, float* y,
+                  int N, int C, size_t V, float slope, float res_slope, ru_stream_t stream);
+int ru_gn_bwd_finalize_l(const float* partials, int nblk, const float* gamma, const float* mean, const float* rstd, float* coef, float* dgamma, float* dbeta,
+                         int N, int C, size_t V, int G, int s2_sign, ru_stream_t stream);
+int ru_gn_bwd_l_nblk(size_t V);
+size_t ru_gn_bwd_l_workspace_bytes(int N, int C, size_t V);
+int ru_gn_bwd_l(const float* x, const float* dact, const float* gamma, const float* scale, const float* shift, const float* mean, const float* rstd, float slope,
+                float* dx, float* dgamma, float* dbeta, float* coef_out, float* partials_out, int N, int C, size_t V, int G, int flags,
+                void* ws, size_t ws_bytes, ru_stream_t stream);
 size_t ru_wgrad1_l_workspace_bytes(int N, int Cin, int Cout, size_t V);
 int ru_wgrad1_l(const float* x, const float* x1, int C0, const float* dy, float* dw, int ldw, int N, int Cin, int Cout, size_t V,
                 int c16, int s2d, int Dc, int Hc, int Wc, int tap_split, const float* dg_w, int dg_ldw, float* dg_y0, float* dg_y1,

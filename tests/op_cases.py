@@ -111,6 +111,19 @@ def cases():
             return as_list([r.y, r.in_sum, r.partials])
         add("conv3_l_route_" + tag, True, run)
 
+    # ---- the in-launch tail of ru_conv3_l (flag bit 8 of the query: the ticket) and ru_gn_bwd_l (partials, coefficients, ticket): a guarded workspace arrives
+    # filled with 0xFF, so the ticket these entries zero on the stream is part of what the cases check
+    gam16, bet16 = _rand(16, seed=111) + 1.0, _rand(16, seed=112)
+    mean16, rstd16 = _rand(16, seed=113, scale=0.3), _rand(16, seed=114, scale=0.1) + 1.0
+
+    def conv3_tail():
+        r = ops.conv3_fused(xs24, wt, in_c16=True, out_c16=True, add=as24, stats=True, tail=1, tail_gamma=gam16, tail_beta=bet16, tail_want_k=True)
+        return as_list([r.y, r.partials] + list(r.fin[0]))
+    add("conv3_l_tail", True, conv3_tail)
+    xg5, dg5 = _c16(2, 16, 1, 3, 683, seed=115), _c16(2, 16, 1, 3, 683, seed=116)          # V = 2049: five partials per (sample, channel)
+    for tag, kw in (("", {}), ("_tail", dict(tail=True)), ("_tail_split", dict(tail=True, split=True)), ("_stop", dict(stop_after_finalize=True))):
+        add("gn_bwd_l" + tag, True, lambda kw=kw: as_list(ops.gn_bwd_c16(xg5, dg5, gam16, sc16, sh16, mean16, rstd16, 0.01, **kw)))
+
     # ---- ru_conv1_l: plain (takes nothing), gather and scatter of 1 x 16 -> 32 at one coarse voxel
     xf, xc = _c16(1, 16, 2, 2, 2, seed=70), _c16(1, 32, 1, 1, 1, seed=71)
     wg, wsc, wp = _rand(32, 16, 2, 2, 2, seed=72, scale=0.3), _rand(32, 16, 2, 2, 2, seed=73, scale=0.3), _rand(32, 16, seed=74, scale=0.3)

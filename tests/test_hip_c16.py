@@ -312,6 +312,22 @@ def test_upsample_c16_equals_ncdhw(shape):
     assert float((dx - dx_ref).abs().max()) <= 1e-5
 
 
+@pytest.mark.parametrize("out_slope", [1.0, 0.01])
+def test_upsample_c16_nontemporal_stores_at_128_mb(out_slope):
+    """1 x 16 x 64^3 -> 128^3: the output is exactly 128 MB, where up2_fwd16_kernel switches to nontemporal stores.  Forward only, against the reference's
+    F.interpolate in float64 (oracle.trilinear_up2) at the bar of test_trilinear_golden_and_ragged in tests/test_hip_ops.py (1e-6 + 1e-5 |ref|)."""
+    from brats2019_amd import ops
+    from oracle import resunet_oracle as O
+    x = _rand(1, 16, 64, 64, 64, seed=5)
+    y = ops.from_c16(ops.upsample2x_c16(ops.to_c16(x), out_slope=out_slope))
+    assert y.numel() * 4 == 128 << 20
+    ref = O.trilinear_up2(x.cpu().double())
+    ref = torch.where(ref > 0, ref, ref * out_slope).cuda()
+    excess = float(((y.double() - ref).abs() / (1e-6 + 1e-5 * ref.abs())).max())
+    print("  up2 128 MB out_slope=%g: error / bar %.3g" % (out_slope, excess))
+    assert excess <= 1.0
+
+
 def test_conv3_voxel_major_volume_beyond_32bit_block_offsets():
     """Maximum sizes: the persistent kernel addresses a 16-channel block of its voxel-major input with 32-bit byte offsets (buffer
     loads), so a volume of 2^25 voxels or more -- 64 bytes per voxel: 2 GiB per block -- must take the one-stage kernel instead of

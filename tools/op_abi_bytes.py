@@ -2,7 +2,8 @@
 """One SHA-256 per output of the entries of csrc/op_abi.hip on seeded inputs: every entry that takes a workspace at the cases of
 tests/op_cases.py (each branch of its carve, the workspace exactly as large as its query says), and the forwarding entries at one small
 shape each.  Two builds of the library compute the same bytes if and only if their listings are equal line for line: run it once per
-library (RU_LIB_PATH selects another build), each in a process of its own, and compare.
+library (RU_LIB_PATH selects another build), each in a process of its own, and compare.  Under RU_LIB_PATH a case whose entry the other build
+does not have yet is listed as absent; the lines both listings have must be equal.
 
 usage: op_abi_bytes.py [--out FILE]"""
 import hashlib
@@ -27,7 +28,12 @@ def say(label, tensors):
 
 
 for name, _, run in cases():
-    say(name, run())
+    try:
+        say(name, run())
+    except AttributeError as e:                # (an entry point added since that build: _lib.load leaves it out under RU_LIB_PATH)
+        if not os.environ.get("RU_LIB_PATH"):
+            raise
+        print("absent  %s  (%s)" % (name, e), flush=True)
 
 x = _rand(1, 16, 3, 5, 6, seed=90)
 y = _rand(1, 16, 3, 5, 6, seed=91)
