@@ -179,6 +179,8 @@ SIGNATURES = {
     "ru_gn_bwd_l_nblk": (_i, [_sz]),
     "ru_gn_bwd_l_workspace_bytes": (_sz, [_i, _i, _sz]),
     "ru_gn_bwd_l": (_i, [_vp] * 7 + [_f] + [_vp] * 5 + [_i, _i, _sz, _i, _i, _vp, _sz, _vp]),
+    "ru_head_grad_l_workspace_bytes": (_sz, [_i, _i, _sz, _i]),
+    "ru_head_grad_l": (_i, [_vp] * 4 + [_d, _f, _f, _f, _f] + [_vp] * 3 + [_i, _i, _sz, _i, _vp, _sz, _vp]),
     "ru_wgrad1_l_workspace_bytes": (_sz, [_i, _i, _i, _sz]),
     "ru_wgrad3_l_workspace_bytes": (_sz, [_i] * 7),
     "ru_wgrad3_l": (_i, [_vp, _vp, _vp] + [_i] * 8 + [_vp, _vp, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, C.POINTER(_i), _vp, _sz, _vp]),

@@ -521,6 +521,38 @@ extern "C" int ru_gn_bwd_l(const float* x, const float* dact, const float* gamma
     return walk_result(A, gn_bwd_l_walk(x, dact, gamma, scale, shift, mean, rstd, slope, dx, dgamma, dbeta, coef_out, partials_out, N, C, V, G, flags, A, (hipStream_t)stream));
 }
 
+// ====================================================================== the head of the backward pass, one route of unet_backward_impl at a time
+// route 0: head_grad_c4_launch (and sigmoid_bwd_launch where dlog is wanted, as the engine adds it for a wide first level); 1: head_grad_c4_crit_launch
+// (`cg` is the criterion, dp is not read); 2: sigmoid_bwd_launch then bias_grad_launch (any C and V; d4 is not written).  The launchers' own checks refuse.
+static int head_grad_l_walk(const float* p, const float* dp, const CritGradArgs& cg, float* d4, float* db, float* dlog, int N, int C, size_t V, int route,
+                            Arena& A, hipStream_t s) {
+    const size_t wsb = bias_grad_workspace_bytes(N, C, V);
+    float* wsp = A.alloc(wsb / sizeof(float) + 1);
+    if (route == 1) {
+        RU_ARENA_RUN(head_grad_c4_crit_launch(p, cg, d4, db, N, C, V, wsp, wsb, s));
+    } else if (route == 0) {
+        RU_ARENA_RUN(head_grad_c4_launch(p, dp, d4, db, N, C, V, wsp, wsb, s));
+        if (dlog) RU_ARENA_RUN(sigmoid_bwd_launch(p, dp, dlog, (size_t)N * C * V, s));
+    } else {
+        RU_ARENA_RUN(sigmoid_bwd_launch(p, dp, dlog, (size_t)N * C * V, s));
+        RU_ARENA_RUN(bias_grad_launch(dlog, db, N, C, V, wsp, wsb, s));
+    }
+    return RU_OK;
+}
+extern "C" size_t ru_head_grad_l_workspace_bytes(int N, int C, size_t V, int route) {
+    return kSlack + dry_need([&](Arena& A) { return head_grad_l_walk(nullptr, nullptr, CritGradArgs{}, nullptr, nullptr, nullptr, N, C, V, route, A, nullptr); });
+}
+extern "C" int ru_head_grad_l(const float* p, const float* dp, const float* target, const double* sums, double count, float w_dice, float w_bce, float bg_weight,
+                              float priority, float* d4, float* db, float* dlog, int N, int C, size_t V, int route, void* ws, size_t ws_bytes, ru_stream_t stream) {
+    RU_REQUIRE(route >= 0 && route <= 2, "ru_head_grad_l: route is 0 (4-channel pass), 1 (4-channel pass with the criterion) or 2 (sigmoid backward, then bias gradient)");
+    RU_REQUIRE(p && db && (route == 1 || dp) && (route == 2 ? dlog != nullptr : d4 != nullptr), "ru_head_grad_l: null argument");
+    RU_REQUIRE(route != 1 || (!dlog && count > 0), "ru_head_grad_l: the criterion route writes no dlog and needs a positive count");
+    RU_REQUIRE(N > 0 && C > 0 && V > 0, "ru_head_grad_l: bad shape");
+    const CritGradArgs cg{target, sums, count, w_dice, w_bce, bg_weight, priority};
+    Arena A = arena_over(ws, ws_bytes);
+    return walk_result(A, head_grad_l_walk(p, dp, cg, d4, db, dlog, N, C, V, route, A, (hipStream_t)stream));
+}
+
 // The voxel-major pointwise family, one launch at a time: thin fillers of Conv1Args / Wgrad1Args (no kernels, no arithmetic of their own).
 static int conv1_l_walk(Conv1Args a, const float* w, size_t stat_floats, int* nblk, int* inst, Arena& A, hipStream_t s) {
     if (a.s2d) {

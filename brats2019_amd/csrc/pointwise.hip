@@ -830,8 +830,8 @@ int bias_grad_launch(const float* dy, float* db, int N, int C, size_t V, void* w
 // Head of the backward pass on the 4-channel path, one pass instead of three (sigmoid backward, 4-channel copy, bias partials):
 // dz = dp*p*(1-p) (model.py:431) goes straight into the zero-padded voxel-major copy [N][V][4] that the head's weight- and
 // data-gradient kernels read, and the bias gradient's partial sums (model.py:348) are taken on the way.  V % 4 == 0.
-// CRIT: `dp` is the TARGET tensor and the incoming gradient is the criterion's (crit_grad_kernel's expression, same float operations in
-// the same order -> the same bits), formed from (p, target) and the per-class constants of `cg`
+// CRIT: `dp` is the TARGET tensor and the incoming gradient is the criterion's (crit_grad_kernel's expression: both call crit_grad_value,
+// pw_helpers.hpp -> the same bits), formed from (p, target) and the per-class constants of `cg`
 template <bool CRIT>
 __global__ __launch_bounds__(256) void head_grad_c4_kernel(const float* __restrict__ p, const float* __restrict__ dp, float* __restrict__ d4,
                                                            float* __restrict__ part, int C, size_t V, int nblk, const CritGradArgs cg) {
@@ -865,10 +865,7 @@ __global__ __launch_bounds__(256) void head_grad_c4_kernel(const float* __restri
                 const float pv[4] = {q.x, q.y, q.z, q.w}, gv[4] = {g.x, g.y, g.z, g.w};
                 float o[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float bce = -(gv[e] / (pv[e] + 1e-6f) - cg.bgw * (1.f - gv[e]) / (one_eps - pv[e]));
-                    o[e] = (kg[c] * gv[e] + kp[c] * pv[e]) + cb * bce;
-                }
+                for (int e = 0; e < 4; ++e) o[e] = crit_grad_value(pv[e], gv[e], kg[c], kp[c], cb, cg.bgw, one_eps);
                 g = make_float4(o[0], o[1], o[2], o[3]);
             }
             d[c][0] = ok ? g.x * q.x * (1.f - q.x) : 0.f;
@@ -887,7 +884,7 @@ __global__ __launch_bounds__(256) void head_grad_c4_kernel(const float* __restri
     }
 }
 int head_grad_c4_launch(const float* p, const float* dp, float* d4, float* db, int N, int C, size_t V, void* ws, size_t ws_bytes, hipStream_t s) {
-    RU_REQUIRE(C > 0 && C <= 4 && V % 4 == 0, "head_grad_c4: 1..4 channels, V % 4 == 0");
+    RU_REQUIRE(C > 0 && C <= 4 && V % 4 == 0, "head_grad_c4: 1..4 channels, V %% 4 == 0");
     if (!ws || ws_bytes < bias_grad_workspace_bytes(N, C, V)) { set_error("head_grad_c4: workspace too small"); return RU_ENOMEM; }
     const int nblk = (int)((V + BG_CHUNK - 1) / BG_CHUNK);
     hipLaunchKernelGGL(head_grad_c4_kernel<false>, dim3(nblk, N), dim3(256), 0, s, p, dp, d4, (float*)ws, C, V, nblk, CritGradArgs{});
@@ -897,7 +894,7 @@ int head_grad_c4_launch(const float* p, const float* dp, float* d4, float* db, i
     return RU_OK;
 }
 int head_grad_c4_crit_launch(const float* p, const CritGradArgs& cg, float* d4, float* db, int N, int C, size_t V, void* ws, size_t ws_bytes, hipStream_t s) {
-    RU_REQUIRE(C > 0 && C <= 4 && V % 4 == 0 && cg.target && cg.sums, "head_grad_c4_crit: 1..4 channels, V % 4 == 0, target and sums");
+    RU_REQUIRE(C > 0 && C <= 4 && V % 4 == 0 && cg.target && cg.sums, "head_grad_c4_crit: 1..4 channels, V %% 4 == 0, target and sums");
     if (!ws || ws_bytes < bias_grad_workspace_bytes(N, C, V)) { set_error("head_grad_c4_crit: workspace too small"); return RU_ENOMEM; }
     const int nblk = (int)((V + BG_CHUNK - 1) / BG_CHUNK);
     hipLaunchKernelGGL(head_grad_c4_kernel<true>, dim3(nblk, N), dim3(256), 0, s, p, cg.target, d4, (float*)ws, C, V, nblk, cg);
@@ -986,8 +983,7 @@ __global__ __launch_bounds__(256) void crit_grad_kernel(const float* __restrict_
     const float one_eps = (float)(1.0 + 1e-6);
     for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < V; v += (size_t)gridDim.x * 256) {
         const float pv = p[row * V + v], gv = g[row * V + v];
-        const float bce = -(gv / (pv + 1e-6f) - bgw * (1.f - gv) / (one_eps - pv));
-        dp[row * V + v] = (cg * gv + cp * pv) + cb * bce;
+        dp[row * V + v] = crit_grad_value(pv, gv, cg, cp, cb, bgw, one_eps);
     }
 }
 int crit_grad_launch(const float* p, const float* g, const double* sums, double count, float w_dice, float w_bce,

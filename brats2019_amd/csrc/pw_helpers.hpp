@@ -32,6 +32,17 @@ __device__ __forceinline__ double block_sum_d(double v, double* buf) {
 }
 __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
+// d(w_dice * Dice + w_bce * BCE)/dp at one element (loss.py:70-79,105-122), the one statement of it: crit_grad_kernel and head_grad_c4_kernel<true> both call
+// this, with kg = (float)(-k / U), kp = (float)(2 k I / U^2), cb = (float)(w_bce / count), one_eps = (float)(1 + 1e-6).  Every rounding is spelled out -- contraction is
+// off and the two fused multiply-adds are explicit -- so that the two kernels cannot contract `(kg*g + kp*p) + cb*bce` differently (they did: one rounded kg*g first,
+// the other kp*p, and about 1 % of the elements differed in the last bit; tests/test_up2_head.py holds them to the same bits).  The form kept is the one
+// crit_grad_kernel had: fma(cb, bce, fma(kp, p, round(kg * g))) -- with a target in {0, 1} the inner product is exact, so the Dice part carries ONE rounding.
+__device__ __forceinline__ float crit_grad_value(float pv, float gv, float kg, float kp, float cb, float bgw, float one_eps) {
+#pragma clang fp contract(off)
+    const float bce = -(gv / (pv + 1e-6f) - bgw * (1.f - gv) / (one_eps - pv));
+    return __builtin_fmaf(cb, bce, __builtin_fmaf(kp, pv, kg * gv));
+}
+
 static inline unsigned grid1d(size_t n, int per_block, unsigned cap = 1u << 20) {
     size_t b = (n + per_block - 1) / per_block;
     if (b < 1) b = 1;

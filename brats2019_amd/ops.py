@@ -117,19 +117,28 @@ def leaky_relu_bwd(y, dy, slope=LEAKY_SLOPE):
     return dx
 
 
-def upsample2x(x):
+def _out(out, shape, device):
+    """the output tensor of an op that takes one (`out`: a caller's contiguous float32 tensor of that shape, e.g. prefilled with NaN)"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of shape %s" % (tuple(shape),))
+    return out
+
+
+def upsample2x(x, out=None):
     """model.Trilinear(scale=2) (model.py:7-14)."""
     x = _prep(x)
     n, c, d, h, w = _dims5(x)
-    y = torch.empty((n, c, 2 * d, 2 * h, 2 * w), dtype=torch.float32, device=x.device)
+    y = _out(out, (n, c, 2 * d, 2 * h, 2 * w), x.device)
     L.check(L.load().ru_upsample2x_trilinear_fwd(L.f32(x), L.f32(y), n, c, d, h, w, L.stream()), "ru_upsample2x_trilinear_fwd")
     return y
 
 
-def upsample2x_bwd(dy):
+def upsample2x_bwd(dy, out=None):
     dy = _prep(dy)
     n, c, d2, h2, w2 = _dims5(dy)
-    dx = torch.empty((n, c, d2 // 2, h2 // 2, w2 // 2), dtype=torch.float32, device=dy.device)
+    dx = _out(out, (n, c, d2 // 2, h2 // 2, w2 // 2), dy.device)
     L.check(L.load().ru_upsample2x_trilinear_bwd(L.f32(dy), L.f32(dx), n, c, d2 // 2, h2 // 2, w2 // 2, L.stream()),
             "ru_upsample2x_trilinear_bwd")
     return dx
@@ -167,6 +176,27 @@ def criterion_grad(p, g, sums, count, w_dice=0.5, w_bce=0.5, bg_weight=1e-2, pri
     L.check(L.load().ru_criterion_grad(L.f32(p), L.f32(g), L.ptr(sums), float(count), w_dice, w_bce, bg_weight, priority,
                                        L.f32(dp), n, c, v, L.stream()), "ru_criterion_grad")
     return dp
+
+
+def head_grad(p, dp=None, *, target=None, sums=None, count=None, w_dice=0.5, w_bce=0.5, bg_weight=1e-2, priority=1.0, generic=False, with_dlog=False):
+    """The head of the backward pass, one route at a time (ru_head_grad_l): d = dp * p * (1 - p) (model.py:431) and db[c] = sum over n, v of d (model.py:348)
+    from p [N, C, ...].  Returns (d4 [N, V, 4], db [C], dlog [N, C, V]), each prefilled with NaN, None where the route does not write it.
+    dp given: the 4-channel pass (dlog only with with_dlog, by the flat sigmoid backward behind it).  dp None: the same pass with the criterion's gradient
+    formed on the way from (target, sums, count -- default p.numel()) as criterion_grad forms it.  generic: the flat sigmoid backward into dlog, then the bias
+    gradient over it (any C and V; no d4)."""
+    p, dp, target = _prep(p), _prep(dp), _prep(target)
+    lib = L.load()
+    n, c, v = _rows(p)
+    route = 2 if generic else (0 if dp is not None else 1)
+    new = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device=p.device)
+    d4 = None if route == 2 else new(n, v, 4)
+    dlog = new(n, c, v) if (route == 2 or (route == 0 and with_dlog)) else None
+    db = new(c)
+    ws = L.workspace(lib.ru_head_grad_l_workspace_bytes(n, c, v, route), p.device)
+    L.check(lib.ru_head_grad_l(L.f32(p), L.ptr(dp, True), L.ptr(target, True), L.ptr(sums, True), float(count if count is not None else p.numel()),
+                               w_dice, w_bce, bg_weight, priority, L.ptr(d4, True), L.f32(db), L.ptr(dlog, True), n, c, v, route,
+                               L.ptr(ws), ws.numel(), L.stream()), "ru_head_grad_l")
+    return d4, db, dlog
 
 
 def criterion_losses(sums, count, priority=1.0, w_dice=0.5, w_bce=0.5):
@@ -1038,20 +1068,20 @@ def from_c16(x):
     return y
 
 
-def upsample2x_c16(x, out_slope=1.0):
+def upsample2x_c16(x, out_slope=1.0, out=None):
     """Trilinear x2 on a C16 tensor [N,C/16,D,H,W,16]; LeakyReLU(out_slope) fused on the output (1 = none)."""
     x = _prep(x)
     n, cb, d, h, w, _ = (int(v) for v in x.shape)
-    y = torch.empty((n, cb, 2 * d, 2 * h, 2 * w, 16), dtype=torch.float32, device=x.device)
+    y = _out(out, (n, cb, 2 * d, 2 * h, 2 * w, 16), x.device)
     L.check(L.load().ru_upsample2x_trilinear_fwd_l(L.f32(x), L.f32(y), n, cb * 16, d, h, w, float(out_slope), L.stream()),
             "ru_upsample2x_trilinear_fwd_l")
     return y
 
 
-def upsample2x_bwd_c16(dy):
+def upsample2x_bwd_c16(dy, out=None):
     dy = _prep(dy)
     n, cb, d2, h2, w2, _ = (int(v) for v in dy.shape)
-    dx = torch.empty((n, cb, d2 // 2, h2 // 2, w2 // 2, 16), dtype=torch.float32, device=dy.device)
+    dx = _out(out, (n, cb, d2 // 2, h2 // 2, w2 // 2, 16), dy.device)
     L.check(L.load().ru_upsample2x_trilinear_bwd_l(L.f32(dy), L.f32(dx), n, cb * 16, d2 // 2, h2 // 2, w2 // 2, L.stream()),
             "ru_upsample2x_trilinear_bwd_l")
     return dx

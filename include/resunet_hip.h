@@ -690,6 +690,15 @@ size_t ru_gn_bwd_l_workspace_bytes(int N, int C, size_t V);
 int ru_gn_bwd_l(const float* x, const float* dact, const float* gamma, const float* scale, const float* shift, const float* mean, const float* rstd, float slope,
                 float* dx, float* dgamma, float* dbeta, float* coef_out, float* partials_out, int N, int C, size_t V, int G, int flags,
                 void* ws, size_t ws_bytes, ru_stream_t stream);
+/* The head of the backward pass, one route of ru_unet_backward at a time: p [N][C][V] (the probabilities) and the gradient w.r.t. them -> d = dp*p*(1-p)
+ * (model.py:431) as d4 [N][V][4] (voxel-major, channels C..3 written as +0) and / or dlog [N][C][V], and db [C] = sum over n, v of d (model.py:348).
+ *   route 0: the 4-channel pass (1..4 channels, V % 4 == 0); dlog (optional) by the flat sigmoid backward behind it.
+ *   route 1: the same pass with dp = ru_criterion_grad(p, target, sums, count, w_dice, w_bce, bg_weight, priority) formed in registers (dp not read, dlog null).
+ *   route 2: the flat sigmoid backward into dlog, then the bias gradient over it (any C and V; d4 not written, may be null).
+ * ru_head_grad_l_workspace_bytes: its dry walk (the bias partials) plus 4096. */
+size_t ru_head_grad_l_workspace_bytes(int N, int C, size_t V, int route);
+int ru_head_grad_l(const float* p, const float* dp, const float* target, const double* sums, double count, float w_dice, float w_bce, float bg_weight,
+                   float priority, float* d4, float* db, float* dlog, int N, int C, size_t V, int route, void* ws, size_t ws_bytes, ru_stream_t stream);
 size_t ru_wgrad1_l_workspace_bytes(int N, int Cin, int Cout, size_t V);
 int ru_wgrad1_l(const float* x, const float* x1, int C0, const float* dy, float* dw, int ldw, int N, int Cin, int Cout, size_t V,
                 int c16, int s2d, int Dc, int Hc, int Wc, int tap_split, const float* dg_w, int dg_ldw, float* dg_y0, float* dg_y1,

@@ -124,6 +124,14 @@ def cases():
     for tag, kw in (("", {}), ("_tail", dict(tail=True)), ("_tail_split", dict(tail=True, split=True)), ("_stop", dict(stop_after_finalize=True))):
         add("gn_bwd_l" + tag, True, lambda kw=kw: as_list(ops.gn_bwd_c16(xg5, dg5, gam16, sc16, sh16, mean16, rstd16, 0.01, **kw)))
 
+    # ---- ru_head_grad_l, one case per route: 2 x 3 classes at V = 16384 + 4 (two bias partials per row; the generic route at V = 16384 + 1)
+    ph, dph = torch.sigmoid(_rand(2, 3, 16388, seed=120, scale=3.0)), _rand(2, 3, 16388, seed=121)
+    gh = (_rand(2, 3, 16388, seed=122) > 0.5).float()
+    add("head_grad_l_c4", True, lambda: as_list(ops.head_grad(ph, dph, with_dlog=True)))
+    sh = ops.criterion_sums(ph, gh)                      # (taken here: the criterion's own workspace is not what the case is about)
+    add("head_grad_l_crit", True, lambda: as_list(ops.head_grad(ph, target=gh, sums=sh, count=3 * ph.numel())))
+    add("head_grad_l_generic", True, lambda: as_list(ops.head_grad(ph[..., :16385], dph[..., :16385], generic=True)))
+
     # ---- ru_conv1_l: plain (takes nothing), gather and scatter of 1 x 16 -> 32 at one coarse voxel
     xf, xc = _c16(1, 16, 2, 2, 2, seed=70), _c16(1, 32, 1, 1, 1, seed=71)
     wg, wsc, wp = _rand(32, 16, 2, 2, 2, seed=72, scale=0.3), _rand(32, 16, 2, 2, 2, seed=73, scale=0.3), _rand(32, 16, seed=74, scale=0.3)
