@@ -32,6 +32,12 @@ SIGNATURES = {
     "ru_conv3d_bwd_data_p": (_i, [_vp, _vp, _vp] + [_i] * 8 + [_vp, _sz, _vp]),
     "ru_conv3d_bwd_weight": (_i, [_vp, _vp, _vp, _vp] + [_i] * 7 + [_vp, _sz, _vp]),
     "ru_conv3d_bwd_weight_p": (_i, [_vp, _vp, _vp, _vp] + [_i] * 8 + [_vp, _sz, _vp]),
+    "ru_conv3d_fwd_splitk_workspace_bytes": (_sz, [_i] * 7),
+    "ru_conv3d_fwd_splitk": (_i, [_vp, _vp, _vp, _vp] + [_i] * 7 + [_vp, _sz, _vp]),
+    "ru_conv3_f32_inst": (_i, [_i] * 6),
+    "ru_wgrad3_inst": (_i, [_i] * 8 + [C.POINTER(_i)]),
+    "ru_conv1_inst": (_i, [_i, _i, _i, _sz]),
+    "ru_wgrad1_inst": (_i, [_i, _i, _i, _sz, C.POINTER(_i)]),
     "ru_groupnorm_workspace_bytes": (_sz, [_i, _i, _sz]),
     "ru_groupnorm_fwd": (_i, [_vp] * 7 + [_i, _i, _sz, _i, _f, _f, _vp, _sz, _vp]),
     "ru_groupnorm_bwd": (_i, [_vp] * 9 + [_i, _i, _sz, _i, _f, _vp, _sz, _vp]),

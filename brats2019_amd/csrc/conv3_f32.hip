@@ -199,6 +199,7 @@ __global__ __launch_bounds__(256, 2) void conv3_f32_kernel(const Conv3Args a0, i
 
 // ------------------------------------------------------------------ host side
 struct C3Choice { int tz, ty, kc, nt; };
+static constexpr int c3_pack(int tz, int ty, int kc, int nt) { return tz | ty << 4 | kc << 8 | nt << 12; }
 
 int conv3_cin_pad(int Cin) { return Cin <= 4 ? 4 : round_up(Cin, 8); }
 
@@ -229,6 +230,11 @@ int conv3_f32_ksplit(int N, int Cin, int Cout, int D, int H, int W) {
     int ks = 1;
     while (nchunk % (ks * 2) == 0 && nchunk / (ks * 2) >= 2 && blocks * (ks * 2) <= 1024) ks *= 2;
     return ks;
+}
+
+int conv3_f32_inst(int N, int Cin, int Cout, int D, int H, int W) {
+    const C3Choice c = conv3_choose(N, Cin, Cout, D, H, W);
+    return c3_pack(c.tz, c.ty, c.kc, c.nt) | conv3_f32_ksplit(N, Cin, Cout, D, H, W) << 16;
 }
 
 int conv3_f32_tiles_per_sample(int N, int Cin, int Cout, int D, int H, int W) {
@@ -275,9 +281,10 @@ int conv3_launch(const Conv3Args& a_in, const Switches& sw, hipStream_t s) {
         return conv3_sb_launch(a, sw, s);
     }
     RU_REQUIRE(a.wp != nullptr, "conv3: f32 mode needs packed weights");
-    const C3Choice c = conv3_choose(a.N, a.Cin, a.Cout, a.D, a.H, a.W);
+    // the one place that picks the instantiation: what conv3_f32_inst reports is what is launched
+    switch (conv3_f32_inst(a.N, a.Cin, a.Cout, a.D, a.H, a.W) & 0xffff) {
 #define RU_C3_CASE(TZ, TY, KC, NT) \
-    if (c.tz == TZ && c.ty == TY && c.kc == KC && c.nt == NT) return launch_cfg<TZ, TY, KC, NT>(a, s);
+    case c3_pack(TZ, TY, KC, NT): return launch_cfg<TZ, TY, KC, NT>(a, s);
     RU_C3_CASE(4, 8, 4, 1)
     RU_C3_CASE(4, 8, 8, 1)
     RU_C3_CASE(2, 8, 8, 1)
@@ -286,8 +293,30 @@ int conv3_launch(const Conv3Args& a_in, const Switches& sw, hipStream_t s) {
     RU_C3_CASE(2, 8, 8, 2)
     RU_C3_CASE(2, 4, 8, 2)
 #undef RU_C3_CASE
+    }
+    const C3Choice c = conv3_choose(a.N, a.Cin, a.Cout, a.D, a.H, a.W);
     set_error("conv3: no kernel for config tz=%d ty=%d kc=%d nt=%d", c.tz, c.ty, c.kc, c.nt);
     return RU_EINVAL;
+}
+
+// The split-K form of an exact-f32 NCDHW convolution, whole: `ksplit` partial output tensors [ksplit][N][Cout][D][H][W] in `part`
+// (conv3_splitk_part_floats), each the sum over its slice of the input-channel chunks, then their sum in slice order into a.y.
+// ksplit = 0: the factor conv3_f32_ksplit gives the shape; a factor of 1 is the plain launch into a.y (part is not touched).
+size_t conv3_splitk_part_floats(int N, int Cin, int Cout, int D, int H, int W, int ksplit) {
+    const int ks = ksplit > 0 ? ksplit : conv3_f32_ksplit(N, Cin, Cout, D, H, W);
+    return ks > 1 ? (size_t)ks * N * Cout * D * H * W : 0;
+}
+int conv3_launch_splitk(const Conv3Args& a_in, float* part, int ksplit, const Switches& sw, hipStream_t s) {
+    Conv3Args a = a_in;
+    const int ks = ksplit > 0 ? ksplit : conv3_f32_ksplit(a.N, a.Cin, a.Cout, a.D, a.H, a.W);
+    if (ks <= 1) { a.ksplit = 0; return conv3_launch(a, sw, s); }
+    RU_REQUIRE(part != nullptr, "conv3_f32: split-K needs its partial tensors");
+    const size_t nel = (size_t)a.N * a.Cout * a.D * a.H * a.W;
+    float* y = a.y;
+    a.y = part; a.stat_partials = nullptr; a.ksplit = ks;
+    const int rc = conv3_launch(a, sw, s);
+    if (rc != RU_OK) return rc;
+    return sum_partials_launch(part, ks, nel, y, s);
 }
 
 __global__ void conv3_pack_kernel(const float* __restrict__ w, float* __restrict__ wp, int Cin_f, int Cout_f, int mode,

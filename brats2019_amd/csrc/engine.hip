@@ -561,11 +561,9 @@ static int conv3_gn(ru_unet* h, Arena& A, hipStream_t s, const float* x, const f
         f.gamma = gamma; f.beta = beta; f.mean = out_gn.mean; f.rstd = out_gn.rstd; f.scale = out_gn.scale; f.shift = out_gn.shift; f.bst_k = out_gn.k;
     }
     if (ksplit > 1) {
-        const size_t nel = (size_t)N * Cout * D * H * W;
-        float* part = A.alloc((size_t)ksplit * nel);
-        a.y = part; a.stat_partials = nullptr; a.ksplit = ksplit;
-        RU_RUN(conv3_launch(a, h->sw, s));
-        RU_RUN(sum_partials_launch(part, ksplit, nel, y, s));
+        float* part = A.alloc(conv3_splitk_part_floats(N, Cin, Cout, D, H, W, ksplit));
+        a.stat_partials = nullptr;
+        RU_RUN(conv3_launch_splitk(a, part, ksplit, h->sw, s));        // the partial tensors, then their sum in slice order into y
         RU_RUN(gn_stats_launch(y, partials, N, Cout, (size_t)D * H * W, s));
     } else {
         t_hint_inst = (a.in_c16 && a.out_c16) ? (Cin == 16 && Cout == 16 ? INST_CONV16_FWD : (Cin >= 32 ? INST_CONV_DEEP_FWD : -1)) : -1;

@@ -198,6 +198,59 @@ extern "C" int ru_conv3d_bwd_weight(const float* x, const float* dy, float* dw, 
     return ru_conv3d_bwd_weight_p(x, dy, dw, db, N, Cin, Cout, D, H, W, k, RU_PREC_F32, ws, ws_bytes, stream);
 }
 
+// The split-K form of the exact-f32 NCDHW 3x3x3 forward, as the engine's small f32 shapes run it (conv3_launch_splitk: partial tensors, the launch with
+// Conv3Args::ksplit, sum_partials_launch).  ksplit = 0: the factor conv3_f32_ksplit gives the shape; 1 (given or chosen): the plain launch.  The launcher refuses a
+// factor that does not divide the input-channel chunks and a bias beside a split.
+static int conv3d_fwd_splitk_walk(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Cout, int D, int H, int W, int ksplit,
+                                  Arena& A, hipStream_t s) {
+    Conv3Args a{};
+    int rc = prep_conv3_weights(a, w, Cin, Cout, 0, RU_PREC_F32, W, A, s);
+    if (rc) return rc;
+    a.x = x; a.bias = bias; a.y = y; a.N = N; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W;
+    float* part = A.alloc(conv3_splitk_part_floats(N, Cin, Cout, D, H, W, ksplit));
+    RU_ARENA_RUN(conv3_launch_splitk(a, part, ksplit, switches_from_env(), s));
+    return RU_OK;
+}
+extern "C" size_t ru_conv3d_fwd_splitk_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W, int ksplit) {
+    return kSlack + dry_need([&](Arena& A) { return conv3d_fwd_splitk_walk(nullptr, nullptr, nullptr, nullptr, N, Cin, Cout, D, H, W, ksplit, A, nullptr); });
+}
+extern "C" int ru_conv3d_fwd_splitk(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int Cout, int D, int H, int W, int ksplit,
+                                    void* ws, size_t ws_bytes, ru_stream_t stream) {
+    RU_REQUIRE(x && w && y, "ru_conv3d_fwd_splitk: null argument");
+    RU_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0 && ksplit >= 0 && ksplit <= 64, "ru_conv3d_fwd_splitk: bad shape or split factor");
+    Arena A = arena_over(ws, ws_bytes);
+    return walk_result(A, conv3d_fwd_splitk_walk(x, w, bias, y, N, Cin, Cout, D, H, W, ksplit, A, (hipStream_t)stream));
+}
+
+// ---------------------------------------------------------------------- what a launch of the NCDHW family would choose: host-only queries (no launch, no workspace)
+// of the functions the launchers themselves switch on
+extern "C" int ru_conv3_f32_inst(int N, int Cin, int Cout, int D, int H, int W) {
+    RU_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, "ru_conv3_f32_inst: bad shape");
+    return conv3_f32_inst(N, Cin, Cout, D, H, W);
+}
+extern "C" int ru_wgrad3_inst(int N, int Cin, int Cout, int D, int H, int W, int precision, int flags, int* out7) {
+    RU_REQUIRE(out7 && N > 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, "ru_wgrad3_inst: bad argument");
+    Wgrad3Args a{};
+    a.N = N; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W; a.mode = precision; a.x_c16 = flags & 1; a.dy_c16 = (flags >> 1) & 1;
+    const W3Inst i = wgrad3_inst(a);
+    out7[0] = i.kernel; out7[1] = i.ot; out7[2] = i.ct; out7[3] = i.x16; out7[4] = i.dy16; out7[5] = i.nbx; out7[6] = i.ntile;
+    return RU_OK;
+}
+extern "C" int ru_conv1_inst(int N, int Cin, int Cout, size_t V) {
+    RU_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && V > 0, "ru_conv1_inst: bad shape");
+    Conv1Args a{};
+    a.N = N; a.C0 = Cin; a.Cout = Cout; a.V = V;
+    return conv1_inst(a);
+}
+extern "C" int ru_wgrad1_inst(int N, int Cin, int Cout, size_t V, int* out3) {
+    RU_REQUIRE(out3 && N > 0 && Cin > 0 && Cout > 0 && V > 0, "ru_wgrad1_inst: bad argument");
+    Wgrad1Args a{};
+    a.N = N; a.Cin = Cin; a.Cout = Cout; a.V = V;
+    out3[0] = wgrad1_inst(a);
+    wgrad1_walk(a, &out3[1], &out3[2]);
+    return RU_OK;
+}
+
 // ====================================================================== GroupNorm
 static int groupnorm_fwd_walk(const float* x, const float* gamma, const float* beta, const float* residual, float* y, float* mean, float* rstd,
                               int N, int C, size_t V, int G, float eps, float slope, Arena& A, hipStream_t s) {
@@ -334,7 +387,7 @@ static int fin_desc_check(const char* who, const ru_fin_desc& d, int C) {
     RU_REQUIRE(d.kind != 2 || d.coef, "%s: a kind-2 tail needs coef", who);
     return RU_OK;
 }
-// The 3x3x3 family, one launch at a time with every fused operand of Conv3Args (except ksplit): a thin filler.  The caller (`who`, for the messages) has put the
+// The 3x3x3 family, one launch at a time with every fused operand of Conv3Args (ksplit has its own entry, ru_conv3d_fwd_splitk, held by tests/test_ncdhw_convs.py): a thin filler.  The caller (`who`, for the messages) has put the
 // tensors, the shape and the fused operands into `a`; the walk decodes `flags` (resunet_hip.h), packs w and launches.  weight_mode = 1 packs the data-gradient form of
 // w = [Cout][Cin][3][3][3] OF THE FORWARD CONVOLUTION (channels swapped, taps mirrored), so that the launch maps x's Cin channels (the forward's outputs) to y's Cout
 // channels as the engine's backward does.  ru_conv3d_fwd_l is this walk with weight_mode 0 and no fused operands or reports.  fd (flag bit 8 on a dry walk): the tail

@@ -136,17 +136,23 @@ __global__ __launch_bounds__(256) void conv1_mfma_kernel(const Conv1Args a, int 
     }
 }
 
-int conv1_launch(const Conv1Args& a, hipStream_t s) {
-    RU_REQUIRE(a.N > 0 && a.C0 > 0 && a.Cout > 0 && a.V > 0 && a.ldw >= a.Cout, "conv1: bad shape");
+int conv1_inst(const Conv1Args& a) {
     const bool vec = (a.V % 4) == 0;
     // few voxels x many channels (deep levels): one voxel and 4 outputs per thread, otherwise the launch is a handful of
     // workgroups each walking hundreds of input channels serially (latency-bound)
     const long wg_big = (long)((a.V / 4 + 255) / 256) * cdiv(a.Cout, 16) * a.N;
-    if (wg_big < 256 && a.C0 + a.C1 >= 32) {
+    if (wg_big < 256 && a.C0 + a.C1 >= 32) return 0;
+    return (!vec || wg_big < 256) ? 1 : 2;
+}
+
+int conv1_launch(const Conv1Args& a, hipStream_t s) {
+    RU_REQUIRE(a.N > 0 && a.C0 > 0 && a.Cout > 0 && a.V > 0 && a.ldw >= a.Cout, "conv1: bad shape");
+    const int inst = conv1_inst(a);
+    if (inst == 0) {
         const int nvt = (int)((a.V + 63) / 64);
         dim3 grid((unsigned)cdiv(nvt, 4), (unsigned)cdiv(a.Cout, 16), (unsigned)a.N);
         hipLaunchKernelGGL(conv1_mfma_kernel, grid, dim3(256), 0, s, a, nvt);
-    } else if (!vec || wg_big < 256) {
+    } else if (inst == 1) {
         dim3 grid((unsigned)((a.V + 255) / 256), (unsigned)cdiv(a.Cout, 4), (unsigned)a.N);
         hipLaunchKernelGGL((conv1_kernel<1, 4>), grid, dim3(256), 0, s, a);
     } else {

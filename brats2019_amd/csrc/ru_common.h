@@ -211,6 +211,13 @@ struct Conv3Args {
 static inline void conv3_set_pack(Conv3Args& a, const void* wfrag, unsigned wforms) { a.wfrag = wfrag; a.wforms = wforms; }
 int conv3_f32_ksplit(int N, int Cin, int Cout, int D, int H, int W);     // split factor the engine uses for an exact-f32 conv of this shape (1 = none)
 int sum_partials_launch(const float* part, int ksplit, size_t n, float* y, hipStream_t s);    // y[i] = part[0][i] + part[1][i] + ... (fixed order)
+// the instantiation conv3_f32_kernel<TZ, TY, KC, NT> conv3_launch takes for an exact-f32 NCDHW shape, and the split factor of the shape:
+// TZ | TY << 4 | KC << 8 | NT << 12 | conv3_f32_ksplit << 16 (the one place that decides; the launcher switches on the low 16 bits)
+int conv3_f32_inst(int N, int Cin, int Cout, int D, int H, int W);
+// the split-K form whole (conv3_f32.hip): the partial tensors in `part` (conv3_splitk_part_floats floats; ksplit 0 = conv3_f32_ksplit's factor), the launch
+// with Conv3Args::ksplit, sum_partials_launch into a.y.  A factor of 1 is the plain launch.  The engine and ru_conv3d_fwd_splitk both call it.
+size_t conv3_splitk_part_floats(int N, int Cin, int Cout, int D, int H, int W, int ksplit);
+int conv3_launch_splitk(const Conv3Args& a, float* part, int ksplit, const Switches& sw, hipStream_t s);
 int conv3_cin_pad(int Cin);                       // CinP for a given Cin
 static inline int conv3_cout_pad(int Cout) { return round_up(Cout, 16); }
 // effective mode for a shape (the split-bf16 kernel needs W % 4 == 0; otherwise the f32 kernel runs)
@@ -327,6 +334,13 @@ struct WgradRedList { std::vector<WgradRedEntry> e; };
 int wgrad_reduce_launch(const float* partials, int nparts, int taps, int CoP, int CiP, int Cout, int Cin, float* dw, int so, int sc, int split, hipStream_t s,
                         int flip_taps = 0, WgradRedList* defer = nullptr);
 int wgrad_reduce_flush(WgradRedList& l, hipStream_t s);
+// what wgrad3_launch takes for `a` (the one place that decides; wgrad3_launch and wgrad3_sb_launch switch on it and ru_wgrad3_inst reports it):
+// kernel 0 = wgrad3_f32_kernel<TZ, TY, OT, CT> (<2,8,1,1> or <2,4,2,2>), 1 = wgrad3_sb_kernel<TZ, 4, OT, X16, DY16> (TZ = 4 for OT 1, 2 for OT 2; CT 1),
+// 2 = the transpose-read kernel (wgrad3_tr_inst says which; the other fields are 0).  nbx workgroups per channel group walk ntile tiles, tile
+// t + k * nbx to workgroup t: ntile > nbx is the persistent walk.
+struct W3Inst { int kernel, ot, ct, x16, dy16, nbx, ntile; };
+W3Inst wgrad3_inst(const Wgrad3Args& a);
+W3Inst wgrad3_sb_inst(const Wgrad3Args& a);
 size_t wgrad3_sb_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W);
 int wgrad3_sb_launch(const Wgrad3Args& a, hipStream_t s);
 // both tensors voxel-major: transpose-read kernel (wgrad_tr.hip); workspace 0 if the channel counts do not fit
@@ -367,6 +381,8 @@ size_t wgrad1_workspace_bytes(int N, int Cin, int Cout, size_t V);
 int wgrad1_launch(const Wgrad1Args& a, hipStream_t s);
 // the kernel wgrad1_launch takes for `a`: ot | ct << 4 (wgrad1_f32_kernel<ot, ct>) | 1 << 8 (wgrad1_s2d_kernel instead) | 1 << 9 (fused data gradient)
 int wgrad1_inst(const Wgrad1Args& a);
+// the walk of that launch: nbx workgroups per channel group over N * nchunk chunks of 256 voxels (more chunks than workgroups: each walks several)
+void wgrad1_walk(const Wgrad1Args& a, int* nbx, int* nchunk);
 
 // ------------------------------------------------------------------ pointwise / small kernels (pointwise.hip)
 // y[n][o][v] = act( sum_c wT[c*ldw + o] * xcat[n][c][v] ) (+ add), xcat = concat(x0[C0], x1[C1]) on channels.
@@ -403,6 +419,9 @@ struct Conv1Args {
 };
 int conv1_16_bst_nblk(const Conv1Args& a);      // partials per (sample, channel) the launch writes; 0: this shape has no fused-statistics form
 int conv1_launch(const Conv1Args& a, hipStream_t s);
+// the route conv1_launch takes for `a` (the one place that decides; the launcher switches on it): 0 = conv1_mfma_kernel (few voxels, >= 32 input channels),
+// 1 = conv1_kernel<1, 4> (V % 4 != 0, or a small grid), 2 = conv1_kernel<4, 16> (float4 over voxels)
+int conv1_inst(const Conv1Args& a);
 int transpose_launch(const float* src, float* dst, int rows, int cols, hipStream_t s);   // dst[c][r] = src[r][c]
 // NCDHW [N][C][V] <-> C16 [N][C/16][V][16] (C % 16 == 0); to_c16 = 1: src NCDHW -> dst C16, 0: the inverse
 int layout_convert_launch(const float* src, float* dst, int N, int C, size_t V, int to_c16, hipStream_t s);

@@ -380,7 +380,7 @@ int wgrad_reduce_flush(WgradRedList& l, hipStream_t s) {
     return RU_OK;
 }
 
-struct W3Choice { int tz, ty, ot, ct, nbx, ngroups, ncg; };
+struct W3Choice { int tz, ty, ot, ct, nbx, ngroups, ncg; long ntile; };
 
 static W3Choice wgrad3_choose(int N, int Cin, int Cout, int D, int H, int W) {
     W3Choice c;
@@ -395,7 +395,15 @@ static W3Choice wgrad3_choose(int N, int Cin, int Cout, int D, int H, int W) {
     if (nbx < 1) nbx = 1;
     if (nbx > ntile) nbx = ntile;
     c.nbx = (int)nbx;
+    c.ntile = ntile;
     return c;
+}
+
+W3Inst wgrad3_inst(const Wgrad3Args& a) {
+    if (a.x_c16 && a.dy_c16) return W3Inst{2, 0, 0, 0, 0, 0, 0};
+    if (a.x_c16 || a.dy_c16 || (a.mode == RU_PREC_BF16X3 && (a.W & 3) == 0)) return wgrad3_sb_inst(a);
+    const W3Choice c = wgrad3_choose(a.N, a.Cin, a.Cout, a.D, a.H, a.W);
+    return W3Inst{0, c.ot, c.ct, 0, 0, c.nbx, (int)c.ntile};
 }
 
 static size_t wgrad3_f32_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W) {
@@ -432,17 +440,17 @@ int wgrad3_launch(const Wgrad3Args& a, hipStream_t s) {
     RU_REQUIRE(a.N > 0 && a.Cin > 0 && a.Cout > 0 && a.D > 0 && a.H > 0 && a.W > 0, "wgrad3: bad shape");
     if (a.x_c16 || a.dy_c16) {
         RU_REQUIRE(a.mode == RU_PREC_BF16X3, "wgrad3: voxel-major tensors need the split-bf16 kernel");
-        if (a.x_c16 && a.dy_c16) return wgrad3_tr_launch(a, s);
-        return wgrad3_sb_launch(a, s);
     }
-    if (a.mode == RU_PREC_BF16X3 && (a.W & 3) == 0) return wgrad3_sb_launch(a, s);
+    const W3Inst inst = wgrad3_inst(a);                   // the one place that picks the kernel
+    if (inst.kernel == 2) return wgrad3_tr_launch(a, s);
+    if (inst.kernel == 1) return wgrad3_sb_launch(a, s);
     const W3Choice c = wgrad3_choose(a.N, a.Cin, a.Cout, a.D, a.H, a.W);
     if (a.ws_bytes < wgrad3_f32_workspace_bytes(a.N, a.Cin, a.Cout, a.D, a.H, a.W) || !a.ws) {
         set_error("wgrad3: workspace too small");
         return RU_ENOMEM;
     }
     // a.db (bias gradient) is produced by bias_grad_launch at the call sites
-    if (c.ot == 2) return wgrad3_cfg<2, 4, 2, 2>(a, c, s);
+    if (inst.ot == 2 && inst.ct == 2) return wgrad3_cfg<2, 4, 2, 2>(a, c, s);
     return wgrad3_cfg<2, 8, 1, 1>(a, c, s);
 }
 
@@ -815,6 +823,12 @@ static int wgrad1_cfg(const Wgrad1Args& a, const W1Choice& c, hipStream_t s) {
 int wgrad1_inst(const Wgrad1Args& a) {
     const W1Choice c = wgrad1_choose(a.N, a.Cin, a.Cout, a.V);
     return c.ot | (c.ct << 4) | ((a.s2d && wgrad1_s2d_usable(a.Cin, a.Cout)) ? 256 : 0) | (a.dg_w ? 512 : 0);
+}
+
+void wgrad1_walk(const Wgrad1Args& a, int* nbx, int* nchunk) {
+    const W1Choice c = wgrad1_choose(a.N, a.Cin, a.Cout, a.V);
+    *nbx = (wgrad1_inst(a) & 256) ? wgrad1_s2d_nbx(a.N, a.Cin, a.Cout, a.V) : c.nbx;
+    *nchunk = c.nchunk;
 }
 
 int wgrad1_launch(const Wgrad1Args& a, hipStream_t s) {

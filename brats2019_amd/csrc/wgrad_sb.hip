@@ -332,7 +332,7 @@ __global__ __launch_bounds__(256, 2) void wgrad3_sb_kernel(const Wgrad3Args a, f
     }
 }
 
-struct WSBChoice { int ot, nbx, ngroups, ncg; };
+struct WSBChoice { int ot, nbx, ngroups, ncg; long ntile; };
 static WSBChoice wsb_choose(int N, int Cin, int Cout, int D, int H, int W) {
     WSBChoice c;
     const int CoP = round_up(Cout, 16), CiP = round_up(Cin, 16);
@@ -345,7 +345,13 @@ static WSBChoice wsb_choose(int N, int Cin, int Cout, int D, int H, int W) {
     if (nbx < 1) nbx = 1;
     if (nbx > ntile) nbx = ntile;
     c.nbx = (int)nbx;
+    c.ntile = ntile;
     return c;
+}
+
+W3Inst wgrad3_sb_inst(const Wgrad3Args& a) {
+    const WSBChoice c = wsb_choose(a.N, a.Cin, a.Cout, a.D, a.H, a.W);
+    return W3Inst{1, c.ot, 1, a.x_c16 ? 1 : 0, a.dy_c16 ? 1 : 0, c.nbx, (int)c.ntile};
 }
 
 size_t wgrad3_sb_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W) {
@@ -379,12 +385,13 @@ int wgrad3_sb_launch(const Wgrad3Args& a, hipStream_t s) {
         set_error("wgrad3_sb: workspace too small");
         return RU_ENOMEM;
     }
-    if (c.ot == 2) {
-        if (a.x_c16) return a.dy_c16 ? wsb_cfg<2, true, true>(a, c, s) : wsb_cfg<2, true, false>(a, c, s);
-        return a.dy_c16 ? wsb_cfg<2, false, true>(a, c, s) : wsb_cfg<2, false, false>(a, c, s);
+    const W3Inst i = wgrad3_sb_inst(a);                  // the one place that picks the instantiation
+    if (i.ot == 2) {
+        if (i.x16) return i.dy16 ? wsb_cfg<2, true, true>(a, c, s) : wsb_cfg<2, true, false>(a, c, s);
+        return i.dy16 ? wsb_cfg<2, false, true>(a, c, s) : wsb_cfg<2, false, false>(a, c, s);
     }
-    if (a.x_c16) return a.dy_c16 ? wsb_cfg<1, true, true>(a, c, s) : wsb_cfg<1, true, false>(a, c, s);
-    return a.dy_c16 ? wsb_cfg<1, false, true>(a, c, s) : wsb_cfg<1, false, false>(a, c, s);
+    if (i.x16) return i.dy16 ? wsb_cfg<1, true, true>(a, c, s) : wsb_cfg<1, true, false>(a, c, s);
+    return i.dy16 ? wsb_cfg<1, false, true>(a, c, s) : wsb_cfg<1, false, false>(a, c, s);
 }
 
 }  // namespace ru

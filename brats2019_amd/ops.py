@@ -27,7 +27,7 @@ def _prep(t):
     return t.contiguous().float() if (not t.is_contiguous() or t.dtype != torch.float32) else t
 
 
-def conv3d(x, w, bias=None, precision="f32"):
+def conv3d(x, w, bias=None, precision="f32", out=None):
     """nn.Conv3d forward as built at model.py:72-73,336,348 (k=3,s=1,p=1), :361-363 (k=2,s=2), :393,401 (k=1).
     `precision`: "f32" (exact) or "bf16x3" (split-bf16, 3 MFMA products; k=3 only)."""
     x, w, bias = _prep(x), _prep(w), _prep(bias)
@@ -37,39 +37,93 @@ def conv3d(x, w, bias=None, precision="f32"):
     if int(w.shape[1]) != cin:
         raise ValueError("weight expects %d input channels, input has %d" % (int(w.shape[1]), cin))
     out_sp = (d, h, wd) if k != 2 else (d // 2, h // 2, wd // 2)
-    y = torch.empty((n, cout) + out_sp, dtype=torch.float32, device=x.device)
+    y = _out(out, (n, cout) + out_sp, x.device)
     ws = L.workspace(lib.ru_conv3d_workspace_bytes(n, cin, cout, d, h, wd, k), x.device)
     L.check(lib.ru_conv3d_fwd_p(L.f32(x), L.f32(w), L.ptr(bias, True), L.f32(y), n, cin, cout, d, h, wd, k, L.PRECISIONS[precision],
                                 L.ptr(ws), ws.numel(), L.stream()), "ru_conv3d_fwd")
     return y
 
 
-def conv3d_bwd_data(dy, w, in_spatial, precision="f32"):
+def conv3d_bwd_data(dy, w, in_spatial, precision="f32", out=None):
     """Data gradient of the conv above; `in_spatial` = (D,H,W) of the conv INPUT."""
     dy, w = _prep(dy), _prep(w)
     lib = L.load()
     n = int(dy.shape[0])
     cout, cin, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
     d, h, wd = [int(v) for v in in_spatial]
-    dx = torch.empty((n, cin, d, h, wd), dtype=torch.float32, device=dy.device)
+    dx = _out(out, (n, cin, d, h, wd), dy.device)
     ws = L.workspace(lib.ru_conv3d_workspace_bytes(n, cin, cout, d, h, wd, k), dy.device)
     L.check(lib.ru_conv3d_bwd_data_p(L.f32(dy), L.f32(w), L.f32(dx), n, cin, cout, d, h, wd, k, L.PRECISIONS[precision],
                                      L.ptr(ws), ws.numel(), L.stream()), "ru_conv3d_bwd_data")
     return dx
 
 
-def conv3d_bwd_weight(x, dy, k, with_bias=False, precision="f32"):
+def conv3d_bwd_weight(x, dy, k, with_bias=False, precision="f32", out=None, out_db=None):
     """Weight (and bias) gradient of the conv above."""
     x, dy = _prep(x), _prep(dy)
     lib = L.load()
     n, cin, d, h, wd = _dims5(x)
     cout = int(dy.shape[1])
-    dw = torch.empty((cout, cin, k, k, k), dtype=torch.float32, device=x.device)
-    db = torch.empty((cout,), dtype=torch.float32, device=x.device) if with_bias else None
+    dw = _out(out, (cout, cin, k, k, k), x.device)
+    db = _out(out_db, (cout,), x.device) if with_bias else None
     ws = L.workspace(lib.ru_conv3d_workspace_bytes(n, cin, cout, d, h, wd, k), x.device)
     L.check(lib.ru_conv3d_bwd_weight_p(L.f32(x), L.f32(dy), L.f32(dw), L.ptr(db, True), n, cin, cout, d, h, wd, k, L.PRECISIONS[precision],
                                        L.ptr(ws), ws.numel(), L.stream()), "ru_conv3d_bwd_weight")
     return (dw, db) if with_bias else dw
+
+
+def conv3d_splitk(x, w, bias=None, ksplit=0, out=None):
+    """The exact-f32 k = 3 forward in its split-K form (ru_conv3d_fwd_splitk), as the engine runs its small exact-f32 shapes: `ksplit` partial tensors over
+    slices of the 8-channel input chunks, summed in slice order.  ksplit = 0: the factor of ncdhw_conv3_inst(...).ksplit; 1: the plain launch."""
+    x, w, bias = _prep(x), _prep(w), _prep(bias)
+    lib = L.load()
+    n, cin, d, h, wd = _dims5(x)
+    cout = int(w.shape[0])
+    if int(w.shape[1]) != cin or tuple(w.shape[2:]) != (3, 3, 3):
+        raise ValueError("expected a [Cout, %d, 3, 3, 3] weight, got %s" % (cin, tuple(w.shape)))
+    y = _out(out, (n, cout, d, h, wd), x.device)
+    ws = L.workspace(lib.ru_conv3d_fwd_splitk_workspace_bytes(n, cin, cout, d, h, wd, int(ksplit)), x.device)
+    L.check(lib.ru_conv3d_fwd_splitk(L.f32(x), L.f32(w), L.ptr(bias, True), L.f32(y), n, cin, cout, d, h, wd, int(ksplit),
+                                     L.ptr(ws), ws.numel(), L.stream()), "ru_conv3d_fwd_splitk")
+    return y
+
+
+# What a launch of the NCDHW family chooses: host-only queries of the functions the launchers switch on (no device needed).
+Conv3F32Inst = collections.namedtuple("Conv3F32Inst", "tz ty kc nt ksplit")
+Wgrad3Inst = collections.namedtuple("Wgrad3Inst", "kernel ot ct x16 dy16 nbx ntile")
+NcdhwWgrad1Inst = collections.namedtuple("NcdhwWgrad1Inst", "ot ct nbx nchunk")
+CONV1_ROUTES = ("conv1_mfma_kernel", "conv1_kernel<1,4>", "conv1_kernel<4,16>")
+
+
+def ncdhw_conv3_inst(n, cin, cout, d, h, w):
+    """conv3_f32_kernel<tz, ty, kc, nt> of an exact-f32 k = 3 convolution of cin -> cout channels (the data gradient: the forward's cout -> cin) and the split
+    factor the engine takes for the shape (ru_conv3_f32_inst)."""
+    p = L.load().ru_conv3_f32_inst(n, cin, cout, d, h, w)
+    if p < 0:
+        raise ValueError("ru_conv3_f32_inst refused the shape")
+    return Conv3F32Inst(p & 15, (p >> 4) & 15, (p >> 8) & 15, (p >> 12) & 15, p >> 16)
+
+
+def ncdhw_wgrad3_inst(n, cin, cout, d, h, w, precision="f32", x_c16=False, dy_c16=False):
+    """the kernel of the k = 3 weight gradient (ru_wgrad3_inst): kernel "f32" (wgrad3_f32_kernel), "sb" (wgrad3_sb_kernel) or "tr" (the transpose-read kernel)."""
+    out = (C.c_int * 7)()
+    L.check(L.load().ru_wgrad3_inst(n, cin, cout, d, h, w, L.PRECISIONS[precision], int(x_c16) | (int(dy_c16) << 1), out), "ru_wgrad3_inst")
+    return Wgrad3Inst(("f32", "sb", "tr")[out[0]], out[1], out[2], bool(out[3]), bool(out[4]), out[5], out[6])
+
+
+def ncdhw_conv1_route(n, cin, cout, v):
+    """the kernel of the pointwise launch behind k = 1 and k = 2 (ru_conv1_inst): one of CONV1_ROUTES."""
+    r = L.load().ru_conv1_inst(n, cin, cout, v)
+    if r < 0:
+        raise ValueError("ru_conv1_inst refused the shape")
+    return CONV1_ROUTES[r]
+
+
+def ncdhw_wgrad1_inst(n, cin, cout, v):
+    """wgrad1_f32_kernel<ot, ct> of the k = 1 / k = 2 weight gradient on NCDHW tensors and its walk: nbx workgroups per channel group over n * nchunk chunks."""
+    out = (C.c_int * 3)()
+    L.check(L.load().ru_wgrad1_inst(n, cin, cout, v, out), "ru_wgrad1_inst")
+    return NcdhwWgrad1Inst(out[0] & 15, (out[0] >> 4) & 15, out[1], out[2])
 
 
 def group_norm(x, gamma, beta, groups=8, eps=1e-5, slope=1.0, residual=None):
@@ -1115,7 +1169,7 @@ def conv3d_layout(x, w, bias=None, in_c16=False, out_c16=False, few_channels=Fal
     return y
 
 
-def conv3d_bwd_weight_layout(x, dy, x_c16=False, dy_c16=False):
+def conv3d_bwd_weight_layout(x, dy, x_c16=False, dy_c16=False, out=None):
     """3x3x3 split-bf16 weight gradient on tensors in NCDHW or C16 storage."""
     x, dy = _prep(x), _prep(dy)
     if x_c16:
@@ -1124,7 +1178,7 @@ def conv3d_bwd_weight_layout(x, dy, x_c16=False, dy_c16=False):
     else:
         n, cin, d, h, wd = _dims5(x)
     cout = int(dy.shape[1]) * 16 if dy_c16 else int(dy.shape[1])
-    dw = torch.empty((cout, cin, 3, 3, 3), dtype=torch.float32, device=x.device)
+    dw = _out(out, (cout, cin, 3, 3, 3), x.device)
     lib = L.load()
     ws = L.workspace(lib.ru_conv3d_workspace_bytes(n, cin, cout, d, h, wd, 3), x.device)
     L.check(lib.ru_conv3d_bwd_weight_l(L.f32(x), L.f32(dy), L.f32(dw), n, cin, cout, d, h, wd, int(x_c16) | (int(dy_c16) << 1),

@@ -77,6 +77,26 @@ int ru_conv3d_bwd_data(const float* dy, const float* w, float* dx,
 int ru_conv3d_bwd_weight(const float* x, const float* dy, float* dw, float* db,
                          int N, int Cin, int Cout, int D, int H, int W, int k,
                          void* ws, size_t ws_bytes, ru_stream_t stream);
+/* The split-K form of the exact-f32 k = 3 forward, as the engine runs its small exact-f32 shapes: `ksplit` partial output tensors, each the sum over its
+ * slice of the 8-channel input chunks, added in slice order.  ksplit = 0: the factor the engine would take for the shape (the high half of
+ * ru_conv3_f32_inst); 1, given or chosen: the plain launch.  Refused: a factor that does not divide the chunks, a bias beside a split.
+ * ru_conv3d_fwd_splitk_workspace_bytes: the dry walk of the entry (packed weight and partial tensors), plus 4096. */
+size_t ru_conv3d_fwd_splitk_workspace_bytes(int N, int Cin, int Cout, int D, int H, int W, int ksplit);
+int ru_conv3d_fwd_splitk(const float* x, const float* w, const float* bias, float* y,
+                         int N, int Cin, int Cout, int D, int H, int W, int ksplit,
+                         void* ws, size_t ws_bytes, ru_stream_t stream);
+/* What a launch of the NCDHW family chooses -- host-only queries of the functions the launchers switch on (no launch, no workspace):
+ * ru_conv3_f32_inst: conv3_f32_kernel<TZ, TY, KC, NT> of an exact-f32 k = 3 convolution (forward, or the data gradient with Cin / Cout exchanged) and the
+ *   engine's split factor: TZ | TY << 4 | KC << 8 | NT << 12 | ksplit << 16; negative: bad shape.
+ * ru_wgrad3_inst: the k = 3 weight gradient; flags 1: x voxel-major, 2: dy voxel-major.  out7 = kernel (0 wgrad3_f32_kernel, 1 wgrad3_sb_kernel, 2 the
+ *   transpose-read kernel: the rest 0, see ru_wgrad3_l), OT, CT, X16, DY16, nbx (workgroups per channel group), ntile (tiles they walk).
+ * ru_conv1_inst: the pointwise launch behind k = 1 (V = D*H*W) and k = 2 (forward: Cin * 8 channels at V / 8 voxels; data gradient: Cout -> Cin * 8):
+ *   0 conv1_mfma_kernel, 1 conv1_kernel<1, 4>, 2 conv1_kernel<4, 16>.
+ * ru_wgrad1_inst: the k = 1 / k = 2 weight gradient on NCDHW tensors: out3 = OT | CT << 4 (as ru_wgrad1_l reports), nbx, nchunk (chunks of 256 voxels per sample). */
+int ru_conv3_f32_inst(int N, int Cin, int Cout, int D, int H, int W);
+int ru_wgrad3_inst(int N, int Cin, int Cout, int D, int H, int W, int precision, int flags, int* out7);
+int ru_conv1_inst(int N, int Cin, int Cout, size_t V);
+int ru_wgrad1_inst(int N, int Cin, int Cout, size_t V, int* out3);
 
 /* ---------------------------------------------------------------- GroupNorm (+ fused LeakyReLU / residual)
  * nn.GroupNorm(G, C), eps, affine (model.py:95-96,338) followed by LeakyReLU(slope) (model.py:93-94; pass

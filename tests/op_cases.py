@@ -53,6 +53,11 @@ def cases():
             add("conv3d_bwd_data_k%d_%s" % (k, prec), False, lambda dy=dy, w=w, prec=prec: as_list(ops.conv3d_bwd_data(dy, w, (s, s, s), precision=prec)))
             add("conv3d_bwd_weight_k%d_%s" % (k, prec), False, lambda x=x, dy=dy, k=k, prec=prec: as_list(ops.conv3d_bwd_weight(x, dy, k, with_bias=(k == 3), precision=prec)))
 
+    # ---- ru_conv3d_fwd_splitk, 1 x 32 -> 32 at 4 x 4 x 16 (tests/test_ncdhw_convs_host.py): the packed weight and two partial tensors; the factor chosen and given
+    xk, wk = _rand(1, 32, 4, 4, 16, seed=45), _rand(32, 32, 3, 3, 3, seed=46, scale=0.05)
+    add("conv3d_fwd_splitk", True, lambda: as_list(ops.conv3d_splitk(xk, wk)))
+    add("conv3d_fwd_splitk_given", True, lambda: as_list(ops.conv3d_splitk(xk, wk, ksplit=2)))
+
     # ---- GroupNorm: N = 1, C = 16, V = 8192 + 1 -- two tiles
     x, dy = _rand(1, 16, 1, 1, 8193, seed=50), _rand(1, 16, 1, 1, 8193, seed=51)
     gamma, beta = _rand(16, seed=52) + 1.0, _rand(16, seed=53)

@@ -2,7 +2,8 @@
 in_sum_out, bias, add, sigmoid, stat_partials, bst_*, products, the data-gradient packing) driven through ru_conv3_l (ops.conv3_fused) against the float64
 restatements of tests/test_conv3_fused_host.py, which proves them against the oracle's autograd, proves the exact family exact, and shows that every bar below can
 fail.  Every case asserts the route it was written for (conv3_sb_route / conv3_f32c_route, the rule the launchers dispatch on), so a routing change cannot
-silently empty a case.  Conv3Args::fin (the tail finalize) is held by tests/test_gn_c16.py on these cases.  Out of scope: ksplit and the NCDHW exact-f32 conv3_f32_kernel.
+silently empty a case.  Conv3Args::fin (the tail finalize) is held by tests/test_gn_c16.py on these cases.  Conv3Args::ksplit and the NCDHW exact-f32
+conv3_f32_kernel are held by tests/test_ncdhw_convs.py.
 
 Two input families per case (CASES of the host file):
   exact   small integers / powers of two, slope 0.5: stored outputs, in_sum_out and the float64 sum of the partials must EQUAL the float64 reference (a lost or

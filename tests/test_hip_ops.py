@@ -4,7 +4,10 @@ oracle on further seeded shapes (ragged extents, channel counts of every network
 
 Tolerances (float32 path, exact-f32 MFMA; only the summation ORDER differs from the CPU):
 forward tensors  |d| <= 1e-5 + 1e-5*|ref|   (K <= 3456 products per output)
-reductions over >= 1e3 voxels (weight grads, GN parameter grads) relative 2e-4 of the tensor's max."""
+reductions over >= 1e3 voxels (weight grads, GN parameter grads) relative 2e-4 of the tensor's max.
+
+The shapes here are chosen for channel pairs.  The launchers' switches -- every conv3_f32_kernel instantiation, split-K, the persistent walks of the weight
+gradients, the routes of conv1_launch, the reduction's forms -- are reached, asserted and held to float64 at these same bars by tests/test_ncdhw_convs.py."""
 import numpy as np
 import pytest
 import torch
