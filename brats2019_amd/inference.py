@@ -251,6 +251,8 @@ def prepare_case_device(image):
 
 def _forward(model, batch, tile, overlap, window):
     """The forward of the batch of flips: whole, or with `tile` set through overlapping tiles blended with `window` (tiling.predict_blended)."""
+    from .model import warn_mx_range
+    warn_mx_range(model)                                         # once per model: parameters outside the fp16 + MX-fp8 operand range (model.MX_RANGE)
     if tile is None:
         return model([batch])[0]
     return tiling.predict_blended(model, batch, tile, overlap=overlap, window=window)

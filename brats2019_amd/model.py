@@ -24,6 +24,66 @@ from .engine import UNetEngine
 
 LEAKY_SLOPE = 1e-2
 
+# Operand windows of the fp16 + MX-fp8 forward 3x3x3 kernels (csrc/conv3_mx.hpp, conv3_wz32mx.hpp: whole-tensor power-of-two scales, so accuracy depends on the
+# operands' magnitude): inside, the scheme holds its bar against float64 (1.2e-4 of the output RMS and 4x the three-product error); below the lower ends the
+# cross terms underflow and the result decays SILENTLY towards one fp16 product (1.4e-3), above the upper ends they saturate, with the same limit.  Measured against
+# float64 on the CPU model of the operand conversions, never against the kernels: tests/test_mx_range_host.py (MX_WINDOW) asserts these numbers; profiles/mx_range.txt
+# has the sweep.  x_rms / x_max: RMS and largest magnitude of the activation tensor; w_max: largest weight magnitude.
+MX_RANGE = {
+    "conv3_mx": dict(x_rms=(0.0617, 31.6), x_max=(0.336, 172.0), w_max=(1.06e-3, 1.09)),
+    "conv3_wz32mx": dict(x_rms=(0.0617, 31.6), x_max=(0.382, 195.0), w_max=(1.50e-3, 0.769)),
+}
+
+
+def mx_kernel_of(cin, cout):
+    """the fp16 + MX-fp8 kernel a forward 3x3x3 convolution of these channel counts can take (shape permitting), or None"""
+    if cin == 16 and cout % 16 == 0:
+        return "conv3_mx"
+    if cin >= 32 and cin % 16 == 0 and cout % 32 == 0:
+        return "conv3_wz32mx"
+    return None
+
+
+def mx_range_report(module_or_state_dict):
+    """Where a set of parameters sits in MX_RANGE (host only: reads the parameters, launches nothing).  One row (dict) per 3x3x3 weight whose forward convolution has
+    an fp16 + MX-fp8 kernel -- value = max |w| against that kernel's weight window -- and one per GroupNorm of such a channel count -- value = max sqrt(gamma^2 +
+    beta^2), the RMS scale of the activation tensor the next convolution reads, against the activation window (x_rms).  Keys: name, kind ("weight" /
+    "activation"), kernel, value, lo, hi, inside."""
+    sd = module_or_state_dict.state_dict() if hasattr(module_or_state_dict, "state_dict") else module_or_state_dict
+    sd = {k: torch.as_tensor(v).detach().double().cpu() for k, v in sd.items()}
+    rows = []
+    for k, v in sd.items():
+        if v.dim() == 5 and tuple(v.shape[2:]) == (3, 3, 3):
+            kernel, kind, value = mx_kernel_of(int(v.shape[1]), int(v.shape[0])), "weight", float(v.abs().max())
+        elif v.dim() == 1 and k.endswith(".weight") and k[:-6] + "bias" in sd and sd[k[:-6] + "bias"].shape == v.shape:
+            kernel, kind, value = mx_kernel_of(int(v.numel()), int(v.numel())), "activation", float((v ** 2 + sd[k[:-6] + "bias"] ** 2).sqrt().max())
+        else:
+            continue
+        if kernel is None:
+            continue
+        lo, hi = MX_RANGE[kernel]["w_max" if kind == "weight" else "x_rms"]
+        rows.append(dict(name=k, kind=kind, kernel=kernel, value=value, lo=lo, hi=hi, inside=bool(lo <= value <= hi)))
+    return rows
+
+
+def warn_mx_range(model):
+    """Once per model object (the inference entry points and Trainer.train call this): a warning that names the layers outside MX_RANGE and the switch that takes
+    the three-product kernels instead.  There is no per-layer fallback: the engine runs what RU_MX says."""
+    import os
+    import warnings
+    if not isinstance(model, UNet) or model.__dict__.get("_mx_range_warned"):
+        return []
+    model.__dict__["_mx_range_warned"] = True
+    if os.environ.get("RU_MX") == "0" or (model.__dict__.get("precision") or default_precision(model.number_of_channels)) != "bf16x3":
+        return []
+    out = [r for r in mx_range_report(model) if not r["inside"]]
+    if out:
+        warnings.warn("%d layer(s) outside the operand range of the fp16 + MX-fp8 forward convolutions, which lose precision silently there (down to one fp16 product): %s.  "
+                      "RU_MX=0 runs the three-product kernels instead." % (len(out), ", ".join("%s %s %.3g not in [%.3g, %.3g] of %s" % (
+                          r["name"], "max|w|" if r["kind"] == "weight" else "max sqrt(gamma^2+beta^2)", r["value"], r["lo"], r["hi"], r["kernel"]) for r in out[:4])
+                          + (" ..." if len(out) > 4 else "")), RuntimeWarning, stacklevel=3)
+    return out
+
 
 def default_precision(number_of_channels):
     """The benchmarked split-bf16 engine needs channel counts divisible by 16 (voxel-major C16 layout); it is what a drop-in user
@@ -308,6 +368,7 @@ class UNet(nn.Module):
     def load_state_dict(self, *args, **kwargs):                   # writes through the aliased flat buffer in place (assign=True: new Parameters)
         self._unfreeze()
         self._drop_param_caches()
+        self.__dict__.pop("_mx_range_warned", None)               # new weights: warn_mx_range looks again
         try:
             return super().load_state_dict(*args, **kwargs)
         finally:

@@ -135,6 +135,8 @@ class Trainer(object):
             self.state.best_val = default_val
         if self.state.cuda:
             self.model.cuda()
+        from .model import warn_mx_range
+        warn_mx_range(self.model)                                # once: parameters outside the fp16 + MX-fp8 operand range (model.MX_RANGE) -- names RU_MX=0
         optimizer, scheduler = self._make_optimizer(optimizer, optimizer_params, scheduler, scheduler_params)
         if self.state.optimizer_state is not None and not continue_form_pretraining:
             optimizer.load_state_dict(self.state.optimizer_state)
