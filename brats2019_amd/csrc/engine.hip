@@ -19,7 +19,7 @@
 #include <string.h>
 
 #include <string>
-#include <vector>
+#include <type_traits>
 
 namespace ru {
 
@@ -168,6 +168,11 @@ struct GNSave {
 struct BlockSave {
     const BlockP* bp = nullptr;
     const float* xprev = nullptr;   // input before the optional down-sampling conv
+    // ... and the block whose output xprev is: the gradient this block's backward produces enters THAT block's norm2.  ru_unet_create
+    // refuses a level without blocks, so a tensor handed from one level or stage to the next is always a block's output; null means
+    // xprev is no block's output at all -- the stem's (the gradient enters norm_input) or a decoder stage's concat 1x1 (it enters no
+    // GroupNorm).  The same holds for DecSave::z_block and ru_unet::head_block.
+    const BlockSave* xprev_block = nullptr;
     float* xs2d = nullptr;          // space-to-depth of xprev (down blocks)
     const float* x = nullptr;       // block input (after down-sampling)
     const GNSave* xg = nullptr;     // ... which is GroupNorm(+activation) of x applied on the fly when set (first block after the stem)
@@ -178,6 +183,7 @@ struct BlockSave {
 
 struct DecSave {
     const float* z = nullptr;      // coarse input
+    const BlockSave* z_block = nullptr;     // ... and the block that produced it (BlockSave::xprev_block)
     float *u = nullptr, *v = nullptr, *c = nullptr;
     const float* skip = nullptr;
     int level = 0;
@@ -226,6 +232,7 @@ struct ru_unet {
     float *y0 = nullptr, *t0 = nullptr, *probs = nullptr;
     GNSave g0;
     const float* head_in = nullptr;
+    const BlockSave* head_block = nullptr;  // ... and the block that produced it (BlockSave::xprev_block)
     std::vector<BlockSave> first_s;
     std::vector<std::vector<BlockSave>> enc_s, dec_s;
     std::vector<DecSave> dstage;
@@ -584,12 +591,13 @@ static int conv3_gn(ru_unet* h, Arena& A, hipStream_t s, const float* x, const f
 // defer_out (the block in front of the head conv): the residual pass does not run -- the caller hands (y2, norm2's scale / shift, the block input x) to the
 // head conv, whose staging forms x + lrelu(norm2(y2)) itself (Conv3Args::in_res) and, in training, writes it to sv.out on the way (in_sum_out: the head's
 // weight gradient reads it); in inference *out stays null and nothing of the block is rewound.
-static int block_fwd(ru_unet* h, const float* params, Arena& A, hipStream_t s, const BlockP& bp, const float* xprev,
+static int block_fwd(ru_unet* h, const float* params, Arena& A, hipStream_t s, const BlockP& bp, const float* xprev, const BlockSave* xprev_block,
                      int N, int D, int H, int W /* extents of xprev */, BlockSave& sv, const float** out, const GNSave* xin_gn = nullptr, bool defer_out = false) {
     sv = BlockSave();
     sv.xg = xin_gn;
     sv.bp = &bp;
     sv.xprev = xprev;
+    sv.xprev_block = xprev_block;
     const int C = bp.c;
     const float* x = xprev;
     // inference: nothing but the block's output survives it -- the output is allocated first and the arena rewound behind it at the end
@@ -671,7 +679,7 @@ static int unet_forward_impl(ru_unet* h, const float* params, const float* x, fl
 
     // stem: conv_input -> norm_input (no activation, model.py:412-413)
     const int C0 = h->ch[0];
-    const BlockSave* head_block = nullptr;               // inference: the block whose residual pass the head conv's staging takes over (block_fwd, defer_out)
+    const BlockSave* res_block = nullptr;                // the block whose residual pass the head conv's staging takes over (block_fwd, defer_out)
     h->x_in = x;
     h->x_in4 = nullptr;
     h->x_in4_planned = false;
@@ -703,10 +711,12 @@ static int unet_forward_impl(ru_unet* h, const float* params, const float* x, fl
         else RU_RUN(gn_apply_launch(h->y0, h->g0.scale, h->g0.shift, nullptr, h->t0, N, C0, Vl(0), 1.0f, s));
     }
     const float* cur = stem_fused ? h->y0 : h->t0;
+    const BlockSave* cur_block = nullptr;                // the block whose output `cur` is (BlockSave::xprev_block): the backward reads who fed whom from here
     h->first_s.assign(h->first_blocks.size(), BlockSave());
     for (size_t j = 0; j < h->first_blocks.size(); ++j) {
-        rc = block_fwd(h, params, A, s, h->first_blocks[j], cur, N, Dl[0], Hl[0], Wl[0], h->first_s[j], &cur, (stem_fused && j == 0) ? &h->g0 : nullptr);
+        rc = block_fwd(h, params, A, s, h->first_blocks[j], cur, cur_block, N, Dl[0], Hl[0], Wl[0], h->first_s[j], &cur, (stem_fused && j == 0) ? &h->g0 : nullptr);
         if (rc) return rc;
+        cur_block = &h->first_s[j];
     }
     // encoder (model.py:416-418)
     h->skips.assign(depth - 1, nullptr);
@@ -716,8 +726,9 @@ static int unet_forward_impl(ru_unet* h, const float* params, const float* x, fl
         h->enc_s[i].assign(h->enc_blocks[i].size(), BlockSave());
         for (size_t j = 0; j < h->enc_blocks[i].size(); ++j) {
             const int lv = j == 0 ? i : i + 1;
-            rc = block_fwd(h, params, A, s, h->enc_blocks[i][j], cur, N, Dl[lv], Hl[lv], Wl[lv], h->enc_s[i][j], &cur);
+            rc = block_fwd(h, params, A, s, h->enc_blocks[i][j], cur, cur_block, N, Dl[lv], Hl[lv], Wl[lv], h->enc_s[i][j], &cur);
             if (rc) return rc;
+            cur_block = &h->enc_s[i][j];
         }
     }
     // decoder (model.py:420-426)
@@ -727,6 +738,7 @@ static int unet_forward_impl(ru_unet* h, const float* params, const float* x, fl
         DecSave& ds = h->dstage[i];
         ds.level = i;
         ds.z = cur;
+        ds.z_block = cur_block;
         ds.skip = h->skips[i];
         const int Ci = h->ch[i], Cc = h->ch[i + 1];
         // C16 flow: the 1x1x1 conv and the trilinear interpolation are both linear and act on different axes, so
@@ -763,6 +775,7 @@ static int unet_forward_impl(ru_unet* h, const float* params, const float* x, fl
         }
         if (recycle) A.rewind(dmark);
         cur = ds.c;
+        cur_block = nullptr;
         h->dec_s[i].assign(h->dec_blocks[i].size(), BlockSave());
         for (size_t j = 0; j < h->dec_blocks[i].size(); ++j) {
             // the block in front of the head conv leaves its residual pass to that conv's staging (inference: one read of y2 and x instead of read y2 +
@@ -770,13 +783,15 @@ static int unet_forward_impl(ru_unet* h, const float* params, const float* x, fl
             const bool defer = i == 0 && j + 1 == h->dec_blocks[i].size() && h->c16 &&
                                (h->precision == RU_PREC_BF16X3 ? conv3_sb_head_takes_residual(h->sw, N, C0, h->nout, Dl[0], Hl[0], Wl[0])
                                                                : (!h->training && conv3_f32c_head_takes_residual(h->sw, C0, h->nout, Wl[0])));       // (exact f32: the voxel-major flow is inference only)
-            rc = block_fwd(h, params, A, s, h->dec_blocks[i][j], cur, N, Dl[i], Hl[i], Wl[i], h->dec_s[i][j], &cur, nullptr, defer);
+            rc = block_fwd(h, params, A, s, h->dec_blocks[i][j], cur, cur_block, N, Dl[i], Hl[i], Wl[i], h->dec_s[i][j], &cur, nullptr, defer);
             if (rc) return rc;
-            if (defer) head_block = &h->dec_s[i][j];
+            cur_block = &h->dec_s[i][j];
+            if (defer) res_block = cur_block;
         }
     }
     // head: conv_output + bias + sigmoid (model.py:429-431)
     h->head_in = cur;
+    h->head_block = cur_block;
     t_hint_c = C0;
     // training: the sigmoid backward reads the probabilities from the CALLER's buffer (kept valid until ru_unet_backward, see the header)
     float* pdst = probs_out;
@@ -785,9 +800,9 @@ static int unet_forward_impl(ru_unet* h, const float* params, const float* x, fl
     a.x = cur; a.wp = h->pack + h->pk_out; a.bias = P(h, params, h->conv_out_b); a.y = pdst; a.sigmoid = 1;
     a.mode = h->precision; h->set_pack(a, h->fk_out); a.in_c16 = h->c16;
     a.N = N; a.Cin = C0; a.Cout = h->nout; a.D = Dl[0]; a.H = Hl[0]; a.W = Wl[0];
-    if (head_block) {                                    // x + lrelu(norm2(conv2)) of the last block, formed in this conv's staging
-        a.x = head_block->y2; a.in_scale = head_block->g2.scale; a.in_shift = head_block->g2.shift; a.in_slope = kSlope; a.in_res = head_block->x;
-        a.in_sum_out = head_block->out;                  // (training: the block output, written on the way; null in inference)
+    if (res_block) {                                     // x + lrelu(norm2(conv2)) of the last block, formed in this conv's staging
+        a.x = res_block->y2; a.in_scale = res_block->g2.scale; a.in_shift = res_block->g2.shift; a.in_slope = kSlope; a.in_res = res_block->x;
+        a.in_sum_out = res_block->out;                   // (training: the block output, written on the way; null in inference)
     }
     RU_RUN(conv3_launch(a, h->sw, s));
     if (!A.dry) { h->packed_params = h->training ? nullptr : params; h->packed_base = h->pack; h->packed_prec = h->precision; h->packed_c16 = h->c16; h->pack_sw = h->sw; }   // a training forward is followed by an optimizer step
@@ -795,48 +810,98 @@ static int unet_forward_impl(ru_unet* h, const float* params, const float* x, fl
 }
 
 // ---------------------------------------------------------------------- backward pieces
-// GroupNorm(+LeakyReLU) backward: d_act -> dy (gradient w.r.t. the raw conv output), dgamma/dbeta written
-// fused_part / fused_nblk: the partial sums were already taken by the conv that produced `dact` (Conv3Args::bst_*): no reduce pass
-// pre: the caller allocated the coefficient buffer next to the fused partials (FusedSums) -- and when pre->done, the kernel that produced
-// the partials has already finalized them in its tail (RU_FUSE_TAIL_FINALIZE): no finalize launch here
-struct FusedSums { float* part = nullptr; int nblk = 0; float* coef = nullptr; bool done = false; };
-static void fill_bwd_tail(ru_unet* h, FinTail& f, const FusedSums& fs, const GNSave& g, const float* gamma, float* dgamma, float* dbeta, int N, int C, size_t V, int s2_sign) {
-    f.ticket = h->next_ticket(); f.kind = 2; f.nblk = fs.nblk; f.N = N; f.C = C; f.G = kGroups; f.V = V; f.eps = kEps; f.s2_sign = s2_sign;
-    f.gamma = gamma; f.mean = g.mean; f.rstd = g.rstd; f.coef = fs.coef; f.dgamma = dgamma; f.dbeta = dbeta;
+// A GroupNorm(+LeakyReLU) as the backward sees it: the raw conv output it normalised, its saved statistics, the slope that follows it, its
+// gamma and where its parameter gradients go.  (A dry walk has null tensors and parameters; the GNSave is the handle's own either way.)
+struct NormRef {
+    const float* y = nullptr;
+    const GNSave* g = nullptr;
+    float slope = kSlope;
+    const float* gamma = nullptr;
+    float *dgamma = nullptr, *dbeta = nullptr;
+    int C = 0;
+};
+static NormRef norm1_of(const ru_unet* h, const float* params, float* grads, const BlockSave& b) {
+    return {b.y1, &b.g1, kSlope, P(h, params, b.bp->n1w), G(h, grads, b.bp->n1w), G(h, grads, b.bp->n1b), b.C};
 }
-static int gn_bwd(ru_unet* h, Arena& A, hipStream_t s, const float* yraw, const float* dact, const GNSave& g, const float* gamma, float slope,
-                  float* dy, float* dgamma, float* dbeta, int N, int C, size_t V, const FusedSums* pre = nullptr,
+static NormRef norm2_of(const ru_unet* h, const float* params, float* grads, const BlockSave& b) {
+    return {b.y2, &b.g2, kSlope, P(h, params, b.bp->n2w), G(h, grads, b.bp->n2w), G(h, grads, b.bp->n2b), b.C};
+}
+static NormRef norm_input_of(const ru_unet* h, const float* params, float* grads) {       // no activation (model.py:412-413): slope 1
+    return {h->y0, &h->g0, 1.0f, P(h, params, h->nin_w), G(h, grads, h->nin_w), G(h, grads, h->nin_b), h->ch[0]};
+}
+
+// GroupNorm-backward partial sums taken by the kernel that PRODUCED the gradient (Conv3Args / Conv1Args::bst_*), with the coefficient buffer
+// next to them; done: that kernel has also finalized them in its tail (RU_FUSE_TAIL_FINALIZE).  nblk == 0: nobody took them.
+struct FusedSums { float* part = nullptr; int nblk = 0; float* coef = nullptr; bool done = false; };
+// The one value that flows along the backward chain: a gradient, and the sums of the GroupNorm it enters if its producer took them.
+// The sums are those of the gradient as its producer stored it: whoever adds to it afterwards hands on the bare gradient (unet_backward_impl).
+struct Grad { const float* d = nullptr; FusedSums sums; };
+
+static void fill_bwd_tail(ru_unet* h, FinTail& f, const FusedSums& fs, const NormRef& n, size_t V, int s2_sign) {
+    f.ticket = h->next_ticket(); f.kind = 2; f.nblk = fs.nblk; f.N = h->N; f.C = n.C; f.G = kGroups; f.V = V; f.eps = kEps; f.s2_sign = s2_sign;
+    f.gamma = n.gamma; f.mean = n.g->mean; f.rstd = n.g->rstd; f.coef = fs.coef; f.dgamma = n.dgamma; f.dbeta = n.dbeta;
+}
+
+// partials per (sample, channel) a producer launch writes when it takes the sums
+static int bst_nblk(const ru_unet* h, const Conv3Args& a) { return sb_nblk(h, a); }
+static int bst_nblk(const ru_unet*, const Conv1Args& a) { return conv1_16_bst_nblk(a); }
+// The launch `a` is about to store the gradient that enters `n`: its store pass takes n's GroupNorm-backward sums (no reduce pass over (y, d)).
+// `may` is the caller's structural decision (layout, fusion bits, the *_usable / *_nblk host functions) -- never a pointer: the dry walk has none.
+// A Conv3Args launch also finalizes them in its last workgroup under RU_FUSE_TAIL_FINALIZE (coefficients, dgamma, dbeta of n; its sums carry the
+// sign of gamma, hence s2_sign 1); the Conv1Args kernel has no tail.
+template <class Args>
+static FusedSums take_bwd_sums(ru_unet* h, Arena& A, Args& a, const NormRef& n, bool may) {
+    FusedSums fs;
+    if (!may) return fs;
+    a.bst_y = n.y; a.bst_k = n.g->k; a.bst_slope = n.slope;      // (constants written by the forward finalize.)  First: the count follows the launch's arguments
+    fs.nblk = bst_nblk(h, a);
+    fs.part = A.alloc((size_t)h->N * n.C * fs.nblk * 2);
+    fs.coef = A.alloc((size_t)h->N * n.C * 3);
+    a.stat_partials = fs.part;
+    if constexpr (std::is_same<Args, Conv3Args>::value) {
+        if (!A.dry && h->tails()) {
+            fill_bwd_tail(h, a.fin, fs, n, (size_t)a.D * a.H * a.W, 1);
+            fs.done = true;
+        }
+    }
+    return fs;
+}
+
+// GroupNorm(+LeakyReLU) backward of `n`: the gradient in.d w.r.t. the activation -> dy (w.r.t. the raw conv output), dgamma / dbeta written.
+// in.sums taken by the producer of in.d: no reduce pass -- and no finalize launch either where that producer's tail has run (FusedSums::done)
+static int gn_bwd(ru_unet* h, Arena& A, hipStream_t s, const NormRef& n, const Grad& in, float* dy, size_t V,
                   float** coef_out = nullptr /* non-null: stop after the finalize; the apply is fused into the weight gradient (Wgrad3Args::gb_*) */,
                   bool split = true /* voxel-major flow: publish dy as hi/lo bf16 packets (read by the transpose-read weight gradient and the
                                        persistent data-gradient conv) or as plain float32 C16 (the generic weight-gradient kernel) */) {
     const bool c16 = h->c16;
-    const bool fused = pre && pre->nblk > 0;
-    const int nblk = fused ? pre->nblk : (c16 ? gn_bwd_tiles16(V) : gn_bwd_tiles(V));
-    float* part = fused ? pre->part : A.alloc((size_t)N * C * nblk * 2);
-    float* coef = fused ? pre->coef : A.alloc((size_t)N * C * 3);
-    bool done = fused && pre->done;
+    const int N = h->N, C = n.C;
+    const GNSave& g = *n.g;
+    FusedSums fs = in.sums;
+    const bool fused = fs.nblk > 0;
     if (!fused) {
+        fs.nblk = c16 ? gn_bwd_tiles16(V) : gn_bwd_tiles(V);
+        fs.part = A.alloc((size_t)N * C * fs.nblk * 2);
+        fs.coef = A.alloc((size_t)N * C * 3);
         if (c16) {
             FinTail f{};
             if (!A.dry && h->tails()) {
-                FusedSums fs; fs.part = part; fs.nblk = nblk; fs.coef = coef;
-                fill_bwd_tail(h, f, fs, g, gamma, dgamma, dbeta, N, C, V, 0);
-                done = true;
+                fill_bwd_tail(h, f, fs, n, V, 0);
+                fs.done = true;
             }
-            RU_RUN(gn_bwd_reduce16_launch(yraw, dact, g.scale, g.shift, g.mean, g.rstd, slope, part, N, C, V, kGroups, s, &f));
+            RU_RUN(gn_bwd_reduce16_launch(n.y, in.d, g.scale, g.shift, g.mean, g.rstd, n.slope, fs.part, N, C, V, kGroups, s, &f));
         } else {
-            RU_RUN(gn_bwd_reduce_launch(yraw, dact, g.scale, g.shift, g.mean, g.rstd, slope, part, N, C, V, kGroups, s));
+            RU_RUN(gn_bwd_reduce_launch(n.y, in.d, g.scale, g.shift, g.mean, g.rstd, n.slope, fs.part, N, C, V, kGroups, s));
         }
     }
-    if (!done) RU_RUN(gn_bwd_finalize_launch(part, nblk, gamma, g.mean, g.rstd, coef, dgamma, dbeta, N, C, V, kGroups, s, fused ? 1 : 0));
-    if (coef_out) { *coef_out = coef; return RU_OK; }
-    if (c16) RU_RUN(gn_bwd_apply16_launch(yraw, dact, g.scale, g.shift, coef, slope, dy, N, C, V, split ? 1 : 0, s));   // split form: read by MFMA kernels only
-    else RU_RUN(gn_bwd_apply_launch(yraw, dact, g.scale, g.shift, coef, slope, dy, N, C, V, s));
+    if (!fs.done) RU_RUN(gn_bwd_finalize_launch(fs.part, fs.nblk, n.gamma, g.mean, g.rstd, fs.coef, n.dgamma, n.dbeta, N, C, V, kGroups, s, fused ? 1 : 0));
+    if (coef_out) { *coef_out = fs.coef; return RU_OK; }
+    if (c16) RU_RUN(gn_bwd_apply16_launch(n.y, in.d, g.scale, g.shift, fs.coef, n.slope, dy, N, C, V, split ? 1 : 0, s));   // split form: read by MFMA kernels only
+    else RU_RUN(gn_bwd_apply_launch(n.y, in.d, g.scale, g.shift, fs.coef, n.slope, dy, N, C, V, s));
     return RU_OK;
 }
 
-// GroupNorm-backward apply fused into the weight gradient's dy staging (Wgrad3Args::gb_*): dy is OUTPUT (split form) then
-struct GbApply { const float* y; const float* d; const GNSave* g; const float* coef; bool g16 = false; };     // g16: publish the gradient-operand form of the MX scheme (conv3_mxg_usable)
+// GroupNorm-backward apply of `n` fused into the weight gradient's dy staging (Wgrad3Args::gb_*): dy is OUTPUT (split form) then
+struct GbApply { NormRef n; const float* d; const float* coef; bool g16 = false; };     // g16: publish the gradient-operand form of the MX scheme (conv3_mxg_usable)
 static int wgrad3_run(Arena& A, hipStream_t s, int mode, const float* x, const GNSave* xg, const float* dy, float* dw, int N, int Cin, int Cout, int D, int H, int W,
                       bool x_c16 = false, bool dy_c16 = false, const float* few4 = nullptr, bool dy_s16 = false, const GbApply* gb = nullptr) {
     const int products = (mode & kOneProduct) ? 1 : 3;
@@ -860,8 +925,8 @@ static int wgrad3_run(Arena& A, hipStream_t s, int mode, const float* x, const G
         const bool swap = x_c16 && use4 && !xg && !gb;
         if (swap) { w.x = fewp; w.dy = x; w.x_c4 = 1; w.dy_c4 = 0; w.dy_s16 = 0; w.swapped = 1; }
         if (gb && !x_c16 && use4) {                              // stem: dy is the GroupNorm-backward apply of norm_input, computed while staging; nobody else reads it
-            w.gb_y = gb->y; w.gb_d = gb->d; w.gb_scale = gb->g->scale; w.gb_shift = gb->g->shift; w.gb_coef = gb->coef; w.gb_slope = gb->g->act_slope;
-            w.gb_out = nullptr; w.dy = gb->y; w.dy_s16 = 0;      // (dy unused in this mode; any valid pointer)
+            w.gb_y = gb->n.y; w.gb_d = gb->d; w.gb_scale = gb->n.g->scale; w.gb_shift = gb->n.g->shift; w.gb_coef = gb->coef; w.gb_slope = gb->n.slope;
+            w.gb_out = nullptr; w.dy = gb->n.y; w.dy_s16 = 0;    // (dy unused in this mode; any valid pointer)
         }
         w.in_scale = xg ? xg->scale : nullptr; w.in_shift = xg ? xg->shift : nullptr; w.in_slope = xg ? xg->act_slope : kSlope;
         w.dw_cin = Cin; w.dw_cout = Cout;
@@ -880,7 +945,7 @@ static int wgrad3_run(Arena& A, hipStream_t s, int mode, const float* x, const G
     w.ws = A.alloc(w.ws_bytes / sizeof(float));
     w.N = N; w.Cin = Cin; w.Cout = Cout; w.D = D; w.H = H; w.W = W;
     if (gb) {
-        w.gb_y = gb->y; w.gb_d = gb->d; w.gb_scale = gb->g->scale; w.gb_shift = gb->g->shift; w.gb_coef = gb->coef; w.gb_slope = kSlope;
+        w.gb_y = gb->n.y; w.gb_d = gb->d; w.gb_scale = gb->n.g->scale; w.gb_shift = gb->n.g->shift; w.gb_coef = gb->coef; w.gb_slope = gb->n.slope;
         w.gb_out = const_cast<float*>(dy); w.dy_s16 = 0; w.gb_g16 = gb->g16 ? 1 : 0;
     }
     t_hint_inst = (x_c16 && dy_c16) ? (Cin == 16 && Cout == 16 ? (gb ? INST_WGRAD16_FUSED : INST_WGRAD16_PLAIN) : (Cin >= 32 ? INST_WGRAD_DEEP : -1)) : -1;
@@ -938,21 +1003,18 @@ static int side_join(ru_unet* h, hipStream_t main) {
     return er == hipSuccess ? RU_OK : hip_fail(er, "side_join");
 }
 
-// Residual backward: dout -> d(xprev); parameter gradients into `grads`
+// Residual backward.  io: on entry the gradient w.r.t. the block's output (with norm2's sums where its producer took
+// them), on return the gradient w.r.t. xprev; parameter gradients into `grads`
+// next: the GroupNorm(+activation) the returned gradient enters -- norm2 of the block that produced xprev, or norm_input -- or null where
+//     nobody is to take its sums here.  They ride on the block's last store pass: the data-gradient conv of conv1 (dx = dout + dgrad), or
+//     a down block's stride-2 scatter (which also adds `join`), and are handed back in io.sums
 // `join`: a second gradient arriving at the block input (the skip connection of a down block); *joined tells whether it was added here
-// part2 / nblk2: the GroupNorm-backward sums of norm2 were taken by the kernel that produced `dout` (Conv3Args::bst_*)
-// nx: the GroupNorm(+activation) the gradient this block produces (dx, for a block without down-sampling conv) enters NEXT -- norm2 of the
-//     previous block of the level, or norm_input: its backward sums are then taken in the epilogue of the data-gradient conv of conv1
-//     (which also adds the skip gradient) and handed back through nx->part / nx->nblk
-struct GNNext {
-    const float* y; const float* k; float slope;
-    const GNSave* g; const float* gamma; float* dgamma; float* dbeta;     // the GroupNorm the produced gradient enters (tail finalize)
-    FusedSums out;                                                        // filled here: partials (+ coefficients) of that GroupNorm
-};
-static int block_bwd(ru_unet* h, const float* params, float* grads, Arena& A, hipStream_t s, const BlockSave& sv, const float* dout,
-                     const float** dxprev_out, const float* join = nullptr, bool* joined = nullptr, const FusedSums* sums2 = nullptr,
-                     GNNext* nx = nullptr) {
+static int block_bwd(ru_unet* h, const float* params, float* grads, Arena& A, hipStream_t s, const BlockSave& sv, Grad& io,
+                     const NormRef* next = nullptr, const float* join = nullptr, bool* joined = nullptr) {
     if (joined) *joined = false;
+    const Grad in = io;
+    const float* dout = in.d;
+    io = Grad();
     const BlockP& bp = *sv.bp;
     const int N = sv.N, C = sv.C, D = sv.D, H = sv.H, W = sv.W;
     t_hint_c = C;
@@ -969,13 +1031,13 @@ static int block_bwd(ru_unet* h, const float* params, float* grads, Arena& A, hi
     // copies them global -> LDS (the Winograd-z routes for them, RU_WZ=2 / 3 of round 5, were measured slower twice and are retired: profiles/r05_notes.txt)
     const bool ds16 = c16;
     float *coef2 = nullptr, *coef1 = nullptr;
-    int rc = gn_bwd(h, A, s, sv.y2, dout, sv.g2, P(h, params, bp.n2w), kSlope, dy2, G(h, grads, bp.n2w), G(h, grads, bp.n2b), N, C, V, sums2,
-                    fa ? &coef2 : nullptr, ds16);
+    const NormRef n1 = norm1_of(h, params, grads, sv), n2 = norm2_of(h, params, grads, sv);
+    int rc = gn_bwd(h, A, s, n2, in, dy2, V, fa ? &coef2 : nullptr, ds16);
     if (rc) return rc;
     // the published gradients of the 16-channel level have ONE reader each, the data-gradient conv that follows: where conv3_mx_kernel<GRAD> takes the shape they are
     // written in the gradient-operand form of the MX scheme (bf16 main + e4m3 cross terms, a per-voxel exponent; RU_MXG=0 or one-product gradients: the split form)
     const bool g16 = fa && h->grad_products() == 3 && conv3_mxg_usable(h->sw, N, C, C, D, H, W);
-    const GbApply gb2{sv.y2, dout, &sv.g2, coef2, g16};
+    const GbApply gb2{n2, dout, coef2, g16};
     // weight gradients whose dy has no other producer role (no fused apply: dy2 / dy1 are complete when gn_bwd returns) leave the chain:
     // on the side stream they run beside the data-gradient convs and the GroupNorm passes of the chain (a 188-register weight-gradient
     // workgroup leaves a third wave's registers free on its CU: the memory-bound passes fit beside it)
@@ -990,25 +1052,13 @@ static int block_bwd(ru_unet* h, const float* params, float* grads, Arena& A, hi
     // the data-gradient conv of conv2 takes the GroupNorm-backward sums of norm1 in its epilogue (its output IS the gradient w.r.t.
     // LeakyReLU(norm1(y1))): no separate reduce pass over (y1, da1)
     const bool fuse1 = c16 && h->precision == RU_PREC_BF16X3 && conv3_sb_bst_usable(N, C, D, H, W) && (h->fusion & RU_FUSE_GN_BWD_STATS);
-    FusedSums sums1;
-    if (fuse1) {
-        d2.bst_y = sv.y1; d2.bst_k = sv.g1.k; d2.bst_slope = kSlope;                                 // constants written by the forward finalize
-        sums1.nblk = sb_nblk(h, d2);
-        sums1.part = A.alloc((size_t)N * C * sums1.nblk * 2);
-        sums1.coef = A.alloc((size_t)N * C * 3);
-        d2.stat_partials = sums1.part;
-        if (!A.dry && h->tails()) {                      // ... and the conv's last workgroup finalizes them (coefficients, dgamma, dbeta of norm1)
-            fill_bwd_tail(h, d2.fin, sums1, sv.g1, P(h, params, bp.n1w), G(h, grads, bp.n1w), G(h, grads, bp.n1b), N, C, V, 1);
-            sums1.done = true;
-        }
-    }
+    const Grad ga1{da1, take_bwd_sums(h, A, d2, n1, fuse1)};
     t_hint_inst = c16 ? (C == 16 ? INST_CONV16_DGRAD : INST_CONV_DEEP_DGRAD) : -1;
     RU_RUN(conv3_launch(d2, h->sw, s));
     float* dy1 = A.alloc((size_t)N * C * V);
-    rc = gn_bwd(h, A, s, sv.y1, da1, sv.g1, P(h, params, bp.n1w), kSlope, dy1, G(h, grads, bp.n1w), G(h, grads, bp.n1b), N, C, V, fuse1 ? &sums1 : nullptr,
-                fa ? &coef1 : nullptr, ds16);
+    rc = gn_bwd(h, A, s, n1, ga1, dy1, V, fa ? &coef1 : nullptr, ds16);
     if (rc) return rc;
-    const GbApply gb1{sv.y1, da1, &sv.g1, coef1, g16};
+    const GbApply gb1{n1, da1, coef1, g16};
     if (aside) { rc = side_fork(h, s); if (rc) return rc; }
     rc = wgrad3_run(A, sw, h->wgrad_mode(), sv.x, sv.xg, dy1, G(h, grads, bp.conv1), N, C, C, D, H, W, c16, c16, nullptr, ds16, fa ? &gb1 : nullptr);
     if (rc) return rc;
@@ -1017,21 +1067,11 @@ static int block_bwd(ru_unet* h, const float* params, float* grads, Arena& A, hi
     d1.x = dy1; d1.wp = h->pack + bp.pk_d1; d1.y = dx; d1.add = dout; d1.mode = h->precision; d1.products = h->grad_products(); h->set_pack(d1, bp.fk_d1);       // skip path: dx = dout + dgrad(conv1)
     d1.in_c16 = c16; d1.out_c16 = c16; d1.in_s16 = ds16; d1.in_g16 = g16;
     d1.N = N; d1.Cin = C; d1.Cout = C; d1.D = D; d1.H = H; d1.W = W;
-    if (nx) nx->out = FusedSums();
-    if (nx && fuse1 && bp.down < 0) {                   // same shape and kernel choice as d2: dx = dout + dgrad(conv1) IS the gradient entering nx
-        d1.bst_y = nx->y; d1.bst_k = nx->k; d1.bst_slope = nx->slope;
-        nx->out.nblk = sb_nblk(h, d1);
-        nx->out.part = A.alloc((size_t)N * C * nx->out.nblk * 2);
-        nx->out.coef = A.alloc((size_t)N * C * 3);
-        d1.stat_partials = nx->out.part;
-        if (!A.dry && h->tails() && nx->g) {
-            fill_bwd_tail(h, d1.fin, nx->out, *nx->g, nx->gamma, nx->dgamma, nx->dbeta, N, C, V, 1);
-            nx->out.done = true;
-        }
-    }
+    // no down-sampling conv, same shape and kernel choice as d2: dx = dout + dgrad(conv1) IS the gradient entering `next`
+    const FusedSums sums_dx = next ? take_bwd_sums(h, A, d1, *next, fuse1 && bp.down < 0) : FusedSums();
     t_hint_inst = c16 ? (C == 16 ? INST_CONV16_DGRAD : INST_CONV_DEEP_DGRAD) : -1;
     RU_RUN(conv3_launch(d1, h->sw, s));
-    if (bp.down < 0) { *dxprev_out = dx; return RU_OK; }
+    if (bp.down < 0) { io = Grad{dx, sums_dx}; return RU_OK; }
     // down-sampling conv backward (Appendix A2): 1x1 over the space-to-depth view
     const int Cp = bp.cin_down;
     {
@@ -1052,235 +1092,163 @@ static int block_bwd(ru_unet* h, const float* params, float* grads, Arena& A, hi
         c1.y = dxp; c1.s2d = 2; c1.Dc = D; c1.Hc = H; c1.Wc = W;
         c1.add = join;                                           // the skip gradient joins in the store
         if (joined) *joined = true;                              // (decided by structure, not by the pointer: the dry walk has null pointers)
-        if (nx && (h->fusion & RU_FUSE_GN_BWD_STATS) && conv1_16_bst_nblk(c1) > 0) {
-            // the scattered gradient (+ skip gradient) IS what enters nx (norm2 of the last block one level up): its GroupNorm-backward sums
-            // are taken in this store pass -- no reduce pass over (y, d) at the finer level
-            nx->out.nblk = conv1_16_bst_nblk(c1);
-            nx->out.part = A.alloc((size_t)N * Cp * nx->out.nblk * 2);
-            nx->out.coef = A.alloc((size_t)N * Cp * 3);
-            c1.bst_y = nx->y; c1.bst_k = nx->k; c1.bst_slope = nx->slope; c1.stat_partials = nx->out.part;
-        }
+        // the scattered gradient (+ skip gradient) IS what enters `next` (norm2 of the last block one level up): its GroupNorm-backward sums
+        // are taken in this store pass -- no reduce pass over (y, d) at the finer level
+        if (next) io.sums = take_bwd_sums(h, A, c1, *next, (h->fusion & RU_FUSE_GN_BWD_STATS) && conv1_16_bst_nblk(c1) > 0);
         RU_RUN(conv1_16_launch(c1, s));
     } else {
         c1.wT = P(h, params, bp.down); c1.ldw = 8 * Cp;
         RU_RUN(conv1_launch(c1, s));
         RU_RUN(d2s_launch(t, dxp, N, Cp, 2 * D, 2 * H, 2 * W, s));
     }
-    *dxprev_out = dxp;
+    io.d = dxp;
     return RU_OK;
 }
 
+static size_t level_voxels(const ru_unet* h, int i) { return (size_t)(h->D >> i) * (h->H >> i) * (h->W >> i); }
+
+// Head backward: sigmoid backward of the incoming gradient, conv_output's bias and weight gradient, and its data gradient -> out, the
+// gradient w.r.t. the head's input (the output of the last decoder block)
 // crit: the incoming gradient is the criterion's (ru_unet_backward_criterion): formed inside the head's first pass where that pass exists
 // (4-channel head path), else materialised into the workspace first
-static int unet_backward_impl(ru_unet* h, const float* params, const float* dprobs, float* grads, float* dx_in, Arena& A, hipStream_t s,
-                              const CritGradArgs* crit = nullptr) {
-    const int N = h->N, depth = h->depth;
-    std::vector<int> Dl(depth), Hl(depth), Wl(depth);
-    for (int i = 0; i < depth; ++i) { Dl[i] = h->D >> i; Hl[i] = h->H >> i; Wl[i] = h->W >> i; }
-    auto Vl = [&](int i) { return (size_t)Dl[i] * Hl[i] * Wl[i]; };
-    const int C0 = h->ch[0];
-    t_hint_c = C0;
-    RU_RUN(fill_launch(grads, 0.f, h->total, s));     // dead parameters keep zero gradient
-    // head
+static int head_bwd(ru_unet* h, const float* params, const float* dprobs, const CritGradArgs* crit, float* grads, Arena& A, hipStream_t s, Grad& out) {
+    const int N = h->N, C0 = h->ch[0], D = h->D, H = h->H, W = h->W;
+    const size_t V = level_voxels(h, 0);
     const bool c16 = h->c16;
-    const bool head4 = c16 && conv3_sb4_usable(N, h->nout, C0, Dl[0], Hl[0], Wl[0]);      // few channels: one 4-channel copy feeds both head kernels
-    float* d4 = head4 ? A.alloc((size_t)N * 4 * Vl(0)) : nullptr;
+    const bool head4 = c16 && conv3_sb4_usable(N, h->nout, C0, D, H, W);      // few channels: one 4-channel copy feeds both head kernels
+    float* d4 = head4 ? A.alloc((size_t)N * 4 * V) : nullptr;
     // the 4-channel copy feeds the head's weight gradient only in the Cin <= 16 && Cout <= 16 branch of wgrad3_run: a wider first level
     // takes the generic kernel, which reads the class gradient in NCDHW form -- it is then written as well
     const bool need_dlog = !head4 || C0 > 16;
-    float* dlog = need_dlog ? A.alloc((size_t)N * h->nout * Vl(0)) : nullptr;
-    const size_t wsb = bias_grad_workspace_bytes(N, h->nout, Vl(0));
+    float* dlog = need_dlog ? A.alloc((size_t)N * h->nout * V) : nullptr;
+    const size_t wsb = bias_grad_workspace_bytes(N, h->nout, V);
     float* wsp = A.alloc(wsb / sizeof(float) + 1);
     const bool crit_fused = crit && head4 && !need_dlog;
-    float* dpb = (!(head4 && !need_dlog) && (crit || A.dry)) ? A.alloc((size_t)N * h->nout * Vl(0)) : nullptr;      // (the dry walk sizes for either entry point)
+    float* dpb = (!(head4 && !need_dlog) && (crit || A.dry)) ? A.alloc((size_t)N * h->nout * V) : nullptr;      // (the dry walk sizes for either entry point)
     if (crit && !crit_fused) {                                   // no pass to ride on: the criterion's gradient is written out like a caller would
-        RU_RUN(crit_grad_launch(h->probs, crit->target, crit->sums, crit->count, crit->w_dice, crit->w_bce, crit->bgw, crit->priority, dpb, N, h->nout, Vl(0), s));
+        RU_RUN(crit_grad_launch(h->probs, crit->target, crit->sums, crit->count, crit->w_dice, crit->w_bce, crit->bgw, crit->priority, dpb, N, h->nout, V, s));
         dprobs = dpb;
     }
     if (crit_fused) {                                            // criterion gradient, sigmoid backward, 4-channel copy and bias gradient in one pass
-        RU_RUN(head_grad_c4_crit_launch(h->probs, *crit, d4, G(h, grads, h->conv_out_b), N, h->nout, Vl(0), wsp, wsb, s));
+        RU_RUN(head_grad_c4_crit_launch(h->probs, *crit, d4, G(h, grads, h->conv_out_b), N, h->nout, V, wsp, wsb, s));
     } else if (head4) {                                          // sigmoid backward, 4-channel copy and bias gradient in one pass
-        RU_RUN(head_grad_c4_launch(h->probs, dprobs, d4, G(h, grads, h->conv_out_b), N, h->nout, Vl(0), wsp, wsb, s));
-        if (need_dlog) RU_RUN(sigmoid_bwd_launch(h->probs, dprobs, dlog, (size_t)N * h->nout * Vl(0), s));
+        RU_RUN(head_grad_c4_launch(h->probs, dprobs, d4, G(h, grads, h->conv_out_b), N, h->nout, V, wsp, wsb, s));
+        if (need_dlog) RU_RUN(sigmoid_bwd_launch(h->probs, dprobs, dlog, (size_t)N * h->nout * V, s));
     } else {
-        RU_RUN(sigmoid_bwd_launch(h->probs, dprobs, dlog, (size_t)N * h->nout * Vl(0), s));
-        RU_RUN(bias_grad_launch(dlog, G(h, grads, h->conv_out_b), N, h->nout, Vl(0), wsp, wsb, s));
+        RU_RUN(sigmoid_bwd_launch(h->probs, dprobs, dlog, (size_t)N * h->nout * V, s));
+        RU_RUN(bias_grad_launch(dlog, G(h, grads, h->conv_out_b), N, h->nout, V, wsp, wsb, s));
     }
-    int rc = wgrad3_run(A, s, h->wgrad_mode(), h->head_in, nullptr, dlog, G(h, grads, h->conv_out_w), N, C0, h->nout, Dl[0], Hl[0], Wl[0], c16, false,
+    int rc = wgrad3_run(A, s, h->wgrad_mode(), h->head_in, nullptr, dlog, G(h, grads, h->conv_out_w), N, C0, h->nout, D, H, W, c16, false,
                         C0 <= 16 ? d4 : nullptr);
     if (rc) return rc;
-    float* dcur_buf = A.alloc((size_t)N * C0 * Vl(0));
+    float* dcur_buf = A.alloc((size_t)N * C0 * V);
     Conv3Args dh{};
-    dh.x = dlog; dh.wp = h->pack + h->pk_out_d; dh.y = dcur_buf; dh.mode = h->precision; h->set_pack(dh, h->fk_out_d); dh.out_c16 = c16; dh.N = N; dh.Cin = h->nout; dh.Cout = C0; dh.D = Dl[0]; dh.H = Hl[0]; dh.W = Wl[0];
+    dh.x = dlog; dh.wp = h->pack + h->pk_out_d; dh.y = dcur_buf; dh.mode = h->precision; h->set_pack(dh, h->fk_out_d); dh.out_c16 = c16; dh.N = N; dh.Cin = h->nout; dh.Cout = C0; dh.D = D; dh.H = H; dh.W = W;
     if (head4) {                                                 // few input channels: tap-pair kernel on the 4-channel copy
         float* wf4 = A.alloc(conv3_sb4_frag_bytes(C0) / sizeof(float) + 64);
         RU_RUN(conv3_sb4_pack_weights(P(h, params, h->conv_out_w), wf4, C0, h->nout, 1, s));
         dh.x = d4; conv3_set_pack(dh, wf4, PACK_HAS_SB4); dh.in_c4 = 1;
     }
-    // the head's data gradient is the gradient entering norm2 of the last decoder block: its GroupNorm-backward sums are taken here
-    const bool no_bst = !(h->fusion & RU_FUSE_GN_BWD_STATS);
-    const BlockSave* hb = (depth >= 2 && !h->dec_s[0].empty()) ? &h->dec_s[0].back() : nullptr;
-    FusedSums hsums;
-    if (head4 && hb && !no_bst && conv3_sb_bst_usable(N, C0, Dl[0], Hl[0], Wl[0])) {
-        dh.bst_y = hb->y2; dh.bst_k = hb->g2.k; dh.bst_slope = kSlope;
-        hsums.nblk = sb_nblk(h, dh);
-        hsums.part = A.alloc((size_t)N * C0 * hsums.nblk * 2);
-        hsums.coef = A.alloc((size_t)N * C0 * 3);
-        dh.stat_partials = hsums.part;
-        if (!A.dry && h->tails()) {
-            const BlockP& lb = *hb->bp;
-            fill_bwd_tail(h, dh.fin, hsums, hb->g2, P(h, params, lb.n2w), G(h, grads, lb.n2w), G(h, grads, lb.n2b), N, C0, Vl(0), 1);
-            hsums.done = true;
-        }
-    }
+    // the head's data gradient is the gradient entering norm2 of the block that produced its input: its GroupNorm-backward sums are taken
+    // here -- on the 4-channel path only (the statistics epilogue needs a voxel-major or 4-channel input: conv3_sb_launch refuses NCDHW)
+    out.d = dcur_buf;
+    out.sums = take_bwd_sums(h, A, dh, norm2_of(h, params, grads, *h->head_block),
+                             head4 && (h->fusion & RU_FUSE_GN_BWD_STATS) && conv3_sb_bst_usable(N, C0, D, H, W));
     RU_RUN(conv3_launch(dh, h->sw, s));
-    const float* dcur = dcur_buf;
-    std::vector<const float*> dskip(depth - 1, nullptr);
-    FusedSums carry = hsums;                                     // sums of the norm2 the current gradient enters, taken by the kernel that produced it
-    // decoder stages, reverse of execution order (forward ran i = depth-2 .. 0)
-    for (int i = 0; i <= depth - 2; ++i) {
-        for (int j = (int)h->dec_s[i].size() - 1; j >= 0; --j) {
-            const bool fused2 = carry.nblk > 0 && j == (int)h->dec_s[i].size() - 1;
-            const FusedSums sin = carry;
-            rc = block_bwd(h, params, grads, A, s, h->dec_s[i][j], dcur, &dcur, nullptr, nullptr, fused2 ? &sin : nullptr);
-            if (rc) return rc;
-        }
-        carry = FusedSums();
-        const DecSave& ds = h->dstage[i];
-        const int Ci = h->ch[i], Cc = h->ch[i + 1];
-        const size_t V = Vl(i);
-        // decoder_convs1x1[i] over cat([skip, v]) (model.py:424-425)
-        const float* wdec = P(h, params, h->dec1_w[i]);          // [Ci][2Ci]
-        float* gdec = G(h, grads, h->dec1_w[i]);
-        float* dsk = A.alloc((size_t)N * Ci * V);
-        float* dv = A.alloc((size_t)N * Ci * V);
-        float* dpre = A.alloc((size_t)N * Ci * V);
-        // Ci <= 32: the weight-gradient kernel of the concat 1x1 also forms its DATA gradient from the dy tile it has staged (both halves,
-        // LeakyReLU backward of the up-sampled half from the staged v): one pass over dcur / skip / v instead of two
-        const bool dg_fused = c16 && Ci <= 32 && (h->fusion & RU_FUSE_PW_DGRAD);
-        if (c16) {                                               // one pass over dcur for both halves of the (never materialised) concat
-            Wgrad1Args w{};
-            w.x = ds.skip; w.x1 = ds.v; w.C0 = Ci; w.dy = dcur; w.dw = gdec; w.ldw = 2 * Ci; w.c16 = 1; w.defer = red_for(s);
-            w.ws_bytes = wgrad1_workspace_bytes(N, 2 * Ci, Ci, V);
-            w.ws = A.alloc(w.ws_bytes / sizeof(float));
-            w.N = N; w.Cin = 2 * Ci; w.Cout = Ci; w.V = V;
-            if (dg_fused) { w.dg_w = wdec; w.dg_ldw = 2 * Ci; w.dg_y0 = dsk; w.dg_y1 = dpre; w.dg_mask_slope = kSlope; }
-            RU_RUN(wgrad1_launch(w, s));
-        } else {
-            rc = wgrad1_run(A, s, ds.skip, dcur, gdec, 2 * Ci, N, Ci, Ci, V, c16);
-            if (rc) return rc;
-            rc = wgrad1_run(A, s, ds.v, dcur, A.dry ? nullptr : gdec + Ci, 2 * Ci, N, Ci, Ci, V, c16);
-            if (rc) return rc;
-        }
-        Conv1Args a1{};
-        a1.x0 = dcur; a1.C0 = Ci; a1.y = dsk; a1.out_slope = 1.f; a1.N = N; a1.Cout = Ci; a1.V = V;
-        Conv1Args a2 = a1;
-        a2.y = dv;
-        if (dg_fused) {
-            // (written by the weight-gradient launch above)
-        } else if (c16) {                                               // [out][in] = the transposed pack [2Ci][Ci]: rows 0..Ci-1 skip half, Ci.. up half
-            a1.wT = h->pack + h->pk_decT[i]; a1.ldw = Ci;
-            a2.wT = h->pack + h->pk_decT[i] + (size_t)Ci * Ci; a2.ldw = Ci;
-            a2.y = dpre; a2.mask = ds.v; a2.mask_slope = kSlope; // LeakyReLU backward (model.py:422) fused into the store
-            Conv1Args a12 = a1;                                  // both halves in one pass over dcur: [2Ci][Ci] weights, split output
-            a12.Cout = 2 * Ci; a12.Cout0 = Ci; a12.y1 = dpre; a12.mask = ds.v; a12.mask_slope = kSlope;
-            RU_RUN(conv1_16_launch(a12, s));
-        } else {
-            a1.wT = wdec; a1.ldw = 2 * Ci;
-            a2.wT = A.dry ? nullptr : wdec + Ci; a2.ldw = 2 * Ci;
-            RU_RUN(conv1_launch(a1, s));
-            RU_RUN(conv1_launch(a2, s));
-        }
-        dskip[i] = dsk;
-        // LeakyReLU backward from the output v (model.py:422; Appendix A4), then upsampling[i][1] (1x1) and Trilinear
-        if (!c16) RU_RUN(lrelu_bwd_launch(ds.v, dv, dpre, (size_t)N * Ci * V, kSlope, s));
-        Conv1Args a3{};
-        a3.x0 = dpre; a3.C0 = Ci; a3.out_slope = 1.f; a3.N = N; a3.Cout = Cc; a3.V = V;
-        float* dz = A.alloc((size_t)N * Cc * Vl(i + 1));
-        float* du = nullptr;
-        if (c16) {                                               // adjoint of up(conv(z)): everything after the transpose-interpolation is coarse
-            float* dzc = A.alloc((size_t)N * Ci * Vl(i + 1));
-            RU_RUN(up2_bwd16_launch(dpre, dzc, N, Ci, Dl[i + 1], Hl[i + 1], Wl[i + 1], s));
-            rc = wgrad1_run(A, s, ds.z, dzc, G(h, grads, h->up_w[i]), Cc, N, Cc, Ci, Vl(i + 1), true);
-            if (rc) return rc;
-            a3.x0 = dzc; a3.y = dz; a3.V = Vl(i + 1);
-            a3.wT = h->pack + h->pk_upT[i]; a3.ldw = Ci;          // [Cc][Ci] = [out][in]
-            // dz is the gradient entering norm2 of the block that produced z (the last block of the next decoder stage, or of the deepest
-            // encoder level): its GroupNorm-backward sums are taken in this launch's store pass
-            carry = FusedSums();
-            // (a middle decoder stage with zero blocks: z is then a 1x1 output, not a block's -- no norm2 whose sums could ride here; the
-            // deepest encoder level's y2 is a tensor of ANOTHER level and must not be read as bst_y)
-            const BlockSave* zb = (i + 1 <= depth - 2) ? (!h->dec_s[i + 1].empty() ? &h->dec_s[i + 1].back() : nullptr)
-                                  : (!h->enc_s[depth - 2].empty() ? &h->enc_s[depth - 2].back() : nullptr);
-            if (zb && (zb->g2.k || A.dry) && (h->fusion & RU_FUSE_GN_BWD_STATS) && conv1_16_bst_nblk(a3) > 0) {
-                carry.nblk = conv1_16_bst_nblk(a3);
-                carry.part = A.alloc((size_t)N * Cc * carry.nblk * 2);
-                carry.coef = A.alloc((size_t)N * Cc * 3);
-                a3.bst_y = zb->y2; a3.bst_k = zb->g2.k; a3.bst_slope = kSlope; a3.stat_partials = carry.part;
-            }
-            RU_RUN(conv1_16_launch(a3, s));
-        } else {
-            rc = wgrad1_run(A, s, ds.u, dpre, G(h, grads, h->up_w[i]), Cc, N, Cc, Ci, V, false);
-            if (rc) return rc;
-            du = A.alloc((size_t)N * Cc * V);
-            a3.y = du;
-            a3.wT = P(h, params, h->up_w[i]); a3.ldw = Cc;
-            RU_RUN(conv1_launch(a3, s));
-            RU_RUN(up2_bwd_launch(du, dz, N, Cc, Dl[i + 1], Hl[i + 1], Wl[i + 1], s));
-        }
-        dcur = dz;
-    }
-    // encoder levels, deepest first; the skip gradient joins at each level's input
-    for (int i = depth - 2; i >= 0; --i) {
-        bool joined = false;
-        FusedSums snext = carry;                                 // sums of the NEXT block's norm2, taken by the kernel that produced its incoming gradient
-        carry = FusedSums();
-        for (int j = (int)h->enc_s[i].size() - 1; j >= 0; --j) {
-            GNNext nx{};
-            nx.slope = kSlope;
-            // the gradient this block produces enters norm2 of the block before it -- for the level's first (down-sampling) block that is the
-            // last block one level up (its stride-2 transpose scatters into that level and adds the skip gradient there)
-            const BlockSave* pb = j >= 1 ? &h->enc_s[i][j - 1] : (i >= 1 ? (h->enc_s[i - 1].empty() ? nullptr : &h->enc_s[i - 1].back())
-                                                                        : (h->first_s.empty() ? nullptr : &h->first_s.back()));
-            if (pb && pb->g2.k) {
-                nx.y = pb->y2; nx.k = pb->g2.k; nx.g = &pb->g2;
-                nx.gamma = P(h, params, pb->bp->n2w); nx.dgamma = G(h, grads, pb->bp->n2w); nx.dbeta = G(h, grads, pb->bp->n2b);
-            }
-            const FusedSums sin = snext;
-            rc = block_bwd(h, params, grads, A, s, h->enc_s[i][j], dcur, &dcur, j == 0 ? dskip[i] : nullptr, j == 0 ? &joined : nullptr, sin.nblk > 0 ? &sin : nullptr,
-                           (pb && (nx.y || A.dry)) ? &nx : nullptr);
-            if (rc) return rc;
-            snext = nx.out;
-        }
-        carry = snext;                                           // (from the level's down-sampling block: the sums of the finer level's last norm2)
-        if (!joined) {
-            float* sum = A.alloc((size_t)N * h->ch[i] * Vl(i));
-            RU_RUN(add_launch(dcur, dskip[i], sum, (size_t)N * h->ch[i] * Vl(i), s));
-            dcur = sum;
-            carry = FusedSums();                                 // (the sums were those of the gradient before the skip gradient joined)
-        }
-    }
-    FusedSums sfirst = carry;
-    for (int j = (int)h->first_s.size() - 1; j >= 0; --j) {
-        // the gradient a first-level block produces enters norm2 of the block before it, or (j = 0) norm_input (no activation: slope 1)
-        GNNext nx{};
-        nx.slope = j >= 1 ? kSlope : 1.0f;
-        if (j >= 1) {
-            const BlockSave& pb = h->first_s[j - 1];
-            nx.y = pb.y2; nx.k = pb.g2.k; nx.g = &pb.g2;
-            nx.gamma = P(h, params, pb.bp->n2w); nx.dgamma = G(h, grads, pb.bp->n2w); nx.dbeta = G(h, grads, pb.bp->n2b);
-        } else {
-            nx.y = h->y0; nx.k = h->g0.k; nx.g = &h->g0;
-            nx.gamma = P(h, params, h->nin_w); nx.dgamma = G(h, grads, h->nin_w); nx.dbeta = G(h, grads, h->nin_b);
-        }
-        const FusedSums sin = sfirst;
-        rc = block_bwd(h, params, grads, A, s, h->first_s[j], dcur, &dcur, nullptr, nullptr, sin.nblk > 0 ? &sin : nullptr, (nx.k || A.dry) ? &nx : nullptr);
+    return RU_OK;
+}
+
+// One decoder stage below its blocks (model.py:420-425), backward: io = the gradient w.r.t. the concat 1x1's output on entry, w.r.t. the
+// coarse input z on return; *dskip = the gradient w.r.t. the skip tensor (it joins the encoder's gradient at level i)
+static int dec_stage_bwd(ru_unet* h, const float* params, float* grads, Arena& A, hipStream_t s, const DecSave& ds, Grad& io, const float** dskip) {
+    const int i = ds.level, N = h->N;
+    const int Dc = h->D >> (i + 1), Hc = h->H >> (i + 1), Wc = h->W >> (i + 1);       // the coarse grid of z
+    const bool c16 = h->c16;
+    const float* dcur = io.d;
+    io = Grad();
+    int rc = RU_OK;
+    const int Ci = h->ch[i], Cc = h->ch[i + 1];
+    const size_t V = level_voxels(h, i), Vc = level_voxels(h, i + 1);
+    // decoder_convs1x1[i] over cat([skip, v]) (model.py:424-425)
+    const float* wdec = P(h, params, h->dec1_w[i]);          // [Ci][2Ci]
+    float* gdec = G(h, grads, h->dec1_w[i]);
+    float* dsk = A.alloc((size_t)N * Ci * V);
+    float* dv = A.alloc((size_t)N * Ci * V);
+    float* dpre = A.alloc((size_t)N * Ci * V);
+    // Ci <= 32: the weight-gradient kernel of the concat 1x1 also forms its DATA gradient from the dy tile it has staged (both halves,
+    // LeakyReLU backward of the up-sampled half from the staged v): one pass over dcur / skip / v instead of two
+    const bool dg_fused = c16 && Ci <= 32 && (h->fusion & RU_FUSE_PW_DGRAD);
+    if (c16) {                                               // one pass over dcur for both halves of the (never materialised) concat
+        Wgrad1Args w{};
+        w.x = ds.skip; w.x1 = ds.v; w.C0 = Ci; w.dy = dcur; w.dw = gdec; w.ldw = 2 * Ci; w.c16 = 1; w.defer = red_for(s);
+        w.ws_bytes = wgrad1_workspace_bytes(N, 2 * Ci, Ci, V);
+        w.ws = A.alloc(w.ws_bytes / sizeof(float));
+        w.N = N; w.Cin = 2 * Ci; w.Cout = Ci; w.V = V;
+        if (dg_fused) { w.dg_w = wdec; w.dg_ldw = 2 * Ci; w.dg_y0 = dsk; w.dg_y1 = dpre; w.dg_mask_slope = kSlope; }
+        RU_RUN(wgrad1_launch(w, s));
+    } else {
+        rc = wgrad1_run(A, s, ds.skip, dcur, gdec, 2 * Ci, N, Ci, Ci, V, c16);
         if (rc) return rc;
-        sfirst = nx.out;
+        rc = wgrad1_run(A, s, ds.v, dcur, A.dry ? nullptr : gdec + Ci, 2 * Ci, N, Ci, Ci, V, c16);
+        if (rc) return rc;
     }
-    // norm_input (no activation: slope 1) and conv_input
+    Conv1Args a1{};
+    a1.x0 = dcur; a1.C0 = Ci; a1.y = dsk; a1.out_slope = 1.f; a1.N = N; a1.Cout = Ci; a1.V = V;
+    Conv1Args a2 = a1;
+    a2.y = dv;
+    if (dg_fused) {
+        // (written by the weight-gradient launch above)
+    } else if (c16) {                                               // [out][in] = the transposed pack [2Ci][Ci]: rows 0..Ci-1 skip half, Ci.. up half
+        a1.wT = h->pack + h->pk_decT[i]; a1.ldw = Ci;
+        a2.wT = h->pack + h->pk_decT[i] + (size_t)Ci * Ci; a2.ldw = Ci;
+        a2.y = dpre; a2.mask = ds.v; a2.mask_slope = kSlope; // LeakyReLU backward (model.py:422) fused into the store
+        Conv1Args a12 = a1;                                  // both halves in one pass over dcur: [2Ci][Ci] weights, split output
+        a12.Cout = 2 * Ci; a12.Cout0 = Ci; a12.y1 = dpre; a12.mask = ds.v; a12.mask_slope = kSlope;
+        RU_RUN(conv1_16_launch(a12, s));
+    } else {
+        a1.wT = wdec; a1.ldw = 2 * Ci;
+        a2.wT = A.dry ? nullptr : wdec + Ci; a2.ldw = 2 * Ci;
+        RU_RUN(conv1_launch(a1, s));
+        RU_RUN(conv1_launch(a2, s));
+    }
+    *dskip = dsk;
+    // LeakyReLU backward from the output v (model.py:422; Appendix A4), then upsampling[i][1] (1x1) and Trilinear
+    if (!c16) RU_RUN(lrelu_bwd_launch(ds.v, dv, dpre, (size_t)N * Ci * V, kSlope, s));
+    Conv1Args a3{};
+    a3.x0 = dpre; a3.C0 = Ci; a3.out_slope = 1.f; a3.N = N; a3.Cout = Cc; a3.V = V;
+    float* dz = A.alloc((size_t)N * Cc * Vc);
+    float* du = nullptr;
+    if (c16) {                                               // adjoint of up(conv(z)): everything after the transpose-interpolation is coarse
+        float* dzc = A.alloc((size_t)N * Ci * Vc);
+        RU_RUN(up2_bwd16_launch(dpre, dzc, N, Ci, Dc, Hc, Wc, s));
+        rc = wgrad1_run(A, s, ds.z, dzc, G(h, grads, h->up_w[i]), Cc, N, Cc, Ci, Vc, true);
+        if (rc) return rc;
+        a3.x0 = dzc; a3.y = dz; a3.V = Vc;
+        a3.wT = h->pack + h->pk_upT[i]; a3.ldw = Ci;          // [Cc][Ci] = [out][in]
+        // dz is the gradient entering norm2 of the block that produced z (the last block of the next decoder stage, or of the deepest
+        // encoder level): its GroupNorm-backward sums are taken in this launch's store pass
+        io.sums = take_bwd_sums(h, A, a3, norm2_of(h, params, grads, *ds.z_block), (h->fusion & RU_FUSE_GN_BWD_STATS) && conv1_16_bst_nblk(a3) > 0);
+        RU_RUN(conv1_16_launch(a3, s));
+    } else {
+        rc = wgrad1_run(A, s, ds.u, dpre, G(h, grads, h->up_w[i]), Cc, N, Cc, Ci, V, false);
+        if (rc) return rc;
+        du = A.alloc((size_t)N * Cc * V);
+        a3.y = du;
+        a3.wT = P(h, params, h->up_w[i]); a3.ldw = Cc;
+        RU_RUN(conv1_launch(a3, s));
+        RU_RUN(up2_bwd_launch(du, dz, N, Cc, Dc, Hc, Wc, s));
+    }
+    io.d = dz;
+    return RU_OK;
+}
+
+// Stem backward: norm_input and conv_input's weight gradient from `in`, the gradient w.r.t. the first block's input; dx_in: d/d(input) as well
+static int stem_bwd(ru_unet* h, const float* params, float* grads, float* dx_in, Arena& A, hipStream_t s, const Grad& in) {
+    const int N = h->N, C0 = h->ch[0], D = h->D, H = h->H, W = h->W;
+    const size_t V = level_voxels(h, 0);
+    const bool c16 = h->c16;
     t_hint_c = C0;
-    float* dy0 = A.alloc((size_t)N * C0 * Vl(0));
+    float* dy0 = A.alloc((size_t)N * C0 * V);
     // voxel-major engine, no d/d(input) wanted: the gradient w.r.t. the stem conv's output is consumed by the stem's weight gradient alone, so
     // the GroupNorm-backward apply of norm_input is computed in that kernel's staging (wgrad3_tz<1,1,3>) and never written
     // (only the Cin <= 16 && Cout <= 16 branch of wgrad3_run computes the apply while staging: a wider stem takes the generic
@@ -1290,11 +1258,11 @@ static int unet_backward_impl(ru_unet* h, const float* params, const float* dpro
     // a stem wider than 16 channels: its weight gradient is the generic mixed-layout kernel (x NCDHW, dy voxel-major float32), which does
     // not read the split form
     const bool split0 = c16 && C0 <= 16;
-    rc = gn_bwd(h, A, s, h->y0, dcur, h->g0, P(h, params, h->nin_w), 1.0f, dy0, G(h, grads, h->nin_w), G(h, grads, h->nin_b), N, C0, Vl(0), sfirst.nblk > 0 ? &sfirst : nullptr,
-                fuse0 ? &coef0 : nullptr, split0);
+    const NormRef n0 = norm_input_of(h, params, grads);
+    int rc = gn_bwd(h, A, s, n0, in, dy0, V, fuse0 ? &coef0 : nullptr, split0);
     if (rc) return rc;
-    const GbApply gb0{h->y0, dcur, &h->g0, coef0};
-    rc = wgrad3_run(A, s, h->wgrad_mode(), h->x_in, nullptr, dy0, G(h, grads, h->conv_in), N, kInCh, C0, Dl[0], Hl[0], Wl[0], false, c16, C0 <= 16 ? h->x_in4 : nullptr, split0,
+    const GbApply gb0{n0, in.d, coef0};
+    rc = wgrad3_run(A, s, h->wgrad_mode(), h->x_in, nullptr, dy0, G(h, grads, h->conv_in), N, kInCh, C0, D, H, W, false, c16, C0 <= 16 ? h->x_in4 : nullptr, split0,
                     fuse0 ? &gb0 : nullptr);
     if (rc) return rc;
     if (dx_in) {
@@ -1309,9 +1277,59 @@ static int unet_backward_impl(ru_unet* h, const float* params, const float* dpro
         } else {
             RU_RUN(conv3_pack_weights(P(h, params, h->conv_in), wpd, kInCh, C0, 1, s));
         }
-        di.x = dy0; di.wp = wpd; di.y = dx_in; di.N = N; di.Cin = C0; di.Cout = kInCh; di.D = Dl[0]; di.H = Hl[0]; di.W = Wl[0];
+        di.x = dy0; di.wp = wpd; di.y = dx_in; di.N = N; di.Cin = C0; di.Cout = kInCh; di.D = D; di.H = H; di.W = W;
         RU_RUN(conv3_launch(di, h->sw, s));
     }
+    return RU_OK;
+}
+
+// The backward walk: the head, then the blocks and stages in reverse of the forward's order, one Grad handed from each to the next
+static int unet_backward_impl(ru_unet* h, const float* params, const float* dprobs, float* grads, float* dx_in, Arena& A, hipStream_t s,
+                              const CritGradArgs* crit = nullptr) {
+    const int N = h->N, depth = h->depth;
+    t_hint_c = h->ch[0];
+    RU_RUN(fill_launch(grads, 0.f, h->total, s));     // dead parameters keep zero gradient
+    Grad g;
+    int rc = head_bwd(h, params, dprobs, crit, grads, A, s, g);
+    if (rc) return rc;
+    std::vector<const float*> dskip(depth - 1, nullptr);
+    // decoder stages, reverse of execution order (forward ran i = depth-2 .. 0)
+    // A decoder block hands no sums to the block before it in its stage (the encoder's and the first level's blocks do, below): norm2 of
+    // that block takes them in its own reduce pass over (y2, d).  Letting them ride would change launches and summation order.
+    const NormRef* const dec_block_rides_on = nullptr;
+    for (int i = 0; i <= depth - 2; ++i) {
+        for (int j = (int)h->dec_s[i].size() - 1; j >= 0; --j) {
+            rc = block_bwd(h, params, grads, A, s, h->dec_s[i][j], g, dec_block_rides_on);
+            if (rc) return rc;
+        }
+        rc = dec_stage_bwd(h, params, grads, A, s, h->dstage[i], g, &dskip[i]);
+        if (rc) return rc;
+    }
+    // the gradient an encoder or first-level block produces enters norm2 of the block that fed it -- for a level's first (down-sampling) block the
+    // last block one level up (its stride-2 transpose scatters into that level and adds the skip gradient there) -- or, on the stem's output, norm_input
+    auto fed_by = [&](const BlockSave& b) { return b.xprev_block ? norm2_of(h, params, grads, *b.xprev_block) : norm_input_of(h, params, grads); };
+    // encoder levels, deepest first; the skip gradient joins at each level's input
+    for (int i = depth - 2; i >= 0; --i) {
+        bool joined = false;
+        for (int j = (int)h->enc_s[i].size() - 1; j >= 0; --j) {
+            const NormRef prev = fed_by(h->enc_s[i][j]);
+            rc = block_bwd(h, params, grads, A, s, h->enc_s[i][j], g, &prev, j == 0 ? dskip[i] : nullptr, j == 0 ? &joined : nullptr);
+            if (rc) return rc;
+        }
+        if (!joined) {
+            const size_t n = (size_t)N * h->ch[i] * level_voxels(h, i);
+            float* sum = A.alloc(n);
+            RU_RUN(add_launch(g.d, dskip[i], sum, n, s));
+            g = Grad{sum};                                       // sums taken before something was added to the gradient are void: the bare gradient goes on
+        }
+    }
+    for (int j = (int)h->first_s.size() - 1; j >= 0; --j) {
+        const NormRef prev = fed_by(h->first_s[j]);
+        rc = block_bwd(h, params, grads, A, s, h->first_s[j], g, &prev);
+        if (rc) return rc;
+    }
+    rc = stem_bwd(h, params, grads, dx_in, A, s, g);
+    if (rc) return rc;
     if (t_red && !t_red->side.e.empty()) RU_RUN(wgrad_reduce_flush(t_red->side, h->side));   // (stream order on the side stream: behind its weight-gradient kernels)
     if (!A.dry) { rc = side_join(h, s); if (rc) return rc; }     // the caller's stream sees every gradient
     if (t_red && !t_red->main.e.empty()) RU_RUN(wgrad_reduce_flush(t_red->main, s));         // every other queued partial-sum reduction, one launch

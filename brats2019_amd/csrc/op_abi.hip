@@ -574,7 +574,7 @@ extern "C" int ru_gn_bwd_l(const float* x, const float* dact, const float* gamma
     return walk_result(A, gn_bwd_l_walk(x, dact, gamma, scale, shift, mean, rstd, slope, dx, dgamma, dbeta, coef_out, partials_out, N, C, V, G, flags, A, (hipStream_t)stream));
 }
 
-// ====================================================================== the head of the backward pass, one route of unet_backward_impl at a time
+// ====================================================================== the head of the backward pass, one route of the engine's head_bwd at a time
 // route 0: head_grad_c4_launch (and sigmoid_bwd_launch where dlog is wanted, as the engine adds it for a wide first level); 1: head_grad_c4_crit_launch
 // (`cg` is the criterion, dp is not read); 2: sigmoid_bwd_launch then bias_grad_launch (any C and V; d4 is not written).  The launchers' own checks refuse.
 static int head_grad_l_walk(const float* p, const float* dp, const CritGradArgs& cg, float* d4, float* db, float* dlog, int N, int C, size_t V, int route,

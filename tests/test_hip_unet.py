@@ -607,24 +607,35 @@ def test_side_stream_weight_gradients_are_bit_identical():
 WIDE = dict(depth=3, encoder_layers=[1, 1, 2], decoder_layers=[1, 1, 1], number_of_channels=[32, 64, 128], number_of_outputs=3)
 
 
-def test_wide_stem_voxel_major_training_fused_equals_unfused_and_oracle():
-    """A voxel-major (C16) configuration whose FIRST channel count is above 16 (number_of_channels=[32,64,128]; bf16x3 is its default):
+# several blocks on the first level and in the decoder stages: a block's gradient enters norm2 of the block BEFORE it on the first level, and
+# the head's / the up-path's gradient enters norm2 of the LAST of several decoder blocks
+CHAIN = dict(depth=3, encoder_layers=[2, 2, 2], decoder_layers=[2, 2, 1], number_of_channels=[16, 32, 64], number_of_outputs=3)
+
+
+@pytest.mark.parametrize("cfg,n,dhw", [(WIDE, 2, (32, 32, 32)), (CHAIN, 2, (24, 40, 48))], ids=["wide", "chain"])
+def test_wide_stem_voxel_major_training_fused_equals_unfused_and_oracle(cfg, n, dhw):
+    """wide: a voxel-major (C16) configuration whose FIRST channel count is above 16 (number_of_channels=[32,64,128]; bf16x3 is its default):
     the stem weight gradient then takes the generic kernel, which has no fused GroupNorm-backward apply -- the gradient w.r.t. the stem
     output must be WRITTEN for it (round-2 advisor finding: with the apply fusion on it was not).  Fusions on and off must agree, and both
-    must agree with the CPU oracle elementwise (relative L2 of the difference)."""
+    must agree with the CPU oracle elementwise (relative L2 of the difference).
+    chain: the same bars on a configuration with two blocks on the first level and in two decoder stages (who feeds which GroupNorm in the
+    backward is then not "the only block of the level"), and the tail finalize on top of every other fusion against the finalize launches at
+    the bars of test_tail_finalize_and_batched_reduce_match_the_separate_launches."""
     from brats2019_amd import model as M
-    assert M.default_precision(WIDE["number_of_channels"]) == "bf16x3"
-    n, dhw, seed = 2, (32, 32, 32), 5
+    assert M.default_precision(cfg["number_of_channels"]) == "bf16x3"
+    seed = 5
+    tails = (True, True, True, True, True, True)
     res = {}
-    for fusion in ((True, True), (False, False)):
-        net, probs, loss, vals = run_train_step(WIDE, n, dhw, seed, "bf16x3", fusion)
+    for fusion in ((True, True), (False, False)) + ((tails,) if cfg is CHAIN else ()):
+        net, probs, loss, vals = run_train_step(cfg, n, dhw, seed, "bf16x3", fusion)
         assert net._get_engine().precision == "bf16x3"
         res[fusion] = (probs.clone(), float(loss), {k: q.grad.detach().clone() for k, q in net.named_parameters() if q.grad is not None})
     pa, la, ga = res[(True, True)]
     pb, lb, gb = res[(False, False)]
     assert torch.equal(pa, pb) and la == lb
-    params = O.make_params(seed, **WIDE)
-    ref_p, ref_loss, ref_grads = O.forward_backward(params, O.make_input(n, *dhw, seed=seed), O.make_target(n, *dhw, seed=seed), **WIDE)
+    params = O.make_params(seed, **cfg)
+    ref_p, ref_loss, ref_grads = O.forward_backward(params, O.make_input(n, *dhw, seed=seed), O.make_target(n, *dhw, seed=seed), **cfg)
+    assert sum(v is None for v in ref_grads.values()) == 7           # the never-executed deepest decoder stage: one block and one 1x1
     assert np.abs(pa.cpu().numpy() - ref_p).max() <= 2e-4
     assert abs(la - ref_loss) < 5e-5
     for k in ga:
@@ -634,6 +645,12 @@ def test_wide_stem_voxel_major_training_fused_equals_unfused_and_oracle():
         for tag, gg in (("fused", ga), ("unfused", gb)):
             rel = float((gg[k].double().cpu() - r).norm() / (r.norm() + 1e-30))
             assert rel < 1e-2, (tag, k, rel)
+    if tails in res:
+        pt, _, gt = res[tails]
+        dp = float((pt - pa).abs().max())
+        worst = max(float(torch.linalg.vector_norm(gt[k].double() - ga[k].double()) / torch.linalg.vector_norm(ga[k].double())) for k in ga)
+        print("chain, tail finalize vs finalize launches: max |dp| %.2e, worst relative L2 gradient difference %.2e" % (dp, worst))
+        assert dp <= 1e-6 and worst <= 1e-4, (dp, worst)
 
 
 def test_default_precision_is_bf16x3_for_the_shipped_configuration():
