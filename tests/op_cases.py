@@ -155,4 +155,22 @@ def cases():
     add("wgrad3_l_deferred", True, lambda: as_list(ops.wgrad3_fused(x3, dy3, deferred=True).dw))
     add("wgrad3_l_xc4", True, lambda: as_list(ops.wgrad3_fused(xs, dy3, x_c4=True, dw_cin=4).dw))
     add("wgrad3_l_dyc4", True, lambda: as_list(ops.wgrad3_fused(x3, dys, dy_c4=True, dw_cout=3).dw))
+
+    # ---- ru_criterion_sums, ru_zscore_stats, ru_case_stats at the smallest two-tile shapes of tests/test_scalar_passes_host.py: 2 x 3 classes at V = 8192 + 1,
+    # 4 channels at V = 16384 + 1, a 40 x 40 x 21 box.  The criterion refuses a short workspace with RU_ENOMEM; the two statistics entries refuse it too, but as a bad
+    # argument (RU_EINVAL, "... workspace too small"), so they have no short case
+    from brats2019_amd import _lib as L
+    pc, gc = torch.sigmoid(_rand(2, 3, 8193, seed=130, scale=3.0)), (_rand(2, 3, 8193, seed=131) > 0.5).float()
+    add("criterion_sums", True, lambda: as_list(ops.criterion_sums(pc, gc)))
+    xz = _rand(4, 16385, seed=132, scale=100.0)
+
+    def zscore():
+        lib = L.load()
+        stats = torch.empty((4, 3), dtype=torch.float64, device=xz.device)
+        ws = L.workspace(lib.ru_zscore_workspace_bytes(4, 16385), xz.device)
+        L.check(lib.ru_zscore_stats(L.f32(xz), L.ptr(stats), 4, 16385, L.ptr(ws), ws.numel(), L.stream()), "ru_zscore_stats")
+        return [stats]
+    add("zscore_stats", False, zscore)                  # (brats2019_amd.dataloader.zscore_stats returns host numbers: the entry is called as it calls it)
+    xb = _rand(4, 42, 41, 23, seed=133, scale=100.0)
+    add("case_stats", False, lambda: as_list(ops.case_stats(xb, (1, 1, 2), (40, 40, 21))))
     return out
