@@ -70,6 +70,11 @@ SIGNATURES = {
     "ru_boundary_grad": (_i, [_vp, _sz, _f, _vp, _vp, _vp]),
     "ru_hddt_sum": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _vp, _vp, _sz, _vp]),
     "ru_hddt_grad": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _vp, _vp, _vp]),
+    "ru_lesion_loss_workspace_bytes": (_sz, [_i] * 5),
+    "ru_lesion_loss_state_bytes": (_sz, [_i] * 5 + [C.POINTER(_sz)]),
+    "ru_lesion_loss_forward": (_i, [_vp, _vp] + [_i] * 6 + [C.c_longlong, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ru_lesion_loss_forward_upto": (_i, [_vp, _vp] + [_i] * 6 + [C.c_longlong, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
+    "ru_lesion_loss_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _vp, _vp] + [_i] * 5 + [_vp]),
     "ru_adam_amsgrad_step": (_i, [_vp] * 5 + [_sz] + [_f] * 5 + [_i, _vp]),
     "ru_adam_step": (_i, [_vp] * 5 + [_sz] + [_f] * 5 + [_i, _vp]),
     "ru_gradnorm_slots": (_sz, [_sz]),

@@ -3,9 +3,10 @@
 //
 //   ls_clear_kernel      : clears the outputs, the per-lesion counters and the pair table.
 //   ls_pack_kernel<KIND> : the masks P and G, and the invalid label voxels (mask_bits.hpp, mask_pack_rows).
-//   ls_dilate_kernel     : one thread per word, one launch per iteration, ping-pong between two planes: the rows (dz, dy) = (0, 0) and
-//                          the four face rows contribute themselves and their x +- 1 shifts (carries cross word boundaries), the four
-//                          diagonal rows themselves only -- the 18-neighbour structure.  Z = Dil(G).
+//   ls_dilate_kernel     : (mask_dilate.hpp, shared with lesion_loss.hip) one thread per word, one launch per iteration, ping-pong
+//                          between two planes: the rows (dz, dy) = (0, 0) and the four face rows contribute themselves and their x +- 1
+//                          shifts (carries cross word boundaries), the four diagonal rows themselves only -- the 18-neighbour
+//                          structure.  Z = Dil(G).
 //   cc_*_kernel<LsPlanes>: the union-find labelling of cc_unionfind.hpp (init, compress, merge, compress) from bit planes, for Z and P of
 //                          every (n, k) in one launch.  Roots are smallest indices.
 //   ls_count_kernel      : the roots of Z are appended to a list; |Q_j| at every root of P (cc_count_members).
@@ -25,6 +26,7 @@
 #include "cc_unionfind.hpp"
 #include "surface_packed.hpp"
 #include "mask_bits.hpp"
+#include "mask_dilate.hpp"
 
 #include <limits.h>
 
@@ -98,32 +100,6 @@ __global__ __launch_bounds__(256) void ls_pack_kernel(const void* __restrict__ p
     u64 c[4];
     mask_pack_rows<KIND, false>(pv, gv, C, K, s, bits, c);
     if ((threadIdx.x & 63) == 0 && c[3]) atomicAdd(counts + (size_t)blockIdx.y * RU_LESION_COUNTS + RU_LESION_C_INVALID, c[3]);
-}
-
-__device__ __forceinline__ u64 ls_word(const u64* __restrict__ b, const MaskGeom& s, int d, int h, int c) {
-    return (d < 0 || d >= s.D || h < 0 || h >= s.H || c < 0 || c >= s.WW) ? 0ull : b[((size_t)d * s.H + h) * s.WW + c];
-}
-// word c of row (d, h) or-ed with its shifts by one voxel along x, the carries taken from the neighbouring words
-__device__ __forceinline__ u64 ls_row3(const u64* __restrict__ b, const MaskGeom& s, int d, int h, int c) {
-    if (d < 0 || d >= s.D || h < 0 || h >= s.H) return 0ull;
-    const u64 m = ls_word(b, s, d, h, c), prev = ls_word(b, s, d, h, c - 1), next = ls_word(b, s, d, h, c + 1);
-    return m | (m << 1) | (prev >> 63) | (m >> 1) | (next << 63);
-}
-
-// grid (blocks, N*K): one iteration, plane `src` -> plane `dst` of every (n, k)
-__global__ __launch_bounds__(256) void ls_dilate_kernel(MaskGeom s, u64* __restrict__ bits, int src, int dst) {
-    const int nk = blockIdx.y;
-    const u64* __restrict__ a = bits + ((size_t)nk * 4 + src) * s.words;
-    u64* __restrict__ o = bits + ((size_t)nk * 4 + dst) * s.words;
-    const u64 last = (s.W & 63) ? (1ull << (s.W & 63)) - 1 : ~0ull;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < s.words; i += (size_t)gridDim.x * 256) {
-        const int c = (int)(i % s.WW);
-        const size_t r = i / s.WW;
-        const int h = (int)(r % s.H), d = (int)(r / s.H);
-        u64 m = ls_row3(a, s, d, h, c) | ls_row3(a, s, d - 1, h, c) | ls_row3(a, s, d + 1, h, c) | ls_row3(a, s, d, h - 1, c) | ls_row3(a, s, d, h + 1, c);
-        m |= ls_word(a, s, d - 1, h - 1, c) | ls_word(a, s, d - 1, h + 1, c) | ls_word(a, s, d + 1, h - 1, c) | ls_word(a, s, d + 1, h + 1, c);
-        o[i] = c == s.WW - 1 ? m & last : m;
-    }
 }
 
 // the labelling's foreground: block (., nk, z) labels plane `zplane` (Z) of (n, k) = nk for z = 0, plane 0 (P) for z = 1

@@ -20,6 +20,12 @@ INTEGRATION.md), each its own autograd function, with float64 host restatements 
 BoundaryLoss and HausdorffDTLoss (csrc/boundary.hip; definitions in INTEGRATION.md) weigh each voxel by its exact Euclidean distance to the
 boundary of the target (and, for the latter, of the thresholded prediction); the maps are made on the device in every step
 (ops.signed_sqdist).  Host restatements: signed_sqdist_host, boundary_host, hddt_host.
+
+LesionWiseDiceLoss (csrc/lesion_loss.hip; definition in INTEGRATION.md) is the training-side counterpart of ops.lesion_metrics: the blob
+loss on Dice_loss_joint's Dice, one Dice per ground-truth lesion over the background and that lesion alone, averaged over lesions and then
+over the (sample, channel) pairs that hold one.  The target is labelled on the device in every step (bit-parallel dilation, union-find
+labelling, 64-bit fixed-point per-lesion sums: no float atomics, identical bytes from identical inputs).  Host restatement with scipy's
+labelling: lesion_dice_host (lesion_labels_host).
 """
 from __future__ import annotations
 
@@ -536,6 +542,59 @@ class HausdorffDTLoss(_LossBase):
         return _HausdorffDTFn.apply(x[self.index], y[self.index], float(self.alpha), float(self.priority), self.data_parallel)
 
 
+# ------------------------------------------------------------------ lesion-wise Dice loss (csrc/lesion_loss.hip)
+# The target is labelled on the device in every step, so the lesions follow zoom, rotation and elastic augmentation.  Like the classes above
+# it always writes d(loss)/d(pred) and is not in _TERM_CLASSES: a list that contains it is evaluated as written.
+class _LesionDiceFn(torch.autograd.Function):
+    """Labelling, one sum pass and one evaluate launch; one all-reduce of two float64 numbers (the sum of the pair losses and the number of
+    pairs with a kept lesion); in backward one gradient pass that reads the global pair count on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, priority, dilation, min_volume, group):
+        totals, _, labels, state = ops.lesion_loss_forward(pred, gt, dilation, min_volume)
+        _all_reduce_sums(totals, group)
+        ctx.save_for_backward(pred, gt, labels, state, totals)
+        ctx.priority = priority
+        value = torch.where(totals[1] > 0, totals[0] / totals[1].clamp(min=1.0), torch.zeros_like(totals[0]))
+        return (value * priority).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, gout):
+        pred, gt, labels, state, totals = ctx.saved_tensors
+        return ops.lesion_loss_grad(pred, gt, labels, state, totals, ctx.priority, gout).to(pred.dtype), None, None, None, None, None
+
+
+class LesionWiseDiceLoss(_LossBase):
+    """priority * the mean over the (sample, channel) pairs that hold a kept lesion of 1 - mean_i Dice_i: the blob loss (Kofler et al. 2022)
+    on Dice_loss_joint's Dice.  The lesions of a pair are the parts of the target mask G = g > 0.5 inside each 26-connected component of G
+    dilated `dilation` times by the 18-neighbour structure -- ops.lesion_metrics' grouping --, kept when larger than `min_volume` voxels;
+    Dice_i = 2 (I + 1e-6) / (U + 2e-6) with I = sum p g, U = sum (p^2 + g) over the background (not G) and lesion i, the other lesions
+    masked out.  The labelling is a constant under differentiation; voxels of a dropped lesion get no gradient; a batch without any
+    kept lesion gives exactly 0.  Inputs are float32 [N, C, D, H, W] with FINITE values in [0, 1]; the target may be soft.
+    `priority` is read on every call.  Under data parallelism the mean runs over the pairs of the global batch."""
+
+    def __init__(self, index=0, priority=1, dilation=3, min_volume=0):
+        super().__init__()
+        _check_lesion_dice(priority, dilation, min_volume)
+        self.index, self.priority, self.dilation, self.min_volume = index, priority, dilation, min_volume
+
+    def forward(self, x, y):
+        assert x[self.index].shape == y[self.index].shape
+        _check_lesion_dice(self.priority, self.dilation, self.min_volume)
+        _check_extents("LesionWiseDiceLoss", x[self.index].shape)
+        return _LesionDiceFn.apply(x[self.index], y[self.index], float(self.priority), int(self.dilation), int(self.min_volume), self.data_parallel)
+
+
+def _check_lesion_dice(priority, dilation, min_volume):
+    import numbers
+    if not _finite(priority):
+        raise ValueError("LesionWiseDiceLoss: priority must be a finite number, got %r" % (priority,))
+    if not (isinstance(dilation, numbers.Integral) and not isinstance(dilation, bool) and 0 <= dilation <= MAX_EXTENT):
+        raise ValueError("LesionWiseDiceLoss: dilation must be an integer in [0, %d], got %r" % (MAX_EXTENT, dilation))
+    if not (isinstance(min_volume, numbers.Integral) and not isinstance(min_volume, bool) and min_volume >= 0):
+        raise ValueError("LesionWiseDiceLoss: min_volume must be an integer >= 0, got %r" % (min_volume,))
+
+
 def _finite(v):
     import math
     import numbers
@@ -718,3 +777,87 @@ def hddt_host(p, g, alpha=2.0, priority=1):
     w = (np.abs(signed_sqdist_host(p)).astype(np.float64) ** (alpha / 2.0) + np.abs(signed_sqdist_host(g)).astype(np.float64) ** (alpha / 2.0))
     d = pd - gd
     return float(priority * (d * d * w).sum() / pd.size), 2.0 * priority * d * w / pd.size
+
+
+LESION_SCALE = 2.0 ** 35          # csrc/lesion_loss.hip: the fixed-point scale of the per-lesion sums
+
+
+def lesion_labels_host(g, dilation=3):
+    """The lesions of a [D, H, W] target as csrc/lesion_loss.hip labels them (scipy): -> (labels int32: -1 outside G = g > 0.5, else the
+    smallest linear index of the voxel's 26-connected component of G dilated `dilation` times by the 18-neighbour structure; roots int64,
+    ascending: one per component)."""
+    import numpy as np
+    from scipy import ndimage
+    G = np.asarray(g, dtype=np.float32) > np.float32(0.5)
+    Z = ndimage.binary_dilation(G, ndimage.generate_binary_structure(3, 2), iterations=int(dilation)) if int(dilation) > 0 else G
+    comp, n = ndimage.label(Z, structure=np.ones((3, 3, 3), dtype=bool))
+    flat = comp.reshape(-1)
+    ids, first = np.unique(flat, return_index=True)                 # the first voxel of a component in raster order is its smallest index
+    roots = first[ids > 0].astype(np.int64)
+    assert len(roots) == n and np.all(np.diff(roots) > 0)           # scipy numbers the components in that order
+    root_of = np.concatenate([[-1], roots])
+    return np.where(G, root_of[comp], -1).astype(np.int32), roots
+
+
+def lesion_dice_host(p, g, priority=1, dilation=3, min_volume=0, quantised=True):
+    """LesionWiseDiceLoss in float64 with scipy's labelling -> (value, d value / d p as float64, table).  quantised=True forms the per-voxel
+    integers of csrc/lesion_loss.hip (rint of the exact float64 products times 2^35), sums them as int64 and goes on from those sums, as the
+    device does; quantised=False sums the float64 products themselves.  table[n][c] = dict(labels: int32 [D, H, W] in the device's
+    convention, root, vol: the lesions in ascending root order (the dropped ones included), kept: bool per lesion, and with quantised
+    qI, qU, qI0, qU0 as int64 (a lesion's own sums and the background's; ops.lesion_loss_table's columns), else I, U, I0, U0 as float64)."""
+    import numpy as np
+    _check_lesion_dice(priority, dilation, min_volume)
+    p32, g32 = np.ascontiguousarray(np.asarray(p, dtype=np.float32)), np.ascontiguousarray(np.asarray(g, dtype=np.float32))
+    _check_extents("lesion_dice_host", p32.shape)
+    if p32.shape != g32.shape:
+        raise ValueError("lesion_dice_host: shapes differ: %s, %s" % (p32.shape, g32.shape))
+    pd, gd = p32.astype(np.float64), g32.astype(np.float64)
+    N, C = pd.shape[:2]
+    V = int(np.prod(pd.shape[2:]))
+    table, pairs = [], []
+    for n in range(N):
+        table.append([])
+        for c in range(C):
+            labels, roots = lesion_labels_host(g32[n, c], dilation)
+            lf, pf, gf = labels.reshape(-1), pd[n, c].reshape(-1), gd[n, c].reshape(-1)
+            slot = np.searchsorted(roots, lf) + 1                    # 1 + the lesion's rank; 0 = background
+            slot[lf < 0] = 0
+            vol = np.bincount(slot, minlength=len(roots) + 1)[1:].astype(np.int64)
+            if quantised:
+                qi = np.rint(pf * gf * LESION_SCALE).astype(np.int64)
+                qu = np.rint(pf * pf * LESION_SCALE).astype(np.int64) + np.rint(gf * LESION_SCALE).astype(np.int64)
+                sI, sU = np.zeros(len(roots) + 1, dtype=np.int64), np.zeros(len(roots) + 1, dtype=np.int64)
+                np.add.at(sI, slot, qi)
+                np.add.at(sU, slot, qu)
+                I = (sI[0] + sI[1:]).astype(np.float64) * (1.0 / LESION_SCALE)
+                U = (sU[0] + sU[1:]).astype(np.float64) * (1.0 / LESION_SCALE)
+                entry = dict(qI=sI[1:].copy(), qU=sU[1:].copy(), qI0=int(sI[0]), qU0=int(sU[0]))
+            else:
+                sI = np.bincount(slot, weights=pf * gf, minlength=len(roots) + 1)
+                sU = np.bincount(slot, weights=pf * pf + gf, minlength=len(roots) + 1)
+                I, U = sI[0] + sI[1:], sU[0] + sU[1:]
+                entry = dict(I=sI[1:].copy(), U=sU[1:].copy(), I0=float(sI[0]), U0=float(sU[0]))
+            kept = vol > int(min_volume)
+            num, den = I + 1e-6, U + 2e-6
+            dice, a, b = 2.0 * num / den, 2.0 / den, 4.0 * num / (den * den)
+            L = int(kept.sum())
+            sd = sa = sb = 0.0
+            for i in np.nonzero(kept)[0]:                            # ascending root order
+                sd, sa, sb = sd + float(dice[i]), sa + float(a[i]), sb + float(b[i])
+            entry.update(labels=labels, root=roots, vol=vol, kept=kept)
+            table[-1].append(entry)
+            pairs.append((slot, np.where(kept, a, 0.0), np.where(kept, b, 0.0), sa, sb, L, 1.0 - sd / L if L else 0.0))
+    M = sum(1 for q in pairs if q[5] >= 1)
+    total = 0.0
+    for q in pairs:
+        if q[5] >= 1:
+            total += q[6]
+    grad = np.zeros((N * C, V), dtype=np.float64)
+    for k, (slot, a, b, sa, sb, L, _) in enumerate(pairs):
+        if M == 0 or L == 0:
+            continue
+        s = float(priority) / (M * float(L))
+        av, bv = np.concatenate([[sa], a])[slot], np.concatenate([[sb], b])[slot]
+        grad[k] = s * (bv * pd.reshape(N * C, V)[k] - av * gd.reshape(N * C, V)[k])
+    value = float(priority) * total / M if M else 0.0
+    return value, grad.reshape(pd.shape), table

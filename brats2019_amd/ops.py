@@ -455,6 +455,98 @@ def hddt_grad(p, g, s_p, s_g, alpha, coef, scale=None):
     return dp
 
 
+def _lesion_loss_args(who, p, g, dilation=0, min_volume=0):
+    if p.dim() != 5 or tuple(p.shape) != tuple(g.shape):
+        raise ValueError("%s: expected two [N, C, D, H, W] tensors of one shape, got %s and %s" % (who, tuple(p.shape), tuple(g.shape)))
+    if p.dtype != torch.float32 or g.dtype != torch.float32:
+        raise ValueError("%s: expected float32 tensors, got %s and %s" % (who, p.dtype, g.dtype))
+    if not all(1 <= int(v) <= 512 for v in p.shape[2:]) or int(p.shape[0]) < 1 or int(p.shape[1]) < 1:
+        raise ValueError("%s: every axis of the volume must be in [1, 512], got %s" % (who, tuple(p.shape)))
+    if int(dilation) != dilation or int(min_volume) != min_volume or int(dilation) < 0 or int(min_volume) < 0:
+        raise ValueError("%s: dilation %r and min_volume %r must be integers >= 0" % (who, dilation, min_volume))
+    return _prep(p), _prep(g)
+
+
+def _lesion_loss_state(n, c, d, h, w):
+    import ctypes
+    off = (ctypes.c_size_t * 5)()
+    nbytes = L.load().ru_lesion_loss_state_bytes(n, c, d, h, w, off)
+    if not nbytes:
+        raise ValueError("lesion loss: unsupported shape %s" % ((n, c, d, h, w),))
+    return int(nbytes), [int(v) for v in off]
+
+
+def lesion_loss_forward(p, g, dilation=3, min_volume=0):
+    """Lesion-wise Dice loss, pass 1 (csrc/lesion_loss.hip; include/resunet_hip.h states the definition): p, g float32 [N, C, D, H, W] with
+    finite values in [0, 1] -> (totals float64 [2] = (the sum of the pair losses of THIS shard's pairs with a kept lesion, their number),
+    stats int64 [N, C, 2] = (lesions, kept lesions), labels int32 of p's shape: -1 outside G = g > 0.5, else the smallest linear index of
+    the voxel's component of the dilated target, state: an opaque uint8 tensor for lesion_loss_grad and lesion_loss_table).  The loss is
+    priority * totals[0] / totals[1] of the all-reduced totals (0 when totals[1] is 0).  No host sync; two calls give identical bytes."""
+    p, g = _lesion_loss_args("lesion_loss_forward", p, g, dilation, min_volume)
+    n, c, d, h, w = _dims5(p)
+    lib = L.load()
+    nstate, _ = _lesion_loss_state(n, c, d, h, w)
+    totals = torch.empty(2, dtype=torch.float64, device=p.device)
+    stats = torch.empty((n, c, 2), dtype=torch.int64, device=p.device)
+    labels = torch.empty(p.shape, dtype=torch.int32, device=p.device)
+    state = torch.empty(nstate, dtype=torch.uint8, device=p.device)
+    ws = L.workspace(lib.ru_lesion_loss_workspace_bytes(n, c, d, h, w), p.device)
+    L.check(lib.ru_lesion_loss_forward(L.f32(p), L.f32(g), n, c, d, h, w, int(dilation), int(min_volume), L.ptr(labels), L.ptr(state),
+                                       L.ptr(totals), L.ptr(stats), L.ptr(ws), ws.numel(), L.stream()), "ru_lesion_loss_forward")
+    return totals, stats, labels, state
+
+
+def _lesion_loss_saved(who, p, labels, state, totals):
+    n, c, d, h, w = _dims5(p)
+    nstate, off = _lesion_loss_state(n, c, d, h, w)
+    if labels.dtype != torch.int32 or labels.shape != p.shape or not labels.is_contiguous():
+        raise ValueError("%s: labels must be a contiguous int32 tensor of the prediction's shape (ops.lesion_loss_forward)" % who)
+    if state.dtype != torch.uint8 or state.numel() != nstate or not state.is_contiguous():
+        raise ValueError("%s: state must be the uint8 tensor ops.lesion_loss_forward returned for this shape" % who)
+    if totals is not None and (totals.dtype != torch.float64 or totals.numel() != 2 or not totals.is_contiguous()):
+        raise ValueError("%s: totals must be a contiguous float64 tensor [2]" % who)
+    return (n, c, d, h, w), off
+
+
+def lesion_loss_grad(p, g, labels, state, totals_global, priority, scale=None):
+    """Lesion-wise Dice loss, pass 2: dp = d loss / d p from what lesion_loss_forward left and the (all-reduced) totals, whose pair count
+    is read on the device; times `scale` (a float32 device scalar) when given, inside the one rounding to float32.  Exact zeros on the
+    voxels of a dropped lesion, on a pair without a kept lesion, and everywhere when no pair of the global batch has one."""
+    p, g = _lesion_loss_args("lesion_loss_grad", p, g)
+    (n, c, d, h, w), _ = _lesion_loss_saved("lesion_loss_grad", p, labels, state, totals_global)
+    import math
+    if not math.isfinite(float(priority)):
+        raise ValueError("lesion_loss_grad: priority must be finite, got %r" % (priority,))
+    dp = torch.empty_like(p)
+    sc = None if scale is None else scale.detach().to(torch.float32).contiguous()
+    L.check(L.load().ru_lesion_loss_grad(L.f32(p), L.f32(g), L.ptr(labels), L.ptr(state), L.ptr(totals_global), float(priority), L.ptr(sc, True),
+                                         L.f32(dp), n, c, d, h, w, L.stream()), "ru_lesion_loss_grad")
+    return dp
+
+
+def lesion_loss_table(labels, state):
+    """Test and debug helper (synchronises): what lesion_loss_forward summed, as int64 numpy.  -> a list over n of lists over c of dicts
+    {root, vol, qI, qU: arrays over the lesions of (n, c) in ascending root order, the dropped ones included; qI0, qU0: the background's
+    sums}.  qI, qU are the lesion's own sums (its domain's sums are qI0 + qI, qU0 + qU), in units of 2^-35."""
+    (n, c, d, h, w), off = _lesion_loss_saved("lesion_loss_table", labels, labels, state, None)
+    nk, v = n * c, d * h * w
+    raw = state.cpu().numpy()
+    pairs = raw[off[0]:off[0] + nk * 64].view("<i8").reshape(nk, 8)
+    vol = raw[off[1]:off[1] + nk * v * 4].view("<i4").reshape(nk, v)
+    qi = raw[off[2]:off[2] + nk * v * 8].view("<i8").reshape(nk, v)
+    qu = raw[off[3]:off[3] + nk * v * 8].view("<i8").reshape(nk, v)
+    out = []
+    for i in range(n):
+        row = []
+        for j in range(c):
+            k = i * c + j
+            root = vol[k].nonzero()[0]
+            row.append(dict(root=root.astype("int64"), vol=vol[k][root].astype("int64"), qI=qi[k][root].copy(), qU=qu[k][root].copy(),
+                            qI0=int(pairs[k, 5]), qU0=int(pairs[k, 6])))
+        out.append(row)
+    return out
+
+
 def adam_amsgrad_step(w, g, m, v, vmax, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
     """torch.optim.Adam(amsgrad=True) update on flat float32 buffers (main.py:133-137)."""
     L.check(L.load().ru_adam_amsgrad_step(L.f32(w), L.f32(g), L.f32(m), L.f32(v), L.f32(vmax), w.numel(), lr, betas[0], betas[1],

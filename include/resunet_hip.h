@@ -256,6 +256,43 @@ int ru_hddt_sum(const float* p, const float* g, const int* s_p, const int* s_g, 
 int ru_hddt_grad(const float* p, const float* g, const int* s_p, const int* s_g, size_t n, float alpha, float coef, const float* scale,
                  float* dp, ru_stream_t stream);
 
+/* ---------------------------------------------------------------- lesion-wise Dice loss (csrc/lesion_loss.hip)
+ * The blob loss (Kofler et al. 2022) on Dice_loss_joint's Dice: the training-side counterpart of ru_lesion_metrics (definition and
+ * degenerate cases: INTEGRATION.md).  p, g: float32 [N][C][D][H][W], finite values in [0, 1]; every extent in [1, 512], D * H * W < 2^31,
+ * N * C <= 65535.  Per (n, c): G = g > 0.5f; Z = G dilated `dilation` times by the 18-neighbour structure; the lesions T_i = G & Z_i, Z_i
+ * the 26-connected components of Z (ru_lesion_metrics' grouping), vol_i = |T_i|; kept: vol_i > min_volume, L of them.  The domain of
+ * lesion i is the background (not G; Z \ G included) and T_i.  Per voxel qI = llrint(p g 2^35), qU = llrint(p p 2^35) + llrint(g 2^35)
+ * from exact float64 products; I_i, U_i = the 64-bit integer sums over the domain times 2^-35; Dice_i = 2 (I_i + 1e-6) / (U_i + 2e-6),
+ * a_i = 2 / (U_i + 2e-6), b_i = 4 (I_i + 1e-6) / (U_i + 2e-6)^2 in float64; pair loss l_nc = 1 - (sum over kept Dice_i) / L where L >= 1.
+ * Loss = priority * (sum of l_nc over the pairs with L >= 1) / M, M = their number in the GLOBAL batch; 0 when M = 0.
+ *   ru_lesion_loss_forward: labels_out int32 [N][C][V]: -1 outside G, else the root of the voxel's component of Z = the smallest linear
+ *                     index of that component (the root itself may lie in Z \ G and then holds -1).  state_out: ru_lesion_loss_state_bytes
+ *                     bytes, 16-byte aligned, five slices at the byte offsets the call reports: [0] per pair 64 bytes {A = sum kept a_i,
+ *                     B = sum kept b_i, l_nc (float64); L, lesions (int64); the background's integer sums qI0, qU0 (uint64); 0};
+ *                     [1] vol int32 [N*C][V], [2] qI and [3] qU uint64 [N*C][V]: a lesion's own sums at its root, 0 elsewhere;
+ *                     [4] (a_i, b_i) float64 pairs [N*C][V], written AT ROOTS ONLY (zeros for a dropped lesion), undefined elsewhere.
+ *                     totals_out float64 [2] = {sum of l_nc over THIS call's pairs with L >= 1, their number}: all that crosses ranks.
+ *                     stats_out int64 [N][C][2] = {lesions, L}.  The number of lesions is not limited.  Integer atomics only; the
+ *                     float64 sums run in an order fixed by the shape: two calls give identical bytes.  No host synchronisation.
+ *                     ws: ru_lesion_loss_workspace_bytes(N, C, D, H, W) (0 for a bad shape).
+ *   ru_lesion_loss_grad: dp = s (b p - a g), s = priority * (*scale when scale != NULL; a float32 DEVICE scalar) / (M * L), M =
+ *                     totals_global[1] read on the device (the all-reduced totals); (a, b) = (a_i, b_i) in a kept lesion, (0, 0) in a
+ *                     dropped one (exact zeros), (A, B) on the background; zeros for a pair with L = 0 and everywhere when M = 0.
+ *                     Float64 arithmetic, rounded once to float32.  One streaming pass, no atomics.
+ *   ru_lesion_loss_forward_upto: the forward cut short after `passes` of its four passes (1: clears, pack, dilation; 2: + labelling;
+ *                     3: + sum; 4: + evaluate = ru_lesion_loss_forward): what tools/lesion_loss_time.py times pass by pass.  The outputs
+ *                     are complete only with passes = 4. */
+size_t ru_lesion_loss_workspace_bytes(int N, int C, int D, int H, int W);
+size_t ru_lesion_loss_state_bytes(int N, int C, int D, int H, int W, size_t* offsets5);
+int ru_lesion_loss_forward(const float* p, const float* g, int N, int C, int D, int H, int W, int dilation, long long min_volume,
+                           int* labels_out, void* state_out, double* totals_out, long long* stats_out, void* ws, size_t ws_bytes,
+                           ru_stream_t stream);
+int ru_lesion_loss_forward_upto(const float* p, const float* g, int N, int C, int D, int H, int W, int dilation, long long min_volume,
+                                int* labels_out, void* state_out, double* totals_out, long long* stats_out, void* ws, size_t ws_bytes,
+                                int passes, ru_stream_t stream);
+int ru_lesion_loss_grad(const float* p, const float* g, const int* labels, const void* state, const double* totals_global, double priority,
+                        const float* scale, float* dp, int N, int C, int D, int H, int W, ru_stream_t stream);
+
 /* ---------------------------------------------------------------- optimizer (main.py:133-142)
  * torch.optim.Adam(amsgrad=True) with L2 weight decay added to the gradient; `step` is 1-based.  */
 int ru_adam_amsgrad_step(float* w, const float* g, float* m, float* v, float* vmax, size_t n,
