@@ -9,6 +9,8 @@
 // The Dice_loss_joint + BCE pair of the training step keeps its own kernels (pointwise.hip, crit_*); this unit serves criterion lists.
 #include "pw_helpers.hpp"
 
+#include <stdint.h>
+
 namespace ru {
 namespace {
 
@@ -36,8 +38,8 @@ __device__ __forceinline__ void cm_add(float (&s)[CM], float p, float g) {
     s[RU_CRIT_M_D2] += d * d;
 }
 
-// grid (tiles, N*C), 256 threads: block (t, row) sums voxels [t*CM_CHUNK, (t+1)*CM_CHUNK) of the row.  VEC4 (V % 4 == 0): float4 loads,
-// the row start is then 16-byte aligned.  part[(row*nblk + t)*CM + m]
+// grid (tiles, N*C), 256 threads: block (t, row) sums voxels [t*CM_CHUNK, (t+1)*CM_CHUNK) of the row.  VEC4: float4 loads; the launcher takes it only when
+// V % 4 == 0 AND p and g are 16-byte aligned (vec4_ok) -- every row start and every tile start is then 16-byte aligned too.  part[(row*nblk + t)*CM + m]
 template <bool LOGS, bool VEC4>
 __global__ __launch_bounds__(256) void crit_moments_kernel(const float* __restrict__ p, const float* __restrict__ g, float* __restrict__ part,
                                                            size_t V, int nblk) {
@@ -225,7 +227,7 @@ __device__ __forceinline__ float crit_f(float p, float g, float a, float b, floa
     return r;
 }
 
-// grid (x, N*C): dp = f(p, g, coef[row]) * (*scale if given).  LOGS = false when no term has d or e (no division)
+// grid (x, N*C): dp = f(p, g, coef[row]) * (*scale if given).  LOGS = false when no term has d or e (no division).  VEC4 under vec4_ok(V, p, g, dp)
 template <bool LOGS, bool VEC4>
 __global__ __launch_bounds__(256) void crit_apply_kernel(const float* __restrict__ p, const float* __restrict__ g, const float* __restrict__ coef,
                                                          const float* __restrict__ scale, float* __restrict__ dp, size_t V) {
@@ -246,6 +248,11 @@ __global__ __launch_bounds__(256) void crit_apply_kernel(const float* __restrict
     } else {
         for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < V; v += step) o[v] = crit_f<LOGS>(pr[v], gr[v], a, b, c, d, e);
     }
+}
+
+// the float4 forms: rows of a multiple of 4 elements that start on a 16-byte boundary, for every pointer the kernel accesses 16 bytes at a time
+bool vec4_ok(size_t V, const void* a, const void* b, const void* c = nullptr) {
+    return V % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15u) == 0;
 }
 
 dim3 apply_grid(size_t V, int vec, int rows) {
@@ -273,7 +280,7 @@ extern "C" int ru_crit_moments(const float* p, const float* g, int N, int C, siz
     RU_REQUIRE(ws && ws_bytes >= ru_crit_moments_workspace_bytes(N, C, V), "ru_crit_moments: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int nblk = cm_tiles(V);
-    const bool logs = (mask & CM_LOG_BITS) != 0, vec = V % 4 == 0;
+    const bool logs = (mask & CM_LOG_BITS) != 0, vec = vec4_ok(V, p, g);
     const dim3 grid(nblk, N * C);
     float* part = (float*)ws;
     if (logs && vec) hipLaunchKernelGGL((crit_moments_kernel<true, true>), grid, dim3(256), 0, s, p, g, part, V, nblk);
@@ -314,7 +321,7 @@ extern "C" int ru_crit_grad(const float* p, const float* g, const float* coef, c
     RU_REQUIRE(p && g && coef && dp && N > 0 && C > 0 && V > 0, "ru_crit_grad: bad argument");
     RU_REQUIRE((long long)N * C <= 65535, "ru_crit_grad: N * C = %lld rows, at most 65535", (long long)N * C);
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = V % 4 == 0;
+    const bool vec = vec4_ok(V, p, g, dp);
     const dim3 grid = apply_grid(V, vec ? 4 : 1, N * C);
     if (with_logs && vec) hipLaunchKernelGGL((crit_apply_kernel<true, true>), grid, dim3(256), 0, s, p, g, coef, scale, dp, V);
     else if (with_logs) hipLaunchKernelGGL((crit_apply_kernel<true, false>), grid, dim3(256), 0, s, p, g, coef, scale, dp, V);

@@ -165,7 +165,9 @@ int ru_criterion_value_device(const double* sums, int C, double count, double pr
  *                     sens_loss_joint does not; Dice_loss_separate ignores its priority; a class absent from the global batch gives
  *                     GDL_joint w_c = inf, so its value and gradient are NaN, as in torch.
  *   ru_crit_grad    : dp = f(p, g, coef[row]) * (*scale when scale != NULL; a float32 DEVICE scalar).  with_logs = 0 skips the d and e
- *                     terms (pass 1 whenever a CE or BCE term is in the list).  */
+ *                     terms (pass 1 whenever a CE or BCE term is in the list).
+ * p, g and dp need only float alignment: the moments and apply passes move 16 bytes at a time when V % 4 == 0 and the pointers they read or
+ * write are 16-byte aligned, and one element at a time otherwise (the same arithmetic per element; the moments' order of summation differs).  */
 #define RU_CRIT_DICE_JOINT 0      /* Dice_loss_joint(index, priority)     loss.py:98-122 */
 #define RU_CRIT_BCE 1             /* BCE_Loss(index, bg_weight)           loss.py:64-79 */
 #define RU_CRIT_MSE 2             /* MSE_Loss(index, priority)            loss.py:15-29 */

@@ -173,4 +173,9 @@ def cases():
     add("zscore_stats", False, zscore)                  # (brats2019_amd.dataloader.zscore_stats returns host numbers: the entry is called as it calls it)
     xb = _rand(4, 42, 41, 23, seed=133, scale=100.0)
     add("case_stats", False, lambda: as_list(ops.case_stats(xb, (1, 1, 2), (40, 40, 21))))
+
+    # ---- ru_crit_moments at 2 x 3 classes, V = 8192 + 1 (two tiles, the one-by-one form), with and without the log moments.  Like the two statistics entries it
+    # refuses a short workspace as a bad argument (RU_EINVAL, "ru_crit_moments: workspace too small"), not with RU_ENOMEM: no short case
+    add("crit_moments_logs", False, lambda: as_list(ops.crit_moments(pc, gc)))
+    add("crit_moments_no_logs", False, lambda: as_list(ops.crit_moments(pc, gc, mask=L.CRIT_MASK_ALL & ~L.CRIT_MASK_LOGS)))
     return out
