@@ -8,6 +8,8 @@
 #include "ru_common.h"
 #include "arena.hpp"
 
+#include <math.h>
+
 namespace ru {
 
 __global__ void gn_scale_shift_kernel(const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
@@ -736,6 +738,10 @@ static int augment_patch_impl(const float* image, const unsigned char* label, co
     for (int i = 0; i < 3; ++i) {
         RU_REQUIRE(patch[i] > 0 && crop_lo[i] >= 0 && crop_lo[i] + patch[i] <= dims[i], "ru_augment_patch: the crop must lie inside the volume");
         RU_REQUIRE(scale[i] > 0.0, "ru_augment_patch: scale must be positive");
+        // zoom_voxel converts floor(scale * index) to int: the largest source coordinate, scale * (P - 1), has to stay well inside its range
+        RU_REQUIRE(isfinite(scale[i]), "ru_augment_patch: scale[%d] is not finite", i);
+        RU_REQUIRE(scale[i] * (double)(patch[i] - 1) < 1073741824.0, "ru_augment_patch: scale[%d] * (patch[%d] - 1) = %g reaches 2^30", i, i,
+                   scale[i] * (double)(patch[i] - 1));
         a.lo[i] = crop_lo[i]; a.P[i] = patch[i]; a.scale[i] = scale[i];
     }
     for (int c = 0; c < C; ++c) { a.mean[c] = mean[c]; a.istd[c] = inv_std[c]; a.gain[c] = gain[c]; a.bias[c] = bias[c]; }

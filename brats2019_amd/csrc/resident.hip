@@ -296,6 +296,9 @@ extern "C" int ru_augment_batch_packed(const ru_case_desc* cases, const ru_patch
             for (int i = 0; i < 3; ++i) {
                 RU_REQUIRE(p.crop_lo[i] >= 0 && p.crop_lo[i] + patch[i] <= c.dims[i], "ru_augment_batch_packed: sample %d: the crop must lie inside the volume", n);
                 RU_REQUIRE(p.scale[i] > 0.0, "ru_augment_batch_packed: sample %d: scale must be positive", n);
+                RU_REQUIRE(isfinite(p.scale[i]), "ru_augment_batch_packed: sample %d: scale[%d] is not finite", n, i);
+                RU_REQUIRE(p.scale[i] * (double)(patch[i] - 1) < 1073741824.0,
+                           "ru_augment_batch_packed: sample %d: scale[%d] * (patch[%d] - 1) = %g reaches 2^30", n, i, i, p.scale[i] * (double)(patch[i] - 1));
             }
         } else {
             RU_REQUIRE(p.mode == RU_AUG_AFFINE, "ru_augment_batch_packed: sample %d: unknown mode %d", n, p.mode);

@@ -145,6 +145,22 @@ def _flags(flips, transpose):
     return sum(1 << i for i, f in enumerate(flips) if f) | (8 if transpose else 0)
 
 
+ZOOM_MAX_COORD = 2.0 ** 30
+
+
+def _check_zoom_scale(scale, patch):
+    """argument check of the zoom pass, ValueError before any launch: the kernel converts floor(scale * index) to a 32-bit integer, so every scale is
+    finite and the largest source coordinate scale * (P - 1) stays below 2^30.  (A scale <= 0 is left to the entry point, which refuses it.)"""
+    sc = np.asarray(scale, np.float64).reshape(-1)
+    if sc.shape != (3,):
+        raise ValueError("zoom: scale must hold three values, got %r" % (scale,))
+    for ax in range(3):
+        if sc[ax] == np.inf:                                 # NaN and -inf are not positive: the entry point's refusal
+            raise ValueError("zoom: scale[%d] is not finite" % ax)
+        if sc[ax] * float(int(patch[ax]) - 1) >= ZOOM_MAX_COORD:
+            raise ValueError("zoom: scale[%d] * (patch[%d] - 1) = %g reaches 2^30" % (ax, ax, sc[ax] * float(int(patch[ax]) - 1)))
+
+
 def augment_patch(case, p, patch_size=None):
     """(data [C,Q0,Q1,P2], target [3,Q0,Q1,P2]) float32 device tensors for explicit parameters `p` (see draw_augment_params).  A case
     with soft targets takes the same pass with the teacher's three channels interpolated in place of the one-hot label
@@ -166,6 +182,8 @@ def augment_patch(case, p, patch_size=None):
     el = p.get("elastic")
     rot = p.get("rotation")
     affine = None if rot is None else _rotation_transform(rot, p["crop_lo"], p["scale"], patch)      # argument checks before any launch
+    if affine is None:
+        _check_zoom_scale(p["scale"], patch)
     noise = None
     if el is not None:                                   # argument checks before any launch
         sigma, alpha = float(el["sigma"]), float(el["alpha"])
@@ -389,6 +407,8 @@ def _check_batch(patch, params_list):
             raise ValueError("resident: sample %d is transposed: a batch needs P0 == P1, got patch %s" % (n, tuple(patch)))
         rot = p.get("rotation")
         affine = None if rot is None else _rotation_transform(rot, p["crop_lo"], p["scale"], patch)
+        if affine is None:
+            _check_zoom_scale(p["scale"], patch)
         descs.append(_patch_desc(_flags(p["flips"], p["transpose"]), p["gain"], p["bias"], crop_lo=p["crop_lo"], scale=p["scale"], affine=affine))
     return descs
 

@@ -926,7 +926,9 @@ int ru_lesion_accumulate(const double* summary, double* acc, int N, int K, int n
  *   z-score ((x - mean) * inv_std), zoom by `scale` per axis (scipy.ndimage.affine_transform with a diagonal matrix, order 1,
  *   mode 'reflect', applied to the modalities and to the one-hot label), flips (flags bit 0/1/2 = axes D/H/W), transpose of D
  *   and H (bit 3), per-channel gain and bias, WT/TC/ET soft targets.  data_out [C][Q0][Q1][P2], target_out [3][Q0][Q1][P2] with
- *   (Q0, Q1) = (P1, P0) when transposed.  The small parameter arrays are HOST pointers, read at launch.  C <= 8. */
+ *   (Q0, Q1) = (P1, P0) when transposed.  The small parameter arrays are HOST pointers, read at launch.  C <= 8.
+ *   Refused (RU_EINVAL, before any launch): a crop outside the volume, a scale that is not positive or not finite, and a scale with
+ *   scale[i] * (patch[i] - 1) >= 2^30 (the source cell floor(scale * index) is held in 32 bits). */
 size_t ru_zscore_workspace_bytes(int C, size_t V);
 int ru_zscore_stats(const float* image, double* stats, int C, size_t V, void* ws, size_t ws_bytes, ru_stream_t stream);
 int ru_augment_patch(const float* image, const unsigned char* label, const float* mean, const float* inv_std,
@@ -1057,7 +1059,7 @@ int ru_intensity_augment(const float* in, float* out, int C, int P0, int P1, int
  *   the kernels instantiate one per-voxel function (csrc/augment_voxel.hpp) on different sources.  A case with soft != NULL gets its targets from
  *   soft.  Every sample has the same channel count and the same patch; a transposed sample (flags bit 3) in a batch of more than one needs
  *   P0 == P1.  No workspace, no atomics, no synchronisation: the call only enqueues.  Refused (RU_EINVAL, before any launch): what the
- *   single-patch entry points refuse (crop outside the volume or scale <= 0 for zoom; matrix or offset not finite, |det| < 1e-6, unknown
+ *   single-patch entry points refuse (crop outside the volume, scale <= 0, not finite or scale * (patch - 1) >= 2^30 for zoom; matrix or offset not finite, |det| < 1e-6, unknown
  *   mapping for affine; flags outside bits 0..3; C outside 1..8; patch extents <= 0 or P0 P1 P2 >= 2^31 - 1), N < 1, an unknown kind or mode, a
  *   box outside its volume, differing channel counts, a transposed sample with P0 != P1 and N > 1. */
 #define RU_PACK_F32 0
