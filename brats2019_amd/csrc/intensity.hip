@@ -206,15 +206,21 @@ __global__ __launch_bounds__(256) void int_lowres_table_kernel(const IntLrArgs a
 // ---------------------------------------------------------------------------------------------------------------- the pointwise chain
 // n(seed, channel, v): key = mix64(seed + (channel + 1) G), z1 = mix64(key + (2 v + 1) G), z2 = mix64(key + (2 v + 2) G), G = 0x9E3779B97F4A7C15;
 // u1 = ((z1 >> 11) + 1) 2^-53 in (0, 1], u2 = (z2 >> 11) 2^-53 in [0, 1); n = sqrt(-2 ln u1) cos(2 pi u2).  The angle is reduced to
-// [-pi, pi) in float64 before it is rounded to float32 (cos has period 1 in u2).
+// [-pi, pi) in float64 before it is rounded to float32 (cos has period 1 in u2).  ln u1 keeps a RELATIVE error: with h = float32(u1),
+// ln u1 = ln h + ln(1 + (u1 - h) / h) = logf(h) + (u1 - h) / h up to 2^-51, the difference exact in float64 -- one logf, no branch.  logf(h)
+// alone leaves -ln u1 an absolute error of 3e-8 where it is about 1e-7 and turns every u1 in (1 - 2^-25, 1] into n = 0 (7.5e-5 off in n
+// among 2 10^6 voxels).
 __device__ __forceinline__ float in_normal(unsigned long long key, unsigned v) {
+#pragma clang fp contract(off)
     const unsigned long long z1 = in_mix64(key + (2ull * v + 1ull) * 0x9E3779B97F4A7C15ull);
     const unsigned long long z2 = in_mix64(key + (2ull * v + 2ull) * 0x9E3779B97F4A7C15ull);
-    const float u1 = (float)((double)((z1 >> 11) + 1ull) * (1.0 / 9007199254740992.0));
+    const double u1 = (double)((z1 >> 11) + 1ull) * (1.0 / 9007199254740992.0);
+    const float h = (float)u1;
+    const float ln1 = logf(h) + (float)(u1 - (double)h) / h;
     double u2 = (double)(z2 >> 11) * (1.0 / 9007199254740992.0);
     if (u2 >= 0.5) u2 -= 1.0;
     const float ang = (float)(u2 * 6.283185307179586476925);
-    return sqrtf(-2.f * logf(u1)) * cosf(ang);
+    return sqrtf(-2.f * ln1) * cosf(ang);
 }
 
 struct IntChan {                 // one channel's constants, in registers
@@ -234,7 +240,8 @@ __device__ __forceinline__ float in_head(const IntChan& k, float x, unsigned v) 
 }
 // from the value that enters contrast to the value at `level`: 0 = that value, 1 = as it enters gamma (negated if inverted), 2 = gamma's y
 // before the retain-stats rescale, 3 = final.  No contraction, so a value is rounded the same way at whatever level it is formed again.
-// t^g = exp2(g log2 t) on v_exp_f32 / v_log_f32 (1 ulp each; a denormal t counts as 0): the error of y stays below range * 1e-6, the size of the rounding of t itself.
+// t^g = exp2(g log2 t) on v_exp_f32 / v_log_f32 (measured 1.41 and 1.97 units of 2^-24 |result|, tools/libm_ulp.py; a denormal t counts as 0): the error
+// of y is range t^g ln2 |g log2 t| times a few 2^-24 -- it grows with g, and tests/intensity_inputs.py carries that term per voxel.
 __device__ __forceinline__ float in_tail(const IntChan& k, float x, int level) {
 #pragma clang fp contract(off)
     if (level == 0) return x;

@@ -871,7 +871,7 @@ def intensity_augment(data, params):
 
 def intensity_noise_host(seed, channel, count):
     """The first `count` values n(seed, channel, v), v = 0 .. count-1, of `ru_intensity_augment`'s noise in float64 (the device rounds ln, sqrt and
-    cos to float32): key = mix64(seed + (channel + 1) G); z1 = mix64(key + (2 v + 1) G), z2 = mix64(key + (2 v + 2) G); u1 = ((z1 >> 11) + 1) / 2^53
+    cos to float32, ln u1 with a relative error: logf(h) + (u1 - h) / h, h = float32(u1); tests/intensity_inputs.py holds n to its roundings): key = mix64(seed + (channel + 1) G); z1 = mix64(key + (2 v + 1) G), z2 = mix64(key + (2 v + 2) G); u1 = ((z1 >> 11) + 1) / 2^53
     in (0, 1], u2 = (z2 >> 11) / 2^53 in [0, 1); n = sqrt(-2 ln u1) cos(2 pi u2).  mix64 and G are `elastic_noise_host`'s."""
     v = np.arange(int(count), dtype=np.uint64)
     with np.errstate(over="ignore"):

@@ -1003,7 +1003,8 @@ int ru_elastic_warp(const float* data_in, int C, const float* target_in, int T, 
  *                      finalizer (ru_elastic_noise's) and G = 0x9E3779B97F4A7C15, all in 64-bit wrapping arithmetic:
  *                        key = mix64(noise_seed + (channel + 1) G),  z1 = mix64(key + (2 v + 1) G),  z2 = mix64(key + (2 v + 2) G),
  *                        u1 = ((z1 >> 11) + 1) / 2^53 in (0, 1],  u2 = (z2 >> 11) / 2^53 in [0, 1),  n = sqrt(-2 ln u1) cos(2 pi u2)   (Box-Muller)
- *                      The device evaluates ln, sqrt and cos in float32.  A pure function of (seed, channel, v): no state, any launch shape.
+ *                      The device evaluates ln, sqrt and cos in float32, ln u1 to a
+ *                      RELATIVE error (logf(h) + (u1 - h) / h, h = float32(u1)): n is good to a few float32 roundings of itself.  A pure function of (seed, channel, v): no state, any launch shape.
  *   RU_INT_BRIGHTNESS  x * brightness
  *   RU_INT_CONTRAST    clip((x - mean) * contrast + mean, min, max) with mean, min, max of the channel as it enters this stage
  *   RU_INT_GAMMA       with min, range = max - min, mean, std (population) of the channel as it enters this stage, after the negation if

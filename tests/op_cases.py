@@ -178,4 +178,13 @@ def cases():
     # refuses a short workspace as a bad argument (RU_EINVAL, "ru_crit_moments: workspace too small"), not with RU_ENOMEM: no short case
     add("crit_moments_logs", False, lambda: as_list(ops.crit_moments(pc, gc)))
     add("crit_moments_no_logs", False, lambda: as_list(ops.crit_moments(pc, gc, mask=L.CRIT_MASK_ALL & ~L.CRIT_MASK_LOGS)))
+
+    # ---- ru_intensity_augment through dataloader.intensity_augment: 4 channels at 3 x 3 x 911 (V = 8192 + 7: two partials per statistic), every carve of the
+    # workspace in use -- both blur intermediates, the low-res tables, the partials and statistics of all three levels.  It refuses a short workspace as a bad
+    # argument (RU_EINVAL, "ru_intensity_augment: workspace too small"), not with RU_ENOMEM: no short case
+    from brats2019_amd import dataloader as DL
+    xi = _rand(4, 3, 3, 911, seed=140)
+    qi = [dict(blur_sigma=1.0, lowres_zoom=0.63, noise_variance=0.1, noise_seed=4, brightness=1.25, contrast=0.75, gamma=1.5, gamma_invert=True, gamma_retain_stats=True),
+          dict(blur_sigma=2.0), {}, dict(lowres_zoom=0.5, gamma=0.7)]
+    add("intensity_augment", False, lambda: as_list(DL.intensity_augment(xi, qi)))
     return out

@@ -16,7 +16,7 @@ from oracle import resunet_oracle as O
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
 
-SHAPES = ((5, 6, 7), (16, 40, 24), (33, 20, 70))       # odd and smaller than the radius; 16-byte rows; rows that are no multiple of 4 and more than one tile
+SHAPES = ((5, 6, 7), (16, 40, 24), (33, 20, 70))       # odd and smaller than the radius; 16-byte rows; rows that are no multiple of 4.  Each is ONE 32 x 128 tile per slice (cdiv(20, 32) * cdiv(70, 128) = 1): the tile rows and columns are tests/test_intensity_f64.py's
 
 # stage: (largest |device - host| measured on an MI355X over this file's cases, bar = 4 x measured)
 BARS = {
@@ -127,7 +127,7 @@ def _all_stages():
 
 @pytest.mark.parametrize("shape", SHAPES + ((64, 64, 64),))
 def test_all_stages_on_all_channels(shape):
-    """(64, 64, 64): 32 partials per channel and statistic, 16-byte accesses, several tiles per slice"""
+    """(64, 64, 64): 32 partials per channel and statistic, 16-byte accesses, two tiles per slice (along H only)"""
     _check(shape, _all_stages(), "all")                              # measured / bar: BARS["all"]
 
 

@@ -4,7 +4,11 @@ p + 1e-6f and (1 + 1e-6)f - p of every criterion case, -x of every sigmoid case)
 library's flags into a temporary directory and runs it once per function, each in a process of its own.  LOGF_UNITS / EXPF_UNITS of
 tests/test_scalar_passes_host.py are these figures rounded up, plus one.
 
-usage: libm_ulp.py"""
+With `intensity`: the same for the functions of csrc/intensity.hip on every distinct argument the cases of tests/intensity_inputs.py hand them -- v_log_f32 on t and
+v_exp_f32 on g log2 t (gamma), logf on the noise's float32(u1), cosf on its angles, the constructed edge draws among them; ULP_LOG2, ULP_EXP2, ULP_LOGF
+and ULP_COS there are these figures rounded up, plus one.  A subnormal argument of v_log_f32 is left out (the bars count it as 0).
+
+usage: libm_ulp.py [intensity] [--probe BUILT_PROBE]"""
 import os
 import subprocess
 import sys
@@ -32,6 +36,17 @@ def exp_args():
     return v[np.isfinite(v)]
 
 
+def intensity_args():
+    import intensity_inputs as I
+    tap = {"log2": [], "exp2": [], "log": [], "cos": []}
+    for case in I.cases():
+        I.run(case, "emu", tap=tap)
+    out = {k: np.unique(np.concatenate([np.asarray(a, np.float32).ravel() for a in v])) for k, v in tap.items()}
+    out["log2"] = out["log2"][out["log2"] >= np.float32(2.0 ** -126)]
+    out["exp2"] = out["exp2"][~np.isnan(out["exp2"])]
+    return out
+
+
 def measure(probe, tmp, op, x, f64):
     a, b = os.path.join(tmp, op + "_in.bin"), os.path.join(tmp, op + "_out.bin")
     x.tofile(a)
@@ -51,8 +66,16 @@ def measure(probe, tmp, op, x, f64):
 
 
 with tempfile.TemporaryDirectory() as tmp:
-    probe = os.path.join(tmp, "libm_ulp_probe")
-    flags = [f for f in B.FLAGS if f not in ("-fPIC", "-fno-gpu-rdc")]
-    subprocess.run([B._hipcc()] + flags + [os.path.join(ROOT, "tools", "libm_ulp_probe.hip"), "-o", probe], check=True)
-    measure(probe, tmp, "log", log_args(), np.log)
-    measure(probe, tmp, "exp", exp_args(), np.exp)
+    if "--probe" in sys.argv:
+        probe = os.path.abspath(sys.argv[sys.argv.index("--probe") + 1])
+    else:
+        probe = os.path.join(tmp, "libm_ulp_probe")
+        flags = [f for f in B.FLAGS if f not in ("-fPIC", "-fno-gpu-rdc")]
+        subprocess.run([B._hipcc()] + flags + [os.path.join(ROOT, "tools", "libm_ulp_probe.hip"), "-o", probe], check=True)
+    if "intensity" in sys.argv:
+        args = intensity_args()
+        for op, f64 in (("log2", np.log2), ("exp2", np.exp2), ("log", np.log), ("cos", np.cos)):
+            measure(probe, tmp, op, args[op], f64)
+    else:
+        measure(probe, tmp, "log", log_args(), np.log)
+        measure(probe, tmp, "exp", exp_args(), np.exp)
