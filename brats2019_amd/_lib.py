@@ -174,7 +174,10 @@ SIGNATURES = {
     "ru_elastic_warp": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "ru_intensity_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ru_intensity_augment": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "ru_layout_convert": (_i, [_vp, _vp, _i, _i, _sz, _i, _vp]),
+    "ru_carvemix_workspace_bytes": (_sz, [_i, _sz]),
+    "ru_carvemix_threshold": (_i, [_vp, _i, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ru_carvemix_mix": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "ru_layout_convert":(_i, [_vp, _vp, _i, _i, _sz, _i, _vp]),
     "ru_upsample2x_trilinear_fwd_l": (_i, [_vp, _vp] + [_i] * 5 + [_f, _vp]),
     "ru_upsample2x_trilinear_bwd_l": (_i, [_vp, _vp] + [_i] * 5 + [_vp]),
     "ru_conv3d_fwd_l": (_i, [_vp, _vp, _vp, _vp] + [_i] * 7 + [_vp, _sz, _vp]),
@@ -240,6 +243,10 @@ PACK_F32, PACK_U16 = 0, 1
 PACK_KINDS = {"float32": PACK_F32, "uint16": PACK_U16}
 AUG_ZOOM, AUG_AFFINE = 0, 1
 AUG_BATCH_MAX = 8
+
+# ru_carvemix_* (include/resunet_hip.h)
+CARVE_SIDES = {"outer": 0, "inner": 1}       # RU_CARVE_OUTER / RU_CARVE_INNER
+CARVE_BATCH_MAX, CARVE_MAX_VOXELS = 8, 1 << 27
 
 
 class FinDesc(C.Structure):

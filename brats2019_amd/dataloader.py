@@ -29,6 +29,12 @@ work ONCE per case and keeps each case cropped to its non-zero box, as uint16 wh
 then only selects a view, `augment_patch` takes the view (`ResidentCase`) in place of a `DeviceCase`, `augment_batch` cuts a whole batch in one launch
 and `ResidentLoader` stands in for the `DataLoader`.  The per-voxel arithmetic is the one function of csrc/augment_voxel.hpp, so every patch equals the
 list reader's bit for bit.
+
+Opt-in: CarveMix (csrc/carvemix.hip), the lesion-aware mix of two cases (Zhang et al., MICCAI 2021; written from the paper, not checked against the
+authors' code).  `carvemix(data, target, donor_data, donor_target, u, side)` carves the region s <= T around each donor's WT lesion -- s the exact
+signed squared distance map of `ops.signed_sqdist`, T an integer threshold formed on the device from the lesion's volume and the draw u -- and
+pastes its voxels and labels into the receivers in place; `carvemix_host` is the numpy restatement, bit for bit.  `SimpleReader(..., carvemix=True)`
+draws everything the option adds from private generators; `ResidentLoader` mixes a batch with one extra gather and one mix launch.
 """
 from __future__ import annotations
 
@@ -117,20 +123,24 @@ class DeviceCase(object):
 _ELASTIC_RNG = random.Random()          # seeds of elastic fields when the caller brings no generator (the reference seeds from the wall clock, :166)
 
 
-def draw_augment_params(bbox, patch_size, channels=4, elastic=False, elastic_rng=None):
+def draw_augment_params(bbox, patch_size, channels=4, elastic=False, elastic_rng=None, rng=None, np_rng=None):
     """The draws of SimpleReader.__getitem__ (dataloader.py:141-199), in its order, from the same global generators.  `elastic=True` keeps
     the two values the reference draws for its switched-off elastic transform (:167-168) and adds `elastic=dict(sigma, alpha, seed)`; the seed
-    comes from `elastic_rng` (a private `random.Random`), never from the global generators, which advance exactly as with `elastic=False`."""
-    center = np.random.rand(3)
+    comes from `elastic_rng` (a private `random.Random`), never from the global generators, which advance exactly as with `elastic=False`.
+    `rng` (a `random.Random`) and `np_rng` (a `numpy.random.RandomState`) stand in for the global `random` / `numpy.random` modules, which are the
+    defaults: the same draws in the same order from private streams (the CarveMix donor's)."""
+    rng = random if rng is None else rng
+    np_rng = np.random if np_rng is None else np_rng
+    center = np_rng.rand(3)
     center = center * (bbox[1] - bbox[0]) + bbox[0]
     left_bottom = (center - np.array(patch_size) / 2.0).astype(np.int32)
-    r_sigma = random.random()                            # sigma / alpha of the elastic transform (:167-168), drawn whether it runs or not
-    r_alpha = random.random()
-    scale = [0.7 + random.random() * 0.6 for _ in range(3)]
-    flips = [random.random() > 0.5 for _ in range(3)]
-    transpose = random.random() > 0.5
-    gain = np.random.uniform(0.9, 1.1, size=(channels, 1, 1, 1)).reshape(-1)
-    bias = np.random.uniform(-0.2, 0.2, size=(channels, 1, 1, 1)).reshape(-1)
+    r_sigma = rng.random()                               # sigma / alpha of the elastic transform (:167-168), drawn whether it runs or not
+    r_alpha = rng.random()
+    scale = [0.7 + rng.random() * 0.6 for _ in range(3)]
+    flips = [rng.random() > 0.5 for _ in range(3)]
+    transpose = rng.random() > 0.5
+    gain = np_rng.uniform(0.9, 1.1, size=(channels, 1, 1, 1)).reshape(-1)
+    bias = np_rng.uniform(-0.2, 0.2, size=(channels, 1, 1, 1)).reshape(-1)
     p = dict(crop_lo=left_bottom, scale=np.array(scale), flips=flips, transpose=transpose, gain=gain, bias=bias)
     if elastic:
         p["elastic"] = dict(sigma=r_sigma * 20 + 10, alpha=r_alpha * 4000 + 200, seed=(elastic_rng or _ELASTIC_RNG).getrandbits(63))
@@ -1026,6 +1036,154 @@ def draw_intensity_params(channels, rng, config=None):
     return params
 
 
+# ---------------------------------------------------------------------------------------------------------------- CarveMix
+# csrc/carvemix.hip (`ru_carvemix_threshold`, `ru_carvemix_mix`) around `ops.signed_sqdist`, and the numpy restatement.  Written from the paper
+# (Zhang et al., MICCAI 2021; NeuroImage 2023), not checked against the authors' code; the definition is INTEGRATION.md's.
+CARVE_SIDES = ("outer", "inner")
+INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def carvemix_r2(volume):
+    """the largest integer q with q^3 <= volume^2 (floor(volume^(2/3))), by integer search: the squared form of the paper's lambda_u = V^(1/3)"""
+    v2 = int(volume) * int(volume)
+    lo, hi = 0, 1 << 18
+    while lo < hi:
+        mid = (lo + hi + 1) >> 1
+        if mid * mid * mid <= v2:
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
+def carvemix_threshold_host(volume, voxels, u, side):
+    """T of one donor: INT32_MIN for an empty lesion, INT32_MAX for a full one, else floor((u u) R2) (outer) or -ceil(((u u) R2) 0.25) (inner) in
+    float64 from plain multiplies"""
+    volume, voxels, u = int(volume), int(voxels), float(u)
+    if volume == 0:
+        return INT32_MIN
+    if volume == voxels:
+        return INT32_MAX
+    a = (u * u) * float(carvemix_r2(volume))
+    return int(np.floor(a)) if side == "outer" else -int(np.ceil(a * 0.25))
+
+
+def _check_carvemix(data_shape, target_shape, donor_data_shape, donor_target_shape, u, side, dst):
+    """argument checks of `carvemix` / `carvemix_host`: ValueError before any launch; returns (u list, side list, dst list)"""
+    ds, ts, dds, dts = (tuple(int(v) for v in s) for s in (data_shape, target_shape, donor_data_shape, donor_target_shape))
+    if len(ds) != 5 or len(ts) != 5 or len(dds) != 5 or len(dts) != 5:
+        raise ValueError("carvemix: data / target must be [N,C,D,H,W] / [N,3,D,H,W] and the donors [K,C,D,H,W] / [K,3,D,H,W], got %s %s %s %s" % (ds, ts, dds, dts))
+    n, c, sp = ds[0], ds[1], ds[2:]
+    k = dds[0]
+    if ts != (n, 3) + sp or dds != (k, c) + sp or dts != (k, 3) + sp:
+        raise ValueError("carvemix: shapes do not agree: data %s, target %s, donor data %s, donor target %s" % (ds, ts, dds, dts))
+    if not 1 <= c <= 8:
+        raise ValueError("carvemix: 1..8 data channels, got %d" % c)
+    if min(sp) < 1 or max(sp) > 512:
+        raise ValueError("carvemix: every axis of the patch must be in [1, 512] (the limit of signed_sqdist), got %s" % (sp,))
+    if not 1 <= k <= n:
+        raise ValueError("carvemix: %d donors into %d receivers: 1 <= K <= N" % (k, n))
+    try:
+        u = [float(v) for v in np.asarray(u, np.float64).reshape(-1)]
+    except (TypeError, ValueError):
+        raise ValueError("carvemix: u must hold one number per donor")
+    side = [side] * k if isinstance(side, str) else list(side)
+    if len(u) != k or len(side) != k:
+        raise ValueError("carvemix: one u and one side per donor (%d), got %d and %d" % (k, len(u), len(side)))
+    for v in u:
+        if not 0.0 <= v < 1.0:
+            raise ValueError("carvemix: u must lie in [0, 1), got %r" % (v,))
+    for sd in side:
+        if sd not in CARVE_SIDES:
+            raise ValueError("carvemix: side must be 'outer' or 'inner', got %r" % (sd,))
+    if dst is None:
+        if k != n:
+            raise ValueError("carvemix: %d donors and %d receivers need a dst list" % (k, n))
+        dst = list(range(k))
+    dst = [int(v) for v in dst]
+    if len(dst) != k or len(set(dst)) != k or not all(0 <= v < n for v in dst):
+        raise ValueError("carvemix: dst must hold %d distinct indices in [0, %d), got %r" % (k, n, dst))
+    return u, side, dst
+
+
+def carvemix(data, target, donor_data, donor_target, u, side, dst=None, want_mask=False):
+    """CarveMix on the device, IN PLACE on the receivers: data [N,C,D,H,W] / target [N,3,D,H,W] (contiguous float32 device tensors), donors
+    donor_data [K,C,D,H,W] / donor_target [K,3,D,H,W], `u` [K] floats in [0, 1), `side` [K] of "outer" / "inner" (or one string).  Donor k goes into
+    receiver dst[k] (distinct indices); with dst=None and N == K the donors pair up in order.  One `ops.signed_sqdist` of the K WT channels, one
+    `ru_carvemix_threshold`, one `ru_carvemix_mix` launch; nothing waits for the host.  Returns (data, target), or with `want_mask`
+    (data, target, mask uint8 [K,D,H,W], T int32 [K], V int64 [K]) as device tensors.  The definition: include/resunet_hip.h, restated by
+    `carvemix_host`.  Arguments are checked before any launch (ValueError)."""
+    from . import ops
+    for t in (data, target, donor_data, donor_target):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError("carvemix: expected float32 tensors")
+    u, side, dst = _check_carvemix(data.shape, target.shape, donor_data.shape, donor_target.shape, u, side, dst)
+    if not (data.is_contiguous() and target.is_contiguous()):
+        raise ValueError("carvemix: the receivers are mixed in place and must be contiguous")
+    L.require_gpu()
+    n, c, d, h, w = (int(v) for v in data.shape)
+    k, vox = int(donor_data.shape[0]), d * h * w
+    donor_data, donor_target = donor_data.contiguous(), donor_target.contiguous()
+    wt = donor_target[:, 0].contiguous()
+    lib = L.load()
+    s = ops.signed_sqdist(wt)
+    thr = torch.empty(k, dtype=torch.int32, device=data.device)
+    vol = torch.empty(k, dtype=torch.int64, device=data.device)
+    ws = L.workspace(lib.ru_carvemix_workspace_bytes(k, vox), data.device)
+    L.check(lib.ru_carvemix_threshold(L.f32(wt), k, vox, _arr(C.c_double, u), _arr(C.c_int, [L.CARVE_SIDES[sd] for sd in side]), L.ptr(thr), L.ptr(vol),
+                                      L.ptr(ws), ws.numel(), L.stream()), "ru_carvemix_threshold")
+    mask = torch.empty((k, d, h, w), dtype=torch.uint8, device=data.device) if want_mask else None
+    L.check(lib.ru_carvemix_mix(L.f32(donor_data), L.f32(donor_target), L.ptr(s), L.ptr(thr), k, _arr(C.c_int, dst), n, c, d, h, w, L.f32(data), L.f32(target),
+                                None if mask is None else L.ptr(mask), L.stream()), "ru_carvemix_mix")
+    return (data, target, mask, thr, vol) if want_mask else (data, target)
+
+
+def carvemix_host(data, target, donor_data, donor_target, u, side, dst=None):
+    """numpy restatement of `carvemix`, the oracle of the device path, built on `loss.signed_sqdist_host`: returns NEW arrays
+    (data, target, mask uint8 [K,D,H,W], T int32 [K], V int64 [K]).  Per donor: G = Ya[0] > 0.5f, V = |G|, s = signed_sqdist(Ya[0]),
+    T = `carvemix_threshold_host`, M = s <= T, and the receiver takes the donor's 32-bit words where M."""
+    from .loss import signed_sqdist_host
+    arrs = [np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, dtype=np.float32) for t in (data, target, donor_data, donor_target)]
+    data, target, donor_data, donor_target = arrs
+    u, side, dst = _check_carvemix(data.shape, target.shape, donor_data.shape, donor_target.shape, u, side, dst)
+    data, target = data.copy(), target.copy()
+    k, vox = donor_data.shape[0], int(np.prod(data.shape[2:]))
+    mask = np.zeros((k,) + data.shape[2:], np.uint8)
+    thr, vol = np.zeros(k, np.int32), np.zeros(k, np.int64)
+    for j in range(k):
+        wt = donor_target[j, 0]
+        vol[j] = int((wt > np.float32(0.5)).sum())
+        thr[j] = carvemix_threshold_host(vol[j], vox, u[j], side[j])
+        m = signed_sqdist_host(wt) <= thr[j]
+        mask[j] = m
+        xb, yb = data[dst[j]].view(np.uint32), target[dst[j]].view(np.uint32)       # words, not numbers: NaN and -0.0 pass through
+        xb[:, m] = donor_data[j].view(np.uint32)[:, m]
+        yb[:, m] = donor_target[j].view(np.uint32)[:, m]
+    return data, target, mask, thr, vol
+
+
+class CarveMixConfig(object):
+    """`p_mix`: the probability per sample that `draw_carvemix_params` mixes a donor in.  0.5 is a placeholder, not a recommendation: a value would
+    need trained weights to argue for."""
+
+    def __init__(self, p_mix=0.5):
+        self.p_mix = float(p_mix)
+        if not 0.0 <= self.p_mix <= 1.0:
+            raise ValueError("carvemix: p_mix must lie in [0, 1], got %r" % (p_mix,))
+
+
+def draw_carvemix_params(rng, config, n_cases):
+    """None, or dict(donor=case index, u=float in [0, 1), side="outer" / "inner"), drawn from `rng` (a private `random.Random`) ONLY.  One draw
+    decides (`p_mix`); only if it fires follow the donor, uniform over the `n_cases` cases (it may be the receiver's own), u and the side (each
+    with probability 1/2)."""
+    cfg = config or CarveMixConfig()
+    if not rng.random() < cfg.p_mix:
+        return None
+    donor = rng.randrange(int(n_cases))
+    u = rng.random()
+    return dict(donor=donor, u=u, side="inner" if rng.random() < 0.5 else "outer")
+
+
 class SimpleReader(torch.utils.data.Dataset):
     """dataloader.py:67-216 over in-memory cases: `cases` is a list of (image [C,D,H,W], label [D,H,W]) arrays (or of callables
     returning such a pair -- the place for a NIfTI reader).  Items are ([data], [target]) like the reference's, on the device.
@@ -1038,10 +1196,16 @@ class SimpleReader(torch.utils.data.Dataset):
     the angles drawn from a private `random.Random(rotation_seed)`: a patch that draws no rotation takes the path above bit for bit, one that does
     keeps its crop, scale, flip, transpose, gain and bias draws, and the global streams are those of `rotation=False`.
     `cases` may be a `ResidentCases` store (built for the same `patch_size`): a change of case then selects a view -- no upload, no host numpy, no
-    synchronisation -- and the draws, their order and the items are those of the list reader over the same cases, bit for bit."""
+    synchronisation -- and the draws, their order and the items are those of the list reader over the same cases, bit for bit.
+    `carvemix=True` (`CarveMixConfig()`, whose p_mix is a placeholder) or a `CarveMixConfig` mixes a donor patch into a sample with probability
+    `p_mix` (see `carvemix`).  Every draw the option adds -- the decision, the donor's case index, u, the side and the donor's OWN crop centre,
+    zoom, flips, transpose, gain and bias -- comes from private generators seeded by `carvemix_seed`; the global streams are those of
+    `carvemix=False`.  The donor is cut by the plain zoom path (no elastic field, no rotation); it takes its own transpose draw when P0 == P1 and
+    the receiver's otherwise (the draw is made either way).  `intensity=` runs after the mix, on the mixed data.  Over a `ResidentCases` store the
+    donor is a view; over a list it costs a `DeviceCase` build (upload, statistics, label box) per mixed sample."""
 
     def __init__(self, cases, patch_size, images_in_epoch=4000, patches_from_single_image=1, device="cuda", elastic=False, elastic_seed=None,
-                 intensity=False, intensity_seed=None, rotation=False, rotation_seed=None):
+                 intensity=False, intensity_seed=None, rotation=False, rotation_seed=None, carvemix=False, carvemix_seed=None):
         super(SimpleReader, self).__init__()
         self.store = cases if isinstance(cases, ResidentCases) else None
         self.cases = cases if self.store is not None else list(cases)
@@ -1057,6 +1221,10 @@ class SimpleReader(torch.utils.data.Dataset):
         self.intensity_rng = random.Random(intensity_seed)
         self.rotation = rotation if isinstance(rotation, RotationConfig) else (RotationConfig() if rotation else None)
         self.rotation_rng = random.Random(rotation_seed)
+        self.carvemix = carvemix if isinstance(carvemix, CarveMixConfig) else (CarveMixConfig() if carvemix else None)
+        self.carvemix_rng = random.Random(carvemix_seed)
+        self.carvemix_np_rng = np.random.RandomState(self.carvemix_rng.getrandbits(32))      # the donor's crop centre, gain and bias
+        self.last_params = None                                                              # the draws of the latest item (see _draw)
         self.real_length = len(self.cases)
         self.patches_from_current_image = self.patches_from_single_image + 1     # first item loads (the reference's constructor + first item do)
         self.current_image_index = 0
@@ -1084,11 +1252,35 @@ class SimpleReader(torch.utils.data.Dataset):
             rot = draw_rotation_params(self.rotation_rng, self.rotation)
             if rot is not None:
                 p["rotation"] = rot
+        if self.carvemix is not None:
+            mix = draw_carvemix_params(self.carvemix_rng, self.carvemix, self.real_length)
+            if mix is not None:
+                mix["case"] = self._donor_case(mix["donor"])
+                q = draw_augment_params(mix["case"].bbox, self.patch_size, int(self.case.image.shape[0]), rng=self.carvemix_rng, np_rng=self.carvemix_np_rng)
+                if int(self.patch_size[0]) != int(self.patch_size[1]):
+                    q["transpose"] = p["transpose"]              # the donor must land in the receiver's layout; its own draw was still made
+                mix["params"] = q
+                p["carvemix"] = mix
+        self.last_params = p
         return p
+
+    def _donor_case(self, index):
+        """the donor's case: a view of the store, or a `DeviceCase` built for this sample (the receiver's own case is reused)"""
+        if self.store is not None:
+            return self.store[index]
+        if index == self.current_image_index and self.case is not None:
+            return self.case
+        src = self.cases[index]
+        item = src() if callable(src) else src
+        return DeviceCase(item[0], item[1], self.patch_size, self.device, soft=item[2] if len(item) > 2 else None)
 
     def __getitem__(self, index):
         p = self._draw(index)
         data, target = augment_patch(self.case, p)
+        mix = p.get("carvemix")
+        if mix is not None:
+            donor_data, donor_target = augment_patch(mix["case"], mix["params"])
+            carvemix(data[None], target[None], donor_data[None], donor_target[None], [mix["u"]], [mix["side"]])
         if self.intensity is not None:
             data = intensity_augment(data, draw_intensity_params(int(data.shape[0]), self.intensity_rng, self.intensity))
         return [data], [target]
@@ -1101,7 +1293,8 @@ class ResidentLoader(object):
     """Stands in for `torch.utils.data.DataLoader` over a `SimpleReader` on a `ResidentCases` store (`Trainer.train` only iterates it and reads
     `len()`): for every index batch of `batch_sampler` -- default `BatchSampler(RandomSampler(reader), batch_size, drop_last)` -- the reader's draws
     are made sample by sample in `__getitem__`'s order, ONE `augment_batch` launch writes the batch (a batch with an elastic sample falls back to
-    per-sample `augment_patch` calls and `torch.stack`), `intensity_augment` runs per sample, and ([data], [target]) is yielded: the batches of
+    per-sample `augment_patch` calls and `torch.stack`), the K samples that drew a CarveMix donor get their donors from ONE more `augment_batch`
+    launch and are mixed in place by one `carvemix` call, `intensity_augment` runs per sample, and ([data], [target]) is yielded: the batches of
     `DataLoader(reader, batch_sampler=..., num_workers=0)` under the same seeds, bit for bit, without the per-sample tensors and the stack."""
 
     def __init__(self, reader, batch_size=1, batch_sampler=None, drop_last=True):
@@ -1127,6 +1320,11 @@ class ResidentLoader(object):
                 data, target = torch.stack([d for d, _ in items]), torch.stack([t for _, t in items])
             else:
                 data, target = _augment_views(views, params, tuple(int(v) for v in r.patch_size))
+            mixed = [n for n, p in enumerate(params) if p.get("carvemix") is not None]
+            if mixed:                                        # the K donors of the batch: one more gather, one map, one threshold call, one mix launch
+                mixes = [params[n]["carvemix"] for n in mixed]
+                donor_data, donor_target = _augment_views([m["case"] for m in mixes], [m["params"] for m in mixes], tuple(int(v) for v in r.patch_size))
+                carvemix(data, target, donor_data, donor_target, [m["u"] for m in mixes], [m["side"] for m in mixes], dst=mixed)
             if r.intensity is not None:
                 data = torch.stack([intensity_augment(data[n], draw_intensity_params(int(data.shape[1]), r.intensity_rng, r.intensity))
                                     for n in range(int(data.shape[0]))])

@@ -1095,6 +1095,34 @@ int ru_case_unpack(const void* image, const unsigned char* label, const float* s
 int ru_augment_batch_packed(const ru_case_desc* cases, const ru_patch_desc* patches, int N, const int* patch, float* data_out, float* target_out,
                             ru_stream_t stream);
 
+/* ---------------------------------------------------------------- CarveMix: lesion-aware mixing of two patches (csrc/carvemix.hip).  Opt-in; the
+ * entry points above are not touched.  Written from the paper (Zhang et al., MICCAI 2021); not checked against the authors' code.
+ * A donor patch (Xa [C][D][H][W], Ya [3][D][H][W]) is carved into a receiver patch (Xb, Yb) of the same shape, float32, channel 0 of the target
+ * being WT, for two host draws u in [0, 1) (float64) and side in {RU_CARVE_OUTER, RU_CARVE_INNER}:
+ *   G = Ya[0] > 0.5f (the mask rule of ru_signed_sqdist), V = |G|, n = D H W;  s = ru_signed_sqdist(Ya[0]) (>= 1 outside G, <= -1 inside);
+ *   R2 = the largest integer q with q^3 <= V^2 (64-bit integer search; floor(V^(2/3)), the squared form of the paper's lambda_u = V^(1/3));
+ *   outer: T = floor((u u) R2);  inner: T = -ceil(((u u) R2) 0.25)  -- float64, plain IEEE multiplies, nothing fused;
+ *   V == 0: T = INT32_MIN (nothing is carved);  V == n: T = INT32_MAX (the output is the donor);
+ *   M = s <= T;  X = M ? Xa : Xb per channel, Y = M ? Ya : Yb: a select of 32-bit words, so NaN and -0.0f pass through bit for bit.
+ * ru_carvemix_threshold: wt [K][n] float32 (the donors' WT channels, as handed to ru_signed_sqdist), u [K] and side [K] HOST arrays that travel as
+ *   kernel arguments (RU_CARVE_BATCH_MAX donors per launch, more are sent in chunks).  V is counted exactly in integers (one partial per workgroup,
+ *   added in a fixed order); T_out int32 [K] and V_out int64 [K] are DEVICE arrays.  n <= 2^27.  ws: ru_carvemix_workspace_bytes(K, n).
+ * ru_carvemix_mix: ONE launch (per RU_CARVE_BATCH_MAX donors) for the batch: donor k (donor_data [K][C][n], donor_target [K][3][n], s [K][n], T [K]
+ *   on the DEVICE) goes into receiver dst[k] of data [N][C][n] / target [N][3][n], IN PLACE; dst is a HOST array of K distinct indices.  Quads
+ *   without a selected voxel are neither loaded nor stored.  mask_out (optional, uint8 [K][n]) receives M.  Tensors of a pair that do not share an
+ *   offset from a 16-byte boundary (or n % 4 != 0) go one voxel at a time.
+ * Both only enqueue: no float atomics, no synchronisation, two calls give identical bytes.  Refused (RU_EINVAL, before any launch): a null or
+ * misaligned pointer, K < 1, K > N, C outside 1..8, an extent <= 0 or n > 2^27, u outside [0, 1), an unknown side, dst outside [0, N) or not
+ * distinct, a donor tensor, the map, T or mask_out overlapping a receiver tensor, a workspace that is too small. */
+#define RU_CARVE_OUTER 0
+#define RU_CARVE_INNER 1
+#define RU_CARVE_BATCH_MAX 8              /* donors per launch: 8 x 64 bytes of pointers and lanes travel as kernel arguments */
+size_t ru_carvemix_workspace_bytes(int K, size_t n);
+int ru_carvemix_threshold(const float* wt, int K, size_t n, const double* u, const int* side, int* T_out, long long* V_out, void* ws,
+                          size_t ws_bytes, ru_stream_t stream);
+int ru_carvemix_mix(const float* donor_data, const float* donor_target, const int* s, const int* T, int K, const int* dst, int N, int C, int D,
+                    int H, int W, float* data, float* target, unsigned char* mask_out, ru_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
