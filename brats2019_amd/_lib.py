@@ -134,6 +134,10 @@ SIGNATURES = {
     "ru_lesion_workspace_bytes": (_sz, [_i] * 7),
     "ru_lesion_metrics": (_i, [_vp, _vp] + [_i] * 7 + [C.c_longlong, _d, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "ru_lesion_accumulate": (_i, [_vp, _vp] + [_i] * 4 + [_vp]),
+    "ru_surface_distances": (_i, [_vp, _vp] + [_i] * 6 + [_d, C.POINTER(C.c_uint), _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ru_surface_extras_accumulate": (_i, [_vp, _vp] + [_i] * 5 + [_vp]),
+    "ru_lesion_distances_workspace_bytes": (_sz, [_i] * 8),
+    "ru_lesion_distances": (_i, [_vp, _vp] + [_i] * 7 + [C.c_longlong, _d, C.POINTER(C.c_uint), _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "ru_tile_gather": (_i, [_vp, _vp] + [_i] * 6 + [C.POINTER(_i), _i, _i, _i, _vp]),
     "ru_tile_scatter": (_i, [_vp, _vp] + [_i] * 6 + [C.POINTER(_i), _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
     "ru_blend_accumulate": (_i, [_vp, _vp, _vp] + [_i] * 8 + [C.POINTER(_i), _i, C.POINTER(_i), _i, C.POINTER(_i), _i, _i, _i, _vp]),
@@ -224,6 +228,18 @@ SURFACE_COLUMNS = {"dice": 0, "sensitivity": 1, "specificity": 2, "hd95": 3}
 # ru_lesion_metrics / ru_lesion_accumulate (include/resunet_hip.h)
 LESION_COUNTS, LESION_TABLE_COLUMNS, LESION_CHUNK = 6, 5, 8
 LESION_COLUMNS = {"dice": 0, "hd95": 1}
+
+# ru_surface_distances / ru_lesion_distances (include/resunet_hip.h): at most SURFACE_MAX_TOL tolerances per call.  For T tolerances the
+# extras' rows are (NSD_0 .. NSD_T-1, ASSD, HD) and the lesion-wise summary's (LesionNSD_0 .. LesionNSD_T-1, LesionASSD).
+SURFACE_MAX_TOL = 8
+
+
+def surface_extras_columns(t):
+    return dict([("nsd%d" % i, i) for i in range(t)] + [("assd", t), ("hd", t + 1)])
+
+
+def lesion_extras_columns(t):
+    return dict([("nsd%d" % i, i) for i in range(t)] + [("assd", t)])
 
 # ru_postprocess_regions (include/resunet_hip.h)
 POSTPROCESS_MASKS, POSTPROCESS_LABELS, POSTPROCESS_REGIONS, POSTPROCESS_STATS = 0, 1, 3, 6

@@ -20,6 +20,8 @@
 //   ls_item_kernel       : one chunk of lesions: (M_i, L_i) as bit planes of the whole grid, handed to surface.hip's packed entry
 //                          (surface_packed.hpp), which writes Dice_i and HD95_i.
 //   ls_summary_kernel    : one thread per (n, k): the float64 sums in ascending lesion order, the counts, the optional table.
+//   ls_summary_ex_kernel : (ru_lesion_distances only) the same loop over the per-lesion {NSD_t, ASSD, HD} that the packed entry's extras
+//                          sibling wrote: LesionNSD_t and LesionASSD, the optional per-lesion table of extras.
 // Integer atomics only.  The one host synchronisation reads the lesion counts back: the chunk loop needs them.
 #include "ru_common.h"
 #include "pw_helpers.hpp"
@@ -50,12 +52,12 @@ struct LsWs {
     int *nles, *nfp, *pz, *pp, *cnt, *roots, *sorted;
     unsigned *vol, *msz, *tp;
     u64 *bits, *tab, *icounts;
-    double* vals;
+    double *vals, *ex;
     void* sf;
     size_t bytes;
 };
 
-LsWs ls_layout(char* base, size_t NK, const MaskGeom& g, unsigned slots, size_t max_lesions) {
+LsWs ls_layout(char* base, size_t NK, const MaskGeom& g, unsigned slots, size_t max_lesions, size_t ex_cols = 0) {
     LsWs w;
     size_t off = 0;
     auto take = [&](size_t bytes) { char* p = base + off; off += align_up(bytes, 256); return p; };
@@ -74,6 +76,7 @@ LsWs ls_layout(char* base, size_t NK, const MaskGeom& g, unsigned slots, size_t 
     w.nles = (int*)take(NK * sizeof(int));
     w.nfp = (int*)take(NK * sizeof(int));
     w.sf = (void*)take(sf_packed_workspace_bytes(RU_LESION_CHUNK, g.D, g.H, g.W));
+    w.ex = (double*)take(NK * max_lesions * ex_cols * sizeof(double));        // ru_lesion_distances only: the per-lesion extras, last
     w.bytes = off;
     return w;
 }
@@ -321,6 +324,40 @@ __global__ void ls_summary_kernel(int NK, int max_lesions, const int* __restrict
     q[4] = (u64)fp;
 }
 
+// grid cdiv(N*K, 64): ex [N*K][max_lesions][T + 2] = surface.hip's {NSD_0..NSD_T-1, ASSD, HD} per lesion; ls_summary_kernel's loop and
+// its kept rule, the sums in the same ascending order
+__global__ void ls_summary_ex_kernel(int NK, int max_lesions, int T, const int* __restrict__ nles, const int* __restrict__ nfp, const unsigned* __restrict__ vol,
+                                     const double* __restrict__ ex, long long min_volume, double empty_value, double* __restrict__ summary_ex,
+                                     double* __restrict__ table_ex) {
+#pragma clang fp contract(off)
+    const int nk = blockIdx.x * blockDim.x + threadIdx.x;
+    if (nk >= NK) return;
+    const int n = nles[nk], fp = nfp[nk], cols = T + 2;
+    u64 kept = 0;
+    double sum[RU_SURFACE_MAX_TOL + 1];
+    for (int t = 0; t <= T; ++t) sum[t] = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const size_t at = (size_t)nk * max_lesions + i;
+        const double* e = ex + at * cols;
+        if (table_ex)
+            for (int t = 0; t < cols; ++t) table_ex[at * cols + t] = e[t];
+        if ((long long)vol[at] <= min_volume) continue;
+        ++kept;
+        for (int t = 0; t <= T; ++t) sum[t] += e[t];
+    }
+    const u64 den = kept + (u64)fp;
+    double* o = summary_ex + (size_t)nk * (T + 1);
+    for (int t = 0; t < T; ++t) o[t] = den ? sum[t] / (double)den : 1.0;
+    o[T] = den ? (sum[T] + (double)fp * empty_value) / (double)den : 0.0;
+}
+
+// the extras of one ru_lesion_distances call; T < 0: none (ru_lesion_metrics)
+struct LsEx {
+    const unsigned* tol_bins;
+    int T;
+    double *summary_ex, *table_ex;
+};
+
 }  // namespace
 }  // namespace ru
 
@@ -331,26 +368,28 @@ extern "C" size_t ru_lesion_workspace_bytes(int kind, int N, int C, int D, int H
     return ls_layout(nullptr, (size_t)N * mask_regions(kind, C), mask_geom(D, H, W), ls_slots(D, H, W), (size_t)max_lesions).bytes;
 }
 
-extern "C" int ru_lesion_metrics(const void* pred, const void* target, int kind, int N, int C, int D, int H, int W, int dilation, long long min_volume,
-                                 double empty_value, double* summary, unsigned long long* counts, double* table, int max_lesions, void* ws,
-                                 size_t ws_bytes, ru_stream_t stream) {
-    RU_REQUIRE(pred && target && summary && counts && N > 0 && C > 0, "ru_lesion_metrics: bad argument");
-    RU_REQUIRE(kind == RU_SURFACE_PROB || (kind == RU_SURFACE_LABEL && C == 1), "ru_lesion_metrics: bad kind %d (C = %d)", kind, C);
+namespace {
+
+int ls_entry(const char* who, const void* pred, const void* target, int kind, int N, int C, int D, int H, int W, int dilation, long long min_volume,
+             double empty_value, double* summary, unsigned long long* counts, double* table, const LsEx& ex, int max_lesions, void* ws,
+             size_t ws_bytes, ru_stream_t stream) {
+    RU_REQUIRE(pred && target && summary && counts && N > 0 && C > 0, "%s: bad argument", who);
+    RU_REQUIRE(kind == RU_SURFACE_PROB || (kind == RU_SURFACE_LABEL && C == 1), "%s: bad kind %d (C = %d)", who, kind, C);
     RU_REQUIRE(D >= 1 && H >= 1 && W >= 1 && D <= MAX_EXTENT && H <= MAX_EXTENT && W <= MAX_EXTENT,
-               "ru_lesion_metrics: extents %d x %d x %d: every axis must be in [1, %d]", D, H, W, MAX_EXTENT);
-    RU_REQUIRE((size_t)D * H * W < (size_t)INT_MAX, "ru_lesion_metrics: volume too large for 32-bit voxel indices");
-    RU_REQUIRE(dilation >= 0 && dilation <= MAX_EXTENT && min_volume >= 0, "ru_lesion_metrics: dilation %d, min_volume %lld: both must be >= 0", dilation,
-               min_volume);
-    RU_REQUIRE(max_lesions >= 1 && max_lesions <= LS_MAX_LESIONS, "ru_lesion_metrics: max_lesions %d: must be in [1, %d]", max_lesions, LS_MAX_LESIONS);
+               "%s: extents %d x %d x %d: every axis must be in [1, %d]", who, D, H, W, MAX_EXTENT);
+    RU_REQUIRE((size_t)D * H * W < (size_t)INT_MAX, "%s: volume too large for 32-bit voxel indices", who);
+    RU_REQUIRE(dilation >= 0 && dilation <= MAX_EXTENT && min_volume >= 0, "%s: dilation %d, min_volume %lld: both must be >= 0", who, dilation, min_volume);
+    RU_REQUIRE(max_lesions >= 1 && max_lesions <= LS_MAX_LESIONS, "%s: max_lesions %d: must be in [1, %d]", who, max_lesions, LS_MAX_LESIONS);
     const int K = mask_regions(kind, C);
-    RU_REQUIRE((long long)N * K <= 65535, "ru_lesion_metrics: N * regions = %lld: the grid needs N * regions <= 65535", (long long)N * K);
-    const size_t need = ru_lesion_workspace_bytes(kind, N, C, D, H, W, max_lesions);
-    RU_REQUIRE(ws && need && ws_bytes >= need, "ru_lesion_metrics: workspace too small");
+    RU_REQUIRE((long long)N * K <= 65535, "%s: N * regions = %lld: the grid needs N * regions <= 65535", who, (long long)N * K);
+    const size_t ex_cols = ex.T >= 0 ? (size_t)ex.T + 2 : 0;
+    const size_t need = ls_layout(nullptr, (size_t)N * K, mask_geom(D, H, W), ls_slots(D, H, W), (size_t)max_lesions, ex_cols).bytes;
+    RU_REQUIRE(ws && ws_bytes >= need, "%s: workspace too small", who);
     hipStream_t st = (hipStream_t)stream;
     const MaskGeom s = mask_geom(D, H, W);
     const unsigned slots = ls_slots(D, H, W);
     const int NK = N * K;
-    const LsWs w = ls_layout((char*)ws, (size_t)NK, s, slots, (size_t)max_lesions);
+    const LsWs w = ls_layout((char*)ws, (size_t)NK, s, slots, (size_t)max_lesions, ex_cols);
     const size_t nclear = std::max((size_t)NK * slots, (size_t)NK * max_lesions);
     hipLaunchKernelGGL(ls_clear_kernel, dim3(grid1d(nclear, 256, 4096)), dim3(256), 0, st, w, (size_t)NK, (size_t)max_lesions, slots, summary, counts);
     RU_CHECK_LAUNCH("ls_clear_kernel");
@@ -387,21 +426,54 @@ extern "C" int ru_lesion_metrics(const void* pred, const void* target, int kind,
     e = hipStreamSynchronize(st);
     if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(lesion counts)");
     for (int nk = 0; nk < NK; ++nk)
-        RU_REQUIRE(nles[nk] <= max_lesions, "ru_lesion_metrics: %d ground-truth lesions in sample %d, region %d: more than max_lesions = %d", nles[nk],
-                   nk / K, nk % K, max_lesions);
+        RU_REQUIRE(nles[nk] <= max_lesions, "%s: %d ground-truth lesions in sample %d, region %d: more than max_lesions = %d", who, nles[nk], nk / K,
+                   nk % K, max_lesions);
     for (int nk = 0; nk < NK; ++nk)
         for (int i0 = 0; i0 < nles[nk]; i0 += RU_LESION_CHUNK) {
             const int items = std::min(RU_LESION_CHUNK, nles[nk] - i0);
             hipLaunchKernelGGL(ls_item_kernel, dim3(D, items), dim3(256), 0, st, s, slots, w.bits, w.pz, w.pp, w.sorted, w.tab, w.vol, w.msz, w.tp, max_lesions, nk,
                                i0, sf_packed_bits(w.sf), w.icounts);
             RU_CHECK_LAUNCH("ls_item_kernel");
-            const int rc = sf_packed_run(items, D, H, W, w.sf, w.icounts, empty_value, w.vals + ((size_t)nk * max_lesions + i0) * 4, st);
+            const size_t at = (size_t)nk * max_lesions + i0;
+            const int rc = ex.T >= 0 ? sf_packed_run_extras(items, D, H, W, w.sf, w.icounts, empty_value, w.vals + at * 4, ex.tol_bins, ex.T,
+                                                            w.ex + at * ex_cols, st)
+                                     : sf_packed_run(items, D, H, W, w.sf, w.icounts, empty_value, w.vals + at * 4, st);
             if (rc) return rc;
         }
     hipLaunchKernelGGL(ls_summary_kernel, dim3(cdiv(NK, 64)), dim3(64), 0, st, NK, max_lesions, w.nles, w.nfp, w.vol, w.msz, w.tp, w.vals, min_volume,
                        empty_value, summary, counts, table);
     RU_CHECK_LAUNCH("ls_summary_kernel");
+    if (ex.T >= 0) {
+        hipLaunchKernelGGL(ls_summary_ex_kernel, dim3(cdiv(NK, 64)), dim3(64), 0, st, NK, max_lesions, ex.T, w.nles, w.nfp, w.vol, w.ex, min_volume,
+                           empty_value, ex.summary_ex, ex.table_ex);
+        RU_CHECK_LAUNCH("ls_summary_ex_kernel");
+    }
     return RU_OK;
+}
+
+}  // namespace
+
+extern "C" int ru_lesion_metrics(const void* pred, const void* target, int kind, int N, int C, int D, int H, int W, int dilation, long long min_volume,
+                                 double empty_value, double* summary, unsigned long long* counts, double* table, int max_lesions, void* ws,
+                                 size_t ws_bytes, ru_stream_t stream) {
+    const LsEx none = {nullptr, -1, nullptr, nullptr};
+    return ls_entry("ru_lesion_metrics", pred, target, kind, N, C, D, H, W, dilation, min_volume, empty_value, summary, counts, table, none,
+                    max_lesions, ws, ws_bytes, stream);
+}
+
+extern "C" size_t ru_lesion_distances_workspace_bytes(int kind, int N, int C, int D, int H, int W, int max_lesions, int T) {
+    if (!ls_shape_ok(kind, N, C, D, H, W, max_lesions) || (size_t)D * H * W >= (size_t)INT_MAX || T < 0 || T > RU_SURFACE_MAX_TOL) return 0;
+    return ls_layout(nullptr, (size_t)N * mask_regions(kind, C), mask_geom(D, H, W), ls_slots(D, H, W), (size_t)max_lesions, (size_t)T + 2).bytes;
+}
+
+extern "C" int ru_lesion_distances(const void* pred, const void* target, int kind, int N, int C, int D, int H, int W, int dilation, long long min_volume,
+                                   double empty_value, const unsigned* tol_bins, int T, double* summary, unsigned long long* counts, double* table,
+                                   double* summary_ex, double* table_ex, int max_lesions, void* ws, size_t ws_bytes, ru_stream_t stream) {
+    RU_REQUIRE(T >= 0 && T <= RU_SURFACE_MAX_TOL && (T == 0 || tol_bins) && summary_ex,
+               "ru_lesion_distances: T = %d tolerances: needs 0 <= T <= %d, their bin limits and `summary_ex`", T, RU_SURFACE_MAX_TOL);
+    const LsEx ex = {tol_bins, T, summary_ex, table_ex};
+    return ls_entry("ru_lesion_distances", pred, target, kind, N, C, D, H, W, dilation, min_volume, empty_value, summary, counts, table, ex,
+                    max_lesions, ws, ws_bytes, stream);
 }
 
 extern "C" int ru_lesion_accumulate(const double* summary, double* acc, int N, int K, int nacc, int column, ru_stream_t stream) {

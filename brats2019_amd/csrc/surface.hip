@@ -18,6 +18,10 @@
 //                           distances, (D-1)^2 + (H-1)^2 + (W-1)^2 + 1 bins.
 //   sf_select_kernel      : one workgroup per (n, k): a prefix scan over the histogram finds the order statistics s_(i), s_(j), then
 //                           the empty rules and numpy's lerp; writes {Dice, sensitivity, specificity, HD95} in float64.
+//   sf_tolerance_kernel   : (ru_surface_distances and the packed sibling only) one workgroup per (n, k) rereads the histogram: the counts
+//                           of the distances within each of T <= RU_SURFACE_MAX_TOL tolerances (64-bit integers), sum h_b sqrt(b) in
+//                           float64 (per-thread partials in bin order, then a fixed LDS tree) and the largest non-empty bin; writes
+//                           {NSD_0..NSD_T-1, ASSD, HD}.  The tolerances are integer bin limits passed by value: nothing is uploaded.
 // column_mean_kernel (a call of its own) adds the batch mean of one of the four columns to a float64 device accumulator.
 #include "ru_common.h"
 #include "surface_packed.hpp"
@@ -179,6 +183,88 @@ __global__ __launch_bounds__(SF_SELECT_THREADS) void sf_select_kernel(const unsi
     o[RU_SURFACE_HD95] = hd;
 }
 
+// the tolerances of one call, by value: bin b counts for tolerance t when b <= tb[t]
+struct SfTol {
+    unsigned tb[RU_SURFACE_MAX_TOL];
+    int T;
+    double* out;                                                                      // [NK][T + 2], or NULL: no extras
+};
+
+// grid (N*K), SF_SELECT_THREADS threads.  ex[nk*(T+2) + 0..T-1] = NSD_t, [T] = ASSD, [T+1] = HD.
+__global__ __launch_bounds__(SF_SELECT_THREADS) void sf_tolerance_kernel(const unsigned* __restrict__ hist, size_t bins, const u64* __restrict__ counts,
+                                                                         double empty_value, SfTol tol) {
+#pragma clang fp contract(off)
+    __shared__ double tree[SF_SELECT_THREADS];
+    __shared__ u64 wsum[SF_SELECT_THREADS / 64][RU_SURFACE_MAX_TOL];
+    __shared__ unsigned wmax[SF_SELECT_THREADS / 64];
+    const int nk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const u64* cn = counts + (size_t)nk * RU_SURFACE_COUNTS;
+    const u64 P = cn[0], G = cn[1], n = cn[3] + cn[4];
+    double* o = tol.out + (size_t)nk * (tol.T + 2);
+    if (P == 0 || G == 0) {                                                           // (uniform over the workgroup)
+        if (tid == 0) {
+            const bool both = P == 0 && G == 0;
+            for (int t = 0; t < tol.T; ++t) o[t] = both ? 1.0 : 0.0;
+            o[tol.T] = o[tol.T + 1] = both ? 0.0 : empty_value;
+        }
+        return;
+    }
+    const unsigned* __restrict__ hn = hist + (size_t)nk * bins;
+    const size_t chunk = (bins + SF_SELECT_THREADS - 1) / SF_SELECT_THREADS;
+    const size_t lo = min(bins, (size_t)tid * chunk), hi = min(bins, lo + chunk);
+    u64 c[RU_SURFACE_MAX_TOL];
+#pragma unroll
+    for (int t = 0; t < RU_SURFACE_MAX_TOL; ++t) c[t] = 0;
+    double a = 0.0;
+    unsigned top = 0;
+    for (size_t b = lo; b < hi; ++b) {
+        const unsigned h = hn[b];
+        if (!h) continue;
+        top = (unsigned)b;
+#pragma unroll
+        for (int t = 0; t < RU_SURFACE_MAX_TOL; ++t) c[t] += (t < tol.T && b <= (size_t)tol.tb[t]) ? h : 0u;
+        a += (double)h * sqrt((double)b);                                             // three roundings: sqrt, product, sum
+    }
+    // integers: wave shuffles, then the 16 wave sums; order is free, the sums are exact
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+        for (int t = 0; t < RU_SURFACE_MAX_TOL; ++t) c[t] += __shfl_xor(c[t], m);
+        top = max(top, (unsigned)__shfl_xor((int)top, m));
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int t = 0; t < RU_SURFACE_MAX_TOL; ++t) wsum[wave][t] = c[t];
+        wmax[wave] = top;
+    }
+    // float64: the fixed tree, thread i adds thread i + o
+    tree[tid] = a;
+    __syncthreads();
+    for (int s = SF_SELECT_THREADS / 2; s >= 1; s >>= 1) {
+        if (tid < s) tree[tid] += tree[tid + s];
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    for (int t = 0; t < tol.T; ++t) {
+        u64 ct = 0;
+        for (int w = 0; w < SF_SELECT_THREADS / 64; ++w) ct += wsum[w][t];
+        o[t] = (double)ct / (double)n;
+    }
+    unsigned m = 0;
+    for (int w = 0; w < SF_SELECT_THREADS / 64; ++w) m = max(m, wmax[w]);
+    o[tol.T] = tree[0] / (double)n;
+    o[tol.T + 1] = sqrt((double)m);
+}
+
+// the tolerances of a call, checked: T in [0, RU_SURFACE_MAX_TOL], host limits, a destination
+bool sf_tol_make(const unsigned* tol_bins, int T, double* extras, SfTol* tol) {
+    if (T < 0 || T > RU_SURFACE_MAX_TOL || (T > 0 && !tol_bins) || !extras) return false;
+    for (int t = 0; t < RU_SURFACE_MAX_TOL; ++t) tol->tb[t] = t < T ? tol_bins[t] : 0u;
+    tol->T = T;
+    tol->out = extras;
+    return true;
+}
+
 // workspace slices of NK pairs of masks: per pair 4 bit planes (P, G, dP, dG) of `words` each, 2 distance maps of V, one histogram of `bins`
 struct SfWs {
     u64* bits;
@@ -204,7 +290,8 @@ size_t sf_workspace_bytes(int kind, int N, int C, int D, int H, int W) {
 
 // clears the first `ncounts` counts and the histograms, then (pack, if any, and) the passes on NK pairs of packed masks
 template <class Pack>
-int sf_run(int D, int H, int W, int NK, void* ws, u64* counts, size_t ncounts, double empty_value, double* values, hipStream_t st, Pack pack) {
+int sf_run(int D, int H, int W, int NK, void* ws, u64* counts, size_t ncounts, double empty_value, double* values, const SfTol& tol, hipStream_t st,
+           Pack pack) {
     const MaskGeom s = mask_geom(D, H, W);
     const SfWs w = sf_layout(ws, (size_t)NK, D, H, W);
     const size_t nhist = (size_t)NK * w.bins;
@@ -220,7 +307,22 @@ int sf_run(int D, int H, int W, int NK, void* ws, u64* counts, size_t ncounts, d
     if (rl) return rl;
     hipLaunchKernelGGL(sf_select_kernel, dim3(NK), dim3(SF_SELECT_THREADS), 0, st, w.hist, s.V, w.bins, counts, empty_value, values);
     RU_CHECK_LAUNCH("sf_select_kernel");
+    if (tol.out) {
+        hipLaunchKernelGGL(sf_tolerance_kernel, dim3(NK), dim3(SF_SELECT_THREADS), 0, st, w.hist, w.bins, counts, empty_value, tol);
+        RU_CHECK_LAUNCH("sf_tolerance_kernel");
+    }
     return RU_OK;
+}
+
+const SfTol SF_NO_TOL = {{0, 0, 0, 0, 0, 0, 0, 0}, 0, nullptr};
+
+// acc[i] += the batch mean of column `column` of rows of `ncols` (column_mean_kernel's sum, for a row stride known at run time)
+__global__ void sf_extras_mean_kernel(const double* __restrict__ values, double* __restrict__ acc, int N, int K, int nacc, int ncols, int column) {
+    const int i = threadIdx.x;
+    if (i >= nacc) return;
+    double sum = 0.0;
+    for (int n = 0; n < N; ++n) sum += values[((size_t)n * K + i) * ncols + column];
+    acc[i] += sum / (double)N;
 }
 
 }  // namespace
@@ -232,7 +334,16 @@ unsigned long long* sf_packed_bits(void* ws) { return (u64*)ws; }
 int sf_packed_run(int items, int D, int H, int W, void* ws, unsigned long long* counts, double empty_value, double* values, hipStream_t st) {
     RU_REQUIRE(ws && counts && values && items > 0 && (long long)items * 2 <= 65535 && mask_shape_ok(RU_SURFACE_PROB, 1, items, D, H, W),
                "sf_packed_run: bad argument");
-    return sf_run(D, H, W, items, ws, counts, 0, empty_value, values, st, [](const MaskGeom&, u64*) { return RU_OK; });
+    return sf_run(D, H, W, items, ws, counts, 0, empty_value, values, SF_NO_TOL, st, [](const MaskGeom&, u64*) { return RU_OK; });
+}
+
+int sf_packed_run_extras(int items, int D, int H, int W, void* ws, unsigned long long* counts, double empty_value, double* values,
+                         const unsigned* tol_bins, int T, double* extras, hipStream_t st) {
+    RU_REQUIRE(ws && counts && values && items > 0 && (long long)items * 2 <= 65535 && mask_shape_ok(RU_SURFACE_PROB, 1, items, D, H, W),
+               "sf_packed_run_extras: bad argument");
+    SfTol tol;
+    RU_REQUIRE(sf_tol_make(tol_bins, T, extras, &tol), "sf_packed_run_extras: bad tolerances (T = %d)", T);
+    return sf_run(D, H, W, items, ws, counts, 0, empty_value, values, tol, st, [](const MaskGeom&, u64*) { return RU_OK; });
 }
 
 }  // namespace ru
@@ -241,17 +352,19 @@ using namespace ru;
 
 extern "C" size_t ru_surface_workspace_bytes(int kind, int N, int C, int D, int H, int W) { return sf_workspace_bytes(kind, N, C, D, H, W); }
 
-extern "C" int ru_surface_metrics(const void* pred, const void* target, int kind, int N, int C, int D, int H, int W, double empty_value,
-                                  double* values, unsigned long long* counts, void* ws, size_t ws_bytes, ru_stream_t stream) {
-    RU_REQUIRE(pred && target && values && counts && N > 0 && C > 0, "ru_surface_metrics: bad argument");
-    RU_REQUIRE(kind == RU_SURFACE_PROB || (kind == RU_SURFACE_LABEL && C == 1), "ru_surface_metrics: bad kind %d (C = %d)", kind, C);
+namespace {
+
+int sf_entry(const char* who, const void* pred, const void* target, int kind, int N, int C, int D, int H, int W, double empty_value, double* values,
+             unsigned long long* counts, const SfTol& tol, void* ws, size_t ws_bytes, ru_stream_t stream) {
+    RU_REQUIRE(pred && target && values && counts && N > 0 && C > 0, "%s: bad argument", who);
+    RU_REQUIRE(kind == RU_SURFACE_PROB || (kind == RU_SURFACE_LABEL && C == 1), "%s: bad kind %d (C = %d)", who, kind, C);
     RU_REQUIRE(D >= 1 && H >= 1 && W >= 1 && D <= MAX_EXTENT && H <= MAX_EXTENT && W <= MAX_EXTENT,
-               "ru_surface_metrics: extents %d x %d x %d: every axis must be in [1, %d]", D, H, W, MAX_EXTENT);
+               "%s: extents %d x %d x %d: every axis must be in [1, %d]", who, D, H, W, MAX_EXTENT);
     const int K = mask_regions(kind, C), NK = N * K;
-    RU_REQUIRE((long long)N * K * 2 <= 65535, "ru_surface_metrics: N * regions = %lld: the grid needs 2 * N * regions <= 65535", (long long)N * K);
-    RU_REQUIRE(ws && ws_bytes >= sf_workspace_bytes(kind, N, C, D, H, W), "ru_surface_metrics: workspace too small");
+    RU_REQUIRE((long long)N * K * 2 <= 65535, "%s: N * regions = %lld: the grid needs 2 * N * regions <= 65535", who, (long long)N * K);
+    RU_REQUIRE(ws && ws_bytes >= sf_workspace_bytes(kind, N, C, D, H, W), "%s: workspace too small", who);
     hipStream_t st = (hipStream_t)stream;
-    return sf_run(D, H, W, NK, ws, counts, (size_t)NK * RU_SURFACE_COUNTS, empty_value, values, st, [&](const MaskGeom& s, u64* bits) {
+    return sf_run(D, H, W, NK, ws, counts, (size_t)NK * RU_SURFACE_COUNTS, empty_value, values, tol, st, [&](const MaskGeom& s, u64* bits) {
         if (kind == RU_SURFACE_PROB)
             hipLaunchKernelGGL(sf_pack_kernel<0>, dim3(D, NK), dim3(256), 0, st, pred, target, C, K, s, bits, counts);
         else
@@ -259,6 +372,30 @@ extern "C" int ru_surface_metrics(const void* pred, const void* target, int kind
         RU_CHECK_LAUNCH("sf_pack_kernel");
         return RU_OK;
     });
+}
+
+}  // namespace
+
+extern "C" int ru_surface_metrics(const void* pred, const void* target, int kind, int N, int C, int D, int H, int W, double empty_value,
+                                  double* values, unsigned long long* counts, void* ws, size_t ws_bytes, ru_stream_t stream) {
+    return sf_entry("ru_surface_metrics", pred, target, kind, N, C, D, H, W, empty_value, values, counts, SF_NO_TOL, ws, ws_bytes, stream);
+}
+
+extern "C" int ru_surface_distances(const void* pred, const void* target, int kind, int N, int C, int D, int H, int W, double empty_value,
+                                    const unsigned* tol_bins, int T, double* values, unsigned long long* counts, double* extras, void* ws,
+                                    size_t ws_bytes, ru_stream_t stream) {
+    SfTol tol;
+    RU_REQUIRE(sf_tol_make(tol_bins, T, extras, &tol), "ru_surface_distances: T = %d tolerances: needs 0 <= T <= %d, their bin limits and `extras`", T,
+               RU_SURFACE_MAX_TOL);
+    return sf_entry("ru_surface_distances", pred, target, kind, N, C, D, H, W, empty_value, values, counts, tol, ws, ws_bytes, stream);
+}
+
+extern "C" int ru_surface_extras_accumulate(const double* extras, double* acc, int N, int K, int nacc, int ncols, int column, ru_stream_t stream) {
+    RU_REQUIRE(extras && acc && N > 0 && K > 0 && nacc > 0 && nacc <= K && nacc <= 64 && ncols >= 1 && column >= 0 && column < ncols,
+               "ru_surface_extras_accumulate: bad argument");
+    hipLaunchKernelGGL(sf_extras_mean_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, extras, acc, N, K, nacc, ncols, column);
+    RU_CHECK_LAUNCH("sf_extras_mean_kernel");
+    return RU_OK;
 }
 
 extern "C" int ru_surface_accumulate(const double* values, double* acc, int N, int K, int nacc, int column, ru_stream_t stream) {

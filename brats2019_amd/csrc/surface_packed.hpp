@@ -11,5 +11,9 @@ namespace ru {
 size_t sf_packed_workspace_bytes(int items, int D, int H, int W);
 unsigned long long* sf_packed_bits(void* ws);
 int sf_packed_run(int items, int D, int H, int W, void* ws, unsigned long long* counts, double empty_value, double* values, hipStream_t st);
+// the same passes and the same `values`, then ru_surface_distances' finalize: extras [items][T + 2] = {NSD_0..NSD_T-1, ASSD, HD} for the
+// T <= RU_SURFACE_MAX_TOL host bin limits `tol_bins` (passed on by value: no upload).  Same workspace.
+int sf_packed_run_extras(int items, int D, int H, int W, void* ws, unsigned long long* counts, double empty_value, double* values,
+                         const unsigned* tol_bins, int T, double* extras, hipStream_t st);
 
 }  // namespace ru

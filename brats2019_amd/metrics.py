@@ -15,7 +15,10 @@ ru_dice1d_accumulate, ru_rmse_accumulate).
 Beyond the reference: the BraTS challenge's `Hausdorff95`, `Sensitivity` and `Specificity`, per channel on the `> 0.5` masks, from one
 pass sequence on the device (ru_surface_metrics: bit-packed masks and surfaces, an exact squared distance transform that fills a
 histogram of surface distances, an exact order statistic) and its accumulate launch (ru_surface_accumulate); and the challenge's
-lesion-wise ranking numbers `LesionWiseDice` and `LesionWiseHausdorff95` (ru_lesion_metrics, ru_lesion_accumulate)."""
+lesion-wise ranking numbers `LesionWiseDice` and `LesionWiseHausdorff95` (ru_lesion_metrics, ru_lesion_accumulate).  From the same
+histogram of surface distances: `SurfaceDice` (NSD at a tolerance), `AverageSurfaceDistance` (ASSD) and `LesionWiseSurfaceDice`
+(ru_surface_distances, ru_lesion_distances, ru_surface_extras_accumulate), and their float64 numpy / scipy restatements
+`surface_distances_host` and `lesion_distances_host`, which the tests hold the device to."""
 from __future__ import annotations
 
 import numpy as np
@@ -388,6 +391,163 @@ class LesionWiseHausdorff95(_LesionMetric):
 
     def __init__(self, name="LesionWiseHausdorff95", input_index=0, target_index=0, classes=4, empty_value=ops.HD95_EMPTY, dilation=3, min_volume=50):
         super(LesionWiseHausdorff95, self).__init__(name, input_index, target_index, classes, empty_value, dilation, min_volume)
+
+
+class _ExtrasMetric(_ColumnMetric):
+    """A column (an index) of ops.surface_distances' extras or ops.lesion_distances' summary_ex, rows of any width."""
+    _accumulate = staticmethod(ops.surface_extras_accumulate)
+
+
+class SurfaceDice(_ExtrasMetric):
+    """The normalized surface Dice (NSD, "surface Dice at tolerance tau") per channel on the `> 0.5` masks: the share of the surface voxels
+    of both masks, pooled, that lie within `tolerance` voxels (unit spacing) of the other mask's surface; surfaces and distances as
+    Hausdorff95's.  This is the voxel-surface form (MONAI's SurfaceDiceMetric counts the same way); it is NOT DeepMind's
+    surface-element-area form, and it was NOT compared with MONAI's code or any official evaluator.  Both masks empty: 1; one empty: 0.
+    update() never synchronises."""
+    column = 0
+
+    def __init__(self, name="SurfaceDice", input_index=0, target_index=0, classes=4, tolerance=1.0):
+        super(SurfaceDice, self).__init__(name, input_index, target_index, classes)
+        ops.tolerance_bins([tolerance])                                               # a bad tolerance fails here, not in the first update
+        self.tolerance = tolerance
+
+    def _score(self, pred, gr):
+        return ops.surface_distances(pred, gr, (self.tolerance,))[2]
+
+
+class AverageSurfaceDistance(_ExtrasMetric):
+    """The average symmetric surface distance (ASSD) per channel, in voxels at unit spacing: the mean over the surface voxels of both
+    masks, pooled, of the distance to the other mask's surface.  Both masks empty: 0; one empty: `empty_value`, Hausdorff95's convention,
+    NOT checked against any official evaluator.  update() never synchronises."""
+    column = 0
+
+    def __init__(self, name="AverageSurfaceDistance", input_index=0, target_index=0, classes=4, empty_value=ops.HD95_EMPTY):
+        super(AverageSurfaceDistance, self).__init__(name, input_index, target_index, classes)
+        self.empty_value = empty_value
+
+    def _score(self, pred, gr):
+        return ops.surface_distances(pred, gr, (), self.empty_value)[2]
+
+
+class LesionWiseSurfaceDice(_ExtrasMetric):
+    """The lesion-wise NSD of LesionWiseDice's matching: SurfaceDice's value per kept lesion against what it matched, 0 for a missed lesion
+    and for every false-positive component, divided by their number (1 when there is none).  NOT checked against the official evaluator.
+    update() synchronises once, as the other lesion-wise metrics do."""
+    column = 0
+
+    def __init__(self, name="LesionWiseSurfaceDice", input_index=0, target_index=0, classes=4, tolerance=1.0, dilation=3, min_volume=50):
+        super(LesionWiseSurfaceDice, self).__init__(name, input_index, target_index, classes)
+        ops.tolerance_bins([tolerance])
+        self.tolerance = tolerance
+        self.dilation = dilation
+        self.min_volume = min_volume
+
+    def _score(self, pred, gr):
+        return ops.lesion_distances(pred, gr, (self.tolerance,), self.dilation, self.min_volume)[2]
+
+
+# ---------------------------------------------------------------------- the definitions restated in float64 numpy / scipy (host)
+_RESTATE_THREADS = 1024                                                               # the finalize kernel's workgroup
+
+
+def _surface_host(a):
+    """the voxels of `a` with a face neighbour outside `a` or outside the grid"""
+    p = np.pad(a, 1)
+    inner = p[1:-1, 1:-1, 1:-1].copy()
+    for ax in range(3):
+        for sh in (1, -1):
+            inner &= np.roll(p, sh, axis=ax)[1:-1, 1:-1, 1:-1]
+    return a & ~inner
+
+
+def surface_histogram_host(p, g):
+    """bool masks [D, H, W], both non-empty -> int64 histogram of the |dP| + |dG| exact squared surface distances, (D-1)^2 + (H-1)^2 +
+    (W-1)^2 + 1 bins"""
+    from scipy import ndimage
+    sp, sg = _surface_host(p), _surface_host(g)
+    to_g = np.rint(ndimage.distance_transform_edt(~sg) ** 2).astype(np.int64)
+    to_p = np.rint(ndimage.distance_transform_edt(~sp) ** 2).astype(np.int64)
+    bins = sum((s - 1) ** 2 for s in p.shape) + 1
+    return np.bincount(np.concatenate([to_g[sp], to_p[sg]]), minlength=bins)
+
+
+def assd_terms_host(hist):
+    """the float64 terms h_b * sqrt(b) of the ASSD sum (one rounding in the square root, one in the product)"""
+    return hist.astype(np.float64) * np.sqrt(np.arange(len(hist), dtype=np.float64))
+
+
+def surface_distances_host(p, g, tolerances=(1.0,), empty_value=ops.HD95_EMPTY):
+    """ops.surface_distances' extras of one pair of bool masks [D, H, W], restated: -> float64 [T + 2] = (NSD per tolerance, ASSD, HD).
+    NSD: an integer count over one float64 division.  ASSD: the kernel's order -- position i of 1024 adds its ceil(bins / 1024)
+    consecutive terms in ascending bin order, then the tree i += i + 512, + 256, ... + 1 -- and one division.  HD: sqrt of the last
+    non-empty bin."""
+    p, g = np.asarray(p, dtype=bool), np.asarray(g, dtype=bool)
+    tb = ops.tolerance_bins(tolerances)
+    t = len(tb)
+    out = np.zeros(t + 2, dtype=np.float64)
+    if not p.any() or not g.any():
+        both = not p.any() and not g.any()
+        out[:t] = 1.0 if both else 0.0
+        out[t:] = 0.0 if both else empty_value
+        return out
+    hist = surface_histogram_host(p, g)
+    n = np.float64(hist.sum())
+    cum = np.cumsum(hist)
+    for i, b in enumerate(tb):
+        out[i] = np.float64(cum[min(b, len(hist) - 1)]) / n
+    chunk = -(-len(hist) // _RESTATE_THREADS)
+    terms = np.zeros(chunk * _RESTATE_THREADS, dtype=np.float64)
+    terms[:len(hist)] = assd_terms_host(hist)
+    terms = terms.reshape(_RESTATE_THREADS, chunk)
+    part = np.zeros(_RESTATE_THREADS, dtype=np.float64)
+    for j in range(chunk):
+        part = part + terms[:, j]
+    s = _RESTATE_THREADS // 2
+    while s >= 1:
+        part[:s] = part[:s] + part[s:2 * s]
+        s //= 2
+    out[t] = part[0] / n
+    out[t + 1] = np.sqrt(np.float64(np.flatnonzero(hist)[-1]))
+    return out
+
+
+def lesion_pairs_host(p, g, dilation=3):
+    """the matching of the lesion-wise scorers with scipy's dilation and labelling (INTEGRATION.md states it): -> (pairs [(M_i, L_i)] in
+    lesion order, n_fp)"""
+    from scipy import ndimage
+    p, g = np.asarray(p, dtype=bool), np.asarray(g, dtype=bool)
+    s18, s26 = ndimage.generate_binary_structure(3, 2), np.ones((3, 3, 3), bool)
+    z, n = ndimage.label(ndimage.binary_dilation(g, s18, iterations=dilation) if dilation else g, s26)
+    q, m = ndimage.label(p, s26)
+    matched = np.zeros(m + 1, bool)
+    pairs = []
+    for i in range(1, n + 1):
+        zi = z == i
+        js = np.unique(q[zi])
+        js = js[js > 0]
+        matched[js] = True
+        pairs.append((np.isin(q, js) & p, g & zi))
+    return pairs, m - int(matched[1:].sum())
+
+
+def lesion_distances_host(p, g, tolerances=(1.0,), dilation=3, min_volume=50, empty_value=ops.HD95_EMPTY):
+    """ops.lesion_distances' extras of one pair of bool masks [D, H, W], restated: -> (summary_ex float64 [T + 1] = (LesionNSD per
+    tolerance, LesionASSD), rows float64 [n_gt, T + 2] = surface_distances_host of every pair (M_i, L_i), n_fp).  The sums run over the
+    kept lesions in ascending order."""
+    t = len(ops.tolerance_bins(tolerances))
+    pairs, n_fp = lesion_pairs_host(p, g, dilation)
+    rows, kept = np.zeros((len(pairs), t + 2), dtype=np.float64), 0
+    sums = np.zeros(t + 1, dtype=np.float64)
+    for i, (mi, li) in enumerate(pairs):
+        rows[i] = surface_distances_host(mi, li, tolerances, empty_value)
+        if int(li.sum()) > min_volume:
+            kept += 1
+            sums = sums + rows[i, :t + 1]
+    den = kept + n_fp
+    out = np.zeros(t + 1, dtype=np.float64)
+    out[:t] = sums[:t] / np.float64(den) if den else 1.0
+    out[t] = (sums[t] + np.float64(n_fp) * np.float64(empty_value)) / np.float64(den) if den else 0.0
+    return out, rows, n_fp
 
 
 def print_metrics(writer, metric, prefix, epoch):

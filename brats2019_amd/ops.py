@@ -7,6 +7,7 @@ from __future__ import annotations
 import collections
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -1195,6 +1196,99 @@ def lesion_accumulate(summary, acc, nacc, column):
     L.check(L.load().ru_lesion_accumulate(L.ptr(summary), L.ptr(acc), n, k, int(nacc), L.LESION_COLUMNS[column], L.stream()),
             "ru_lesion_accumulate")
     return acc
+
+
+def tolerance_bins(tolerances):
+    """For each tolerance tau (a float in voxels at unit spacing, >= 0, finite or inf) the largest integer b >= 0 with
+    numpy.sqrt(numpy.float64(b)) <= tau, clamped to 2**32 - 1: the limit on the exact integer SQUARED distance that makes the kernel's
+    test `s <= b` mean what numpy means by `sqrt(s) <= tau`.  floor(tau**2) corrected by steps of one, since tau**2 is rounded.
+    -> list of ints.  ValueError for a negative or NaN tolerance and for more than SURFACE_MAX_TOL of them."""
+    taus = [np.float64(t) for t in tolerances]
+    if len(taus) > L.SURFACE_MAX_TOL:
+        raise ValueError("tolerance_bins: %d tolerances, one call takes at most %d" % (len(taus), L.SURFACE_MAX_TOL))
+    top, out = 2 ** 32 - 1, []
+    for tau in taus:
+        if not tau >= 0:                                                              # negative or NaN
+            raise ValueError("tolerance_bins: tolerance %r: must be >= 0" % (float(tau),))
+        if tau >= 65536.0:                                                            # sqrt(2**32 - 1) < 65536: every bin a uint32 can name
+            out.append(top)
+            continue
+        b = int(np.floor(tau * tau))
+        while b < top and np.sqrt(np.float64(b + 1)) <= tau:
+            b += 1
+        while b > 0 and np.sqrt(np.float64(b)) > tau:
+            b -= 1
+        out.append(b)
+    return out
+
+
+def _distance_args(who, pred, target, tolerances):
+    """the checks that need no device, then surface_metrics' preparation -> (pred, target, kind, n, c, d, h, w, k, bins as a C array, T)"""
+    if tuple(pred.shape) != tuple(target.shape) or pred.dtype != target.dtype:
+        raise ValueError("%s: shapes or dtypes differ: %s %s / %s %s" % (who, tuple(pred.shape), pred.dtype, tuple(target.shape), target.dtype))
+    bins = tolerance_bins(tolerances)
+    if pred.dtype == torch.uint8:
+        if pred.dim() != 4:
+            raise ValueError("%s: uint8 label volumes are [N, D, H, W], got %s" % (who, tuple(pred.shape)))
+        L.require_gpu()
+        pred, target = pred.contiguous(), target.contiguous()
+        kind, (n, d, h, w), c, k = L.SURFACE_LABEL, (int(v) for v in pred.shape), 1, L.SURFACE_REGIONS
+    else:
+        pred, target = _prep(pred), _prep(target)
+        kind, (n, c, d, h, w) = L.SURFACE_PROB, _dims5(pred)
+        k = c
+    return pred, target, kind, n, c, d, h, w, k, (C.c_uint * max(len(bins), 1))(*bins), len(bins)
+
+
+def surface_distances(pred, target, tolerances=(1.0,), empty_value=HD95_EMPTY):
+    """surface_metrics and, from the same histogram of surface distances, the normalized surface Dice at each of T <= 8 `tolerances`, the
+    average symmetric surface distance and the Hausdorff distance (include/resunet_hip.h, ru_surface_distances):
+    -> (values [N, K, 4], counts [N, K, 6], extras float64 [N, K, T + 2] = (NSD_0 .. NSD_T-1, ASSD, HD)); values and counts are
+    surface_metrics' byte for byte.  Tolerances are in voxels at unit spacing (tolerance_bins states how `<=` is decided).  Both masks
+    empty: NSD 1, ASSD = HD = 0; exactly one empty: NSD 0, ASSD = HD = `empty_value`.  One more launch than surface_metrics, the same
+    workspace; nothing synchronises, the tolerances travel as kernel arguments."""
+    pred, target, kind, n, c, d, h, w, k, bins, t = _distance_args("surface_distances", pred, target, tolerances)
+    lib = L.load()
+    values = torch.empty((n, k, 4), dtype=torch.float64, device=pred.device)
+    counts = torch.empty((n, k, L.SURFACE_COUNTS), dtype=torch.int64, device=pred.device)
+    extras = torch.empty((n, k, t + 2), dtype=torch.float64, device=pred.device)
+    ws = L.workspace(lib.ru_surface_workspace_bytes(kind, n, c, d, h, w), pred.device)
+    L.check(lib.ru_surface_distances(L.ptr(pred), L.ptr(target), kind, n, c, d, h, w, float(empty_value), bins, t, L.ptr(values), L.ptr(counts),
+                                     L.ptr(extras), L.ptr(ws), ws.numel(), L.stream()), "ru_surface_distances")
+    return values, counts, extras
+
+
+def surface_extras_accumulate(extras, acc, nacc, column):
+    """acc[i] += batch mean of extras[:, i, column] (float64, on the device), i < nacc, for surface_distances' extras or lesion_distances'
+    summary_ex: rows of any width, `column` an index into them."""
+    n, k, ncols = (int(v) for v in extras.shape)
+    assert extras.dtype == torch.float64 and extras.is_contiguous() and 0 <= int(column) < ncols
+    assert acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() >= nacc
+    L.check(L.load().ru_surface_extras_accumulate(L.ptr(extras), L.ptr(acc), n, k, int(nacc), ncols, int(column), L.stream()),
+            "ru_surface_extras_accumulate")
+    return acc
+
+
+def lesion_distances(pred, target, tolerances=(1.0,), dilation=3, min_volume=50, empty_value=HD95_EMPTY, want_table=False, max_lesions=LESION_MAX):
+    """lesion_metrics and the lesion-wise surface Dice and average surface distance of the same matching (include/resunet_hip.h,
+    ru_lesion_distances): -> (summary [N, K, 2], counts [N, K, 6], summary_ex float64 [N, K, T + 1] = (LesionNSD_0 .. LesionNSD_T-1,
+    LesionASSD)), and with want_table: table [N, K, max_lesions, 5] and table_ex float64 [N, K, max_lesions, T + 2] = (NSD_i per
+    tolerance, ASSD_i, HD_i), rows from n_gt on zero.  summary, counts and table are lesion_metrics' byte for byte.  A missed lesion has
+    NSD 0 and ASSD `empty_value`; a false-positive component adds NSD 0 and ASSD `empty_value`.  Synchronises once, as lesion_metrics."""
+    if int(dilation) < 0 or int(min_volume) < 0 or int(max_lesions) < 1:
+        raise ValueError("lesion_distances: dilation %s and min_volume %s must be >= 0, max_lesions %s >= 1" % (dilation, min_volume, max_lesions))
+    pred, target, kind, n, c, d, h, w, k, bins, t = _distance_args("lesion_distances", pred, target, tolerances)
+    lib = L.load()
+    summary = torch.empty((n, k, 2), dtype=torch.float64, device=pred.device)
+    counts = torch.empty((n, k, L.LESION_COUNTS), dtype=torch.int64, device=pred.device)
+    summary_ex = torch.empty((n, k, t + 1), dtype=torch.float64, device=pred.device)
+    table = torch.zeros((n, k, int(max_lesions), L.LESION_TABLE_COLUMNS), dtype=torch.float64, device=pred.device) if want_table else None
+    table_ex = torch.zeros((n, k, int(max_lesions), t + 2), dtype=torch.float64, device=pred.device) if want_table else None
+    ws = L.workspace(lib.ru_lesion_distances_workspace_bytes(kind, n, c, d, h, w, int(max_lesions), t), pred.device)
+    L.check(lib.ru_lesion_distances(L.ptr(pred), L.ptr(target), kind, n, c, d, h, w, int(dilation), int(min_volume), float(empty_value), bins, t,
+                                    L.ptr(summary), L.ptr(counts), L.ptr(table, allow_none=True), L.ptr(summary_ex),
+                                    L.ptr(table_ex, allow_none=True), int(max_lesions), L.ptr(ws), ws.numel(), L.stream()), "ru_lesion_distances")
+    return (summary, counts, summary_ex, table, table_ex) if want_table else (summary, counts, summary_ex)
 
 
 def to_c16(x):

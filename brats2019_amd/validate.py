@@ -15,6 +15,11 @@ TC = {1,3,4} and ET = {3,4} (3 counts as 4), from one pass sequence of ru_surfac
 lesion-wise Dice and HD95 and the counts of ground-truth, kept, found, missed and false-positive lesions (ru_lesion_metrics; INTEGRATION.md
 states the definition).  Not checked against the challenge's own evaluator.
 
+`--nsd TOL [TOL ...]` (with `--regions` or `--lesionwise`) adds the normalized surface Dice at each tolerance (voxels, at most 8): with
+`--regions` one NSD row per tolerance and the average symmetric surface distance ASSD, with `--lesionwise` one LesionNSD row per
+tolerance, from the same passes (ru_surface_distances, ru_lesion_distances).  The voxel-surface form of NSD; not compared with MONAI's
+code or any official evaluator.
+
 `--uncertainty_path DIR [--thresholds 25 50 75 100]` scores the BraTS uncertainty task instead: DIR holds `<case>_unc_whole.npy`,
 `<case>_unc_core.npy`, `<case>_unc_enhance.npy` (uint8 [D,H,W], 0 certain .. 100 uncertain) as `python -m brats2019_amd.test
 --uncertainty_output DIR` writes them.  At a threshold t the voxels with a map value above t are filtered out and TP, FP, FN, TN of the
@@ -46,6 +51,8 @@ parser.add_argument("--lesionwise", action="store_true", default=argparse.SUPPRE
                     help="score the lesion-wise Dice and HD95 of the regions WT, TC, ET")
 parser.add_argument("--dilation", default=argparse.SUPPRESS, type=int, help="lesion-wise: dilation iterations that join ground-truth fragments (default 3)")
 parser.add_argument("--min_volume", default=argparse.SUPPRESS, type=int, help="lesion-wise: ground-truth lesions of at most this many voxels are not scored (default 50)")
+parser.add_argument("--nsd", default=argparse.SUPPRESS, type=float, nargs="+", metavar="TOL",
+                    help="with --regions or --lesionwise: add the surface Dice at these tolerances in voxels (and ASSD with --regions)")
 
 UNCERTAINTY_THRESHOLDS = (25, 50, 75, 100)
 UNCERTAINTY_COLUMNS = ("score", "AUC_Dice", "AUC_FTP", "AUC_FTN")
@@ -92,16 +99,29 @@ def score(cases):
     return names, torch.stack(rows).cpu().numpy(), total.cpu().numpy() / len(names)
 
 
-def score_regions(cases):
+def _nsd_names(prefix, nsd):
+    return tuple("%s@%g" % (prefix, t) for t in nsd)
+
+
+def score_regions(cases, nsd=None):
     """cases: iterable of (name, ground-truth labels, predicted labels), read one at a time.  -> (names, results float64 [cases, 4, 3],
     mean float64 [4, 3]): rows Dice, sensitivity, specificity, HD95; columns WT, TC, ET.  The values stay on the device until the end:
-    one host copy for all cases."""
+    one host copy for all cases.  With `nsd` (T tolerances in voxels): results [cases, 4 + T + 1, 3], the further rows NSD per
+    tolerance and ASSD."""
+    if nsd is not None:
+        nsd = [float(t) for t in nsd]
+        ops.tolerance_bins(nsd)                                                       # a bad list fails before any upload
+    nex = 0 if nsd is None else len(nsd) + 1
     names, rows = [], []
     for name, label, predict in cases:
         if tuple(label.shape) != tuple(predict.shape) or np.ndim(label) != 3:
             raise ValueError("%s: prediction shape %s and label shape %s must be one [D, H, W]" % (name, tuple(predict.shape), tuple(label.shape)))
         g, p = _upload(label, name + " (labels)"), _upload(predict, name + " (prediction)")
-        values, counts = ops.surface_metrics(p[None], g[None])                  # [1, 3, 4], [1, 3, 6]
+        if nsd is None:
+            values, counts = ops.surface_metrics(p[None], g[None])              # [1, 3, 4], [1, 3, 6]
+        else:
+            values, counts, extras = ops.surface_distances(p[None], g[None], nsd)           # and [1, 3, T + 2]
+            values = torch.cat([values, extras[..., :nex]], dim=2)
         names.append(name)
         rows.append(torch.cat([values.reshape(-1), counts[0, 0, 5:].to(torch.float64)]))
     if not names:
@@ -111,33 +131,43 @@ def score_regions(cases):
     if bad.any():
         k = int(np.argmax(bad > 0))
         raise ValueError("%s: labels outside {0,1,2,3,4} in %d voxels" % (names[k], int(bad[k])))
-    results = np.ascontiguousarray(host[:, :-1].reshape(len(names), 3, 4).transpose(0, 2, 1))
+    results = np.ascontiguousarray(host[:, :-1].reshape(len(names), 3, 4 + nex).transpose(0, 2, 1))
     return names, results, results.mean(axis=0)
 
 
-def score_lesionwise(cases, dilation=3, min_volume=50):
+def score_lesionwise(cases, dilation=3, min_volume=50, nsd=None):
     """cases: iterable of (name, ground-truth labels, predicted labels), read one at a time.  -> (names, results float64 [cases, 2, 3],
     mean float64 [2, 3], counts int64 [cases, 3, 5]): rows lesion-wise Dice and HD95; columns WT, TC, ET; counts n_gt, n_kept, n_tp, n_fn,
-    n_fp per region.  The values stay on the device until the end: one host copy for all cases."""
+    n_fp per region.  The values stay on the device until the end: one host copy for all cases.  With `nsd` (T tolerances in voxels):
+    results [cases, 2 + T, 3], the further rows LesionNSD per tolerance."""
     if int(dilation) < 0 or int(min_volume) < 0:
         raise ValueError("validate: dilation %s and min_volume %s must be >= 0" % (dilation, min_volume))
+    if nsd is not None:
+        nsd = [float(t) for t in nsd]
+        ops.tolerance_bins(nsd)
+    nex = 0 if nsd is None else len(nsd)
     names, rows = [], []
     for name, label, predict in cases:
         if tuple(label.shape) != tuple(predict.shape) or np.ndim(label) != 3:
             raise ValueError("%s: prediction shape %s and label shape %s must be one [D, H, W]" % (name, tuple(predict.shape), tuple(label.shape)))
         g, p = _upload(label, name + " (labels)"), _upload(predict, name + " (prediction)")
-        summary, counts = ops.lesion_metrics(p[None], g[None], dilation=dilation, min_volume=min_volume)     # [1, 3, 2], [1, 3, 6]
+        if nsd is None:
+            summary, counts = ops.lesion_metrics(p[None], g[None], dilation=dilation, min_volume=min_volume)     # [1, 3, 2], [1, 3, 6]
+        else:
+            summary, counts, ex = ops.lesion_distances(p[None], g[None], nsd, dilation=dilation, min_volume=min_volume)     # and [1, 3, T + 1]
+            summary = torch.cat([summary, ex[..., :nex]], dim=2)
         names.append(name)
         rows.append(torch.cat([summary.reshape(-1), counts.reshape(-1).to(torch.float64)]))
     if not names:
         raise ValueError("validate: no cases")
     host = torch.stack(rows).cpu().numpy()
-    counts = host[:, 6:].reshape(len(names), 3, 6).astype(np.int64)
+    nv = 3 * (2 + nex)
+    counts = host[:, nv:].reshape(len(names), 3, 6).astype(np.int64)
     bad = counts[:, 0, 5]
     if bad.any():
         k = int(np.argmax(bad > 0))
         raise ValueError("%s: labels outside {0,1,2,3,4} in %d voxels" % (names[k], int(bad[k])))
-    results = np.ascontiguousarray(host[:, :6].reshape(len(names), 3, 2).transpose(0, 2, 1))
+    results = np.ascontiguousarray(host[:, :nv].reshape(len(names), 3, 2 + nex).transpose(0, 2, 1))
     return names, results, results.mean(axis=0), np.ascontiguousarray(counts[:, :, :5])
 
 
@@ -193,12 +223,14 @@ def _uncertainty_cases(opt, series):
         yield f, np.load(os.path.join(opt.data_path, f + ".npy")), np.load(os.path.join(opt.predictions_path, f + ".npy")), np.stack(maps)
 
 
-def _region_row(r):
-    return "  ".join("%s %s" % (m, " ".join("%s %.4f" % (k, v) for k, v in zip(REGION_NAMES, row))) for m, row in zip(REGION_METRICS, r))
+def _region_row(r, nsd=()):
+    metrics = REGION_METRICS + ((_nsd_names("NSD", nsd) + ("ASSD",)) if len(r) > len(REGION_METRICS) else ())
+    return "  ".join("%s %s" % (m, " ".join("%s %.4f" % (k, v) for k, v in zip(REGION_NAMES, row))) for m, row in zip(metrics, r))
 
 
-def _lesion_row(r, counts=None):
-    row = "  ".join("%s %s" % (m, " ".join("%s %.4f" % (k, v) for k, v in zip(REGION_NAMES, vals))) for m, vals in zip(LESION_METRICS, r))
+def _lesion_row(r, counts=None, nsd=()):
+    metrics = LESION_METRICS + _nsd_names("LesionNSD", nsd)
+    row = "  ".join("%s %s" % (m, " ".join("%s %.4f" % (k, v) for k, v in zip(REGION_NAMES, vals))) for m, vals in zip(metrics, r))
     if counts is None:
         return row
     return row + "  " + "  ".join("%s %s" % (n, " ".join("%s %d" % (k, v) for k, v in zip(LESION_COUNTS, c))) for n, c in zip(REGION_NAMES, counts))
@@ -208,7 +240,8 @@ def main(argv=None):
     """-> (per-case results float64 [cases, 4] = [d1, d2, d3, dWT], their mean).  With --regions: (results float64 [cases, 4, 3], their
     mean [4, 3]), rows Dice, sensitivity, specificity, HD95 and columns WT, TC, ET.  With --uncertainty_path: (results float64 [cases, 3, 4],
     their mean [3, 4]), rows WT, TC, ET and columns score, AUC_Dice, AUC_FTP, AUC_FTN.  With --lesionwise: (results float64 [cases, 2, 3],
-    their mean [2, 3]), rows lesion-wise Dice and HD95 and columns WT, TC, ET."""
+    their mean [2, 3]), rows lesion-wise Dice and HD95 and columns WT, TC, ET.  --nsd adds rows to the last two (score_regions,
+    score_lesionwise)."""
     opt = parser.parse_args(argv)
     print(torch.__version__)
     print(opt)
@@ -220,17 +253,18 @@ def main(argv=None):
         print("mean", _uncertainty_row(mean))
         return results, mean
     cases = ((f, np.load(os.path.join(opt.data_path, f + ".npy")), np.load(os.path.join(opt.predictions_path, f + ".npy"))) for f in series)
+    nsd = getattr(opt, "nsd", None)
     if getattr(opt, "lesionwise", False):
-        series, results, mean, counts = score_lesionwise(cases, getattr(opt, "dilation", 3), getattr(opt, "min_volume", 50))
+        series, results, mean, counts = score_lesionwise(cases, getattr(opt, "dilation", 3), getattr(opt, "min_volume", 50), nsd)
         for f, r, c in zip(series, results, counts):
-            print(f, _lesion_row(r, c))
-        print("mean", _lesion_row(mean))
+            print(f, _lesion_row(r, c, nsd or ()))
+        print("mean", _lesion_row(mean, None, nsd or ()))
         return results, mean
     if getattr(opt, "regions", False):
-        series, results, mean = score_regions(cases)
+        series, results, mean = score_regions(cases, nsd)
         for f, r in zip(series, results):
-            print(f, _region_row(r))
-        print("mean", _region_row(mean))
+            print(f, _region_row(r, nsd or ()))
+        print("mean", _region_row(mean, nsd or ()))
         return results, mean
     series, results, mean = score(cases)
     for f, r in zip(series, results):

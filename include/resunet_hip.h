@@ -865,7 +865,27 @@ int ru_rmse_accumulate(const double* sums, double* acc, ru_stream_t stream);
  *                          shape or kind): 8 B per voxel for two distance maps, the four bit masks, and one histogram of
  *                          (D-1)^2 + (H-1)^2 + (W-1)^2 + 1 uint32 bins per (n, k).  RU_EINVAL for a bad kind, an extent outside
  *                          [1, 512], 2 * N * K > 65535 (the launch grids) or an undersized workspace.
- *   ru_surface_accumulate: acc[i] += mean over the N samples of values[n][i][column] in float64, i < nacc (<= K, <= 64). */
+ *   ru_surface_accumulate: acc[i] += mean over the N samples of values[n][i][column] in float64, i < nacc (<= K, <= 64).
+ *   ru_surface_distances : ru_surface_metrics' passes in the same workspace, `values` and `counts` byte for byte the same, and one more
+ *                          launch that rereads the histogram: extras [N][K][T + 2] float64 = {NSD_0 .. NSD_T-1, ASSD, HD} for T in
+ *                          [0, RU_SURFACE_MAX_TOL] tolerances.  With n = |dP| + |dG| and h_b the number of distances whose square is b:
+ *                            NSD_t = #{s in S : s <= tol_bins[t]} / n, an exact 64-bit count and one float64 division (the normalized
+ *                                    surface Dice, "surface Dice at tolerance tau", in the voxel-surface form: every surface voxel counts
+ *                                    once, no surface-element areas).  tol_bins is a HOST array of integer limits on the SQUARED distance:
+ *                                    for a tolerance tau the caller passes the largest b with sqrt((double)b) <= tau, which makes the test
+ *                                    sqrt(s) <= tau exact; a limit at or beyond the number of bins means every distance.  The limits
+ *                                    travel as kernel arguments: nothing is uploaded and nothing waits.
+ *                            ASSD  = sum_b h_b * sqrt((double)b) / n (the average symmetric surface distance), float64 without contraction:
+ *                                    thread i of 1024 adds its ceil(bins / 1024) consecutive bins in ascending order, then a fixed tree
+ *                                    (thread i += thread i + 512, + 256, ... + 1), one division.  No floating-point atomics: the same bytes
+ *                                    for the same bytes.
+ *                            HD    = sqrt((double)max S), the symmetric Hausdorff distance.
+ *                          Empty rules (conventions of this library, not checked against any official evaluator): P and G both empty:
+ *                          NSD = 1, ASSD = HD = 0; exactly one empty: NSD = 0, ASSD = HD = empty_value.  Unit spacing only; the overlap of
+ *                          each direction on its own is not offered.  RU_EINVAL as ru_surface_metrics, and for T outside
+ *                          [0, RU_SURFACE_MAX_TOL], tol_bins == NULL with T > 0, or extras == NULL.
+ *   ru_surface_extras_accumulate: acc[i] += mean over the N samples of extras[n][i][column] in float64 for rows of `ncols` columns
+ *                          (ncols = T + 2 for ru_surface_distances' extras, T + 1 for ru_lesion_distances' summary_ex), i < nacc. */
 #define RU_SURFACE_PROB 0
 #define RU_SURFACE_LABEL 1
 #define RU_SURFACE_REGIONS 3
@@ -879,6 +899,11 @@ size_t ru_surface_workspace_bytes(int kind, int N, int C, int D, int H, int W);
 int ru_surface_metrics(const void* pred, const void* target, int kind, int N, int C, int D, int H, int W, double empty_value,
                        double* values, unsigned long long* counts, void* ws, size_t ws_bytes, ru_stream_t stream);
 int ru_surface_accumulate(const double* values, double* acc, int N, int K, int nacc, int column, ru_stream_t stream);
+#define RU_SURFACE_MAX_TOL 8
+int ru_surface_distances(const void* pred, const void* target, int kind, int N, int C, int D, int H, int W, double empty_value,
+                         const unsigned* tol_bins, int T, double* values, unsigned long long* counts, double* extras, void* ws,
+                         size_t ws_bytes, ru_stream_t stream);
+int ru_surface_extras_accumulate(const double* extras, double* acc, int N, int K, int nacc, int ncols, int column, ru_stream_t stream);
 
 /* ---------------------------------------------------------------- lesion-wise Dice and HD95 (csrc/lesion.hip)
  * Per sample n and region k, P and G are the masks of ru_surface_metrics (same kinds, same regions, every extent in [1, 512], and
@@ -918,6 +943,20 @@ int ru_lesion_metrics(const void* pred, const void* target, int kind, int N, int
                       double empty_value, double* summary, unsigned long long* counts, double* table, int max_lesions, void* ws,
                       size_t ws_bytes, ru_stream_t stream);
 int ru_lesion_accumulate(const double* summary, double* acc, int N, int K, int nacc, int column, ru_stream_t stream);
+/* ru_lesion_distances: ru_lesion_metrics' sequence with ru_surface_distances' finalize on every pair (M_i, L_i); `summary`, `counts` and
+ *   `table` come out byte for byte as ru_lesion_metrics writes them.  Per lesion NSD_{i,t}, ASSD_i and HD_i follow ru_surface_distances
+ *   (a missed lesion, M_i empty: NSD_i = 0, ASSD_i = HD_i = empty_value).  summary_ex [N][K][T + 1] float64, sums over the kept lesions
+ *   in ascending lesion order without contraction, den = n_kept + n_fp:
+ *     LesionNSD_t = sum_kept NSD_{i,t} / den (a false-positive component adds 0); 1 when den = 0;
+ *     LesionASSD  = (sum_kept ASSD_i + n_fp * empty_value) / den; 0 when den = 0.
+ *   table_ex, optional (NULL): [N][K][max_lesions][T + 2] float64 = {NSD_{i,0..T-1}, ASSD_i, HD_i} for the n_gt lesions, the dropped ones
+ *   included; rows from n_gt on are not written.  tol_bins, T as ru_surface_distances.  Still one synchronisation, the lesion counts.
+ *   ws: ru_lesion_distances_workspace_bytes(kind, N, C, D, H, W, max_lesions, T) = ru_lesion_workspace_bytes' plus 8 (T + 2) B per lesion
+ *   of max_lesions and (n, k); 0 for a bad shape, kind, max_lesions or T.  Conventions of this library, not checked against any evaluator. */
+size_t ru_lesion_distances_workspace_bytes(int kind, int N, int C, int D, int H, int W, int max_lesions, int T);
+int ru_lesion_distances(const void* pred, const void* target, int kind, int N, int C, int D, int H, int W, int dilation, long long min_volume,
+                        double empty_value, const unsigned* tol_bins, int T, double* summary, unsigned long long* counts, double* table,
+                        double* summary_ex, double* table_ex, int max_lesions, void* ws, size_t ws_bytes, ru_stream_t stream);
 
 /* ---------------------------------------------------------------- training input pipeline (dataloader.py:100-216, SimpleReader)
  * ru_zscore_stats: per channel stats[c] = { #(x > 0), sum x, sum x^2 } over all V voxels in float64 -- the three numbers the
