@@ -4,9 +4,9 @@
 //   test.py:47-49,85-87     bounding box of the non-zero voxels           -> bbox_kernel            (ru_case_bbox)
 //   test.py:92-113          crop, zero-pad to x16, non-zero z-score       -> case_stats_*_kernel + case_prepare_kernel
 //   test.py:115-120         the four test-time flips                      -> written by case_prepare_kernel as one batch
-//   test.py:134-144         un-flip, average, un-pad, threshold, count    -> tta_merge_box_kernel   (ru_tta_merge_box)
+//   test.py:134-144         un-flip, average, un-pad, threshold, count    -> ensemble.hip's merge_kernel (ru_tta_merge_box)
 //   test.py:51-62,162-164   26-connected components, ratio-0.1 rejection  -> cc_* kernels           (ru_cc_reject)
-//   test.py:167-168         paste into the full volume                    -> paste_labels_kernel    (ru_paste_labels)
+//   test.py:167-168         paste into the full volume                    -> ensemble.hip's paste_kernel (ru_paste_labels)
 //   loader_helper.py:42-60  zero-padded tile extract (`copy`)             -> tile_gather_kernel     (ru_tile_gather), T tiles per launch
 //   loader_helper.py:82-97  centre paste (`copy_back`)                    -> tile_scatter_kernel    (ru_tile_scatter)
 //
@@ -161,40 +161,6 @@ __global__ __launch_bounds__(256) void case_prepare_kernel(const float* __restri
     }
 }
 
-// ------------------------------------------------------------------ TTA merge on a sub-box (test.py:134-144)
-// as tta_merge_kernel (pointwise.hip: un-flip, ((p0 + p1) + p2 + ...) / K in float32, > 0.5), for the voxels of `b` only -- the padding
-// is dropped here, so the per-class counts are those of the un-padded volume (the ET > 32 rule of test.py:157 counts them)
-__global__ __launch_bounds__(256) void tta_merge_box_kernel(const float* __restrict__ p, int K, unsigned flips, float* __restrict__ mean_out,
-                                                            unsigned char* __restrict__ mask_out, unsigned long long* __restrict__ counts,
-                                                            int C, int D, int H, int W, Box3 b) {
-    __shared__ unsigned int cnt[4];
-    const size_t Vb = (size_t)b.size[0] * b.size[1] * b.size[2];
-    const int c = blockIdx.y;
-    if (threadIdx.x < 4) cnt[threadIdx.x] = 0;
-    __syncthreads();
-    unsigned int local = 0;
-    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < Vb; v += (size_t)gridDim.x * 256) {
-        const int x = (int)(v % b.size[2]) + b.lo[2];
-        const size_t r = v / b.size[2];
-        const int y = (int)(r % b.size[1]) + b.lo[1], z = (int)(r / b.size[1]) + b.lo[0];
-        float acc = 0.f;
-        for (int k = 0; k < K; ++k) {
-            const unsigned f = (flips >> (3 * k)) & 7u;
-            const int zz = (f & 1u) ? D - 1 - z : z, yy = (f & 2u) ? H - 1 - y : y, xx = (f & 4u) ? W - 1 - x : x;
-            const float t = p[(((size_t)k * C + c) * D + zz) * H * W + (size_t)yy * W + xx];
-            acc = k == 0 ? t : acc + t;
-        }
-        const float m = acc / (float)K;
-        if (mean_out) mean_out[(size_t)c * Vb + v] = m;
-        const bool on = m > 0.5f;
-        mask_out[(size_t)c * Vb + v] = on ? 1 : 0;
-        local += on ? 1u : 0u;
-    }
-    atomicAdd(&cnt[threadIdx.x >> 6], local);
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(&counts[c], (unsigned long long)cnt[0] + cnt[1] + cnt[2] + cnt[3]);
-}
-
 // ------------------------------------------------------------------ 26-connected components + small-region rejection (test.py:51-62,162-164)
 // The labelling is cc_unionfind.hpp's (shared with lesion.hip): union-find on the voxel indices, roots count their members.  The reference
 // numbers its components differently (skimage.morphology.label), but only component SIZES enter test.py:51-62, so the result is identical:
@@ -236,19 +202,6 @@ __global__ __launch_bounds__(256) void cc_apply_kernel(unsigned char* __restrict
         if (p < 0) continue;
         const int root = cc_find(parent, (int)v);
         if ((double)count[root] < thr) labels[v] = 0;
-    }
-}
-
-// full[D][H][W] = 0 except the box, which takes lab[size] (test.py:167-168)
-__global__ __launch_bounds__(256) void paste_labels_kernel(const unsigned char* __restrict__ lab, unsigned char* __restrict__ full, int D, int H, int W, Box3 b) {
-    const size_t V = (size_t)D * H * W;
-    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < V; v += (size_t)gridDim.x * 256) {
-        const int x = (int)(v % W) - b.lo[2];
-        const size_t r = v / W;
-        const int y = (int)(r % H) - b.lo[1], z = (int)(r / H) - b.lo[0];
-        unsigned char o = 0;
-        if (z >= 0 && z < b.size[0] && y >= 0 && y < b.size[1] && x >= 0 && x < b.size[2]) o = lab[((size_t)z * b.size[1] + y) * b.size[2] + x];
-        full[v] = o;
     }
 }
 
@@ -337,15 +290,9 @@ extern "C" int ru_case_prepare(const float* image, const double* stats, float* b
 extern "C" int ru_tta_merge_box(const float* probs, int K, unsigned flips, float* mean_out, unsigned char* mask, unsigned long long* counts,
                                 int C, int D, int H, int W, const int* lo, const int* size, ru_stream_t stream) {
     RU_REQUIRE(probs && mask && counts && lo && size && K >= 1 && K <= 8 && C >= 1, "ru_tta_merge_box: bad argument");
-    Box3 b;
-    int rc = make_box(b, lo, size, D, H, W, "ru_tta_merge_box");
-    if (rc) return rc;
-    hipError_t e = hipMemsetAsync(counts, 0, sizeof(unsigned long long) * C, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(counts)");
-    hipLaunchKernelGGL(tta_merge_box_kernel, dim3(grid1d((size_t)size[0] * size[1] * size[2], 256 * 8, 512), C), dim3(256), 0, (hipStream_t)stream,
-                       probs, K, flips, mean_out, mask, counts, C, D, H, W, b);
-    RU_CHECK_LAUNCH("tta_merge_box_kernel");
-    return RU_OK;
+    // the ensemble of one: first, final, M = 1 (S / 1.0f is S)
+    return merge_launch("ru_tta_merge_box", false, probs, K, flips, nullptr, nullptr, 1, 1, 0, mean_out, mask, counts, nullptr, C, D, H, W, lo, size,
+                        (hipStream_t)stream);
 }
 
 extern "C" size_t ru_cc_workspace_bytes(int D, int H, int W) { return 512 + 2 * align_up((size_t)D * H * W * sizeof(int), 256); }
@@ -376,10 +323,5 @@ extern "C" int ru_cc_reject(unsigned char* labels, int D, int H, int W, double r
 
 extern "C" int ru_paste_labels(const unsigned char* lab, unsigned char* full, int D, int H, int W, const int* lo, const int* size, ru_stream_t stream) {
     RU_REQUIRE(lab && full && lo && size, "ru_paste_labels: null argument");
-    Box3 b;
-    int rc = make_box(b, lo, size, D, H, W, "ru_paste_labels");
-    if (rc) return rc;
-    hipLaunchKernelGGL(paste_labels_kernel, dim3(grid1d((size_t)D * H * W, 256 * 4, 4096)), dim3(256), 0, (hipStream_t)stream, lab, full, D, H, W, b);
-    RU_CHECK_LAUNCH("paste_labels_kernel");
-    return RU_OK;
+    return paste_launch("ru_paste_labels", lab, full, 1, D, H, W, lo, size, (hipStream_t)stream);
 }

@@ -344,7 +344,9 @@ extern "C" int ru_adam_step(float* w, const float* g, float* m, float* v, float*
 extern "C" int ru_tta_merge(const float* probs, int K, unsigned flips, float* mean_out, unsigned char* mask, unsigned long long* counts,
                             int C, int D, int H, int W, ru_stream_t stream) {
     RU_REQUIRE(probs && mask && counts, "ru_tta_merge: null argument");
-    return tta_merge_launch(probs, K, flips, mean_out, mask, counts, C, D, H, W, (hipStream_t)stream);
+    RU_REQUIRE(K >= 1 && K <= 8 && C >= 1, "tta_merge: 1..8 predictions");
+    const int lo[3] = {0, 0, 0}, size[3] = {D, H, W};                   // the box covering the whole volume
+    return merge_launch("ru_tta_merge", false, probs, K, flips, nullptr, nullptr, 1, 1, 0, mean_out, mask, counts, nullptr, C, D, H, W, lo, size, (hipStream_t)stream);
 }
 extern "C" int ru_compose_labels(const unsigned char* mask, const unsigned long long* counts, unsigned long long et_min, unsigned char* labels,
                                  size_t V, ru_stream_t stream) {

@@ -999,39 +999,7 @@ int crit_grad_launch(const float* p, const float* g, const double* sums, double 
     return RU_OK;
 }
 
-// ------------------------------------------------------------------ inference post-processing (test.py:134-159)
-// TTA merge: K predictions p[k] of flipped inputs (flip mask bit0 = D, bit1 = H, bit2 = W reversed) are un-flipped and
-// averaged in the reference's order ((p0 + p1) + p2 + ...) / K (float32, bit-exact vs numpy), thresholded at 0.5 and counted.
-__global__ __launch_bounds__(256) void tta_merge_kernel(const float* __restrict__ p, int K, unsigned flips, float* __restrict__ mean_out,
-                                                        unsigned char* __restrict__ mask_out, unsigned long long* __restrict__ counts,
-                                                        int C, int D, int H, int W) {
-    __shared__ unsigned int cnt[4];
-    const size_t V = (size_t)D * H * W;
-    const int c = blockIdx.y;
-    if (threadIdx.x < 4) cnt[threadIdx.x] = 0;
-    __syncthreads();
-    unsigned int local = 0;
-    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < V; v += (size_t)gridDim.x * 256) {
-        const int x = (int)(v % W);
-        const int y = (int)((v / W) % H);
-        const int z = (int)(v / ((size_t)W * H));
-        float acc = 0.f;
-        for (int k = 0; k < K; ++k) {
-            const unsigned f = (flips >> (3 * k)) & 7u;
-            const int zz = (f & 1u) ? D - 1 - z : z, yy = (f & 2u) ? H - 1 - y : y, xx = (f & 4u) ? W - 1 - x : x;
-            const float t = p[(((size_t)k * C + c) * D + zz) * H * W + (size_t)yy * W + xx];
-            acc = k == 0 ? t : acc + t;
-        }
-        const float m = acc / (float)K;
-        if (mean_out) mean_out[(size_t)c * V + v] = m;
-        const bool on = m > 0.5f;
-        mask_out[(size_t)c * V + v] = on ? 1 : 0;
-        local += on ? 1u : 0u;
-    }
-    atomicAdd(&cnt[threadIdx.x >> 6], local);
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(&counts[c], (unsigned long long)cnt[0] + cnt[1] + cnt[2] + cnt[3]);   // integer: order independent
-}
+// ------------------------------------------------------------------ inference post-processing (test.py:153-159; the TTA merge is ensemble.hip's)
 // labels: 2 where WT, then 1 where TC, then 4 where ET if the ET count exceeds `et_min` (test.py:153-159)
 __global__ __launch_bounds__(256) void compose_labels_kernel(const unsigned char* __restrict__ mask, const unsigned long long* __restrict__ counts,
                                                              unsigned long long et_min, unsigned char* __restrict__ labels, size_t V) {
@@ -1043,15 +1011,6 @@ __global__ __launch_bounds__(256) void compose_labels_kernel(const unsigned char
         if (et_on && mask[2 * V + v]) l = 4;
         labels[v] = l;
     }
-}
-int tta_merge_launch(const float* p, int K, unsigned flips, float* mean_out, unsigned char* mask, unsigned long long* counts, int C, int D, int H, int W, hipStream_t s) {
-    RU_REQUIRE(K >= 1 && K <= 8 && C >= 1, "tta_merge: 1..8 predictions");
-    hipError_t e = hipMemsetAsync(counts, 0, sizeof(unsigned long long) * C, s);
-    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(counts)");
-    const size_t V = (size_t)D * H * W;
-    hipLaunchKernelGGL(tta_merge_kernel, dim3(grid1d(V, 256 * 8, 512), C), dim3(256), 0, s, p, K, flips, mean_out, mask, counts, C, D, H, W);
-    RU_CHECK_LAUNCH("tta_merge_kernel");
-    return RU_OK;
 }
 int compose_labels_launch(const unsigned char* mask, const unsigned long long* counts, unsigned long long et_min, unsigned char* labels, size_t V, hipStream_t s) {
     hipLaunchKernelGGL(compose_labels_kernel, dim3(grid1d(V, 256, 4096)), dim3(256), 0, s, mask, counts, et_min, labels, V);

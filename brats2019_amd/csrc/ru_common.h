@@ -498,7 +498,15 @@ int crit_sums_launch(const float* p, const float* g, double* sums, int N, int C,
 int crit_grad_launch(const float* p, const float* g, const double* sums, double count, float w_dice, float w_bce,
                      float bgw, float priority, float* dp, int N, int C, size_t V, hipStream_t s);
 int crit_value_launch(const double* sums, int C, double count, double priority, double w_dice, double w_bce, double* out3, hipStream_t s);
-int tta_merge_launch(const float* p, int K, unsigned flips, float* mean_out, unsigned char* mask, unsigned long long* counts, int C, int D, int H, int W, hipStream_t s);
+// The flip-merge family (ensemble.hip): every merge of K un-flipped copies on a box, with argument checks (reported as `who`), make_box, one
+// grid rule and the clearing of `counts`.  M = 0: accumulate only (acc[, acc2] are written); M >= 1: the last model, finalized into mean_out
+// (may be null) / mask / counts[ / unc].  `moment` adds the second-moment sum acc2 and the map unc of `measure`; without it they are not touched.
+int merge_launch(const char* who, bool moment, const float* probs, int K, unsigned flips, float* acc, float* acc2, int first, int M, int measure, float* mean_out,
+                 unsigned char* mask, unsigned long long* counts, unsigned char* unc, int C, int D, int H, int W, const int* lo, const int* size, hipStream_t s);
+int merge_finalize_launch(const char* who, bool moment, const float* acc, const float* acc2, int M, int K, int measure, float* mean_out, unsigned char* mask,
+                          unsigned long long* counts, unsigned char* unc, int C, size_t Vbox, hipStream_t s);
+// full [C][D][H][W] = 0 outside the box, src [C][size] inside, bytes (ensemble.hip; ru_paste_labels is C = 1)
+int paste_launch(const char* who, const unsigned char* src, unsigned char* full, int C, int D, int H, int W, const int* lo, const int* size, hipStream_t s);
 int compose_labels_launch(const unsigned char* mask, const unsigned long long* counts, unsigned long long et_min, unsigned char* labels, size_t V, hipStream_t s);
 int dice_counts_launch(const float* p, const float* g, unsigned long long* counts, int rows, size_t V, hipStream_t s);
 int dice_accumulate_launch(const unsigned long long* counts, double* acc, int N, int C, int nacc, hipStream_t s);

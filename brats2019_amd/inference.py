@@ -1,5 +1,5 @@
 """Inference driver around the forward pass: the per-case pipeline of the reference's test.py (:82-164), on the device from the upload
-of the case to the download of its label volume (kernels in csrc/inference.hip) --
+of the case to the download of its label volume (kernels in csrc/inference.hip, the merge and the paste in the one family of csrc/ensemble.hip) --
 
   ru_case_bbox      bounding box of the non-zero voxels (test.py:47-49,85-87); its 6 integers are the only values that visit the host
                     in between: they fix the tensor shapes of everything downstream;
@@ -316,15 +316,11 @@ def ensemble_merge_host(outs_list, pad_left=(0, 0, 0), size=None):
     un-flipped float32 mean (((o0 + o1) + o2) + o3) / K of test.py:134-138 on the un-padded box, then `ensemble_mean_host` over the models,
     the 0.5 threshold and the per-region counts (test.py:144).  Returns (mean float32 [3,*size], mask bool, (wt, tc, et))."""
     per_model = []
-    for outs in outs_list:
-        un = [np.flip(np.asarray(o, np.float32), axis=ax) if ax else np.asarray(o, np.float32) for o, ax in zip(outs, TTA_FLIPS)]
-        acc = un[0]
-        for o in un[1:]:
+    for copies in _members_host(outs_list, pad_left, size):
+        acc = copies[0]
+        for o in copies[1:]:
             acc = acc + o
-        p = acc / np.float32(len(un))
-        sz = p.shape[1:] if size is None else size
-        per_model.append(p[:, int(pad_left[0]):int(pad_left[0]) + int(sz[0]), int(pad_left[1]):int(pad_left[1]) + int(sz[1]),
-                           int(pad_left[2]):int(pad_left[2]) + int(sz[2])])
+        per_model.append(acc / np.float32(len(copies)))
     mean = ensemble_mean_host(per_model)
     mask = mean > 0.5
     return mean, mask, tuple(int(v) for v in mask.sum(axis=(1, 2, 3)))

@@ -563,14 +563,8 @@ def tta_merge(probs, flip_axes, want_mean=False):
     Returns (mask uint8 [C,D,H,W], counts uint64-as-int64 [C], mean or None)."""
     probs = _prep(probs)
     k, c, d, h, w = [int(v) for v in probs.shape]
-    flips = 0
-    for i, axes in enumerate(flip_axes):
-        for ax in axes:
-            flips |= TTA_FLIP_BITS[ax] << (3 * i)
-    mask = torch.empty((c, d, h, w), dtype=torch.uint8, device=probs.device)
-    counts = torch.empty(c, dtype=torch.int64, device=probs.device)
-    mean = torch.empty((c, d, h, w), dtype=torch.float32, device=probs.device) if want_mean else None
-    L.check(L.load().ru_tta_merge(L.f32(probs), k, flips, L.ptr(mean, True), L.ptr(mask), L.ptr(counts), c, d, h, w, L.stream()), "ru_tta_merge")
+    mask, counts, mean = _merge_outputs(c, (d, h, w), probs.device, want_mean)
+    L.check(L.load().ru_tta_merge(L.f32(probs), k, _flip_bits(flip_axes), L.ptr(mean, True), L.ptr(mask), L.ptr(counts), c, d, h, w, L.stream()), "ru_tta_merge")
     return mask, counts, mean
 
 
@@ -594,6 +588,30 @@ def _flip_bits(flip_axes):
         for ax in axes:
             flips |= TTA_FLIP_BITS[ax] << (3 * i)
     return flips
+
+
+# The merge family (csrc/ensemble.hip: tta_merge*, ens_*, unc_accumulate*, unc_finalize) shares its box, its outputs and the checks of its running sums.
+def _merge_box(probs, lo=None, size=None):
+    probs = _prep(probs)
+    if probs.dim() == 4:
+        probs = probs[None]                                            # an already merged prediction: one copy, no flips
+    k, c, d, h, w = [int(v) for v in probs.shape]
+    lo = (0, 0, 0) if lo is None else tuple(int(v) for v in lo)
+    size = (d, h, w) if size is None else tuple(int(v) for v in size)
+    return probs, (k, c, d, h, w), lo, size
+
+
+def _merge_outputs(c, size, device, want_mean):
+    mask = torch.empty((c,) + tuple(size), dtype=torch.uint8, device=device)
+    counts = torch.empty(c, dtype=torch.int64, device=device)
+    mean = torch.empty((c,) + tuple(size), dtype=torch.float32, device=device) if want_mean else None
+    return mask, counts, mean
+
+
+def _merge_sums(who, c, size, acc=None, acc2=None):
+    for name, t in (("acc", acc), ("acc2", acc2)):
+        if t is not None and (tuple(t.shape) != (c,) + size or t.dtype != torch.float32):
+            raise ValueError("%s: %s %s does not match %d channels of a %s box" % (who, name, tuple(t.shape), c, size))
 
 
 def tile_gather(data, tile_shape, origins):
@@ -716,11 +734,8 @@ def tta_merge_box(probs, flip_axes, lo, size, want_mean=False):
     """tta_merge restricted to the box [lo, lo+size) of the padded prediction (test.py:134-144 with the padding removed):
     (mask uint8 [C,*size], counts int64 [C], mean or None)."""
     probs = _prep(probs)
-    k, c, d, h, w = [int(v) for v in probs.shape]
-    size = tuple(int(v) for v in size)
-    mask = torch.empty((c,) + size, dtype=torch.uint8, device=probs.device)
-    counts = torch.empty(c, dtype=torch.int64, device=probs.device)
-    mean = torch.empty((c,) + size, dtype=torch.float32, device=probs.device) if want_mean else None
+    k, c, d, h, w = [int(v) for v in probs.shape]                      # five dimensions, as tta_merge: no merged [C,D,H,W] form here
+    mask, counts, mean = _merge_outputs(c, tuple(int(v) for v in size), probs.device, want_mean)
     L.check(L.load().ru_tta_merge_box(L.f32(probs), k, _flip_bits(flip_axes), L.ptr(mean, True), L.ptr(mask), L.ptr(counts), c, d, h, w,
                                       _ints(lo), _ints(size), L.stream()), "ru_tta_merge_box")
     return mask, counts, mean
@@ -807,36 +822,18 @@ def paste_labels(lab, full_shape, lo):
     return full
 
 
-def _ens_box(probs, lo, size):
-    probs = _prep(probs)
-    if probs.dim() == 4:
-        probs = probs[None]                                            # an already merged prediction: one copy, no flips
-    k, c, d, h, w = [int(v) for v in probs.shape]
-    lo = (0, 0, 0) if lo is None else tuple(int(v) for v in lo)
-    size = (d, h, w) if size is None else tuple(int(v) for v in size)
-    return probs, (k, c, d, h, w), lo, size
-
-
 def ens_accumulate(probs, flip_axes=((),), acc=None, lo=None, size=None):
     """One model of an ensemble (csrc/ensemble.hip): acc [C,*size] float32 takes S_m = S_(m-1) + p_m with p_m the un-flipped mean of
     probs [K,C,D,H,W] on the box [lo, lo+size) (test.py:134-144), in float32 in call order.  acc=None starts a sum (S_1 = p_1, written
     without a memset).  probs [C,D,H,W] with the defaults accumulates an already merged prediction.  Returns acc."""
-    probs, (k, c, d, h, w), lo, size = _ens_box(probs, lo, size)
+    probs, (k, c, d, h, w), lo, size = _merge_box(probs, lo, size)
     first = acc is None
     if first:
         acc = torch.empty((c,) + size, dtype=torch.float32, device=probs.device)
-    elif tuple(acc.shape) != (c,) + size or acc.dtype != torch.float32:
-        raise ValueError("ens_accumulate: acc %s does not match %d channels of a %s box" % (tuple(acc.shape), c, size))
+    _merge_sums("ens_accumulate", c, size, acc)
     L.check(L.load().ru_ens_accumulate(L.f32(probs), k, _flip_bits(flip_axes), L.f32(acc), int(first), c, d, h, w, _ints(lo), _ints(size), L.stream()),
             "ru_ens_accumulate")
     return acc
-
-
-def _ens_outputs(c, size, device, want_mean):
-    mask = torch.empty((c,) + tuple(size), dtype=torch.uint8, device=device)
-    counts = torch.empty(c, dtype=torch.int64, device=device)
-    mean = torch.empty((c,) + tuple(size), dtype=torch.float32, device=device) if want_mean else None
-    return mask, counts, mean
 
 
 def ens_finalize(acc, m, want_mean=False):
@@ -845,7 +842,7 @@ def ens_finalize(acc, m, want_mean=False):
     if not (acc.is_cuda and acc.is_contiguous() and acc.dtype == torch.float32 and acc.dim() >= 2):
         raise ValueError("ens_finalize: contiguous float32 device tensor [C, ...]")
     c = int(acc.shape[0])
-    mask, counts, mean = _ens_outputs(c, acc.shape[1:], acc.device, want_mean)
+    mask, counts, mean = _merge_outputs(c, acc.shape[1:], acc.device, want_mean)
     L.check(L.load().ru_ens_finalize(L.f32(acc), int(m), L.ptr(mean, True), L.ptr(mask), L.ptr(counts), c, acc.numel() // c, L.stream()), "ru_ens_finalize")
     return mask, counts, mean
 
@@ -853,10 +850,9 @@ def ens_finalize(acc, m, want_mean=False):
 def ens_accumulate_finalize(probs, flip_axes, acc, m, lo=None, size=None, want_mean=False):
     """The LAST model's ens_accumulate fused with ens_finalize (one pass, acc is not written; acc=None: an ensemble of one): the same
     (mask, counts, mean or None), bit for bit."""
-    probs, (k, c, d, h, w), lo, size = _ens_box(probs, lo, size)
-    if acc is not None and (tuple(acc.shape) != (c,) + size or acc.dtype != torch.float32):
-        raise ValueError("ens_accumulate_finalize: acc %s does not match %d channels of a %s box" % (tuple(acc.shape), c, size))
-    mask, counts, mean = _ens_outputs(c, size, probs.device, want_mean)
+    probs, (k, c, d, h, w), lo, size = _merge_box(probs, lo, size)
+    _merge_sums("ens_accumulate_finalize", c, size, acc)
+    mask, counts, mean = _merge_outputs(c, size, probs.device, want_mean)
     L.check(L.load().ru_ens_accumulate_finalize(L.f32(probs), k, _flip_bits(flip_axes), L.ptr(acc, True), int(acc is None), int(m), L.ptr(mean, True),
                                                 L.ptr(mask), L.ptr(counts), c, d, h, w, _ints(lo), _ints(size), L.stream()), "ru_ens_accumulate_finalize")
     return mask, counts, mean
@@ -884,24 +880,18 @@ def paste_probs(mean, full_shape, lo):
     return full
 
 
-def _unc_sums(who, acc, acc2, c, size):
-    for name, t in (("acc", acc), ("acc2", acc2)):
-        if t is not None and (tuple(t.shape) != (c,) + size or t.dtype != torch.float32):
-            raise ValueError("%s: %s %s does not match %d channels of a %s box" % (who, name, tuple(t.shape), c, size))
-
-
 def unc_accumulate(probs, flip_axes=((),), acc=None, acc2=None, lo=None, size=None):
     """ens_accumulate plus the second-moment sum (csrc/uncertainty.hip), one pass over probs [K,C,D,H,W]: acc takes S_m exactly as
     ens_accumulate writes it, acc2 [C,*size] takes T_m = T_(m-1) + q_m with q_m = ((o0*o0 + o1*o1) + o2*o2) + o3*o3 of the un-flipped
     copies, float32 without fma.  acc=None (then acc2 too) starts both sums.  Returns (acc, acc2)."""
-    probs, (k, c, d, h, w), lo, size = _ens_box(probs, lo, size)
+    probs, (k, c, d, h, w), lo, size = _merge_box(probs, lo, size)
     first = acc is None
     if first != (acc2 is None):
         raise ValueError("unc_accumulate: acc and acc2 start together")
     if first:
         acc = torch.empty((c,) + size, dtype=torch.float32, device=probs.device)
         acc2 = torch.empty((c,) + size, dtype=torch.float32, device=probs.device)
-    _unc_sums("unc_accumulate", acc, acc2, c, size)
+    _merge_sums("unc_accumulate", c, size, acc, acc2)
     L.check(L.load().ru_unc_accumulate(L.f32(probs), k, _flip_bits(flip_axes), L.f32(acc), L.f32(acc2), int(first), c, d, h, w, _ints(lo), _ints(size),
                                        L.stream()), "ru_unc_accumulate")
     return acc, acc2
@@ -917,12 +907,12 @@ def unc_accumulate_finalize(probs, flip_axes, acc, acc2, m, measure="std", lo=No
     """The LAST member's unc_accumulate fused with the finalize: ens_accumulate_finalize's (mask, counts, mean or None), bit for bit, plus
     the uint8 uncertainty map [C,*size] (0 certain .. 100 uncertain) of `measure` "std" or "entropy".  acc = acc2 = None: an ensemble of
     one; acc2 may also be None with "entropy"."""
-    probs, (k, c, d, h, w), lo, size = _ens_box(probs, lo, size)
+    probs, (k, c, d, h, w), lo, size = _merge_box(probs, lo, size)
     kind = _unc_measure(measure)
     if acc is None and acc2 is not None or acc is not None and acc2 is None and measure == "std":
         raise ValueError("unc_accumulate_finalize: the std measure needs both running sums")
-    _unc_sums("unc_accumulate_finalize", acc, acc2, c, size)
-    mask, counts, mean = _ens_outputs(c, size, probs.device, want_mean)
+    _merge_sums("unc_accumulate_finalize", c, size, acc, acc2)
+    mask, counts, mean = _merge_outputs(c, size, probs.device, want_mean)
     unc = torch.empty((c,) + size, dtype=torch.uint8, device=probs.device)
     L.check(L.load().ru_unc_accumulate_finalize(L.f32(probs), k, _flip_bits(flip_axes), L.ptr(acc, True), L.ptr(acc2, True), int(acc is None), int(m), kind,
                                                 L.ptr(mean, True), L.ptr(mask), L.ptr(counts), L.ptr(unc), c, d, h, w, _ints(lo), _ints(size), L.stream()),
@@ -939,8 +929,8 @@ def unc_finalize(acc, acc2, m, k=1, measure="std", want_mean=False):
     c = int(acc.shape[0])
     if acc2 is None and measure == "std":
         raise ValueError("unc_finalize: the std measure needs the second-moment sum")
-    _unc_sums("unc_finalize", None, acc2, c, tuple(acc.shape[1:]))
-    mask, counts, mean = _ens_outputs(c, acc.shape[1:], acc.device, want_mean)
+    _merge_sums("unc_finalize", c, tuple(acc.shape[1:]), acc2=acc2)
+    mask, counts, mean = _merge_outputs(c, acc.shape[1:], acc.device, want_mean)
     unc = torch.empty(tuple(acc.shape), dtype=torch.uint8, device=acc.device)
     L.check(L.load().ru_unc_finalize(L.f32(acc), L.ptr(acc2, True), int(m), int(k), kind, L.ptr(mean, True), L.ptr(mask), L.ptr(counts), L.ptr(unc), c,
                                      acc.numel() // c, L.stream()), "ru_unc_finalize")

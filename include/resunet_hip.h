@@ -479,6 +479,8 @@ int ru_comm_group_end(void);
  * which axes (bit0 D, bit1 H, bit2 W) copy k was reversed along (test.py:117-120 uses {none, D, H, D+H}).  Each prediction
  * is un-flipped (test.py:134-136) and they are averaged as sum(outputs)/K in list order (test.py:138, float32).  Outputs:
  * mean_out [C][D][H][W] (may be NULL), mask [C][V] uint8 = mean > 0.5 (test.py:144), counts[C] = voxels set per channel.
+ * It is ru_tta_merge_box on the box covering the volume, served by the merge family of csrc/ensemble.hip: 32-bit voxel indices, so
+ * D*H*W >= INT_MAX is refused (RU_EINVAL, "volume too large for 32-bit voxel indices"), and C <= 65535.
  * ru_compose_labels: labels[v] = 2 where mask[0], then 1 where mask[1], then 4 where mask[2] if counts[2] > et_min
  * (test.py:153-159, et_min = 32).  counts is read on the device: no host synchronisation.  */
 int ru_tta_merge(const float* probs, int K, unsigned flips, float* mean_out, unsigned char* mask, unsigned long long* counts,
@@ -527,13 +529,16 @@ int ru_case_stats(const float* image, double* stats, int C, int D, int H, int W,
 int ru_case_prepare(const float* image, const double* stats, float* batch, int C, int D, int H, int W, const int* lo, const int* size,
                     const int* pad_left, const int* padded, int K, unsigned flips, ru_stream_t stream);
 /* ru_tta_merge restricted to the box [lo, lo + size) of the padded prediction (test.py:140-144 removes the padding before the masks are
- * counted): mean_out / mask are [C][size], counts[C] the voxels set inside the box.  */
+ * counted): mean_out / mask are [C][size], counts[C] the voxels set inside the box.  It is ru_ens_accumulate_finalize(first = 1, M = 1)
+ * and shares its kernel (csrc/ensemble.hip) and its refusals: D*H*W >= INT_MAX ("volume too large for 32-bit voxel indices"), and C > 65535
+ * is RU_EINVAL ("bad argument") before any launch, where the launch itself used to fail.  */
 int ru_tta_merge_box(const float* probs, int K, unsigned flips, float* mean_out, unsigned char* mask, unsigned long long* counts,
                      int C, int D, int H, int W, const int* lo, const int* size, ru_stream_t stream);
 /* Post-processing (test.py:51-62,162-164): 26-connected components of labels > 0 by union-find on the device, every component smaller
  * than ratio * (V - size of the most frequent label, background included) is zeroed in place.  Only component sizes enter the rule, so
  * the result equals skimage.morphology.label + reject_small_regions whatever the numbering.  ru_paste_labels (test.py:167-168):
- * full [D][H][W] = 0 outside the box, lab [size] inside.  */
+ * full [D][H][W] = 0 outside the box, lab [size] inside: ru_paste_u8c with one channel (csrc/ensemble.hip, 32-bit voxel indices:
+ * D*H*W >= INT_MAX is refused with "volume too large for 32-bit voxel indices").  */
 size_t ru_cc_workspace_bytes(int D, int H, int W);
 int ru_cc_reject(unsigned char* labels, int D, int H, int W, double ratio, void* ws, size_t ws_bytes, ru_stream_t stream);
 int ru_paste_labels(const unsigned char* lab, unsigned char* full, int D, int H, int W, const int* lo, const int* size, ru_stream_t stream);

@@ -63,6 +63,7 @@ vb = box[0] * box[1] * box[2]
 mb = 3 * vb * 4 / 1e6                                   # one float32 copy of the box, three channels
 acc = ops.ens_accumulate(probs, INF.TTA_FLIPS, None, left, box)
 mean = ops.ens_finalize(acc, 3, want_mean=True)[2]
+labels = (torch.rand(box, generator=gen, device="cuda") * 5).to(torch.uint8)
 full_shape = (240, 240, 155)
 lo = tuple((s - b) // 2 for s, b in zip(full_shape, box))
 passes = [
@@ -74,6 +75,8 @@ passes = [
     ("finalize + mean (1 read, mask, 1 write)", lambda: ops.ens_finalize(acc, 3, want_mean=True), 2.25 * mb),
     ("paste_probs into 3 x 240 x 240 x 155 (1 read, full write)", lambda: ops.paste_probs(mean, full_shape, lo), mb + 3 * 240 * 240 * 155 * 4 / 1e6),
     ("tta_merge_box, one model at once (4 reads, mask) -- the existing pass", lambda: ops.tta_merge_box(probs, INF.TTA_FLIPS, left, box), 4.25 * mb),
+    ("tta_merge on the whole padded volume (4 reads, mask)", lambda: ops.tta_merge(probs, INF.TTA_FLIPS), 4.25 * 3 * padded[0] * padded[1] * padded[2] * 4 / 1e6),
+    ("paste_labels into 240 x 240 x 155 (1 read, full write)", lambda: ops.paste_labels(labels, full_shape, lo), (vb + 240 * 240 * 155) / 1e6),
 ]
 print("box %s of a padded %s prediction, 3 channels; the times include the output allocation of the ops wrapper" % (box, padded))
 for what, fn, mbytes in passes:
@@ -84,7 +87,7 @@ g = (torch.rand(p.shape, generator=gen, device="cuda") < 0.2).float()
 mbc = 2 * p.numel() * 4 / 1e6
 t0, t1 = timed(lambda: ops.crit_moments(p, g), False), timed(lambda: ops.crit_moments(p, g), True)
 print("%-72s %7.1f us back to back (%.2f TB/s), %7.1f us after a MALL flush (%.2f TB/s); %.0f MB" % ("criteria moments pass, 4 x 3 x 128^3 (2 reads) -- the comparison", t0 * 1e3, mbc / t0 / 1e3, t1 * 1e3, mbc / t1 / 1e3, mbc))
-del probs, acc, mean, p, g, _flush
+del probs, acc, mean, labels, p, g, _flush
 _flush = None
 torch.cuda.empty_cache()
 
