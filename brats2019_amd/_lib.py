@@ -128,6 +128,10 @@ SIGNATURES = {
     "ru_overlap_accumulate": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ru_dice1d_accumulate": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "ru_rmse_accumulate": (_i, [_vp, _vp, _vp]),
+    "ru_calib_histogram": (_i, [_vp, _vp, _i, _i, _i, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ru_calib_accumulate": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ru_calib_summary": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "ru_threshold_regions": (_i, [_vp, _i, _sz, C.POINTER(_f), _vp, _vp, _vp]),
     "ru_surface_workspace_bytes": (_sz, [_i] * 6),
     "ru_surface_metrics": (_i, [_vp, _vp] + [_i] * 6 + [_d, _vp, _vp, _vp, _sz, _vp]),
     "ru_surface_accumulate": (_i, [_vp, _vp] + [_i] * 4 + [_vp]),
@@ -216,6 +220,10 @@ CRIT_M_D2 = 6
 # ru_label_confusion / ru_overlap_accumulate (include/resunet_hip.h)
 CONF_PROB, CONF_LABEL, OVERLAP_MAX_LABELS = 0, 1, 8
 OVERLAP_MODES = {"itk": 0, "wt": 1, "validate": 2}
+
+# ru_calib_* / ru_threshold_regions (include/resunet_hip.h)
+CALIB_TARGET_REGIONS, CALIB_TARGET_LABELS = 0, 1
+CALIB_MIN_NB, CALIB_MAX_NB, CALIB_DEFAULT_NB, CALIB_MAX_C = 16, 1024, 256, 8
 
 # ru_unc_* (include/resunet_hip.h): measures, histogram extents [regions][levels][TP FP FN TN]
 UNC_MEASURES = {"std": 0, "entropy": 1}

@@ -20,7 +20,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 OBJDIR = os.path.join(PKG, "build")
 LIB = os.path.join(LIBDIR, "libresunet_hip.so")
-SOURCES = ["conv3_f32.hip", "conv3_f32c.hip", "conv3_sb.hip", "conv3_sb2_c16.hip", "conv3_sb2_c16_p1.hip", "conv3_sb2_mixed.hip", "conv3_wz.hip", "conv3_wz32.hip", "conv3_mx.hip", "conv3_wz32mx.hip", "wgrad_f32.hip", "wgrad_sb.hip", "wgrad_tr.hip", "pointwise.hip", "pointwise_c16.hip", "inference.hip", "postprocess.hip", "blend.hip", "ensemble.hip", "uncertainty.hip", "engine.hip", "op_abi.hip", "comm.hip", "metrics.hip", "criteria.hip", "overlap.hip", "surface.hip", "lesion.hip", "lesion_loss.hip", "elastic.hip", "intensity.hip", "rotate.hip", "resident.hip", "optim.hip", "boundary.hip", "carvemix.hip", "hardcrit.hip"]
+SOURCES = ["conv3_f32.hip", "conv3_f32c.hip", "conv3_sb.hip", "conv3_sb2_c16.hip", "conv3_sb2_c16_p1.hip", "conv3_sb2_mixed.hip", "conv3_wz.hip", "conv3_wz32.hip", "conv3_mx.hip", "conv3_wz32mx.hip", "wgrad_f32.hip", "wgrad_sb.hip", "wgrad_tr.hip", "pointwise.hip", "pointwise_c16.hip", "inference.hip", "postprocess.hip", "blend.hip", "ensemble.hip", "uncertainty.hip", "engine.hip", "op_abi.hip", "comm.hip", "metrics.hip", "criteria.hip", "overlap.hip", "calibration.hip", "surface.hip", "lesion.hip", "lesion_loss.hip", "elastic.hip", "intensity.hip", "rotate.hip", "resident.hip", "optim.hip", "boundary.hip", "carvemix.hip", "hardcrit.hip"]
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hpp"))) + [os.path.join(os.path.dirname(PKG), "include", "resunet_hip.h")]
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-fno-slp-vectorize", "-Wall", "-Wno-unused-function"]

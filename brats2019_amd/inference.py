@@ -220,10 +220,18 @@ def compose_masks_host(mask, counts, et_min=32):
     return out
 
 
-def _labels_from_masks(mask, counts, mean, postprocess):
-    """masks of the merge -> (label volume in the crop frame, counts): the region pass of `postprocess` (if any), test.py:153-159, and the
-    reference's rejection on the union of all labels unless `postprocess` switches it off"""
+def _check_thresholds(thresholds):
+    """thresholds=None | a scalar | (wt, tc, et): the region masks are `mean > t` instead of the merge's `mean > 0.5`"""
+    return None if thresholds is None else tuple(ops.region_thresholds(thresholds, 3))
+
+
+def _labels_from_masks(mask, counts, mean, postprocess, thresholds=None):
+    """masks of the merge -> (label volume in the crop frame, counts): with `thresholds` the masks and counts rewritten from the mean
+    (`ops.threshold_regions`), the region pass of `postprocess` (if any), test.py:153-159, and the reference's rejection on the union of
+    all labels unless `postprocess` switches it off"""
     ratio = 0.1
+    if thresholds is not None:
+        mask, counts = ops.threshold_regions(mean, thresholds)
     if postprocess is not None:
         mask, counts = ops.postprocess_regions(mask, probs=mean if postprocess.needs_probs else None, **postprocess.regions())
         ratio = postprocess.reject_ratio
@@ -264,17 +272,21 @@ def _check_tiled(model, tile, overlap, window):
         tiling._check_tile(model, tile)
 
 
-def predict_case_device(model, image, uncertainty=None, tile=None, overlap=0.5, window="gaussian", postprocess=None):
+def predict_case_device(model, image, uncertainty=None, tile=None, overlap=0.5, window="gaussian", postprocess=None, thresholds=None):
     """The per-case pipeline of test.py:82-168 with every array on the device: image [4,D,H,W] device tensor -> (uint8 device label volume
     [D,H,W] with values {0,1,2,4}, int64 device tensor of the (wt, tc, et) voxel counts).  uncertainty="std" | "entropy": the model is
     served as an ensemble of one and the uint8 [3,D,H,W] uncertainty maps of its four flips are appended.  tile=(td, th, tw): the padded
     crop does not go through the network whole but in tiles overlapping by `overlap`, blended with `window` ("gaussian" | "constant");
     everything behind the forward is the same.  postprocess=PostProcess(...): the region pass (`ops.postprocess_regions`) runs on the merged
     masks in the crop frame before the labels are composed, so the ET > 32 rule and the returned counts are those of the post-processed
-    masks; the uncertainty maps are not touched."""
+    masks; the uncertainty maps are not touched.  thresholds=(wt, tc, et) or a scalar (e.g. from `validate --calibration`): the merge is
+    asked for its mean and the region masks and counts are `mean > t` (`ops.threshold_regions`) before `postprocess`, the ET > 32 rule and
+    the label composition; None: the merge's own `mean > 0.5`, no further launch; 0.5 gives the same labels byte for byte."""
     _check_postprocess(postprocess)
+    thresholds = _check_thresholds(thresholds)
     if uncertainty is not None:
-        return predict_case_ensemble_device([model], image, uncertainty=uncertainty, tile=tile, overlap=overlap, window=window, postprocess=postprocess)
+        return predict_case_ensemble_device([model], image, uncertainty=uncertainty, tile=tile, overlap=overlap, window=window, postprocess=postprocess,
+                                            thresholds=thresholds)
     _check_tiled(model, tile, overlap, window)
     image = image.contiguous().float()
     batch, lo, size, left, _padded = prepare_case_device(image)
@@ -283,21 +295,24 @@ def predict_case_device(model, image, uncertainty=None, tile=None, overlap=0.5, 
         model.freeze_params(True)
     with torch.no_grad():
         probs = _forward(model, batch, tile, overlap, window)        # [4,3,Dp,Hp,Wp]
-    mask, counts, mean = ops.tta_merge_box(probs, TTA_FLIPS, left, size, want_mean=postprocess is not None and postprocess.needs_probs)
-    labels, counts = _labels_from_masks(mask, counts, mean, postprocess)
+    mask, counts, mean = ops.tta_merge_box(probs, TTA_FLIPS, left, size, want_mean=thresholds is not None or (postprocess is not None and postprocess.needs_probs))
+    labels, counts = _labels_from_masks(mask, counts, mean, postprocess, thresholds)
     return ops.paste_labels(labels, image.shape[1:], lo), counts
 
 
-def predict_case(model, image, uncertainty=None, tile=None, overlap=0.5, window="gaussian", postprocess=None):
+def predict_case(model, image, uncertainty=None, tile=None, overlap=0.5, window="gaussian", postprocess=None, thresholds=None):
     """Full per-case pipeline of test.py:82-168 for one multimodal volume `image` [4,D,H,W] (numpy or tensor): one upload, the device
     pipeline above, one download.  Returns (uint8 label volume [D,H,W] with values {0,1,2,4}, (wt, tc, et) voxel counts) and, with
-    uncertainty="std" | "entropy", the uint8 [3,D,H,W] uncertainty maps.  `tile`, `overlap`, `window`, `postprocess`: as `predict_case_device`."""
+    uncertainty="std" | "entropy", the uint8 [3,D,H,W] uncertainty maps.  `tile`, `overlap`, `window`, `postprocess`, `thresholds`: as
+    `predict_case_device`."""
     _check_postprocess(postprocess)
+    thresholds = _check_thresholds(thresholds)
     if uncertainty is not None:
-        return predict_case_ensemble([model], image, uncertainty=uncertainty, tile=tile, overlap=overlap, window=window, postprocess=postprocess)
+        return predict_case_ensemble([model], image, uncertainty=uncertainty, tile=tile, overlap=overlap, window=window, postprocess=postprocess,
+                                     thresholds=thresholds)
     _check_tiled(model, tile, overlap, window)
     img = torch.as_tensor(np.asarray(image) if not isinstance(image, torch.Tensor) else image, dtype=torch.float32).cuda()
-    full, counts = predict_case_device(model, img, tile=tile, overlap=overlap, window=window, postprocess=postprocess)
+    full, counts = predict_case_device(model, img, tile=tile, overlap=overlap, window=window, postprocess=postprocess, thresholds=thresholds)
     return full.cpu().numpy(), tuple(int(v) for v in counts.cpu().tolist())
 
 
@@ -456,16 +471,19 @@ def _check_ensemble(models):
     return models
 
 
-def predict_case_ensemble_device(models, image, want_probs=False, uncertainty=None, tile=None, overlap=0.5, window="gaussian", postprocess=None):
+def predict_case_ensemble_device(models, image, want_probs=False, uncertainty=None, tile=None, overlap=0.5, window="gaussian", postprocess=None,
+                                 thresholds=None):
     """`predict_case_device` for a list of models: the case is prepared once, every model runs on the same batch of four flips and its
     prediction enters the running sum before the next forward starts; then labels, component rejection and paste as for one model.
     Returns (labels, counts) and, with want_probs, the float32 [3,D,H,W] mean probabilities pasted into the case's frame (zero outside
     the crop box).  An ensemble of one is `predict_case_device`.  uncertainty="std" | "entropy" appends the uint8 [3,D,H,W] uncertainty
     maps (WT, TC, ET; 0 certain .. 100 uncertain, zero outside the crop box) of the models x flips members, made in the same passes; the
     other results do not change.  `tile`, `overlap`, `window`: every model's forward runs as in `predict_case_device`.  `postprocess`: as
-    there, on the masks of the ensemble mean; the soft labels and the uncertainty maps are those of the merge, not post-processed."""
+    there, on the masks of the ensemble mean; the soft labels and the uncertainty maps are those of the merge, not post-processed.
+    `thresholds`: as there, on the ensemble mean; the soft labels and the uncertainty maps do not change."""
     _check_uncertainty(uncertainty)
     _check_postprocess(postprocess)
+    thresholds = _check_thresholds(thresholds)
     models = _check_ensemble(models)
     for model in models:
         _check_tiled(model, tile, overlap, window)
@@ -480,10 +498,11 @@ def predict_case_ensemble_device(models, image, want_probs=False, uncertainty=No
             model.freeze_params(True)
         with torch.no_grad():
             probs = _forward(model, batch, tile, overlap, window)    # [4,3,Dp,Hp,Wp]; merged below, released before the next forward
-        acc, out = _merge_step(acc, probs, i, len(models), left, size, want_probs or (postprocess is not None and postprocess.needs_probs), uncertainty)
+        acc, out = _merge_step(acc, probs, i, len(models), left, size,
+                               want_probs or thresholds is not None or (postprocess is not None and postprocess.needs_probs), uncertainty)
         del probs
     mask, counts, mean = out[:3]
-    labels, counts = _labels_from_masks(mask, counts, mean, postprocess)
+    labels, counts = _labels_from_masks(mask, counts, mean, postprocess, thresholds)
     res = (ops.paste_labels(labels, image.shape[1:], lo), counts)
     if want_probs:
         res += (ops.paste_probs(mean, image.shape[1:], lo),)
@@ -492,17 +511,18 @@ def predict_case_ensemble_device(models, image, want_probs=False, uncertainty=No
     return res
 
 
-def predict_case_ensemble(models, image, want_probs=False, uncertainty=None, tile=None, overlap=0.5, window="gaussian", postprocess=None):
+def predict_case_ensemble(models, image, want_probs=False, uncertainty=None, tile=None, overlap=0.5, window="gaussian", postprocess=None, thresholds=None):
     """`predict_case` for a list of models (numpy or tensor in, numpy out): one upload, `predict_case_ensemble_device`, one download.
     Returns (labels, counts), then the mean probabilities with want_probs, then the uncertainty maps with `uncertainty`."""
     _check_uncertainty(uncertainty)
     _check_postprocess(postprocess)
+    thresholds = _check_thresholds(thresholds)
     models = _check_ensemble(models)
     for model in models:
         _check_tiled(model, tile, overlap, window)
     img = torch.as_tensor(np.asarray(image) if not isinstance(image, torch.Tensor) else image, dtype=torch.float32).cuda()
     out = predict_case_ensemble_device(models, img, want_probs=want_probs, uncertainty=uncertainty, tile=tile, overlap=overlap, window=window,
-                                       postprocess=postprocess)
+                                       postprocess=postprocess, thresholds=thresholds)
     return (out[0].cpu().numpy(), tuple(int(v) for v in out[1].cpu().tolist())) + tuple(t.cpu().numpy() for t in out[2:])
 
 
@@ -531,3 +551,24 @@ def postprocess_from_args(opt):
     return PostProcess(min_volume=tuple(getattr(opt, "min_volume", (0, 0, 0))), min_confidence=tuple(getattr(opt, "min_confidence", (0.0, 0.0, 0.0))),
                        keep_largest=which("keep_largest"), fill_holes=which("fill_holes"), nest=getattr(opt, "nest", False),
                        reject_ratio=None if getattr(opt, "no_reject", False) else 0.1)
+
+
+# ---------------------------------------------------------------------- the threshold flags of test and ensemble
+def add_threshold_arguments(parser):
+    """--thresholds WT TC ET, --thresholds_file FILE.  SUPPRESS: without them the namespace does not change."""
+    import argparse
+    parser.add_argument("--thresholds", default=argparse.SUPPRESS, type=float, nargs=3, metavar=("WT", "TC", "ET"),
+                        help="region masks are `probability > threshold` instead of `> 0.5`")
+    parser.add_argument("--thresholds_file", default=argparse.SUPPRESS, type=str,
+                        help="the JSON `python -m brats2019_amd.validate --calibration --thresholds_output` writes")
+
+
+def thresholds_from_args(opt):
+    """The `thresholds=` of a parsed namespace; None when neither flag of `add_threshold_arguments` was given."""
+    if hasattr(opt, "thresholds") and hasattr(opt, "thresholds_file"):
+        raise ValueError("--thresholds and --thresholds_file exclude each other")
+    if hasattr(opt, "thresholds_file"):
+        import json
+        with open(opt.thresholds_file) as f:
+            return _check_thresholds(json.load(f)["thresholds"])
+    return _check_thresholds(getattr(opt, "thresholds", None))

@@ -18,7 +18,12 @@ histogram of surface distances, an exact order statistic) and its accumulate lau
 lesion-wise ranking numbers `LesionWiseDice` and `LesionWiseHausdorff95` (ru_lesion_metrics, ru_lesion_accumulate).  From the same
 histogram of surface distances: `SurfaceDice` (NSD at a tolerance), `AverageSurfaceDistance` (ASSD) and `LesionWiseSurfaceDice`
 (ru_surface_distances, ru_lesion_distances, ru_surface_extras_accumulate), and their float64 numpy / scipy restatements
-`surface_distances_host` and `lesion_distances_host`, which the tests hold the device to."""
+`surface_distances_host` and `lesion_distances_host`, which the tests hold the device to.
+
+Calibration and the operating point: `ExpectedCalibrationError`, `BrierScore` and `DiceAtThreshold` pool the integer tables of one binning
+pass over (probability, target) on the device (ru_calib_histogram, ru_calib_accumulate, ru_calib_summary, ru_threshold_regions);
+`calibration_host` restates tables, curves and summary in numpy from the definitions in INTEGRATION.md, and `choose_threshold` picks the
+threshold from a mean Dice curve."""
 from __future__ import annotations
 
 import numpy as np
@@ -548,6 +553,222 @@ def lesion_distances_host(p, g, tolerances=(1.0,), dilation=3, min_volume=50, em
     out[:t] = sums[:t] / np.float64(den) if den else 1.0
     out[t] = (sums[t] + np.float64(n_fp) * np.float64(empty_value)) / np.float64(den) if den else 0.0
     return out, rows, n_fp
+
+
+# ---------------------------------------------------------------------- calibration and the threshold search ("Calibration")
+BRATS_REGION_LABELS = ((1, 2, 3, 4), (1, 3, 4), (3, 4))                               # WT, TC, ET
+
+
+def _bin_sums(key, weight, size):
+    """exact int64 sums of the non-negative int64 `weight` (< 2^25) per key: two bincounts over 13-bit halves, each below 2^53 in float64"""
+    hi = np.bincount(key, weights=(weight >> 13).astype(np.float64), minlength=size).astype(np.int64)
+    lo = np.bincount(key, weights=(weight & 8191).astype(np.float64), minlength=size).astype(np.int64)
+    return (hi << 13) + lo
+
+
+def calibration_tables_host(pred, target, nb=256):
+    """The integer tables of ops.calib_histogram restated from the definitions: pred float32 [N,C,...]; target float32 of the same shape
+    or a uint8 label volume [N,...] (C = 3) -> (hist, conf, sq, invalid) as int64 arrays [N,C,nb+1,2], [N,C,nb+1,2], [N,C,2,2], [N,C]."""
+    p = np.asarray(pred, dtype=np.float32)
+    n, c = p.shape[:2]
+    p = p.reshape(n, c, -1)
+    t = np.asarray(target)
+    labels = t.dtype == np.uint8
+    t = t.reshape(n, -1) if labels else t.astype(np.float32).reshape(n, c, -1)
+    k1 = nb + 1
+    hist, conf = np.zeros((n, c, k1, 2), np.int64), np.zeros((n, c, k1, 2), np.int64)
+    sq, invalid = np.zeros((n, c, 2, 2), np.int64), np.zeros((n, c), np.int64)
+    for i in range(n):
+        for j in range(c):
+            x = p[i, j].astype(np.float64)
+            with np.errstate(invalid="ignore"):
+                ok = (x >= 0.0) & (x <= 1.0)
+                if labels:
+                    ok &= t[i] <= 4
+                    y = np.isin(t[i], BRATS_REGION_LABELS[j])
+                else:
+                    ok &= ~np.isnan(t[i, j])
+                    y = t[i, j] > np.float32(0.5)
+            x, y = x[ok], y[ok].astype(np.int64)
+            k = np.ceil(x * nb).astype(np.int64)
+            r = np.floor(x * 16777216.0).astype(np.int64)
+            key = 2 * k + y
+            invalid[i, j] = ok.size - int(ok.sum())
+            hist[i, j] = np.bincount(key, minlength=2 * k1).reshape(k1, 2)
+            conf[i, j] = _bin_sums(key, r, 2 * k1).reshape(k1, 2)
+            r2 = r.astype(np.uint64) * r.astype(np.uint64)
+            for cls in (0, 1):
+                sel = r2[y == cls]
+                sq[i, j, cls, 0] = int((sel & np.uint64(0xffffffff)).sum(dtype=np.uint64))
+                sq[i, j, cls, 1] = int((sel >> np.uint64(32)).sum(dtype=np.uint64))
+    return hist, conf, sq, invalid
+
+
+def calibration_curves_host(hist):
+    """hist int64 [..., nb+1, 2] -> float64 [..., 3, nb+1]: Dice_b, Sens_b, Spec_b of the mask k > b, from exact integers, one division each,
+    1 for a zero denominator"""
+    h = np.asarray(hist, dtype=np.int64)
+    tot = h.sum(axis=-2, keepdims=True)
+    above = tot - np.cumsum(h, axis=-2)                                               # sums over k > b
+    fp, tp = above[..., 0], above[..., 1]
+    fn, tn = tot[..., 1] - tp, tot[..., 0] - fp
+
+    def ratio(num, den):
+        return np.where(den > 0, num.astype(np.float64) / np.maximum(den, 1).astype(np.float64), 1.0)
+    return np.stack([ratio(2 * tp, 2 * tp + fp + fn), ratio(tp, tp + fn), ratio(tn, tn + fp)], axis=-2)
+
+
+def calibration_summary_host(pool_hist, pool_conf, pool_s2, m=16):
+    """Pooled tables of ONE channel (hist, conf int64 [nb+1,2]; pool_s2 = the exact Python ints (S2(y=0), S2(y=1))) -> (summary float64 [7] =
+    ECE, MCE, Brier, mean confidence, prevalence, n, non-empty coarse bins; table float64 [m,3] = n_m, conf_m, freq_m).  Every ratio is one
+    correctly rounded division of exact Python integers; ECE adds its rounded products in order of the coarse bin."""
+    h, s = np.asarray(pool_hist, dtype=np.int64), np.asarray(pool_conf, dtype=np.int64)
+    nb = h.shape[0] - 1
+    assert nb % m == 0
+    width = nb // m
+    coarse = (np.maximum(np.arange(nb + 1), 1) - 1) // width
+    table, out = np.zeros((m, 3), np.float64), np.zeros(7, np.float64)
+    n, n1 = int(h.sum()), int(h[:, 1].sum())
+    if n == 0:
+        return out, table
+    ece, mce, used = 0.0, 0.0, 0
+    for b in range(m):
+        sel = coarse == b
+        nm, nm1, rm = int(h[sel].sum()), int(h[sel, 1].sum()), int(s[sel].sum())
+        if nm == 0:
+            continue
+        cf, fr = rm / (nm * (1 << 24)), nm1 / nm
+        gap = abs(fr - cf)
+        ece = ece + (nm / n) * gap
+        mce = max(mce, gap)
+        used += 1
+        table[b] = (nm, cf, fr)
+    r, r1 = int(s.sum()), int(s[:, 1].sum())
+    num = int(pool_s2[0]) + n1 * (1 << 48) - (1 << 25) * r1 + int(pool_s2[1])
+    out[:] = (ece, mce, num / (n * (1 << 48)), r / (n * (1 << 24)), n1 / n, n, used)
+    return out, table
+
+
+def choose_threshold(dice_curve):
+    """The bin b in 1..nb-1 with the largest value of the (mean) Dice curve [nb+1]; ties go to the b closest to nb / 2, then to the lower b.
+    The threshold is b / nb."""
+    d = np.asarray(dice_curve, dtype=np.float64)
+    nb = d.shape[0] - 1
+    best = max(d[1:nb])
+    return min((b for b in range(1, nb) if d[b] == best), key=lambda b: (abs(b - nb // 2), b))
+
+
+def calibration_host(pred, target, nb=256, m=16):
+    """The numpy restatement of the calibration scorer, written from the definitions and independent of the kernels: a dict with the
+    per-sample tables `hist`, `conf`, `sq`, `invalid` (int64), `s2` (Python ints [N][C][2]), `curves` float64 [N,C,3,nb+1]; the pooled
+    `pool_hist`, `pool_conf` (int64 [C,nb+1,2]), `pool_s2` (Python ints [C][2]), `pool_sq` (int64 [C,2,2], carried: low word < 2^32),
+    `curve_sum` float64 [C,3,nb+1] (the samples added in order); and `summary` float64 [C,7], `table` float64 [C,m,3]."""
+    hist, conf, sq, invalid = calibration_tables_host(pred, target, nb)
+    n, c = hist.shape[:2]
+    s2 = [[[int(sq[i, j, y, 1]) * (1 << 32) + int(sq[i, j, y, 0]) for y in (0, 1)] for j in range(c)] for i in range(n)]
+    pool_s2 = [[sum(s2[i][j][y] for i in range(n)) for y in (0, 1)] for j in range(c)]
+    pool_sq = np.array([[[v & 0xffffffff, v >> 32] for v in pool_s2[j]] for j in range(c)], dtype=np.int64)
+    curves = calibration_curves_host(hist)
+    curve_sum = curves[0].copy()
+    for i in range(1, n):
+        curve_sum = curve_sum + curves[i]
+    pool_hist, pool_conf = hist.sum(axis=0), conf.sum(axis=0)
+    rows = [calibration_summary_host(pool_hist[j], pool_conf[j], pool_s2[j], m) for j in range(c)]
+    return {"hist": hist, "conf": conf, "sq": sq, "invalid": invalid, "s2": s2, "curves": curves, "curve_sum": curve_sum, "pool_hist": pool_hist,
+            "pool_conf": pool_conf, "pool_s2": pool_s2, "pool_sq": pool_sq, "summary": np.stack([r[0] for r in rows]),
+            "table": np.stack([r[1] for r in rows])}
+
+
+class _CalibrationMetric(Metrics):
+    """Pools ops.calib_histogram's integer tables over the update() calls on the device (no host sync); get() runs ops.calib_summary on
+    them and returns column `_column` per channel as a float64 array [C].  `data_parallel` (Trainer.train sets it on train metrics when
+    world > 1): get() all-reduces (SUM) a copy of the pooled integer tables before the summary, as RMSE does with its sums."""
+    _column = 0
+
+    def __init__(self, name, input_index, target_index, bins, nb):
+        super(_CalibrationMetric, self).__init__(name)
+        self.input_index = input_index
+        self.target_index = target_index
+        self.bins, self.nb = int(bins), int(nb)
+        self.data_parallel = False
+        self.pool = None
+
+    def reset(self):
+        super(_CalibrationMetric, self).reset()
+        self.pool = None
+
+    def update(self, ground, predict):
+        pred = predict[self.input_index].detach()
+        gr = ground[self.target_index].detach()
+        assert gr.shape == pred.shape
+        pred, gr = pred.cuda().float(), gr.cuda().float()
+        hist, conf, sq, _ = ops.calib_histogram(pred, gr, self.nb)
+        if self.pool is None:
+            self.pool = ops.calib_pool(int(pred.shape[1]), self.nb, pred.device)
+        ops.calib_accumulate(hist, conf, sq, self.pool)
+        self.samples += 1
+
+    def summary(self):
+        """(out float64 [C,7], table float64 [C,bins,3]) device tensors of the pooled tables so far"""
+        if self.pool is None:
+            raise RuntimeError("%s: no update() yet" % self.name)
+        tables = self.pool[:3]
+        if self.data_parallel:
+            from .loss import _all_reduce_sums
+            tables = [t.clone() for t in tables]
+            # pool_sq's carried {low, high} words add up to the same S2; the summary reads them as such
+            for t in tables:
+                _all_reduce_sums(t, self.data_parallel)
+        return ops.calib_summary(tables[0], tables[1], tables[2], self.bins)
+
+    def get(self):
+        return self.summary()[0][:, self._column].cpu().numpy()
+
+
+class ExpectedCalibrationError(_CalibrationMetric):
+    """ECE per channel over everything seen since reset(): `bins` equal-width confidence bins over `nb` fine bins (include/resunet_hip.h,
+    ru_calib_summary).  `max_error()` is the MCE, `reliability()` the table [C,bins,3] = (n_m, conf_m, freq_m)."""
+
+    def __init__(self, name="ECE", input_index=0, target_index=0, bins=16, nb=256):
+        super(ExpectedCalibrationError, self).__init__(name, input_index, target_index, bins, nb)
+
+    def max_error(self):
+        return self.summary()[0][:, 1].cpu().numpy()
+
+    def reliability(self):
+        return self.summary()[1].cpu().numpy()
+
+
+class BrierScore(_CalibrationMetric):
+    """Brier score per channel over everything seen since reset(), on the probabilities truncated to 24 fractional bits."""
+    _column = 2
+
+    def __init__(self, name="Brier", input_index=0, target_index=0, nb=256):
+        super(BrierScore, self).__init__(name, input_index, target_index, 16, nb)
+
+
+class DiceAtThreshold(Metrics):
+    """metrics.Dice with the masks `p > threshold` (a scalar or one value per channel) in place of `p > 0.5`: ops.threshold_regions per
+    sample, then Dice's own counts and accumulate launches.  get(): float64 array [C]."""
+
+    def __init__(self, threshold, name="DiceAtThreshold", input_index=0, target_index=0):
+        super(DiceAtThreshold, self).__init__(name)
+        self.threshold = threshold
+        self.input_index = input_index
+        self.target_index = target_index
+
+    def update(self, ground, predict):
+        pred = predict[self.input_index].detach().cuda().float().contiguous()
+        gr = ground[self.target_index].detach().cuda()
+        assert gr.shape == pred.shape
+        masks = torch.stack([ops.threshold_regions(pred[i], self.threshold)[0] for i in range(int(pred.shape[0]))]).float()
+        counts = ops.dice_counts(masks, gr)
+        c = int(counts.shape[1])
+        ops.dice_accumulate(counts, _acc(self, c, counts.device), c)
+        self.samples += 1
+
+    def get(self):
+        return _get_array(self)
 
 
 def print_metrics(writer, metric, prefix, epoch):

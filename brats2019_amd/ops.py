@@ -1099,6 +1099,119 @@ def rmse_accumulate(sums, acc):
     return acc
 
 
+def _calib_nb(who, nb):
+    nb = int(nb)
+    if not (L.CALIB_MIN_NB <= nb <= L.CALIB_MAX_NB and nb & (nb - 1) == 0):
+        raise ValueError("%s: nb = %d is no power of two in %d..%d" % (who, nb, L.CALIB_MIN_NB, L.CALIB_MAX_NB))
+    return nb
+
+
+def calib_histogram(pred, target, nb=L.CALIB_DEFAULT_NB):
+    """One integer pass for calibration scoring and the threshold search (include/resunet_hip.h, ru_calib_histogram): pred float32
+    [N,C,...] probabilities, C <= 8; target float32 of the same shape (y = g > 0.5) or a uint8 label volume [N,...] (C = 3: the regions
+    WT, TC, ET) -> (hist int64 [N,C,nb+1,2]: voxels per bin k = ceil(p*nb) and class y; conf int64 [N,C,nb+1,2]: sums of r = floor(p*2^24);
+    sq int64 [N,C,2,2]: per y the sums of the low and high 32-bit halves of r*r; invalid int64 [N,C]: voxels with p outside [0, 1], a NaN
+    target or a label above 4, which are in no bin).  Contiguous views at any 4-byte alignment are taken as they are."""
+    nb = _calib_nb("calib_histogram", nb)
+    L.require_gpu()
+    if not (pred.is_cuda and pred.dtype == torch.float32 and pred.dim() >= 3):
+        raise ValueError("calib_histogram: pred must be a float32 device tensor [N,C,...], got %s %s" % (tuple(pred.shape), pred.dtype))
+    if not target.is_cuda or target.dtype not in (torch.float32, torch.uint8):
+        raise ValueError("calib_histogram: target must be a float32 or uint8 device tensor, got %s" % target.dtype)
+    pred, target = pred.contiguous(), target.contiguous()
+    n, c = int(pred.shape[0]), int(pred.shape[1])
+    v = pred.numel() // max(n * c, 1)
+    if target.dtype == torch.uint8:
+        kind = L.CALIB_TARGET_LABELS
+        if c != 3 or int(target.shape[0]) != n or target.numel() != n * v:
+            raise ValueError("calib_histogram: a label volume %s needs pred [N,3,...] of the same extents, got %s" % (tuple(target.shape), tuple(pred.shape)))
+    else:
+        kind = L.CALIB_TARGET_REGIONS
+        if tuple(target.shape) != tuple(pred.shape):
+            raise ValueError("calib_histogram: shapes differ: %s vs %s" % (tuple(pred.shape), tuple(target.shape)))
+    if not (1 <= c <= L.CALIB_MAX_C and n >= 1 and 1 <= v <= 1 << 31):
+        raise ValueError("calib_histogram: %d channels (1..%d), %d samples, %d voxels (1..2^31)" % (c, L.CALIB_MAX_C, n, v))
+    dev = pred.device
+    hist = torch.empty((n, c, nb + 1, 2), dtype=torch.int64, device=dev)
+    conf = torch.empty((n, c, nb + 1, 2), dtype=torch.int64, device=dev)
+    sq = torch.empty((n, c, 2, 2), dtype=torch.int64, device=dev)
+    invalid = torch.empty((n, c), dtype=torch.int64, device=dev)
+    L.check(L.load().ru_calib_histogram(L.ptr(pred), L.ptr(target), kind, n, c, v, nb, L.ptr(hist), L.ptr(conf), L.ptr(sq), L.ptr(invalid), L.stream()),
+            "ru_calib_histogram")
+    return hist, conf, sq, invalid
+
+
+def calib_pool(c, nb, device):
+    """Zeroed running state for calib_accumulate: (pool_hist int64 [C,nb+1,2], pool_conf int64 [C,nb+1,2], pool_sq int64 [C,2,2],
+    curve_acc float64 [C,3,nb+1])."""
+    nb = _calib_nb("calib_pool", nb)
+    return (torch.zeros((c, nb + 1, 2), dtype=torch.int64, device=device), torch.zeros((c, nb + 1, 2), dtype=torch.int64, device=device),
+            torch.zeros((c, 2, 2), dtype=torch.int64, device=device), torch.zeros((c, 3, nb + 1), dtype=torch.float64, device=device))
+
+
+def calib_accumulate(hist, conf, sq, pool, want_curves=False):
+    """One launch (ru_calib_accumulate): pool = calib_pool's tuple; the pooled tables += calib_histogram's per-sample tables (pool_sq is
+    kept carried: low word < 2^32), curve_acc [C,3,nb+1] += the sum over the samples of the (Dice, sensitivity, specificity) curves at
+    the thresholds b / nb, b = 0..nb.  Returns curves float64 [N,C,3,nb+1] with want_curves, else None."""
+    n, c, k = int(hist.shape[0]), int(hist.shape[1]), int(hist.shape[2])
+    nb = _calib_nb("calib_accumulate", k - 1)
+    pool_hist, pool_conf, pool_sq, curve_acc = pool
+    for name, t, shape in (("hist", hist, (n, c, k, 2)), ("conf", conf, (n, c, k, 2)), ("sq", sq, (n, c, 2, 2)), ("pool_hist", pool_hist, (c, k, 2)),
+                           ("pool_conf", pool_conf, (c, k, 2)), ("pool_sq", pool_sq, (c, 2, 2))):
+        if not (t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError("calib_accumulate: %s must be a contiguous int64 tensor %s, got %s %s" % (name, shape, tuple(t.shape), t.dtype))
+    if not (curve_acc.dtype == torch.float64 and curve_acc.is_contiguous() and tuple(curve_acc.shape) == (c, 3, k)):
+        raise ValueError("calib_accumulate: curve_acc must be a contiguous float64 tensor %s" % ((c, 3, k),))
+    curves = torch.empty((n, c, 3, k), dtype=torch.float64, device=hist.device) if want_curves else None
+    L.check(L.load().ru_calib_accumulate(L.ptr(hist), L.ptr(conf), L.ptr(sq), n, c, nb, L.ptr(pool_hist), L.ptr(pool_conf), L.ptr(pool_sq), L.ptr(curve_acc),
+                                         L.ptr(curves, allow_none=True), L.stream()), "ru_calib_accumulate")
+    return curves
+
+
+def calib_summary(pool_hist, pool_conf, pool_sq, bins=16):
+    """From the pooled tables, one launch (ru_calib_summary) -> (out float64 [C,7] = ECE, MCE, Brier, mean confidence, prevalence, n,
+    non-empty coarse bins; table float64 [C,bins,3] = n_m, conf_m, freq_m).  `bins` divides nb."""
+    c, k = int(pool_hist.shape[0]), int(pool_hist.shape[1])
+    nb, bins = _calib_nb("calib_summary", k - 1), int(bins)
+    if bins < 1 or nb % bins:
+        raise ValueError("calib_summary: bins = %d must divide nb = %d" % (bins, nb))
+    for name, t, shape in (("pool_hist", pool_hist, (c, k, 2)), ("pool_conf", pool_conf, (c, k, 2)), ("pool_sq", pool_sq, (c, 2, 2))):
+        if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError("calib_summary: %s must be a contiguous int64 device tensor %s" % (name, shape))
+    out = torch.empty((c, 7), dtype=torch.float64, device=pool_hist.device)
+    table = torch.empty((c, bins, 3), dtype=torch.float64, device=pool_hist.device)
+    L.check(L.load().ru_calib_summary(L.ptr(pool_hist), L.ptr(pool_conf), L.ptr(pool_sq), c, nb, bins, L.ptr(out), L.ptr(table), L.stream()), "ru_calib_summary")
+    return out, table
+
+
+def region_thresholds(thresholds, c):
+    """A scalar or a sequence of c thresholds -> a list of c Python floats (rounded to float32, as the kernel compares)."""
+    import numpy as np
+    t = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+    if t.size == 1:
+        t = np.repeat(t, c)
+    if t.size != c or np.isnan(t).any():
+        raise ValueError("thresholds: a scalar or %d values without NaN, got %r" % (c, thresholds))
+    return [float(np.float32(x)) for x in t]
+
+
+def threshold_regions(probs, thresholds):
+    """probs float32 [C,...] -> (mask uint8 = p > t[c] (NaN gives 0), counts int64 [C]: exact voxels set), one launch
+    (ru_threshold_regions).  At 0.5 these are ens_finalize's mask and counts on the same mean, bit for bit."""
+    if not (probs.is_cuda and probs.is_contiguous() and probs.dtype == torch.float32 and probs.dim() >= 2):
+        raise ValueError("threshold_regions: contiguous float32 device tensor [C, ...]")
+    import ctypes
+    c = int(probs.shape[0])
+    if not 1 <= c <= L.CALIB_MAX_C:
+        raise ValueError("threshold_regions: %d channels, 1..%d" % (c, L.CALIB_MAX_C))
+    t = region_thresholds(thresholds, c)
+    mask = torch.empty(probs.shape, dtype=torch.uint8, device=probs.device)
+    counts = torch.empty(c, dtype=torch.int64, device=probs.device)
+    L.check(L.load().ru_threshold_regions(L.ptr(probs), c, probs.numel() // c, (ctypes.c_float * c)(*t), L.ptr(mask), L.ptr(counts), L.stream()),
+            "ru_threshold_regions")
+    return mask, counts
+
+
 # ---------------------------------------------------------------------- engine-internal voxel-major layout (tests / probes)
 HD95_EMPTY = 373.12866                  # sqrt(240^2 + 240^2 + 155^2): the diagonal of a BraTS volume
 

@@ -20,6 +20,9 @@ csrc/blend.hip) -- for a case whose padded crop does not fit the device whole.
 `--min_volume WT TC ET`, `--min_confidence WT TC ET`, `--keep_largest wt|tc|et ...`, `--fill_holes wt|tc|et ...`, `--nest`, `--no_reject`
 post-process the merged masks per region on the device before the labels are composed (`inference.PostProcess`, csrc/postprocess.hip;
 INTEGRATION.md states the definition); `--no_reject` drops the reference's rejection on the union of all labels.
+
+`--thresholds WT TC ET` or `--thresholds_file FILE` (the JSON `python -m brats2019_amd.validate --calibration --thresholds_output` writes) make the
+region masks `mean probability > threshold` instead of `> 0.5`, before the post-processing and the label composition (csrc/calibration.hip).
 """
 from __future__ import annotations
 
@@ -47,6 +50,7 @@ parser.add_argument("--tile", default=argparse.SUPPRESS, type=int, nargs=3, meta
 parser.add_argument("--overlap", default=argparse.SUPPRESS, type=float, help="overlap of neighbouring tiles as a fraction of the tile, 0 .. 0.75 (with --tile; default 0.5)")
 parser.add_argument("--window", default=argparse.SUPPRESS, choices=["gaussian", "constant"], help="blend window (with --tile; default gaussian)")
 inference.add_postprocess_arguments(parser)
+inference.add_threshold_arguments(parser)
 
 
 def _load_net(name, opt):
@@ -70,6 +74,9 @@ def main(argv=None):
     post = inference.postprocess_from_args(opt)
     if post is not None:
         tiled["postprocess"] = post
+    thresholds = inference.thresholds_from_args(opt)
+    if thresholds is not None:
+        tiled["thresholds"] = thresholds
     print(torch.__version__)
     print(opt)
     net = _load_net(opt.name, opt)

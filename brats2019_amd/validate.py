@@ -27,6 +27,13 @@ region are counted on the rest: Dice_t = 2TP/(2TP+FP+FN) (1 for an empty denomin
 FTN_t likewise; the AUCs are trapezoid sums over the thresholds divided by their span, score = (AUC_Dice + (1 - AUC_FTP) + (1 - AUC_FTN)) / 3.
 One histogram pass and one small launch per case (ru_unc_histogram, ru_unc_score).  Neither the default thresholds nor the
 empty-denominator values have been checked against the challenge's own evaluator.
+
+`--calibration --probs_path DIR [--bins 16] [--nb 256] [--thresholds_output FILE] [--host]` scores the calibration of the region probabilities
+instead: DIR holds `<case>.npy` float32 [3,D,H,W] (WT, TC, ET) as `python -m brats2019_amd.test --probs_output DIR` writes them.  Per region it
+prints ECE, MCE and the Brier score over all cases' voxels, the mean Dice over the cases at 0.5, the threshold b / nb with the best mean Dice
+and that Dice, and the reliability table; `--thresholds_output` writes the thresholds as the JSON `test --thresholds_file` reads.  One
+histogram pass and one small launch per case, one summary launch (ru_calib_histogram, ru_calib_accumulate, ru_calib_summary; INTEGRATION.md
+states the definitions); `--host` computes the same with numpy.  The conventions are this library's own, not checked against another package.
 """
 from __future__ import annotations
 
@@ -53,6 +60,13 @@ parser.add_argument("--dilation", default=argparse.SUPPRESS, type=int, help="les
 parser.add_argument("--min_volume", default=argparse.SUPPRESS, type=int, help="lesion-wise: ground-truth lesions of at most this many voxels are not scored (default 50)")
 parser.add_argument("--nsd", default=argparse.SUPPRESS, type=float, nargs="+", metavar="TOL",
                     help="with --regions or --lesionwise: add the surface Dice at these tolerances in voxels (and ASSD with --regions)")
+parser.add_argument("--calibration", action="store_true", default=argparse.SUPPRESS,
+                    help="score the calibration of the region probabilities in --probs_path and search the best threshold per region")
+parser.add_argument("--probs_path", default=argparse.SUPPRESS, type=str, help="directory of <case>.npy float32 [3,D,H,W] region probabilities (test.py --probs_output)")
+parser.add_argument("--bins", default=argparse.SUPPRESS, type=int, help="calibration: coarse confidence bins, a divisor of --nb (default 16)")
+parser.add_argument("--nb", default=argparse.SUPPRESS, type=int, help="calibration: fine bins = candidate thresholds b / nb, a power of two in 16..1024 (default 256)")
+parser.add_argument("--thresholds_output", default=argparse.SUPPRESS, type=str, help="calibration: write the chosen thresholds to this JSON file")
+parser.add_argument("--host", action="store_true", default=argparse.SUPPRESS, help="calibration: compute with the numpy restatement instead of the device")
 
 UNCERTAINTY_THRESHOLDS = (25, 50, 75, 100)
 UNCERTAINTY_COLUMNS = ("score", "AUC_Dice", "AUC_FTP", "AUC_FTN")
@@ -210,6 +224,94 @@ def score_uncertainty(cases, thresholds=UNCERTAINTY_THRESHOLDS):
     return names, np.ascontiguousarray(host[:-1, :12].reshape(len(names), 3, 4)), host[-1, :12].reshape(3, 4) / len(names)
 
 
+CALIBRATION_COLUMNS = ("ECE", "MCE", "Brier", "mean_conf", "prevalence", "n", "bins_used")
+
+
+def score_calibration(cases, nb=256, bins=16, host=False):
+    """cases: iterable of (name, ground-truth labels uint8 [D,H,W], region probabilities float32 [3,D,H,W] in the order WT, TC, ET), read
+    one at a time.  One histogram pass and one small launch per case (ru_calib_histogram, ru_calib_accumulate), one summary launch and
+    one host copy at the end.  -> dict: `names`; `curves` float64 [cases,3,3,nb+1] (region; Dice, Sens, Spec; threshold b / nb);
+    `mean_curve` [3,3,nb+1]; `summary` [3,7] (CALIBRATION_COLUMNS) and `table` [3,bins,3] (n_m, conf_m, freq_m) over all cases' voxels;
+    `best_bin` [3], `thresholds` [3] = best_bin / nb (metrics.choose_threshold on the mean Dice curve), `dice` [3] there and
+    `dice_at_half` [3] at 0.5.  host=True computes the same with the numpy restatement (metrics.calibration_host), without a GPU."""
+    from . import metrics
+    nb, bins = int(nb), int(bins)
+    if not (16 <= nb <= 1024 and nb & (nb - 1) == 0) or bins < 1 or nb % bins:
+        raise ValueError("validate: nb = %d must be a power of two in 16..1024 and bins = %d must divide it" % (nb, bins))
+    names, curves, invalid, pool = [], [], [], None
+    for name, label, probs in cases:
+        probs = np.ascontiguousarray(probs, dtype=np.float32)
+        if np.ndim(label) != 3 or tuple(probs.shape) != (3,) + tuple(label.shape):
+            raise ValueError("%s: label shape %s and probability shape %s must be [D,H,W] and [3,D,H,W]" % (name, tuple(label.shape), tuple(probs.shape)))
+        label = np.ascontiguousarray(label)
+        if label.dtype != np.uint8:
+            if label.size and (label.min() < 0 or label.max() > 4 or not np.array_equal(label, np.round(label))):
+                raise ValueError("%s (labels): labels outside {0,1,2,3,4}" % name)
+            label = label.astype(np.uint8)
+        if host:
+            h = metrics.calibration_host(probs[None], label[None], nb, bins)
+            if pool is None:
+                pool = [np.zeros_like(h["pool_hist"]), np.zeros_like(h["pool_conf"]), [[0, 0] for _ in range(3)], np.zeros_like(h["curve_sum"])]
+            pool[0] += h["pool_hist"]
+            pool[1] += h["pool_conf"]
+            pool[2] = [[a + b for a, b in zip(x, y)] for x, y in zip(pool[2], h["pool_s2"])]
+            pool[3] = pool[3] + h["curve_sum"]
+            curves.append(h["curves"][0])
+            invalid.append(h["invalid"][0])
+        else:
+            p, g = torch.from_numpy(probs).cuda(), torch.from_numpy(label).cuda()
+            hist, conf, sq, inv = ops.calib_histogram(p[None], g[None], nb)
+            if pool is None:
+                pool = ops.calib_pool(3, nb, p.device)
+            curves.append(ops.calib_accumulate(hist, conf, sq, pool, want_curves=True)[0])
+            invalid.append(inv[0])
+        names.append(name)
+    if not names:
+        raise ValueError("validate: no cases")
+    if host:
+        rows = [metrics.calibration_summary_host(pool[0][c], pool[1][c], pool[2][c], bins) for c in range(3)]
+        summary, table = np.stack([r[0] for r in rows]), np.stack([r[1] for r in rows])
+        curves, bad, curve_sum = np.stack(curves), np.stack(invalid), pool[3]
+    else:
+        out, tab = ops.calib_summary(pool[0], pool[1], pool[2], bins)
+        flat = torch.cat([torch.stack(curves).reshape(-1), pool[3].reshape(-1), out.reshape(-1), tab.reshape(-1),
+                          torch.stack(invalid).reshape(-1).to(torch.float64)]).cpu().numpy()          # the one host copy
+        k = 9 * (nb + 1)
+        cuts = np.cumsum([len(names) * k, k, 21, 9 * bins])
+        curves, curve_sum, summary, table, bad = np.split(flat, cuts)
+        curves, curve_sum = curves.reshape(len(names), 3, 3, nb + 1), curve_sum.reshape(3, 3, nb + 1)
+        summary, table, bad = summary.reshape(3, 7), table.reshape(3, bins, 3), bad.reshape(len(names), 3)
+    if bad.any():
+        k = int(np.argmax(bad.sum(axis=1) > 0))
+        raise ValueError("%s: %d voxels with a label outside {0,1,2,3,4} or a probability outside [0, 1]" % (names[k], int(bad[k].max())))
+    mean_curve = curve_sum / len(names)
+    best = [metrics.choose_threshold(mean_curve[c, 0]) for c in range(3)]
+    return {"names": names, "curves": curves, "mean_curve": mean_curve, "summary": summary, "table": table, "best_bin": best, "nb": nb,
+            "thresholds": [b / nb for b in best], "dice": [float(mean_curve[c, 0, best[c]]) for c in range(3)],
+            "dice_at_half": [float(mean_curve[c, 0, nb // 2]) for c in range(3)]}
+
+
+def write_thresholds(path, res):
+    """the small JSON `python -m brats2019_amd.test --thresholds_file` and `ensemble --thresholds_file` read"""
+    import json
+    with open(path, "w") as f:
+        json.dump({"thresholds": [float(t) for t in res["thresholds"]], "nb": int(res["nb"]), "dice": [float(v) for v in res["dice"]],
+                   "dice_at_half": [float(v) for v in res["dice_at_half"]]}, f)
+        f.write("\n")
+
+
+def _calibration_lines(res):
+    lines = []
+    for c, region in enumerate(REGION_NAMES):
+        s = res["summary"][c]
+        lines.append("%s ECE %.6f MCE %.6f Brier %.6f Dice@0.5 %.4f best_threshold %.6f Dice@best %.4f" %
+                     (region, s[0], s[1], s[2], res["dice_at_half"][c], res["thresholds"][c], res["dice"][c]))
+        m = len(res["table"][c])
+        for b, (n, cf, fr) in enumerate(res["table"][c]):
+            lines.append("%s bin %2d (%.4f, %.4f] n %d conf %.6f freq %.6f" % (region, b, b / m, (b + 1) / m, int(n), cf, fr))
+    return lines
+
+
 def _uncertainty_row(r):
     return "  ".join("%s %s" % (n, " ".join("%s %.4f" % (k, v) for k, v in zip(UNCERTAINTY_COLUMNS, row))) for n, row in zip(REGION_NAMES, r))
 
@@ -246,6 +348,16 @@ def main(argv=None):
     print(torch.__version__)
     print(opt)
     series = sorted(f[:-4] for f in os.listdir(opt.data_path) if f.endswith(".npy") and os.path.isfile(os.path.join(opt.data_path, f)))
+    if getattr(opt, "calibration", False):
+        if not getattr(opt, "probs_path", None):
+            raise ValueError("validate: --calibration needs --probs_path")
+        cases = ((f, np.load(os.path.join(opt.data_path, f + ".npy")), np.load(os.path.join(opt.probs_path, f + ".npy"))) for f in series)
+        res = score_calibration(cases, getattr(opt, "nb", 256), getattr(opt, "bins", 16), getattr(opt, "host", False))
+        for line in _calibration_lines(res):
+            print(line)
+        if getattr(opt, "thresholds_output", None):
+            write_thresholds(opt.thresholds_output, res)
+        return res["summary"], res["thresholds"]
     if getattr(opt, "uncertainty_path", None):
         series, results, mean = score_uncertainty(_uncertainty_cases(opt, series), getattr(opt, "thresholds", UNCERTAINTY_THRESHOLDS))
         for f, r in zip(series, results):

@@ -852,6 +852,52 @@ int ru_overlap_accumulate(const unsigned long long* conf, int N, int L, int mode
 int ru_dice1d_accumulate(const unsigned long long* counts, double* acc, int N, int C, int classes, ru_stream_t stream);
 int ru_rmse_accumulate(const double* sums, double* acc, ru_stream_t stream);
 
+/* ---------------------------------------------------------------- calibration scoring and the per-region threshold search (csrc/calibration.hip)
+ * One integer pass over (probability, target) that bins the probability; the Dice / sensitivity / specificity curve at every threshold and
+ * the calibration numbers are small functions of its tables.  Opt-in: nothing else calls these.  The conventions are this library's own and
+ * were not checked against any other package.
+ *   NB        fine bins: a power of two, RU_CALIB_MIN_NB <= NB <= RU_CALIB_MAX_NB.  p * NB is exact in float32 and b / NB is representable.
+ *   valid     a probability p (float32) is valid iff 0 <= p <= 1; -0.0 is valid, NaN, negatives, values above 1 and infinities are not.
+ *   k(p)      = ceil(p * NB) in 0..NB: NB + 1 bins, bin 0 holds exactly p == 0, and p > b / NB <=> k(p) > b; b = NB / 2 is the rule p > 0.5.
+ *   r(p)      = floor(p * 2^24) in 0..2^24, the fixed-point confidence (the product is exact; r = p * 2^24 on [0.5, 1], truncated below).
+ *   target    RU_CALIB_TARGET_REGIONS: float32 [N][C][V], y = g > 0.5, a NaN target is invalid.  RU_CALIB_TARGET_LABELS: uint8 [N][V] label
+ *             volume, C = 3 regions WT = {1,2,3,4}, TC = {1,3,4}, ET = {3,4}; a label outside 0..4 is invalid for all three.
+ *   A voxel that is invalid for a channel counts in invalid[n][c] and in no bin.
+ * ru_calib_histogram: pred float32 [N][C][V], C <= RU_CALIB_MAX_C, 1 <= V <= 2^31, any 4-byte alignment -> per (n, c), all uint64, written (not
+ *   accumulated) and cleared by a kernel of the call:  hist [N][C][NB+1][2] = voxels per (k, y);  conf [N][C][NB+1][2] = the sum of r;
+ *   sq [N][C][2][2] = per y {sum of (r*r & 0xffffffff), sum of (r*r >> 32)}, so that S2 = sq[y][1] * 2^32 + sq[y][0] is the exact sum of r^2;
+ *   invalid [N][C].  Integer atomics only: two calls give identical bytes.  The prediction and a float32 target are read once; a label volume
+ *   is read once per region (1 byte a voxel beside the prediction's 4).
+ * ru_calib_accumulate: one launch.  pool_hist [C][NB+1][2], pool_conf [C][NB+1][2] += the sums over the N samples; pool_sq [C][2][2] takes the
+ *   samples' S2 and is kept carried (its low word < 2^32).  With the mask k > b for b = 0..NB:  TP_b = sum_{k>b} hist[k][1], FP_b = sum_{k>b} hist[k][0],
+ *   FN_b = sum_{k<=b} hist[k][1], TN_b = sum_{k<=b} hist[k][0] (exact integers), and in float64, one division each,
+ *   Dice_b = 2TP / (2TP + FP + FN), Sens_b = TP / (TP + FN), Spec_b = TN / (TN + FP), each 1 for a zero denominator.
+ *   curve_acc [C][3][NB+1] (Dice, Sens, Spec) += ((v_0 + v_1) + ...) + v_(N-1), the samples in order; curves_out [N][C][3][NB+1] may be NULL.
+ * ru_calib_summary: from the pooled tables, with M coarse bins (M divides NB), coarse bin m = (max(k, 1) - 1) / (NB / M):
+ *   n_m = voxels, conf_m = (double)R_m / ((double)n_m * 2^24) with R_m the sum of r, freq_m = (double)n_m(y=1) / (double)n_m,
+ *   ECE = sum over the non-empty bins in order of m of ((double)n_m / (double)n) * |freq_m - conf_m| (product rounded, then added),
+ *   MCE = the largest |freq_m - conf_m|, Brier = T / ((double)n * 2^48) with the exact integer T = S2(y=0) + n(y=1) * 2^48 - 2^25 * R(y=1) + S2(y=1)
+ *   converted as (double)(T >> 64) * 2^64 + (double)(T mod 2^64).  out [C][7] = {ECE, MCE, Brier, mean confidence = (double)R / ((double)n * 2^24),
+ *   prevalence = (double)n(y=1) / (double)n, n, non-empty coarse bins}, table [C][M][3] = {n_m, conf_m, freq_m} (zeros for an empty bin), float64.
+ *   An empty channel (n = 0) gives zeros.
+ * ru_threshold_regions: probs float32 [C][V], thresholds = HOST float[C] (no NaN) -> mask uint8 [C][V] = p > t (a NaN p gives 0), counts [C] = exact
+ *   voxels set.  At t = 0.5 the mask and counts are ru_ens_finalize's on the same mean, bit for bit. */
+#define RU_CALIB_TARGET_REGIONS 0
+#define RU_CALIB_TARGET_LABELS 1
+#define RU_CALIB_MIN_NB 16
+#define RU_CALIB_MAX_NB 1024
+#define RU_CALIB_DEFAULT_NB 256
+#define RU_CALIB_MAX_C 8
+int ru_calib_histogram(const float* pred, const void* target, int kind, int N, int C, size_t V, int NB, unsigned long long* hist,
+                       unsigned long long* conf, unsigned long long* sq, unsigned long long* invalid, ru_stream_t stream);
+int ru_calib_accumulate(const unsigned long long* hist, const unsigned long long* conf, const unsigned long long* sq, int N, int C, int NB,
+                        unsigned long long* pool_hist, unsigned long long* pool_conf, unsigned long long* pool_sq, double* curve_acc,
+                        double* curves_out, ru_stream_t stream);
+int ru_calib_summary(const unsigned long long* pool_hist, const unsigned long long* pool_conf, const unsigned long long* pool_sq, int C, int NB, int M,
+                     double* out, double* table, ru_stream_t stream);
+int ru_threshold_regions(const float* probs, int C, size_t V, const float* thresholds, unsigned char* mask, unsigned long long* counts,
+                         ru_stream_t stream);
+
 /* ---------------------------------------------------------------- BraTS challenge metrics: Dice, sensitivity, specificity, HD95
  * Per sample n and region k, P and G are binary masks on the D x H x W grid, every extent in [1, 512] (larger: RU_EINVAL).
  *   kind RU_SURFACE_PROB : pred, target = [N][C][D][H][W] float32, P = pred > 0.5 and G = target > 0.5 per channel, K = C regions.
